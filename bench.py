@@ -13,7 +13,10 @@ GPU) when it is not already running under a launcher; under `python -m torch.dis
 (RANK / LOCAL_RANK / WORLD_SIZE in the environment) it is one of the ranks.  One rank per GPU, RCCL ("nccl").
 `HEFX_BENCH_BACKEND=gloo` (development only) lets several ranks share the GPUs that exist.
 
-Besides the headline, the same JSON line carries:
+A plain run sets up, warms up, times the --steps steps and prints the headline: metric, value, unit, ms_per_step (wall
+time of one timed step), the roofline fraction of those steps' HIP-event time, the library hashes.  --dump-outputs DIR
+also writes a fixed sample of the last timed step's outputs (dump_outputs).  With --full, the same JSON line carries
+besides the headline:
   verified      outs[0] and outs[B-1] of the timed loop compared word for word with the CPU oracle
   variants      the same batch with 16 distinct steps / Galois keys round-robin (the headline shares one key)
   lt_sharded    Linear_Transform_Plain (helper.h:237-262) at C3, d = 16 and 512, diagonals sharded over the ranks with one
@@ -546,6 +549,25 @@ def secondary_bench(name, Engine, local_rank, rank, world, timed, key32, seconds
                          "valu_frac": value / world / valu["peak_ops_per_s"]}}
 
 
+def dump_outputs(out_dir: str, outs, budget_bytes: int = 60 << 20):
+    """--dump-outputs: whole output ciphertexts of a fixed, seeded sample of the batch items (the first and the last among
+    them) as DIR/rotate_multiply_plain_out.npy, float64 [items][2][L][N][2] -- each u64 residue split into its low and high
+    32-bit halves, both exact in float64 -- and the item indices as DIR/rotate_multiply_plain_items.npy.  Same arguments,
+    same inputs (device-drawn from fixed seeds), so two builds can be compared word for word."""
+    import numpy as np
+    B = len(outs)
+    per_item = 2 * 8 * int(np.prod(outs[0].shape))
+    n = max(1, min(16, B, budget_bytes // per_item))
+    rest = np.random.default_rng(0x5EA1).choice(np.arange(1, B - 1), size=max(0, min(n - 2, B - 2)), replace=False) \
+        if B > 2 else np.arange(1, B)
+    items = sorted({0, B - 1} | {int(i) for i in rest})
+    words = np.stack([outs[i].download() for i in items])
+    halves = np.stack([words & np.uint64(0xFFFFFFFF), words >> np.uint64(32)], axis=-1).astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "rotate_multiply_plain_out.npy"), halves)
+    np.save(os.path.join(out_dir, "rotate_multiply_plain_items.npy"), np.asarray(items, dtype=np.float64))
+
+
 def _hashes():
     """(source hash, library hash) of the engine that runs: written into the line and compared with the hashes the
     profile tools wrote into profiles/*_pmc_traffic.json / *_sq_counters.json -- counters of other kernels are stale"""
@@ -576,10 +598,16 @@ def main():
     ap.add_argument("--composites", default="matmul_C3_n4,matmul_C5_n8,lr_rows_2000x8", help="SURVEY 8(d)'s scaling workloads "
                     "(serial ms; sharded + bits_equal_serial with more than one rank); '' disables")
     ap.add_argument("--ladder", default="1,16,256,1024", help="batch sizes of the `batch_ladder` block (SURVEY 8d); '' disables")
-    ap.add_argument("--quick", action="store_true", help="headline only (A/B and profiler runs): no CPU baseline, variants, "
-                    "key-per-item, secondary sets, sustained pass or linear-transform legs")
+    ap.add_argument("--quick", action="store_true", help="with --full: headline, verification and per-kernel profile only "
+                    "(A/B and profiler runs): no CPU baseline, variants, key-per-item, secondary sets, sustained pass or "
+                    "linear-transform legs")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline: the oracle check of the timed "
+                    "outputs, the per-kernel profile, the board sampler, the committed counter files and every leg above "
+                    "that is not disabled; without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write a fixed sample of "
+                    "what the last step computed to DIR/*.npy (float64, under 64 MB)")
     args = ap.parse_args()
-    if args.quick:
+    if args.quick or not args.full:
         args.cpu_seconds, args.variant_keys, args.stream_keys, args.key_per_item = 0.0, 0, 0, 0
         args.lt, args.lt_direct, args.secondary, args.sustain = "", 0, "", 0.0
         args.composites, args.ladder = "", ""
@@ -684,10 +712,12 @@ def main():
             dt = float(tt.item())
         return dt, gpu_ms
 
-    board = BoardSampler(local_rank) if rank == 0 else None
+    board = BoardSampler(local_rank) if rank == 0 and args.full else None
     if board:
         board.start()
     dt, gpu_ms = timed(step, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs)  # before any later pass writes into `outs`
     # a second, longer self-timed pass of the SAME step: at least `--sustain` seconds whatever --steps
     # is, so that the board sampler (and anybody watching from outside) sees the device busy more than once and the clock /
     # power it settles at; reported next to the headline, never instead of it
@@ -752,7 +782,7 @@ def main():
     # what was timed is checked: one item of EVERY chunk of the launch sequence (the engine cuts the batch into chunks of
     # at most 256 items on alternating internal streams) plus the last item, word for word against the CPU oracle (rank 0)
     verified, verified_items = None, []
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             from oracle import oracle as O
             o = O.Oracle(N, primes)
@@ -765,12 +795,14 @@ def main():
 
     # per-launch-kind durations: a short profiled pass (serial, HIP events between the launches).  The host-side
     # verification above left the device idle and its clock low: two untimed steps bring it back first.
-    step()
-    step()
-    e.sync()
-    e.profile_begin()
-    step()
-    stage_ms, nchunks = e.profile_end()
+    stage_ms, nchunks = {}, 0
+    if args.full:
+        step()
+        step()
+        e.sync()
+        e.profile_begin()
+        step()
+        stage_ms, nchunks = e.profile_end()
 
     # secondary pass: the same batch with `nk` distinct steps / keys round-robin (a linear transform rotates by distinct
     # steps with distinct keys: no key sharing between neighbouring items, nk keys competing for the caches)
@@ -868,7 +900,7 @@ def main():
         traffic, traffic_src, traffic_stale = None, None, None
         for rnd in ("r06", "r05", "r04", "r03", "r02", "r01"):
             pmc = os.path.join(ROOT, "profiles", f"{rnd}_bench_pmc_traffic.json")
-            if args.set == "C3" and os.path.exists(pmc):
+            if args.full and args.set == "C3" and os.path.exists(pmc):
                 try:
                     pj = json.load(open(pmc))
                     pb = pj["per_op_bytes"]
@@ -886,7 +918,7 @@ def main():
         issue = None
         sqf = next((f for f in (os.path.join(ROOT, "profiles", f"{r}_bench_sq_counters.json") for r in ("r06", "r05", "r04", "r03"))
                     if os.path.exists(f)), "")
-        if args.set == "C3" and sqf:
+        if args.full and args.set == "C3" and sqf:
             try:
                 sq = json.load(open(sqf))
                 meta = sq.pop("_meta", {})
@@ -902,7 +934,7 @@ def main():
                     issue["frac_of_issue_bound_at_5_cycles"] = 5.0 / cyc
             except Exception:
                 issue = None
-        dom = max(stage_ms, key=stage_ms.get)
+        dom = max(stage_ms, key=stage_ms.get, default=None)
         tot = sum(stage_ms.values())
         valu = valu_bound_ops_per_s(N, primes, L)
         per_gpu = value / world
@@ -996,6 +1028,13 @@ def main():
                 line["cpu_baseline"] = {"value": None, "error": repr(ex)}
         else:
             line["cpu_baseline"] = None
+        if not args.full:  # a plain run: the headline and what its own timed steps give, nothing that needs a pass of its own
+            line = {kk: line[kk] for kk in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
+                                            "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "libhefx_sha16",
+                                            "csrc_sha16", "rescale_mode", "config", "roofline")}
+            line["roofline"] = {kk: line["roofline"][kk] for kk in ("bound", "achieved", "peak", "unit", "frac",
+                                                                    "algorithmic_GB_per_step", "note")}
+        line["full"] = args.full  # False: verification, profiles, baselines and the other legs ran only with --full
 
     def emit():
         if rank == 0:

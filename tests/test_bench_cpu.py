@@ -75,3 +75,36 @@ def test_committed_traffic_and_counter_files_agree_with_the_bench_line():
     assert abs(line["roofline"]["valu"]["issue"]["valu_wave_instr_per_op"] - per_op) < 1.0
     assert 1.4e6 < per_op < 1.7e6 and 15e6 < pb["fetch_x2"] + pb["write"] < 18e6
     assert line["verified"] is True and len(line["verified_items"]) == 19
+
+
+def test_dump_outputs_writes_a_fixed_exact_sample(tmp_path):
+    """--dump-outputs: whole ciphertexts of a seeded sample of the batch (first and last item included), each u64 word
+    split into two exact float64 halves, under the 64 MB cap, the same items on every call."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Fake:  # what bench.dump_outputs needs of a DeviceArray
+        def __init__(self, a):
+            self.shape, self._a = a.shape, a
+
+        def download(self):
+            return self._a.copy()
+
+    rng = np.random.default_rng(5)
+    B, shape = 40, (2, 5, 16384)
+    host = [rng.integers(0, 1 << 60, size=shape, dtype=np.uint64) for _ in range(B)]
+    outs = [Fake(a) for a in host]
+    bench.dump_outputs(str(tmp_path / "a"), outs)
+    bench.dump_outputs(str(tmp_path / "b"), outs)
+    got = np.load(tmp_path / "a" / "rotate_multiply_plain_out.npy")
+    items = np.load(tmp_path / "a" / "rotate_multiply_plain_items.npy")
+    assert got.dtype == np.float64 and items.dtype == np.float64
+    assert (got == np.load(tmp_path / "b" / "rotate_multiply_plain_out.npy")).all()
+    assert (items == np.load(tmp_path / "b" / "rotate_multiply_plain_items.npy")).all()
+    idx = [int(i) for i in items]
+    assert idx[0] == 0 and idx[-1] == B - 1 and len(set(idx)) == len(idx) == got.shape[0] == 16
+    assert got.shape == (16,) + shape + (2,)
+    assert got.nbytes + items.nbytes <= 64 << 20
+    words = got[..., 0].astype(np.uint64) + (got[..., 1].astype(np.uint64) << np.uint64(32))
+    assert all((words[j] == host[i]).all() for j, i in enumerate(idx))

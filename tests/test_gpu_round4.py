@@ -37,7 +37,8 @@ def _bench(extra_env, *flags, timeout=900):
     for v in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(v, None)  # the bench launches its own ranks
     t0 = time.monotonic()
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *flags], cwd=ROOT, env=env, capture_output=True,
+    # --full: the sharded legs, the oracle check and the other records these tests assert on run only with it
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", *flags], cwd=ROOT, env=env, capture_output=True,
                        text=True, timeout=timeout)
     return r, time.monotonic() - t0
 

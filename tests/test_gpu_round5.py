@@ -103,7 +103,7 @@ def test_bench_world1_over_nccl_takes_the_collective_branches():
     barriers around the timed region, the MAX all-reduce of the wall time, the diagonal-sharded linear transform with its
     all-reduce through torch.distributed AND behind the C-ABI -- one JSON line, bits equal serial."""
     env = _clean_env(HEFX_BENCH_FORCE_PG="1", HEFX_BENCH_C_ABI_COMM="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "512",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--batch", "512",
                         "--cpu-seconds", "0", "--lt", "16", "--lt-direct", "0", "--key-per-item", "0", "--variant-keys", "0",
                         "--stream-keys", "0", "--secondary", "C2", "--sustain", "0.3"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=840)
