@@ -482,7 +482,8 @@ struct MacF {
         a1x += ArithF64::mm(x.x, k.k1x, c);
         a1y += ArithF64::mm(x.y, k.k1y, c);
     }
-    // |inner sums| <= L * 0.52q < 2^45 (L <= 61): valid left operands of mm as they are
+    // |inner sums| <= L * 0.52q < 61 * 0.52 * 2^41 < 2^46 (L <= 61; below 2^45 only for L <= 30 at q near 2^41): valid left
+    // operands of mm as they are, whose exactness argument holds up to 2^49 (hefx_ntt.cuh, InvRecentre)
     __device__ __forceinline__ void mac_diag(const MacF &in, const ulonglong2 &dg, const Ctx &c)
     {
         const double dx = ArithF64::from_u64(dg.x), dy = ArithF64::from_u64(dg.y);
@@ -491,8 +492,8 @@ struct MacF {
         a1x += ArithF64::mm(in.a1x, dx, c);
         a1y += ArithF64::mm(in.a1y, dy, c);
     }
-    // Data-prime rows (round 5): the UNFINISHED sums as doubles -- |a| <= L * 0.52 q < 2^45 -- which the mod-down epilogue
-    // subtracts its unfinished transform value from as they are (ArithF64::moddown: |acc - f| < 2^46, a valid left operand of
+    // Data-prime rows (round 5): the UNFINISHED sums as doubles -- |a| <= L * 0.52 q < 2^46 -- which the mod-down epilogue
+    // subtracts its unfinished transform value from as they are (ArithF64::moddown: |acc - f| < 2^47, a valid left operand of
     // the modmul, hefx_ntt.cuh InvRecentre); no canonicalisation here (eight instructions per word) and no u64 -> f64
     // conversion there (two).  The special prime's row stays canonical (result): the inverse transform reads it.
     template <bool LT2Q = false>

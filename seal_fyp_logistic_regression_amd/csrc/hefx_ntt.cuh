@@ -420,7 +420,9 @@ struct ArithF64 {
     __device__ static __forceinline__ u64 moddown(V f, u64 acc, u64 sadd, u64 pt, bool has_pt, const Ctx &c,
                                                   const double2 &pinv)
     {
-        double z = unraw(acc) - f;  // acc: the key MAC's unfinished FP64 sum as a double (MacF::result_data, |acc| < 2^45); exact: |f| < 2^45
+        // acc: the key MAC's unfinished FP64 sum as a double (MacF::result_data, |acc| < 61 * 0.52q < 2^46); |f| < 2^45, so
+        // z is exact and below 2^47: inside the 2^49 up to which mm() stays exact (InvRecentre below)
+        double z = unraw(acc) - f;
         z = mm(z, pinv.x, c) + from_u64(sadd);
         if (has_pt) {  // the product is already in (-0.52q, 0.52q): no re-centring before the sign fix-up
             z = mm(z, from_u64(pt), c);

@@ -32,28 +32,42 @@ def min_primitive_root(two_n, q):
     raise ValueError
 
 
+_VDM = {}
+
+
+def _vandermonde(psi, q, n, inverse):
+    """rows [x_i^k for k < n] with x_i = psi^(2 bitrev(i) + 1) (its inverse for the inverse transform): the definition's
+    matrix, built once per (psi, q, n) with plain big-int products"""
+    key = (psi, q, n, inverse)
+    if key not in _VDM:
+        logn = n.bit_length() - 1
+        rows = []
+        for i in range(n):
+            x = pow(psi, 2 * bitrev(i, logn) + 1, q)
+            if inverse:
+                x = pow(x, -1, q)
+            row, p = [], 1
+            for _ in range(n):
+                row.append(p)
+                p = p * x % q
+            rows.append(row)
+        _VDM[key] = rows
+    return _VDM[key]
+
+
 def ntt_def(a, psi, q):
-    n = len(a)
-    logn = n.bit_length() - 1
-    out = []
-    for i in range(n):
-        x = pow(psi, 2 * bitrev(i, logn) + 1, q)
-        out.append(sum(int(a[k]) * pow(x, k, q) for k in range(n)) % q)
-    return out
+    """out[i] = a(psi^(2 bitrev(i) + 1)) mod q"""
+    a = [int(v) for v in a]
+    return [sum(x * y for x, y in zip(a, row)) % q for row in _vandermonde(psi, q, len(a), False)]
 
 
 def intt_def(A, psi, q):
+    """out[k] = n^-1 sum_i A[i] psi^-(2 bitrev(i) + 1) k mod q"""
     n = len(A)
-    logn = n.bit_length() - 1
     ninv = pow(n, -1, q)
-    out = []
-    for k in range(n):
-        s = 0
-        for i in range(n):
-            x = pow(psi, -(2 * bitrev(i, logn) + 1) * k, q)
-            s += int(A[i]) * x
-        out.append(s * ninv % q)
-    return out
+    A = [int(v) for v in A]
+    M = _vandermonde(psi, q, n, True)
+    return [sum(A[i] * M[i][k] for i in range(n)) * ninv % q for k in range(n)]
 
 
 def galois_table(n, elt):
@@ -114,3 +128,45 @@ def rescale_floor(ct, primes, psis, L):
             rows.append([((int(poly[j][a]) - x[a]) * qinv) % q for a in range(len(d))])
         out.append(rows)
     return out
+
+
+def rescale_round(ct, primes, psis, L):
+    """App. A.9, the rounded division (SEAL >= 3.5 divide_and_round_q_last; csrc/hefx_keyswitch.hip K8):
+    out_j = (c_j - ([c_l + floor(q_l/2)]_(q_l) mod q_j - (floor(q_l/2) mod q_j))) * q_l^-1 mod q_j,
+    i.e. round(c / q_l) in every row.  ct [size][L][n] -> [size][L-1][n]"""
+    last = L - 1
+    ql = primes[last]
+    half = ql >> 1
+    out = []
+    for poly in ct:
+        d = [(v + half) % ql for v in intt_def(poly[last], psis[last], ql)]
+        rows = []
+        for j in range(last):
+            q = primes[j]
+            x = ntt_def([(v - half) % q for v in d], psis[j], q)
+            qinv = pow(ql % q, -1, q)
+            rows.append([((int(poly[j][a]) - x[a]) * qinv) % q for a in range(len(d))])
+        out.append(rows)
+    return out
+
+
+def galois_coef(a, elt, q):
+    """a(X) -> a(X^elt) in Z_q[X]/(X^n + 1), coefficient domain (X^n = -1)"""
+    n = len(a)
+    out = [0] * n
+    for i, v in enumerate(a):
+        e = i * elt % (2 * n)
+        if e < n:
+            out[e] = (out[e] + int(v)) % q
+        else:
+            out[e - n] = (out[e - n] - int(v)) % q
+    return out
+
+
+def apply_galois(ct, elt, key, primes, psis, L):
+    """App. A.7: each NTT row is taken to the coefficient domain, mapped X -> X^elt there and transformed back (no
+    permutation table), then c1's image is key-switched onto c0's.  ct [2][L][n] NTT form."""
+    rot = [[ntt_def(galois_coef(intt_def(ct[c][j], psis[j], primes[j]), elt, primes[j]), psis[j], primes[j])
+            for j in range(L)] for c in range(2)]
+    zero = [[0] * len(rot[0][0]) for _ in range(L)]
+    return switch_key([rot[0], zero], rot[1], key, primes, psis, L)

@@ -474,7 +474,10 @@ def test_primes_at_the_top_of_the_admissible_range_bit_exact(N):
     """The integer NTT policy keeps values in [0,8q) forward / [0,4q) inverse (under-estimated Shoup quotient), which is
     tight against 2^64 for primes just below 2^61 -- the largest hefx_context_create admits (SEAL's own primes stop at
     60 bits).  NTT round trip, key switch (rotation, fused product, relinearisation) and both rescales against the
-    oracle on the four largest such primes, with all-(q-1) inputs as the worst case for every lazy sum."""
+    oracle on the four largest such primes.  All-(q-1) coefficients load the forward transform; in the NTT domain an
+    all-(q-1) ciphertext is the constant polynomial -1, whose digits have one nonzero coefficient each, so the key
+    switch also gets the ciphertext whose COEFFICIENTS are all q-1 (every digit coefficient q_i - 1: the worst input of
+    the forward digit transforms)."""
     from oracle import oracle as O
     from seal_fyp_logistic_regression_amd import Engine
     from seal_fyp_logistic_regression_amd.seal import _is_prime
@@ -496,7 +499,9 @@ def test_primes_at_the_top_of_the_admissible_range_bit_exact(N):
     key = _rand_key(o, 7)
     dkey = e.to_device(key)
     ct_worst = np.stack([worst[:L], worst[:L]])
-    for ct in (o.uniform(L, 2, 11), ct_worst):
+    coef_max = np.stack([o.ntt_fwd(j, worst[j]) for j in range(L)])
+    ct_coef_max = np.stack([coef_max, coef_max])
+    for ct in (o.uniform(L, 2, 11), ct_worst, ct_coef_max):
         pt = o.uniform(L, 1, 12)[0]
         for elt in (3, 2 * N - 1, O.galois_elt_from_step(N, -5)):
             assert (e.apply_galois(L, e.to_device(ct), elt, dkey).download() == o.apply_galois(ct, elt, key)).all()
