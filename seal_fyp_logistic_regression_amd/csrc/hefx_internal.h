@@ -95,8 +95,7 @@ constexpr int KS_RING = 32;  // (a laned linear transform submits ten batches an
 // mod-down epilogue gather them from the source ciphertext (galois_index).
 struct KsScratch {
     u64 *d;    // [chunk][L][N]        digits in coefficient form
-    u64 *x;    // [sub][L][L+1][N]     digit i transformed to modulus slot jj != i (jj==L: special prime); only a
-               //                      SUB-chunk of items at a time, so this largest scratch array stays cache-resident
+    u64 *x;    // [chunk][L][L+1][N]   digit i transformed to modulus slot jj != i (jj==L: special prime)
     u64 *acc;  // [chunk][2][L+1][N]   sum_i x_i * key_i, reduced
     u64 *u;    // [chunk][2][N]        INTT_P(acc_P) + P/2, coefficient form
     u64 *alias;  // [chunk][2][L][N]   copies of the inputs of in-place rotations (c_in == c_out), else unused
@@ -148,8 +147,8 @@ struct KsProf {
 // nsrc > 0: exact hoisting (ks_mac_exact_kernel) -- d_items[n .. n + nsrc) describe the chunk's distinct source
 // ciphertexts; they are decomposed and extended once (scr.d / scr.x hold SOURCE rows), every item runs the gathered MAC
 hipError_t launch_keyswitch_chunk(const DevTables &T, int L, int n, const KsItem *d_items, bool relin,
-                                  const KsScratch &scr, int sub, bool alias, const KsItem *small_items,
-                                  int quarter, hipStream_t s, KsProf *prof, int nsrc = 0);
+                                  const KsScratch &scr, bool alias, const KsItem *small_items, int quarter,
+                                  hipStream_t s, KsProf *prof, int nsrc = 0);
 // tables of exact hoisting: rows[e][m][.] = the flip mask (coefficient order) of the Galois element whose inverse mod 2N is
 // d_ginv[e], once per modulus row m = 0..k-1; the caller transforms the rows
 hipError_t launch_flip_rows(const DevTables &T, const uint32_t *d_ginv, int count, u64 *rows, hipStream_t s);

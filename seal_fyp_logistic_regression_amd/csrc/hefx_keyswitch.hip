@@ -30,15 +30,10 @@
 //   N = 16384: inverse digits 138 vs 107 -> 2;  digit NTTs 455 vs 489, mod-down finish 318 vs 436 -> 4 (one
 //              512-thread workgroup per CU cannot overlap its memory phases with another's butterflies)
 //   N = 32768: 1024-thread workgroups own the whole register file at 128 VGPRs either way.
-// -DHEFX_WAVES=n overrides every kernel (tools/build_variant.sh).
 template <int LOGN>
 struct KsWaves {
-#ifdef HEFX_WAVES
-    static constexpr int INV = HEFX_WAVES, FWD = HEFX_WAVES;
-#else
     static constexpr int INV = LOGN <= 14 ? 2 : 4;  // ks_intt_digits, ks_moddown_intt, rs_intt
     static constexpr int FWD = LOGN <= 13 ? 2 : 4;  // ks_ntt_digits, ks_moddown_finish, rs_finish
-#endif
     // load batches of the first (split) stage: all sixteen coefficient pairs are fetched at once in the 256-VGPR
     // builds of N <= 8192 (a few percent there; at N = 16384 the inverse kernels lose 5-15 % with one batch)
     // (N = 8192 forward: two batches since round 3 -- with the lane-contiguous loader (eo_lane) one batch took the
@@ -114,12 +109,8 @@ __device__ static __forceinline__ uint32_t eo_nat(int t, int r)
 //                  folded sum < 4 L q^2 = 12 q^2 < q 2^64
 __device__ __forceinline__ int mac_x_slack(const ModConst &mc, const ModConstF &mf, int L)
 {
-#ifdef HEFX_NO_LT2Q  // A/B knob (tools/build_variant.sh): canonical operands always
-    return 0;
-#else
     if (mf.q != 0.0 || (mc.q >> 60) != 0) return 0;
     return L <= 3 ? 2 : (L <= 5 ? 1 : 0);
-#endif
 }
 
 // The coefficient column a thread of a forward split workgroup loads (ntt_fwd_core's t0): the first half of the workgroup
@@ -134,11 +125,7 @@ __device__ static __forceinline__ int eo_lane(int t)
 }
 // From N = 8192 on (C3 +2.7 %, C5 +3.3 %: profiles/r03/ab_eo_lane.txt; C2 +2.5 % together with two load batches, see
 // KsWaves: ab_c2_eo_lane.txt).  The smaller rings keep column t.
-#ifdef HEFX_NO_EO_LANE  // A/B knob (tools/build_variant.sh): column t everywhere
-#define HEFX_EO_LANE(SC, t) (t)
-#else
 #define HEFX_EO_LANE(SC, t) (SC::N >= 8192 ? eo_lane<SC>(t) : (t))
-#endif
 
 // ------------------------------------------------------------------------------------------------
 // Galois-gathered reads.  The rotated inputs perm_g(c0), perm_g(c1) are never written out: their three readers --
@@ -254,8 +241,8 @@ __global__ __launch_bounds__(SplitCfg<LOGN>::T, KsWaves<LOGN>::INV) void ks_intt
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool slot_is_f64(const DevTables &T, int L, int jj);
 template <int LOGN>
-__device__ __forceinline__ void ntt_digit_row(const DevTables &T, int L, int rows, int item0, int stream_x,
-                                              const KsScratch &S, u64 *lds)
+__device__ __forceinline__ void ntt_digit_row(const DevTables &T, int L, int rows, int stream_x, const KsScratch &S,
+                                              u64 *lds)
 {
     using SC = SplitCfg<LOGN>;
     using C = typename SC::C;
@@ -290,8 +277,7 @@ __device__ __forceinline__ void ntt_digit_row(const DevTables &T, int L, int row
         group_decode(blockIdx.x, L, g, jj, h);  // g = digit (b, i); jj = one of its L target moduli
     if (g >= rows || (S.gate_mode == 2 && ks_gated_out(S))) return;  // (mode 1 gates only the launch that writes outputs)
     const int t = threadIdx.x;
-    const int bl = g / L, i = g % L;  // bl: item index inside the sub-chunk
-    const int b = item0 + bl;
+    const int b = g / L, i = g % L;
     if (jj >= i) ++jj;  // skip the diagonal; jj == L is the special prime
     const int m = jj < L ? jj : T.k - 1;
     const ModConst mc = T.mods[m];
@@ -311,7 +297,7 @@ __device__ __forceinline__ void ntt_digit_row(const DevTables &T, int L, int row
     const ModConstF mf = T.modsf[m];
     split_fwd<LOGN, KsWaves<LOGN>::NB_FWD, true>(v, ld, mode, lds, ntt_tables(T, m), mc, mf, t, h, tl,
                                                  mac_x_slack(mc, mf, L));
-    u64 *__restrict__ xd = S.x + (((size_t)bl * L + i) * (L + 1) + jj) * SC::N + (size_t)h * SC::H;
+    u64 *__restrict__ xd = S.x + (((size_t)b * L + i) * (L + 1) + jj) * SC::N + (size_t)h * SC::H;
     // stream_x: the chunk's digit x modulus products exceed the Infinity Cache, so they are written (here) and read
     // (MAC) with streaming accesses that leave the caches to the rows that are reused -- digits, twiddles, key
     if (stream_x & 1) {
@@ -515,17 +501,6 @@ __device__ __forceinline__ bool slot_is_f64(const DevTables &T, int L, int jj)
 {
     return T.modsf[jj < L ? jj : T.k - 1].q != 0.0;
 }
-// the y-th integer-policy target slot among 0..L (block-uniform scalar loop)
-__device__ __forceinline__ int nth_int_slot(const DevTables &T, int L, int y)
-{
-    int jj = 0;
-    for (;; ++jj) {
-        if (slot_is_f64(T, L, jj)) continue;
-        if (y == 0) break;
-        --y;
-    }
-    return jj;
-}
 
 // policy of target modulus m in a key switch over L digits (block-uniform); f(policy tag) runs the templated body
 template <class F>
@@ -622,39 +597,30 @@ __device__ __forceinline__ void mac_items(const DevTables &T, const u64 *key, in
 #pragma unroll
     for (int e = 0; e < NI; ++e) {
         ulonglong2 r0, r1;
-        if (jj < L) {  // a data prime's row: what the mod-down epilogue reads (result_data)
-#ifdef HEFX_NO_LT2Q
-            A[e].result_data(r0, r1, cx);
-#else
+        if (jj < L)  // a data prime's row: what the mod-down epilogue reads (result_data)
             A[e].template result_data<true>(r0, r1, cx);
-#endif
-        } else {  // the special prime's row: the inverse transform's input
-#ifdef HEFX_NO_LT2Q
-            A[e].result(r0, r1, cx);
-#else
+        else  // the special prime's row: the inverse transform's input
             A[e].template result<true>(r0, r1, cx);
-#endif
-        }
         mac_store<STREAM>(acc0[e], acc1[e], w, r0, r1);
     }
 }
 
-// one MAC unit: target slot jj, the item pair (bl0, bl0 + 1) of the (sub-)chunk, pair index w of the row
+// one MAC unit: target slot jj, the item pair (bl0, bl0 + 1) of the chunk, pair index w of the row
 template <bool STREAM>
-__device__ __forceinline__ void mac_unit(const DevTables &T, const KsItem *__restrict__ items, int L, int relin, int item0,
-                                         int count, const KsScratch &S, int jj, int bl0, size_t w)
+__device__ __forceinline__ void mac_unit(const DevTables &T, const KsItem *__restrict__ items, int L, int relin, int count,
+                                         const KsScratch &S, int jj, int bl0, size_t w)
 {
     const size_t n = (size_t)1 << T.logn;
     const int m = jj < L ? jj : T.k - 1;
     const bool two = bl0 + 1 < count;
     // both descriptors once, up front (the second one of an odd tail repeats the first: loads stay unconditional)
-    const KsItem it0 = items[item0 + bl0], it1 = items[item0 + bl0 + (two ? 1 : 0)];
+    const KsItem it0 = items[bl0], it1 = items[bl0 + (two ? 1 : 0)];
     const int ownrow = jj < L ? jj : 0;  // jj == L has no own-prime term; the pointer is then unused
     const u64 *const own[2] = {it0.c_in + ((size_t)(relin ? 2 * L : L) + ownrow) * n,
                                it1.c_in + ((size_t)(relin ? 2 * L : L) + ownrow) * n};
     const uint32_t own_elt[2] = {relin ? 1u : item_elt(it0), relin ? 1u : item_elt(it1)};
     auto xrow2 = [&](int e, int i) { return S.x + (((size_t)(bl0 + e) * L + i) * (L + 1) + jj) * n; };
-    auto accrow = [&](int bl, int c) { return S.acc + (((size_t)(item0 + bl) * 2 + c) * (L + 1) + jj) * n; };
+    auto accrow = [&](int bl, int c) { return S.acc + (((size_t)bl * 2 + c) * (L + 1) + jj) * n; };
     u64 *const acc0[2] = {accrow(bl0, 0), accrow(bl0 + 1, 0)}, *const acc1[2] = {accrow(bl0, 1), accrow(bl0 + 1, 1)};
     mac_dispatch(T, m, L, [&](auto pol) {
         using P = decltype(pol);
@@ -673,16 +639,15 @@ __device__ __forceinline__ void mac_unit(const DevTables &T, const KsItem *__res
 
 template <bool STREAM>
 __global__ __launch_bounds__(256) void ks_mac_kernel(DevTables T, const KsItem *__restrict__ items, int L, int relin,
-                                                     int item0, int count, int int_only, KsScratch S)
+                                                     int count, KsScratch S)
 {
-    // int_only: the FP64-policy target slots were accumulated by ks_ntt_macf_kernel; blockIdx.y counts the others
     if (S.gate_mode == 2 && ks_gated_out(S)) return;
-    const int jj = int_only ? nth_int_slot(T, L, blockIdx.y) : (int)blockIdx.y;
+    const int jj = blockIdx.y;
 #ifdef HEFX_STAMP
     const int wg = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
     if (threadIdx.x == 0 && wg < 1024) hefx_stamp_buf[((size_t)2 * 1024 + wg) * 16] = wall_clock64();
 #endif
-    mac_unit<STREAM>(T, items, L, relin, item0, count, S, jj, 2 * blockIdx.z, (size_t)blockIdx.x * blockDim.x + threadIdx.x);
+    mac_unit<STREAM>(T, items, L, relin, count, S, jj, 2 * blockIdx.z, (size_t)blockIdx.x * blockDim.x + threadIdx.x);
 #ifdef HEFX_STAMP
     if (HEFX_STAMP > 1) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     if (threadIdx.x == 0 && wg < 1024) hefx_stamp_buf[((size_t)2 * 1024 + wg) * 16 + 15] = wall_clock64();
@@ -692,12 +657,12 @@ __global__ __launch_bounds__(256) void ks_mac_kernel(DevTables T, const KsItem *
 // (2) as a launch
 template <int LOGN>
 __global__ __launch_bounds__(SplitCfg<LOGN>::T, KsWaves<LOGN>::FWD) void ks_ntt_digits_kernel(DevTables T, int L, int rows,
-                                                                             int item0, int stream_x, KsScratch S)
+                                                                             int stream_x, KsScratch S)
 {
     extern __shared__ __align__(16) u64 lds[];
     HEFX_STAMP_KERNEL(1);
     HEFX_STAMP_AT(0);
-    ntt_digit_row<LOGN>(T, L, rows, item0, stream_x, S, lds);
+    ntt_digit_row<LOGN>(T, L, rows, stream_x, S, lds);
     HEFX_STAMP_AT(15);
 }
 
@@ -901,157 +866,6 @@ __global__ __launch_bounds__(256) void lt2_c0_kernel(DevTables T, const KsItem *
     }
     reinterpret_cast<ulonglong2 *>(partial + ((size_t)ch * L + j) * n)[w] =
         make_ulonglong2(barrett128(xl, xh, mc), barrett128(yl, yh, mc));
-}
-
-// ------------------------------------------------------------------------------------------------
-// (2+3 fused, hybrid) -- the digit x modulus products of the FP64-policy target moduli are never stored.
-// One launch, two kinds of workgroup (N/16 threads, eight coefficients per thread, hefx_ntt8.cuh):
-//   role F  (item b, FP64 target slot jj, half h): walks the L digits, transforms each one to modulus m in the FP64
-//           policy and multiplies the UNFINISHED transform value straight into two FP64 accumulators per coefficient
-//           (MacF arithmetic: the exact six-instruction modmul, |term| < 0.52 q, the L terms add exactly) that live in
-//           registers for the whole loop -- 32 VGPRs, where the 128-bit accumulators of a 60-bit target need 64 and
-//           spilled (round 2).  acc[b][c][jj] = canon(sum_i NTT_m([d_i]_m) * key[i][c][m]), the same integer sum as
-//           ks_ntt_digits + ks_mac, hence the same bits.
-//   role I  (item b, digit i, integer-policy target slot jj != i, half h): the plain digit transform, canonical words
-//           to scratch x -- only these rows still travel (9 of 25 at C3); ks_mac_kernel then runs over the integer
-//           target slots alone (int_only).
-// All workgroups of an item share an XCD (the L digit rows they read are then served by that XCD's L2); the long
-// role-F workgroups of an item come first.  x traffic per op at C3: 25 rows written + 25 read -> 9 + 9.
-// ------------------------------------------------------------------------------------------------
-template <int LOGN>
-struct FusedCfg {
-    using C = Ntt8Cfg<LOGN - 1>;
-    static constexpr int N = 1 << LOGN;
-    static constexpr int H = N / 2;
-    static constexpr int T = C::T;  // N/16 threads
-    static constexpr size_t LDS_BYTES = sizeof(u64) * C::LDS_WORDS;
-};
-template <int LOGN>
-__global__ __launch_bounds__(FusedCfg<LOGN>::T, 4) void ks_ntt_macf_kernel(DevTables T, const KsItem *__restrict__ items, int L,
-                                                                         int relin, int groups, int nf, int per_item,
-                                                                         int stream_x, KsScratch S)
-{
-    using FC = FusedCfg<LOGN>;
-    using C = typename FC::C;
-    extern __shared__ __align__(16) u64 lds[];
-    const int xq = blockIdx.x & 7, rest = blockIdx.x >> 3;
-    const int slot = rest % per_item, b = (rest / per_item) * 8 + xq;
-    if (b >= groups) return;
-    const int t = threadIdx.x;
-    const int h = slot & 1, role = slot >> 1;
-    const size_t off = (size_t)h * FC::H;
-    static_assert(C::T % 2 == 0, "EO loader assumes an even thread count");
-    // coefficient j = idx_nat(t, r) = t + T r of a row stored [evens | odds]: parity is the thread's
-    const uint32_t e0 = (uint32_t)((t & 1) * FC::H + (t >> 1));
-    if (role < nf) {
-        // ---- role F ----
-        int jj = 0;
-        for (int cnt = 0;; ++jj) {
-            if (!slot_is_f64(T, L, jj)) continue;
-            if (cnt == role) break;
-            ++cnt;
-        }
-        const int m = jj < L ? jj : T.k - 1;
-        const ModConst mc = T.mods[m];
-        const ArithF64::Ctx cx = ArithF64::make(T.modsf[m]);
-        const double *__restrict__ tw = T.twf + ((size_t)m << LOGN);
-        const KsItem it = items[b];
-        double a0[8], a1[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) a0[r] = a1[r] = 0.0;
-        for (int i = 0; i < L; ++i) {
-            double f[8];
-            if (i == jj) {  // the digit in NTT form modulo its own prime: the (rotated) input row itself
-                const u64 *__restrict__ xr = it.c_in + ((size_t)(relin ? 2 * L : L) + i) * FC::N;
-                const uint32_t elt = relin ? 1u : item_elt(it);
-#pragma unroll
-                for (int r = 0; r < 8; r += 2) {
-                    const uint32_t rec = (uint32_t)((off + C::idx_out(t, r)) >> 1);
-                    const ulonglong2 v = gather_pair(xr, rec, elt, LOGN);
-                    f[r] = ArithF64::from_u64(v.x);
-                    f[r + 1] = ArithF64::from_u64(v.y);
-                }
-            } else {
-                const u64 *__restrict__ dd = S.d + ((size_t)b * L + i) * FC::N;
-                const InMode mode = {false, T.modsf[i].q == 0.0, false, 0};
-                auto ld = [&](int r, u64 &x, u64 &y) {
-                    const uint32_t e = e0 + (uint32_t)(C::T / 2) * (uint32_t)r;
-                    x = dd[e];
-                    y = dd[e + FC::H / 2];
-                };
-                split8_fwd_raw<LOGN, ArithF64>(f, ld, mode, mc, lds, tw, cx, t, h);
-            }
-            const u64 *__restrict__ k0 = it.key + ((size_t)i * 2 * T.k + m) * FC::N + off;
-            const u64 *__restrict__ k1 = k0 + (size_t)T.k * FC::N;
-            HEFX_STAGE_FENCE();  // keeps the key loads (32 VGPRs) from being hoisted above the transform
-            ulonglong2 kv0[4], kv1[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                kv0[r] = gld16(k0 + C::idx_out(t, 2 * r));
-                kv1[r] = gld16(k1 + C::idx_out(t, 2 * r));
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                a0[2 * r] += ArithF64::mm(f[2 * r], ArithF64::from_u64(kv0[r].x), cx);
-                a0[2 * r + 1] += ArithF64::mm(f[2 * r + 1], ArithF64::from_u64(kv0[r].y), cx);
-                a1[2 * r] += ArithF64::mm(f[2 * r], ArithF64::from_u64(kv1[r].x), cx);
-                a1[2 * r + 1] += ArithF64::mm(f[2 * r + 1], ArithF64::from_u64(kv1[r].y), cx);
-            }
-            // the next digit's first exchange reuses the LDS words this transform's last pass read
-            if (i != jj) __syncthreads();
-        }
-        u64 *__restrict__ o0 = S.acc + (((size_t)b * 2 + 0) * (L + 1) + jj) * FC::N + off;
-        u64 *__restrict__ o1 = S.acc + (((size_t)b * 2 + 1) * (L + 1) + jj) * FC::N + off;
-#pragma unroll
-        for (int r = 0; r < 8; r += 2) {
-            // (data primes: unfinished doubles, MacF::result_data; the special prime: canonical)
-            *reinterpret_cast<ulonglong2 *>(o0 + C::idx_out(t, r)) =
-                jj < L ? make_ulonglong2(ArithF64::raw(a0[r]), ArithF64::raw(a0[r + 1]))
-                       : make_ulonglong2(ArithF64::canon(a0[r], cx), ArithF64::canon(a0[r + 1], cx));
-            *reinterpret_cast<ulonglong2 *>(o1 + C::idx_out(t, r)) =
-                jj < L ? make_ulonglong2(ArithF64::raw(a1[r]), ArithF64::raw(a1[r + 1]))
-                       : make_ulonglong2(ArithF64::canon(a1[r], cx), ArithF64::canon(a1[r + 1], cx));
-        }
-        return;
-    }
-    // ---- role I ----
-    int rr = role - nf, jj = 0;
-    for (;; ++jj) {
-        if (slot_is_f64(T, L, jj)) continue;
-        const int nd = jj < L ? L - 1 : L;  // digits that are transformed to this slot
-        if (rr < nd) break;
-        rr -= nd;
-    }
-    int i = rr;
-    if (jj < L && i >= jj) ++i;
-    const int m = jj < L ? jj : T.k - 1;
-    const ModConst mc = T.mods[m];
-    const u64 *__restrict__ dd = S.d + ((size_t)b * L + i) * FC::N;
-    const InMode mode = {T.mods[i].q > mc.q, false, false, 0};
-    auto ld = [&](int r, u64 &x, u64 &y) {
-        const uint32_t e = e0 + (uint32_t)(C::T / 2) * (uint32_t)r;
-        x = dd[e];
-        y = dd[e + FC::H / 2];
-    };
-    u64 v[8];
-    fwd_int_dispatch(mc, [&](auto pol) {
-        using A = decltype(pol);
-        const typename A::Ctx cx = A::make(mc);
-        split8_fwd_raw<LOGN, A>(v, ld, mode, mc, lds, T.tw + ((size_t)m << LOGN), cx, t, h);
-#pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] = A::fwd_finish(v[r], cx);
-    });
-    u64 *__restrict__ xd = S.x + (((size_t)b * L + i) * (L + 1) + jj) * FC::N + off;
-#pragma unroll
-    for (int r = 0; r < 8; r += 2) {
-        const u64 w0 = v[r], w1 = v[r + 1];
-        u64 *p = xd + C::idx_out(t, r);
-        if (stream_x) {
-            nt_store16(p, w0, w1);
-        } else {
-            *reinterpret_cast<ulonglong2 *>(p) = make_ulonglong2(w0, w1);
-        }
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1681,21 +1495,11 @@ __device__ __forceinline__ void pair_mac_body(const DevTables &T, const KsItem &
     }
     ulonglong2 ra, rb, dead_a, dead_b;  // (slot 0 of each accumulator set; slot 1 is dead)
     if (jj < L) {
-#ifdef HEFX_NO_LT2Q
-        A0.result_data(ra, dead_a, cx);
-        A1.result_data(rb, dead_b, cx);
-#else
         A0.template result_data<true>(ra, dead_a, cx);
         A1.template result_data<true>(rb, dead_b, cx);
-#endif
     } else {
-#ifdef HEFX_NO_LT2Q
-        A0.result(ra, dead_a, cx);
-        A1.result(rb, dead_b, cx);
-#else
         A0.template result<true>(ra, dead_a, cx);
         A1.template result<true>(rb, dead_b, cx);
-#endif
     }
     if (jj < L) {
         u64 *a = S.acc + (((size_t)b * 2 + c) * (L + 1) + jj) * N + 4 * (size_t)g;
@@ -1892,26 +1696,18 @@ static void set_lds(K kernel, size_t bytes)
 
 template <int LOGN>
 static hipError_t launch_keyswitch_chunk_t(const DevTables &T, int L, int n, const KsItem *batch, bool relin,
-                                           const KsScratch &scr, int sub, bool alias,
-                                           const KsSmallItems *small, int quarter, hipStream_t s, KsProf *prof, int nsrc)
+                                           const KsScratch &scr, bool alias, const KsSmallItems *small, int quarter,
+                                           hipStream_t s, KsProf *prof, int nsrc)
 {
     using SC = SplitCfg<LOGN>;
     const size_t lds = SC::LDS_BYTES;
-    // experiment knobs: a larger LDS request as an occupancy cap per kernel (bytes; workgroups per CU = 160 KiB / request)
-    auto lds_knob = [lds](const char *name) {
-        const char *e = getenv(name);
-        const size_t v = e ? (size_t)atol(e) : 0;
-        return v > lds ? v : lds;
-    };
-    static const size_t lds_fin = lds_knob("HEFX_FIN_LDS"), lds_ntt = lds_knob("HEFX_NTT_LDS"),
-                        lds_intt = lds_knob("HEFX_INTT_LDS"), lds_mdi = lds_knob("HEFX_MDI_LDS");
     static PerDeviceOnce attr_once;
     if (attr_once.first()) {
-        set_lds(ks_intt_digits_kernel<LOGN>, lds_intt);
+        set_lds(ks_intt_digits_kernel<LOGN>, lds);
         set_lds(ks_intt_digits_small_kernel<LOGN>, lds);
-        set_lds(ks_ntt_digits_kernel<LOGN>, lds_ntt);
-        set_lds(ks_moddown_intt_kernel<LOGN>, lds_mdi);
-        set_lds(ks_moddown_finish_kernel<LOGN>, lds_fin);
+        set_lds(ks_ntt_digits_kernel<LOGN>, lds);
+        set_lds(ks_moddown_intt_kernel<LOGN>, lds);
+        set_lds(ks_moddown_finish_kernel<LOGN>, lds);
         if (getenv("HEFX_DEBUG")) {
             int nb = -1;
             (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ks_ntt_digits_kernel<LOGN>, SC::T, lds);
@@ -1932,37 +1728,36 @@ static hipError_t launch_keyswitch_chunk_t(const DevTables &T, int L, int n, con
         hs.gate_mode = 1;
         fb.gate_mode = 2;
         mark(1);
-        hipLaunchKernelGGL((ks_intt_digits_kernel<LOGN>), dim3(split_grid(nsrc * L)), dim3(SC::T), lds_intt, s, T, batch + n, L,
+        hipLaunchKernelGGL((ks_intt_digits_kernel<LOGN>), dim3(split_grid(nsrc * L)), dim3(SC::T), lds, s, T, batch + n, L,
                            0, 1, nsrc * L, hs);
         mark(2);
-        hipLaunchKernelGGL((ks_ntt_digits_kernel<LOGN>), dim3(group_grid(nsrc * L, L)), dim3(SC::T), lds_ntt, s, T, L, nsrc * L,
-                           0, 0, hs);
+        hipLaunchKernelGGL((ks_ntt_digits_kernel<LOGN>), dim3(group_grid(nsrc * L, L)), dim3(SC::T), lds, s, T, L, nsrc * L, 0,
+                           hs);
         mark(3);
         hipLaunchKernelGGL(ks_mac_exact_kernel, dim3(SC::N / 2 / 256, L + 1, n), dim3(256), 0, s, T, batch, L, hs);
         mark(4);
-        hipLaunchKernelGGL((ks_moddown_intt_kernel<LOGN>), dim3(split_grid(n * 2)), dim3(SC::T), lds_mdi, s, T, L, n * 2, hs);
+        hipLaunchKernelGGL((ks_moddown_intt_kernel<LOGN>), dim3(split_grid(n * 2)), dim3(SC::T), lds, s, T, L, n * 2, hs);
         mark(5);
-        hipLaunchKernelGGL((ks_moddown_finish_kernel<LOGN>), dim3(group_grid(n * 2, L)), dim3(SC::T), lds_fin, s, T, batch, L,
+        hipLaunchKernelGGL((ks_moddown_finish_kernel<LOGN>), dim3(group_grid(n * 2, L)), dim3(SC::T), lds, s, T, batch, L,
                            0, n * 2, hs);
         // the fallback: the ordinary five launches, which exit at once unless a source of this chunk held a zero coefficient
         mark(7);
-        hipLaunchKernelGGL((ks_intt_digits_kernel<LOGN>), dim3(split_grid(n * L)), dim3(SC::T), lds_intt, s, T, batch, L, 0, 0,
+        hipLaunchKernelGGL((ks_intt_digits_kernel<LOGN>), dim3(split_grid(n * L)), dim3(SC::T), lds, s, T, batch, L, 0, 0,
                            n * L, fb);
-        hipLaunchKernelGGL((ks_ntt_digits_kernel<LOGN>), dim3(group_grid(n * L, L)), dim3(SC::T), lds_ntt, s, T, L, n * L, 0, 0,
+        hipLaunchKernelGGL((ks_ntt_digits_kernel<LOGN>), dim3(group_grid(n * L, L)), dim3(SC::T), lds, s, T, L, n * L, 0, fb);
+        hipLaunchKernelGGL(ks_mac_kernel<false>, dim3(SC::N / 2 / 256, L + 1, (n + 1) / 2), dim3(256), 0, s, T, batch, L, 0, n,
                            fb);
-        hipLaunchKernelGGL(ks_mac_kernel<false>, dim3(SC::N / 2 / 256, L + 1, (n + 1) / 2), dim3(256), 0, s, T, batch, L, 0, 0, n,
-                           0, fb);
-        hipLaunchKernelGGL((ks_moddown_intt_kernel<LOGN>), dim3(split_grid(n * 2)), dim3(SC::T), lds_mdi, s, T, L, n * 2, fb);
-        hipLaunchKernelGGL((ks_moddown_finish_kernel<LOGN>), dim3(group_grid(n * 2, L)), dim3(SC::T), lds_fin, s, T, batch, L,
+        hipLaunchKernelGGL((ks_moddown_intt_kernel<LOGN>), dim3(split_grid(n * 2)), dim3(SC::T), lds, s, T, L, n * 2, fb);
+        hipLaunchKernelGGL((ks_moddown_finish_kernel<LOGN>), dim3(group_grid(n * 2, L)), dim3(SC::T), lds, s, T, batch, L,
                            0, n * 2, fb);
         mark(-1);
         return hipGetLastError();
     }
-    // quarter rows: a small chunk that cannot fill the chip with split-2 workgroups (unfused, no aliasing / hoisting).
+    // quarter rows: a small chunk that cannot fill the chip with split-2 workgroups (no aliasing / hoisting).
     // `quarter` is a mask over the four transform launches (KS_Q_*): the scratch arrays have one layout, so each launch
     // picks its own workgroup shape -- ks_run gives quarter rows to the launches whose quarter grid still fits the chip in
     // one round (at n = 8, L = 5: the two inverse launches and not the 200 digit transforms).
-    if (small && (quarter & KS_Q_PAIR) && sub >= n) {  // the pair path: four launches, two transform phases (ks_pair_*)
+    if (small && (quarter & KS_Q_PAIR)) {  // the pair path: four launches, two transform phases (ks_pair_*)
         static PerDeviceOnce attrp;
         const size_t ldsq = QuarterCfg<LOGN>::LDS_BYTES;
         if (attrp.first()) {
@@ -1985,14 +1780,12 @@ static hipError_t launch_keyswitch_chunk_t(const DevTables &T, int L, int n, con
         mark(-1);
         return hipGetLastError();
     }
-    // heavy-first dispatch order of the digit transforms (ntt_digit_row) while the launch is a few resident waves:
-    // HEFX_HEAVY_FIRST=0 switches it off, HEFX_HEAVY_MAX=<workgroups> moves the bound.  Measured at L = 5 (C4 ring,
-    // profiles/r06/heavy_first_ab.txt): n = 8 80.3 -> 77.6 us, n = 12 90.9 -> 90.4, n = 16 even, n = 24 / 32 +1.5 / +2 us (several
-    // rounds of workgroups: the grouped order's L2 locality wins again) -- hence up to ~2.5 workgroups per CU
-    static const bool heavy_on = !(getenv("HEFX_HEAVY_FIRST") && atoi(getenv("HEFX_HEAVY_FIRST")) == 0);
-    static const int heavy_max = getenv("HEFX_HEAVY_MAX") ? atoi(getenv("HEFX_HEAVY_MAX")) : 640;
-    auto heavy_order = [&](int m) { return heavy_on && m * L * L * 2 <= heavy_max ? 2 : 0; };
-    if (small && (quarter & KS_Q_ALL) && sub >= n) {
+    // heavy-first dispatch order of the digit transforms (ntt_digit_row) while the launch is a few resident waves, up to
+    // 640 workgroups.  Measured at L = 5 (C4 ring, profiles/r06/heavy_first_ab.txt): n = 8 80.3 -> 77.6 us, n = 12 90.9 ->
+    // 90.4, n = 16 even, n = 24 / 32 +1.5 / +2 us (several rounds of workgroups: the grouped order's L2 locality wins again)
+    // -- hence up to ~2.5 workgroups per CU
+    const int heavy_order = n * L * L * 2 <= 640 ? 2 : 0;
+    if (small && (quarter & KS_Q_ALL)) {
         static PerDeviceOnce attrq;
         const size_t ldsq = QuarterCfg<LOGN>::LDS_BYTES;
         if (attrq.first()) {
@@ -2014,32 +1807,28 @@ static hipError_t launch_keyswitch_chunk_t(const DevTables &T, int L, int n, con
             hipLaunchKernelGGL((ks_ntt_digits_q_kernel<LOGN>), fan_grid(n * L, 4 * L), dim3(TQ), ldsq, s, T, L,
                                n * L, scr);
         else
-            hipLaunchKernelGGL((ks_ntt_digits_kernel<LOGN>), dim3(group_grid(n * L, L)), dim3(SC::T), lds_ntt, s, T, L,
-                               n * L, 0, heavy_order(n), scr);
+            hipLaunchKernelGGL((ks_ntt_digits_kernel<LOGN>), dim3(group_grid(n * L, L)), dim3(SC::T), lds, s, T, L,
+                               n * L, heavy_order, scr);
         mark(3);
-        hipLaunchKernelGGL(ks_mac_kernel<false>, dim3(SC::N / 2 / 256, L + 1, (n + 1) / 2), dim3(256), 0, s, T, batch, L, rl, 0,
-                           n, 0, scr);
+        hipLaunchKernelGGL(ks_mac_kernel<false>, dim3(SC::N / 2 / 256, L + 1, (n + 1) / 2), dim3(256), 0, s, T, batch, L, rl, n,
+                           scr);
         mark(4);
         if (quarter & KS_Q_MDI)
             hipLaunchKernelGGL((ks_moddown_intt_q_kernel<LOGN>), dim3(quarter_grid(n * 2)), dim3(TQ), ldsq, s, T, L, n * 2,
                                scr);
         else
-            hipLaunchKernelGGL((ks_moddown_intt_kernel<LOGN>), dim3(split_grid(n * 2)), dim3(SC::T), lds_mdi, s, T, L, n * 2,
+            hipLaunchKernelGGL((ks_moddown_intt_kernel<LOGN>), dim3(split_grid(n * 2)), dim3(SC::T), lds, s, T, L, n * 2,
                                scr);
         mark(5);
         if (quarter & KS_Q_FIN)
             hipLaunchKernelGGL((ks_moddown_finish_q_kernel<LOGN>), fan_grid(n * 2, 4 * L), dim3(TQ), ldsq, s, T,
                                batch, L, rl, n * 2, scr);
         else
-            hipLaunchKernelGGL((ks_moddown_finish_kernel<LOGN>), dim3(group_grid(n * 2, L)), dim3(SC::T), lds_fin, s, T,
+            hipLaunchKernelGGL((ks_moddown_finish_kernel<LOGN>), dim3(group_grid(n * 2, L)), dim3(SC::T), lds, s, T,
                                batch, L, rl, n * 2, scr);
         mark(-1);
         return hipGetLastError();
     }
-    static const int force_stream_x = getenv("HEFX_STREAM_X") ? atoi(getenv("HEFX_STREAM_X")) : -1;
-    auto stream_x_of = [&](int m) {  // x of m items against the 256 MB Infinity Cache: beyond it, stream x
-        return force_stream_x >= 0 ? force_stream_x : ((size_t)m * L * (L + 1) * SC::N * 8 > ((size_t)256 << 20) ? 1 : 0);
-    };
     if (alias) {  // in-place rotations: their inputs move to scratch first (see ks_alias_copy_kernel)
         mark(0);
         hipLaunchKernelGGL(ks_alias_copy_kernel, dim3(SC::N / 2 / 256, 2 * L, n), dim3(256), 0, s, T, batch, L);
@@ -2049,55 +1838,24 @@ static hipError_t launch_keyswitch_chunk_t(const DevTables &T, int L, int n, con
         hipLaunchKernelGGL((ks_intt_digits_small_kernel<LOGN>), dim3(split_grid(n * L)), dim3(SC::T), lds, s, T, *small,
                            const_cast<KsItem *>(batch), n, L, rl, n * L, scr);
     else
-        hipLaunchKernelGGL((ks_intt_digits_kernel<LOGN>), dim3(split_grid(n * L)), dim3(SC::T), lds_intt, s, T, batch, L, rl, 0,
+        hipLaunchKernelGGL((ks_intt_digits_kernel<LOGN>), dim3(split_grid(n * L)), dim3(SC::T), lds, s, T, batch, L, rl, 0,
                            n * L, scr);
-    if (sub < 0) {  // hybrid fused digit-NTT + MAC (LOGN <= 14): only the integer-policy targets' products travel
-        if constexpr (LOGN <= 14) {
-            static PerDeviceOnce fattr;
-            if (fattr.first()) set_lds(ks_ntt_macf_kernel<LOGN>, FusedCfg<LOGN>::LDS_BYTES);
-            // sub = -1 - (nf | special_int << 8), from ks_run: nf = FP64-policy target slots among 0..L at this level,
-            // special_int = the special prime is an integer-policy slot
-            const int code = -sub - 1, nf = code & 0xff;
-            const bool special_int = (code >> 8) & 1;
-            const int nint = L + 1 - nf;  // integer-policy target slots
-            // digits transformed to an integer slot: L - 1 for a data prime, L for the special prime
-            const int pairs = special_int ? (nint - 1) * (L - 1) + L : nint * (L - 1);
-            const int per_item = 2 * (nf + pairs);
-            const int stream_x = (size_t)n * pairs * SC::N * 8 > ((size_t)256 << 20) ? 1 : 0;
-            mark(6);
-            hipLaunchKernelGGL((ks_ntt_macf_kernel<LOGN>), dim3(((n + 7) / 8) * 8 * per_item), dim3(FusedCfg<LOGN>::T),
-                               FusedCfg<LOGN>::LDS_BYTES, s, T, batch, L, rl, n, nf, per_item, stream_x, scr);
-            if (nint > 0) {
-                mark(3);
-                if (stream_x)
-                    hipLaunchKernelGGL(ks_mac_kernel<true>, dim3(SC::N / 2 / 256, nint, (n + 1) / 2), dim3(256), 0, s, T, batch,
-                                       L, rl, 0, n, 1, scr);
-                else
-                    hipLaunchKernelGGL(ks_mac_kernel<false>, dim3(SC::N / 2 / 256, nint, (n + 1) / 2), dim3(256), 0, s, T, batch,
-                                       L, rl, 0, n, 1, scr);
-            }
-        }
-    } else
-    // digit x modulus products only ever exist for `sub` items: K2 writes them, the MAC consumes them right away
-    for (int item0 = 0; item0 < n; item0 += sub) {
-        const int m = n - item0 < sub ? n - item0 : sub;
-        mark(2);
-        // x of this (sub-)chunk against the 256 MB Infinity Cache: beyond it, stream x (HEFX_STREAM_X=0/1 overrides)
-        const int stream_x = stream_x_of(m);
-        hipLaunchKernelGGL((ks_ntt_digits_kernel<LOGN>), dim3(group_grid(m * L, L)), dim3(SC::T), lds_ntt, s, T, L, m * L,
-                           item0, stream_x | heavy_order(m), scr);
-        mark(3);
-        if (stream_x)
-            hipLaunchKernelGGL(ks_mac_kernel<true>, dim3(SC::N / 2 / 256, L + 1, (m + 1) / 2), dim3(256), 0, s, T, batch,
-                               L, rl, item0, m, 0, scr);
-        else
-            hipLaunchKernelGGL(ks_mac_kernel<false>, dim3(SC::N / 2 / 256, L + 1, (m + 1) / 2), dim3(256), 0, s, T, batch,
-                               L, rl, item0, m, 0, scr);
-    }
+    mark(2);
+    // the chunk's digit x modulus products against the 256 MB Infinity Cache: beyond it, stream them
+    const int stream_x = (size_t)n * L * (L + 1) * SC::N * 8 > ((size_t)256 << 20) ? 1 : 0;
+    hipLaunchKernelGGL((ks_ntt_digits_kernel<LOGN>), dim3(group_grid(n * L, L)), dim3(SC::T), lds, s, T, L, n * L,
+                       stream_x | heavy_order, scr);
+    mark(3);
+    if (stream_x)
+        hipLaunchKernelGGL(ks_mac_kernel<true>, dim3(SC::N / 2 / 256, L + 1, (n + 1) / 2), dim3(256), 0, s, T, batch, L, rl, n,
+                           scr);
+    else
+        hipLaunchKernelGGL(ks_mac_kernel<false>, dim3(SC::N / 2 / 256, L + 1, (n + 1) / 2), dim3(256), 0, s, T, batch, L, rl, n,
+                           scr);
     mark(4);
-    hipLaunchKernelGGL((ks_moddown_intt_kernel<LOGN>), dim3(split_grid(n * 2)), dim3(SC::T), lds_mdi, s, T, L, n * 2, scr);
+    hipLaunchKernelGGL((ks_moddown_intt_kernel<LOGN>), dim3(split_grid(n * 2)), dim3(SC::T), lds, s, T, L, n * 2, scr);
     mark(5);
-    hipLaunchKernelGGL((ks_moddown_finish_kernel<LOGN>), dim3(group_grid(n * 2, L)), dim3(SC::T), lds_fin, s, T, batch, L,
+    hipLaunchKernelGGL((ks_moddown_finish_kernel<LOGN>), dim3(group_grid(n * 2, L)), dim3(SC::T), lds, s, T, batch, L,
                        rl, n * 2, scr);
     mark(-1);
     return hipGetLastError();
@@ -2144,7 +1902,7 @@ static hipError_t launch_lt2_decompose_t(const DevTables &T, int L, const KsItem
     const int chunks = (nrot + LT2_CHUNK - 1) / LT2_CHUNK;
     hipLaunchKernelGGL((ks_intt_digits_kernel<LOGN>), dim3(split_grid(L)), dim3(SC::T), lds, s, T, src_item, L, 0, 1, L,
                        scr);
-    hipLaunchKernelGGL((ks_ntt_digits_kernel<LOGN>), dim3(group_grid(L, L)), dim3(SC::T), lds, s, T, L, L, 0, 0, scr);
+    hipLaunchKernelGGL((ks_ntt_digits_kernel<LOGN>), dim3(group_grid(L, L)), dim3(SC::T), lds, s, T, L, L, 0, scr);
     hipLaunchKernelGGL(lt2_mac_kernel, dim3(SC::N / 2 / 256, L + 1, chunks), dim3(256), 0, s, T, rot_items, L, nrot, scr,
                        ct_new + (size_t)L * SC::N, partial_s);
     hipLaunchKernelGGL(lt2_c0_kernel, dim3(SC::N / 2 / 256, L, chunks), dim3(256), 0, s, T, rot_items, L, nrot, ct_new,
@@ -2203,8 +1961,8 @@ int lt2_chunk() { return LT2_CHUNK; }
 
 int ks_small_max() { return KS_SMALL_MAX; }
 hipError_t launch_keyswitch_chunk(const DevTables &T, int L, int n, const KsItem *batch, bool relin,
-                                  const KsScratch &scr, int sub, bool alias, const KsItem *small_items,
-                                  int quarter, hipStream_t s, KsProf *prof, int nsrc)
+                                  const KsScratch &scr, bool alias, const KsItem *small_items, int quarter,
+                                  hipStream_t s, KsProf *prof, int nsrc)
 {
     KsSmallItems sm;
     const KsSmallItems *small = nullptr;
@@ -2214,7 +1972,7 @@ hipError_t launch_keyswitch_chunk(const DevTables &T, int L, int n, const KsItem
         small = &sm;
     }
     if (T.logn < 12) quarter = 0;  // quarter rows of N = 2048 would be half-wave workgroups
-#define CALL(LN) launch_keyswitch_chunk_t<LN>(T, L, n, batch, relin, scr, sub, alias, small, quarter, s, prof, nsrc)
+#define CALL(LN) launch_keyswitch_chunk_t<LN>(T, L, n, batch, relin, scr, alias, small, quarter, s, prof, nsrc)
     HEFX_DISPATCH_SPLIT(T.logn, CALL)
 #undef CALL
 }

@@ -1,6 +1,5 @@
-// hefx_ntt8.cuh -- NTT cores with EIGHT coefficients per thread (radix-8 passes), used by the fused
-// "digit NTT + key MAC" kernel (two FP64 accumulators per coefficient = 32 VGPRs next to the transform's working set,
-// where sixteen coefficients per thread would need 64) and by the quarter-row kernels of the small-batch path.
+// hefx_ntt8.cuh -- NTT cores with EIGHT coefficients per thread (radix-8 passes), used by the quarter-row kernels of
+// the small-batch path.
 // Same conventions as hefx_ntt.cuh (policies ArithU64 / ArithF64, twiddle prefix `pre`, one-pass-ahead twiddle
 // prefetch, one barrier per LDS exchange, padding G words every 8*G words -> conflict-free b64 accesses).
 #pragma once
@@ -142,32 +141,6 @@ __device__ __forceinline__ void ntt8_fwd_core(typename A::V (&v)[8], typename A:
     typename A::TW w[7];
     load_pass_tw8<LOGN, A>(w, tw, 0, t, pre);
     ntt8_fwd_core_w<LOGN, A>(v, w, lds, tw, cx, t, pre, t);
-}
-
-// Half h of a forward transform of size 2^LOGN: ld(r, x, y) delivers the raw words of coefficients idx_nat(t,r) and
-// idx_nat(t,r) + N/2, `mode` says how they become inputs (reduction in the row's policy); on return
-// f[r] = UNFINISHED NTT value at h*N/2 + idx_out(t,r) (A::fwd_finish / A::mac_operand make it a stored word).
-template <int LOGN, class A, class LD>
-__device__ __forceinline__ void split8_fwd_raw(typename A::V (&f)[8], const LD &ld, const InMode &mode,
-                                               const ModConst &mc, u64 *lds, const typename A::TW *__restrict__ tw,
-                                               const typename A::Ctx &cx, int t, int h)
-{
-    const typename A::TW w1 = A::half_twiddle(tw[1], cx, h);
-    auto stage = [&](auto red) {
-        constexpr int RED = decltype(red)::value;
-        u64 x[8], y[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) ld(r, x[r], y[r]);
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-            f[r] = A::ct_half(A::template input<RED>(x[r], mode, cx, mc), A::template input<RED>(y[r], mode, cx, mc), w1, cx);
-        HEFX_STAGE_FENCE();
-    };
-    if (A::IS_F64 ? mode.red_f64 : mode.red_int)
-        stage(std::integral_constant<int, 1>{});
-    else
-        stage(std::integral_constant<int, 0>{});
-    ntt8_fwd_core<LOGN - 1, A>(f, reinterpret_cast<typename A::V *>(lds), tw, cx, t, 2 + h);
 }
 
 // Inverse core with eight coefficients per thread: v[r] = NTT value idx_out(t,r) on entry (U64: [0,4q); F64: |v| < 2^45),

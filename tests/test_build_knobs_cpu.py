@@ -1,7 +1,9 @@
 """Every compile-time knob the tree still documents must keep compiling: the front end of hipcc
 (-fsyntax-only, device pass, every template instantiated; no code generation, so seconds per knob instead of minutes)
 over hefx_keyswitch.hip with each -DHEFX_* define.  The knobs whose experiments are closed were deleted in round 4
-(HEFX_EPI*, HEFX_MAC_WAVES, HEFX_MAC_GROUP, HEFX_NB_FWD, HEFX_EO_LANE_MIN, HEFX_INV_NAT): profiles/EXPERIMENTS.md."""
+(HEFX_EPI*, HEFX_MAC_WAVES, HEFX_MAC_GROUP, HEFX_NB_FWD, HEFX_EO_LANE_MIN, HEFX_INV_NAT) and after round 6 (the A/B
+knobs of round 3's adopted changes, and the runtime switches of closed experiments): profiles/EXPERIMENTS.md.
+The environment variables the library reads are pinned the same way (RUNTIME_KNOBS)."""
 import os
 import re
 import shutil
@@ -17,11 +19,23 @@ KNOBS = {
     "-DHEFX_ONLY_LOGN=14": "development builds that instantiate one ring size (tools/build_variant.sh, tools/probe_ks.sh)",
     "-DHEFX_ONLY_LOGN=13": "... any ring size",
     "-DHEFX_STAMP=1": "clock stamps inside the small-batch kernels (tools/stamp_timeline.py)",
-    "-DHEFX_WAVES=2": "one register budget for every NTT kernel (occupancy experiments)",
     "-DHEFX_SMALL_MAX=8": "how many descriptors travel in the first launch's kernel arguments",
-    "-DHEFX_NO_L16": "A/B: the [0,8q) integer butterfly everywhere (round 3's 16q range off)",
-    "-DHEFX_NO_LT2Q": "A/B: canonical MAC operands and results (round 3's lazy words off)",
-    "-DHEFX_NO_EO_LANE": "A/B: column t in the forward transforms' first reads (round 3's lane-contiguous loader off)",
+}
+# environment variable -> what it is for.  Test levers force a path that the automatic rules also take, so the tests can
+# reach it at any size; none selects a path of its own.
+RUNTIME_KNOBS = {
+    "HEFX_CHUNK": "test lever: items per launch sequence (default: sized from the scratch budget)",
+    "HEFX_STREAMS": "test lever: =0 runs the chunks serially on the caller's stream (no internal streams)",
+    "HEFX_NO_FP64": "test lever: the integer arithmetic policy for every prime (no FP64 policy below 2^41)",
+    "HEFX_QUARTER": "test lever: =0/1 quarter-row workgroups for none / all launches of a small batch",
+    "HEFX_QMASK": "test lever: any mask of quarter-row launches and the pair path for a small batch",
+    "HEFX_PAIR": "test lever: =0/1 the small-batch pair path off / on",
+    "HEFX_SHARE_SRC": "test lever: =0 switches exact hoisting of shared sources off",
+    "HEFX_FLIPW_MB": "test lever: memory budget of exact hoisting's flip-mask tables",
+    "HEFX_POOL_MB": "test lever: how much freed device memory the hefx_malloc pool keeps parked",
+    "HEFX_LT_LANES": "test lever: =0 runs a rotation forest on one lane",
+    "HEFX_RESCALE": "semantics: =floor presets floor division for rescale_to_next (the default rounds)",
+    "HEFX_DEBUG": "diagnostics: host-side timings and occupancy on stderr",
 }
 
 
@@ -32,7 +46,7 @@ def _hipcc():
     return None
 
 
-def test_documented_knobs_are_exactly_the_ones_in_the_sources():
+def test_documented_build_knobs_are_exactly_the_ones_in_the_sources():
     """a knob in the sources that this file does not list (or the other way round) fails: no silent growth"""
     found = set()
     for f in os.listdir(CSRC):
@@ -42,6 +56,15 @@ def test_documented_knobs_are_exactly_the_ones_in_the_sources():
     internal = {"HEFX_STAGE_FENCE", "HEFX_H", "HEFX_GLOBAL_AS"}  # macros, not knobs
     listed = {re.match(r"-D(HEFX_[A-Z0-9_]+)", k).group(1) for k in KNOBS}
     assert found - internal == listed, (sorted(found - internal - listed), sorted(listed - found))
+
+
+def test_documented_runtime_knobs_are_exactly_the_ones_the_library_reads():
+    """an environment variable the library reads that this file does not list (or the other way round) fails"""
+    found = set()
+    for f in os.listdir(CSRC):
+        if f.endswith((".hip", ".cuh", ".h", ".cpp")):
+            found.update(re.findall(r'getenv\("(HEFX_[A-Z0-9_]+)"\)', open(os.path.join(CSRC, f)).read()))
+    assert found == set(RUNTIME_KNOBS), (sorted(found - set(RUNTIME_KNOBS)), sorted(set(RUNTIME_KNOBS) - found))
 
 
 def test_every_documented_knob_still_compiles():

@@ -350,8 +350,8 @@ def test_invalid_arguments_raise(c2):
 
 
 def test_alternative_launch_paths_bit_exact(c3):
-    """The optional paths must give the same bits as the default one: fused digit-NTT+MAC kernel (HEFX_FUSED=1),
-    integer-only arithmetic policy (HEFX_NO_FP64=1), serial chunks (HEFX_STREAMS=0), small chunks + sub-chunks."""
+    """The optional paths must give the same bits as the default one: integer-only arithmetic policy (HEFX_NO_FP64=1),
+    serial chunks (HEFX_STREAMS=0), small chunks."""
     import subprocess, sys, os, json
     from oracle import oracle as O
     o, e, primes = c3
@@ -371,8 +371,7 @@ def test_alternative_launch_paths_bit_exact(c3):
         "outs=e.rotate_multiply_plain_batch(L,[e.to_device(c) for c in cts],[3]*n,[dk]*n,[e.to_device(p) for p in pts])\n"
         "ok=all((outs[i].download()==o.rotate_mulplain(cts[i],3,key,pts[i])).all() for i in range(n))\n"
         "print('PARITY', ok)\n") % (root, primes)
-    for env in ({"HEFX_FUSED": "1"}, {"HEFX_NO_FP64": "1"}, {"HEFX_STREAMS": "0"}, {"HEFX_CHUNK": "4", "HEFX_SUB": "2"},
-                {"HEFX_FUSED": "1", "HEFX_NO_FP64": "1", "HEFX_CHUNK": "5"}):
+    for env in ({"HEFX_NO_FP64": "1"}, {"HEFX_STREAMS": "0"}, {"HEFX_CHUNK": "4"}, {"HEFX_NO_FP64": "1", "HEFX_CHUNK": "5"}):
         r = subprocess.run([sys.executable, "-c", code], env={**os.environ, **env}, capture_output=True, text=True,
                            timeout=600)
         assert "PARITY True" in r.stdout, (env, r.stdout[-500:], r.stderr[-1500:])

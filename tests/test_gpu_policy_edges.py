@@ -316,14 +316,12 @@ print("PARITY", ok)
 """
 
 
-@pytest.mark.parametrize("knob", ["HEFX_PAIR=0", "HEFX_PAIR=1", "HEFX_QUARTER=0", "HEFX_QUARTER=1", "HEFX_FUSED=1",
-                                  "HEFX_NO_FP64=1"])
+@pytest.mark.parametrize("knob", ["HEFX_PAIR=0", "HEFX_PAIR=1", "HEFX_QUARTER=0", "HEFX_QUARTER=1", "HEFX_NO_FP64=1"])
 def test_mixed_sets_under_every_path_knob(knob):
-    """both mixed sets (every prime class interleaved in one launch) with the pair path, quarter rows and the fused
-    transforms forced on / off, and with the FP64 policy off (every row on the integer policy): batches of 1, 8, 40
+    """both mixed sets (every prime class interleaved in one launch) with the pair path and quarter rows forced on / off,
+    and with the FP64 policy off (every row on the integer policy): batches of 1, 8, 40
     rotations, fused products, relinearisations and both rescales against the oracle, in a child process per knob"""
-    env = {k: v for k, v in os.environ.items() if k not in ("HEFX_QUARTER", "HEFX_QMASK", "HEFX_PAIR", "HEFX_PAIR_MAX",
-                                                              "HEFX_FUSED", "HEFX_NO_FP64")}
+    env = {k: v for k, v in os.environ.items() if k not in ("HEFX_QUARTER", "HEFX_QMASK", "HEFX_PAIR", "HEFX_NO_FP64")}
     k, v = knob.split("=")
     env[k] = v
     r = subprocess.run([sys.executable, "-c", _CHILD % ROOT], env=env, capture_output=True, text=True, timeout=300)

@@ -147,10 +147,11 @@ def test_c4_apply_galois_relinearize_rescale_bit_exact(c4):
             assert (e.rescale_to_next(L, 3, e.to_device(m), rounded=rounded).download() == o.rescale(m, rounded=rounded)).all()
 
 
-@pytest.mark.parametrize("env,n", [(None, 40), ({"HEFX_CHUNK": "16"}, 40), ({"HEFX_CHUNK": "8", "HEFX_SUB": "3"}, 19)])
+@pytest.mark.parametrize("env,n", [(None, 40), ({"HEFX_CHUNK": "16"}, 40), ({"HEFX_CHUNK": "8"}, 19)])
 def test_c4_rotate_multiply_plain_batches_bit_exact(env, n):
     """L=8 and L=7 at N=16384: one chunk big enough to stream x (40 items x 72 rows > 256 MB), three chunks alternating
-    on the two internal streams, and sub-chunked x; distinct keys per step so the MAC's one-item path runs too."""
+    on the two internal streams, and three chunks with a tail of three items; distinct keys per step so the MAC's one-item
+    path runs too."""
     from oracle import oracle as O
     o, e, primes = _mk("C4", env)
     keys = {s: _rand_key(o, 1000 + s) for s in (1, 2, 3)}
@@ -567,7 +568,7 @@ for name in ("C2", "C3", "C4", "C5", "toy4096", "toy2048"):
         ok &= bool((dd.download() == o.apply_galois(ct, 3, keys[0])).all())
 print("PARITY", ok)
 """ % (root, root)
-    env = {k: v for k, v in os.environ.items() if k not in ("HEFX_QUARTER", "HEFX_QMASK", "HEFX_PAIR", "HEFX_PAIR_MAX")}
+    env = {k: v for k, v in os.environ.items() if k not in ("HEFX_QUARTER", "HEFX_QMASK", "HEFX_PAIR")}
     if knob != "auto":
         env[knob.split("=")[0]] = knob.split("=")[1]
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=900)

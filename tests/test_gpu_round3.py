@@ -32,7 +32,7 @@ def test_bench_configuration_default_chunking_every_output_bit_exact():
     from oracle import oracle as O
     from seal_fyp_logistic_regression_amd import Engine
     from seal_fyp_logistic_regression_amd.seal import galois_elt_from_step
-    for v in ("HEFX_CHUNK", "HEFX_SUB", "HEFX_STREAMS", "HEFX_STREAM_X", "HEFX_FUSED", "HEFX_NO_FP64", "HEFX_QUARTER"):
+    for v in ("HEFX_CHUNK", "HEFX_STREAMS", "HEFX_NO_FP64", "HEFX_QUARTER"):
         if v in os.environ:
             pytest.skip(f"{v} is set: this test is about the DEFAULT launch structure (the knob runs have their own tests)")
     N, primes = C3

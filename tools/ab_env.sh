@@ -1,6 +1,6 @@
 #!/bin/bash
 # Same-box A/B of ENVIRONMENT settings over bench sets (development aid, GPU box):
-#   tools/ab_env.sh "C3 C2" "HEFX_FUSED=0" "HEFX_FUSED=1" ...   two interleaved rounds, one line each
+#   tools/ab_env.sh "C3 C2" "HEFX_SHARE_SRC=0" "HEFX_SHARE_SRC=1" ...   two interleaved rounds, one line each
 sets=$1; shift
 for round in 1 2; do
 for set in $sets; do

@@ -1,7 +1,7 @@
 """Latency per level of the rotate-by-1 + add_inplace chains of helper.h:472-476 at the LR driver's shape (N = 16384,
 {60,40x7,60}; after the dot product's rescale the chains run at L = 7 .. 2) -- one engine call for the whole chain
 (hefx_rotate_add_chain) against one fused call per level (hefx_apply_galois_add_batch) and the round-3 sequence
-(hefx_apply_galois_batch + hefx_add per level).  HEFX_CHAIN_GRAPH=0 switches the graph replay off.
+(hefx_apply_galois_batch + hefx_add per level).
     python tools/chain_latency.py [n=8] [L=2] [steps=500]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -45,6 +45,6 @@ def separate_levels():
         a = e.add_batch(L, 2, a, d)
 
 
-print(f"n={n} L={L} steps={steps} graph={os.environ.get('HEFX_CHAIN_GRAPH', '1')}: "
+print(f"n={n} L={L} steps={steps}: "
       f"chain call {timed(chain):.1f} us/level, fused call per level {timed(fused_levels):.1f}, "
       f"rotate + add calls per level {timed(separate_levels):.1f}", flush=True)

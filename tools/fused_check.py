@@ -1,6 +1,6 @@
 """Bit-exactness of the key-switch paths at C3 (N=16384, L=5 and L=3) against the CPU oracle, for A/B builds that only
-instantiate one ring size (tools/build_variant.sh ... -DHEFX_ONLY_LOGN=14) and for the HEFX_FUSED modes:
-    HEFX_FUSED=3 HEFX_LIB=build/libhefx_x.so python tools/fused_check.py"""
+instantiate one ring size (tools/build_variant.sh ... -DHEFX_ONLY_LOGN=14):
+    HEFX_LIB=build/libhefx_x.so python tools/fused_check.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -27,5 +27,5 @@ for L, n in ((k - 1, 37), (3, 9), (k - 1, 1)):
     c3 = o.multiply(cts[0], cts[0])
     got = e.relinearize(L, e.to_device(c3), dkeys[0]).download()
     bad += not bool((got == o.relinearize(c3, keys[0])).all())
-print("fused_check:", "ALL BIT-EXACT" if bad == 0 else f"{bad} MISMATCHES", f"(HEFX_FUSED={os.environ.get('HEFX_FUSED', '')}, lib={os.environ.get('HEFX_LIB', 'default')})")
+print("fused_check:", "ALL BIT-EXACT" if bad == 0 else f"{bad} MISMATCHES", f"(lib={os.environ.get('HEFX_LIB', 'default')})")
 sys.exit(1 if bad else 0)
