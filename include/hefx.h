@@ -368,8 +368,13 @@ int hefx_linear_transform_plain_bsgs(hefx_context *ctx, int L, const uint64_t *d
  *      matrix_mult_benchmark.cpp:291-323, logistic_regression_ckks.cpp:222-225,302-305, helper.h:333-343):
  *      `count` vectors of `nvalues` <= N/2 slot values each (host arrays; h_im may be NULL for real vectors) ->
  *      `count` contiguous NTT-form plaintexts of L rows at d_out.  Canonical embedding with slot i <-> root
- *      zeta^(3^i), coefficients rounded half away from zero like std::round.  Floating point: matches any other
- *      correct encoder to +-1 in a small fraction of coefficients, not bit for bit.
+ *      zeta^(3^i), coefficients rounded half away from zero like std::round.  Floating point: every coefficient is an
+ *      integer within 0.5 + (FFT rounding error) of the exact p_k * scale, the same integer in every RNS row; against
+ *      another correct encoder that is +-1 where p_k * scale lies next to a half-integer, not bit for bit.
+ *      Range: every |value| * scale must be finite and below 2^62 (|p_k| <= max |value|, and the kernel holds
+ *      |round(p_k * scale)| in one 64-bit word).  Anything else -- a NaN or an infinity among the values included --
+ *      returns HEFX_ERR_INVALID before any work is queued; wider coefficients need an exact host encoder followed by
+ *      hefx_ntt_forward.
  *      The host arrays are copied into pinned staging memory before the call returns (they may be transient); the call
  *      does not wait for the stream -- at most for an earlier encode that still owns the staging buffer it wants. */
 int hefx_ckks_encode(hefx_context *ctx, int L, const double *h_re, const double *h_im, int nvalues, int count,

@@ -2002,6 +2002,21 @@ static int ensure_encode_tables(hefx_context *c)
     return HEFX_OK;
 }
 
+// every |v_i| * scale < 2^62 and finite?  |p_k| <= max|v_i|, and the kernel converts |round(p_k * scale)| to a 64-bit
+// word: beyond the range that conversion is undefined, not an error.  One vectorisable pass over the components
+// (max(|re|, |im|) * scale < 2^61 implies |v| * scale < 2^62); the exact modulus only where that does not decide.
+static bool encode_values_in_range(const double *re, const double *im, size_t n, double scale)
+{
+    bool undecided = false;
+    for (size_t i = 0; i < n; ++i) undecided |= !(fabs(re[i]) * scale < 0x1p61);
+    if (im)
+        for (size_t i = 0; i < n; ++i) undecided |= !(fabs(im[i]) * scale < 0x1p61);
+    if (!undecided) return true;
+    for (size_t i = 0; i < n; ++i)
+        if (!((im ? hypot(re[i], im[i]) : fabs(re[i])) * scale < 0x1p62)) return false;  // NaN and inf fail too
+    return true;
+}
+
 extern "C" int hefx_ckks_encode(hefx_context *c, int L, const double *h_re, const double *h_im, int nvalues,
                                 int count, double scale, uint64_t *d_out, void *stream)
 {
@@ -2013,6 +2028,8 @@ extern "C" int hefx_ckks_encode(hefx_context *c, int L, const double *h_re, cons
     if (!(scale > 0)) return fail(HEFX_ERR_INVALID, "scale out of bounds");
     if (int rc = ensure_encode_tables(c)) return rc;
     const size_t nv = (size_t)nvalues * count, need = nv * (h_im ? 2 : 1);
+    if (!encode_values_in_range(h_re, h_im, nv, scale))  // before the values go into staging
+        return fail(HEFX_ERR_INVALID, "values out of range: every |value| * scale must be finite and below 2^62");
     if (c->vals_cap < need) {
         if (c->d_vals) {
             HIPCHK(hipDeviceSynchronize());
@@ -2083,6 +2100,8 @@ extern "C" int hefx_ckks_encode_batch(hefx_context *c, int L, const double *h_re
     CTXCHK(c);
     if (int rc = check_level(c, L)) return rc;
     if (!d_outs || count < 1) return fail(HEFX_ERR_INVALID, "values has invalid size");
+    if (h_re && nvalues >= 1 && scale > 0 && !encode_values_in_range(h_re, h_im, (size_t)nvalues * count, scale))
+        return fail(HEFX_ERR_INVALID, "values out of range: every |value| * scale must be finite and below 2^62");
     if (c->logn == 15) {  // out-of-place transform: vector by vector
         for (int i = 0; i < count; ++i)
             if (int rc = hefx_ckks_encode(c, L, h_re + (size_t)i * nvalues, h_im ? h_im + (size_t)i * nvalues : nullptr, nvalues, 1,

@@ -403,6 +403,17 @@ GaloisKeys = KSwitchKeys
 RelinKeys = KSwitchKeys
 
 
+def _c_round(x):
+    """C's round() -- halves away from zero, what SEAL's encoder calls -- for every double: numpy array in, float64 array
+    of integers out; a Python float in, a Python int out.  (np.rint and Python's round() send halves to the even
+    neighbour; floor(x + 0.5) is wrong at 0.49999999999999994 and above 2^52.)  x - trunc(x) is exact in float64."""
+    if isinstance(x, float):
+        t = math.trunc(x)
+        return t + (0 if abs(x - t) < 0.5 else (1 if x > 0 else -1))
+    t = np.trunc(x)
+    return t + np.where(np.abs(x - t) >= 0.5, np.sign(x), 0.0)
+
+
 def _key32(seed) -> bytes:
     """32-byte ChaCha20 key of the backend sampler: fresh OS randomness when seed is None (production), else a
     deterministic expansion of the integer seed (tests: randomness is an input of the parity chain)."""
@@ -584,7 +595,7 @@ class CKKSEncoder:
         L = parms_id if parms_id is not None else ctx.first_parms_id()
         out = destination if destination is not None else Plaintext()
         if np.isscalar(values):  # encode(double, scale, pt): every NTT slot = round(v*scale) mod q
-            c = int(round(float(values) * scale))
+            c = _c_round(float(values) * float(scale))
             rows = np.empty((L, N), dtype=np.uint64)
             for j in range(L):
                 rows[j, :] = c % ctx.primes[j]
@@ -603,7 +614,7 @@ class CKKSEncoder:
             A[self._r1[: v.size]] = v
             A[self._r2[: v.size]] = np.conj(v)
             a = np.fft.fft(A) / N
-            coeffs = np.rint(np.real(a * np.conj(self._zeta)) * scale)
+            coeffs = _c_round(np.real(a * np.conj(self._zeta)) * scale)
             rows = self._to_rns(coeffs, L)
             out.is_zero = not coeffs.any()
             out.data = be.ntt_forward(be.from_host(rows), 1, L, 0)

@@ -1,10 +1,13 @@
 """GPU CKKS encode (hefx_ckks_encode) against the CPU oracle's encoder.
 
-Floating point, so the bar is the tolerance stated here, not bit equality: the two encoders run different FFTs, so
-round(p_k * scale) may differ by exactly one unit where p_k * scale sits within FFT error (~N * 2^-52 * scale) of a
-half-integer.  Tolerances: |coefficient difference| <= 1 on every coefficient, on fewer than 1 % of them;
-decode(encode(v)) == v to 1e-7 at scale 2^40.  Everything downstream of the plaintext is integer work and stays
-bit-exact (tests/test_gpu_parity.py, tests/test_gpu_composites.py)."""
+Both sides are float FFTs, so this file compares two inexact encoders: round(p_k * scale) may differ by exactly one unit
+where p_k * scale sits within FFT error (~N * 2^-52 * scale) of a half-integer.  Tolerances: |coefficient difference| <= 1
+on every coefficient, on fewer than 1 % of them; decode(encode(v)) == v to 1e-7 at scale 2^40.  It cannot say which side
+is off, nor see an encoder that is wrong by one on a few coefficients: the judge for that is the exact integer reference
+of tests/exact_ckks.py, which tests/test_gpu_frontend_edges.py holds the kernel to coefficient by coefficient (ties,
+one-hot masks, values just under 2^62, tiny and 61-bit rows) and tests/test_exact_ckks_cpu.py the oracle and the host
+encoder.  Everything downstream of the plaintext is integer work and stays bit-exact (tests/test_gpu_parity.py,
+tests/test_gpu_composites.py)."""
 import numpy as np
 import pytest
 
