@@ -40,6 +40,10 @@ struct KsWaves {
     // 256-thread workgroups two registers past 128 and with them the fourth workgroup per CU; two batches + eo_lane:
     // digit NTTs 94 -> 87 us, mod-down finish 102 -> 98 us per chunk, profiles/r03/ab_c2_eo_lane.txt)
     static constexpr int NB_INV = (INV <= 2 && LOGN <= 13) ? 1 : 2, NB_FWD = (FWD <= 2 && LOGN < 13) ? 1 : 2;
+    // digit transforms cut by coefficient parity, last stage in the regular key MAC (parity_fwd_raw, mac_items).  On for
+    // every ring size by the instruction counts alone: one pair of bench runs at N = 16384 is all that was measured
+    // (profiles/EXPERIMENTS.md, round 7), no other ring size was.  A per-LOGN exception belongs here.
+    static constexpr bool PARITY_CUT = true;
 };
 
 namespace hefx {
@@ -238,9 +242,19 @@ __global__ __launch_bounds__(SplitCfg<LOGN>::T, KsWaves<LOGN>::INV) void ks_intt
 
 // ------------------------------------------------------------------------------------------------
 // (2) digit i -> modulus slot jj != i: x[b][i][jj] = NTT_m(d[b][i] mod m)
+// Two contracts for a row of x, chosen per launch together with the row's reader (launch_digits_and_mac):
+//   CUT = false  the finished row, halves [0, N/2) and [N/2, N) from the two workgroups (split_fwd: first stage while
+//                loading, both halves read all N words), in the MAC's operand format (mac_operand / mac_operand_lazy).
+//                Readers: ks_mac_exact_kernel, lt2_*, the regular MAC of a launch that says so.
+//   CUT = true   [E | O]: workgroup h transforms parity class h of the coefficients -- its own half of the [evens | odds]
+//                digit -- through all stages but the last (parity_fwd_raw) and stores the class in its transform's order.
+//                No first-stage code, no second read or conversion of the other half, and for the limb MAC's rows no
+//                reduction at all.  row[2w], row[2w+1] = E[w] +- tw[N/2 + w] O[w] is left to the regular MAC, whose
+//                thread w owns that pair (mac_items).  Operand format by the MAC's policy: parity_fwd_a.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool slot_is_f64(const DevTables &T, int L, int jj);
-template <int LOGN>
+__device__ __forceinline__ int mac_kind(const DevTables &T, int m, int L);
+template <int LOGN, bool CUT>
 __device__ __forceinline__ void ntt_digit_row(const DevTables &T, int L, int rows, int stream_x, const KsScratch &S,
                                               u64 *lds)
 {
@@ -287,16 +301,23 @@ __device__ __forceinline__ void ntt_digit_row(const DevTables &T, int L, int row
     // [d_i]_m: the U64 policy needs it only when q_i > m; the FP64 policy takes any integer below 2^49 as input,
     // so a digit of a prime < 2^41 needs no reduction at all (the transform is linear and ends canonical)
     const InMode mode = {qi > mc.q, T.modsf[i].q == 0.0, false, 0};
-    const int tl = HEFX_EO_LANE(SC, t);
-    auto ld = [&](int r, u64 &x, u64 &y) {
-        const uint32_t e = eo_nat<SC>(tl, r);
-        x = dd[e];
-        y = dd[e + SC::H / 2];
-    };
-    // MAC-operand format: canonical words for the integer-policy moduli, unfinished doubles for the FP64 ones
     const ModConstF mf = T.modsf[m];
-    split_fwd<LOGN, KsWaves<LOGN>::NB_FWD, true>(v, ld, mode, lds, ntt_tables(T, m), mc, mf, t, h, tl,
-                                                 mac_x_slack(mc, mf, L));
+    if constexpr (CUT) {
+        // parity class h of the row: its own N/2 words, contiguous in the [evens | odds] digit and lane-adjacent as they are
+        const u64 *__restrict__ dh = dd + (size_t)h * SC::H;
+        parity_fwd<LOGN>(v, [&](int r) { return dh[C::idx_nat(t, r)]; }, mode, lds, ntt_tables(T, m), mc, mf, t,
+                         mac_kind(T, m, L));
+    } else {
+        const int tl = HEFX_EO_LANE(SC, t);
+        auto ld = [&](int r, u64 &x, u64 &y) {
+            const uint32_t e = eo_nat<SC>(tl, r);
+            x = dd[e];
+            y = dd[e + SC::H / 2];
+        };
+        // MAC-operand format: canonical words for the integer-policy moduli, unfinished doubles for the FP64 ones
+        split_fwd<LOGN, KsWaves<LOGN>::NB_FWD, true>(v, ld, mode, lds, ntt_tables(T, m), mc, mf, t, h, tl,
+                                                     mac_x_slack(mc, mf, L));
+    }
     u64 *__restrict__ xd = S.x + (((size_t)b * L + i) * (L + 1) + jj) * SC::N + (size_t)h * SC::H;
     // stream_x: the chunk's digit x modulus products exceed the Infinity Cache, so they are written (here) and read
     // (MAC) with streaming accesses that leave the caches to the rows that are reused -- digits, twiddles, key
@@ -341,6 +362,16 @@ struct MacW {
     };
     __device__ static __forceinline__ X xin(const ulonglong2 &bits, bool, const Ctx &) { return bits; }
     __device__ static __forceinline__ K kin(const ulonglong2 &k0, const ulonglong2 &k1, const Ctx &) { return K{k0, k1}; }
+    // parity cut (mac_items): the last forward stage on (E[w], O[w]).  Canonical words in (parity_fwd_a, MAC_W), the
+    // [0,8q) butterfly -- any prime below 2^61 -- and canonical words out, as this policy's mac takes them.
+    typedef ulonglong2 LTW;
+    __device__ static __forceinline__ LTW ltw(const NttTables &nt, size_t i) { return gld16(nt.tw + i); }
+    __device__ static __forceinline__ X xin_cut(u64 e, u64 o, const LTW &w, const Ctx &c, int)
+    {
+        const ArithU64::Ctx ac = ArithU64::make(c.mc);
+        ArithU64::ct(e, o, w, ac, 0);
+        return make_ulonglong2(ArithU64::fwd_finish(e, ac), ArithU64::fwd_finish(o, ac));
+    }
     u64 a0xl = 0, a0xh = 0, a0yl = 0, a0yh = 0, a1xl = 0, a1xh = 0, a1yl = 0, a1yh = 0;
     __device__ __forceinline__ void mac(const X &x, const K &k, const Ctx &)
     {
@@ -394,6 +425,25 @@ struct MacL {
     __device__ static __forceinline__ K kin(const ulonglong2 &k0, const ulonglong2 &k1, const Ctx &)
     {
         return K{lo30(k0.x), hi30(k0.x), lo30(k0.y), hi30(k0.y), lo30(k1.x), hi30(k1.x), lo30(k1.y), hi30(k1.y)};
+    }
+    // parity cut: E, O arrive as the L16 transform left them, below 16q (parity_fwd_a, MAC_L; q < 2^60).  The butterfly in
+    // its odd-stage form (E -> below 8q first) is valid for either parity of the stage count: results below 12q.  Then the
+    // reductions the producer of a finished row makes (mac_operand_lazy / mac_operand): down to what `slack` allows
+    // (mac_x_slack: 2 -> below 4q, 1 -> below 2q, 0 -> canonical).  The MAC's sums see the same residues either way.
+    typedef ulonglong2 LTW;
+    __device__ static __forceinline__ LTW ltw(const NttTables &nt, size_t i) { return gld16(nt.tw + i); }
+    __device__ static __forceinline__ u64 cut_reduce(u64 x, const ArithU64L::Ctx &ac, int slack)
+    {
+        x = csubn(csubn(x, ac.n8q), ac.n4q);       // < 12q -> < 4q
+        if (slack < 2) x = csubn(x, ac.n2q);       // (block-uniform)
+        if (slack < 1) x = csubn(x, ac.nq);
+        return x;
+    }
+    __device__ static __forceinline__ X xin_cut(u64 e, u64 o, const LTW &w, const Ctx &c, int slack)
+    {
+        const ArithU64L::Ctx ac = ArithU64L::make(c.mc);
+        ArithU64L::ct(e, o, w, ac, 1);
+        return xin(make_ulonglong2(cut_reduce(e, ac, slack), cut_reduce(o, ac, slack)), false, c);
     }
     u64 c[4][3] = {};  // [a0x, a0y, a1x, a1y][column]
     __device__ static __forceinline__ void mad(u64 (&col)[3], uint32_t xl, uint32_t xh, uint32_t kl, uint32_t kh)
@@ -460,6 +510,17 @@ struct MacF {
     {
         return K{ArithF64::from_u64(k0.x), ArithF64::from_u64(k0.y), ArithF64::from_u64(k1.x), ArithF64::from_u64(k1.y)};
     }
+    // parity cut: E, O are unfinished doubles with |E|, |O| < 2^41 + (LOGN-1) * 0.52q < 2^45 (parity_fwd_raw): O is a valid
+    // left operand of mm, and the two results are below 2^41 + LOGN * 0.52q < 2^45 -- the very bound of a finished row's
+    // unfinished doubles (ArithF64::mac_operand), valid left operands of mac
+    typedef double LTW;
+    __device__ static __forceinline__ LTW ltw(const NttTables &nt, size_t i) { return nt.twf[i]; }
+    __device__ static __forceinline__ X xin_cut(u64 e, u64 o, const LTW &w, const Ctx &c, int)
+    {
+        double x = ArithF64::unraw(e), y = ArithF64::unraw(o);
+        ArithF64::ct(x, y, w, c, 0);
+        return make_double2(x, y);
+    }
     double a0x = 0.0, a0y = 0.0, a1x = 0.0, a1y = 0.0;
     __device__ __forceinline__ void mac(const X &x, const K &k, const Ctx &c)
     {
@@ -514,6 +575,26 @@ __device__ __forceinline__ void mac_dispatch(const DevTables &T, int m, int L, c
         f(MacW());
 }
 
+// ... and as a number, for the producer of a parity-cut row (parity_fwd_a): the SAME rule, so that what the digit
+// transforms hand over is what the policy's xin_cut expects
+__device__ __forceinline__ int mac_kind(const DevTables &T, int m, int L)
+{
+    int kind = MAC_W;
+    mac_dispatch(T, m, L, [&](auto pol) {
+        using P = decltype(pol);
+        kind = std::is_same<P, MacF>::value ? MAC_F : std::is_same<P, MacL>::value ? MAC_L : MAC_W;
+    });
+    return kind;
+}
+
+// lanes 2v <-> 2v+1 of a wave swap one 64-bit word (DPP quad_perm [1,0,3,2]; every lane of the MAC kernels is active)
+__device__ __forceinline__ u64 lane_pair_swap(u64 v)
+{
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, 0xB1, 0xF, 0xF, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), 0xB1, 0xF, 0xF, false);
+    return ((u64)(uint32_t)hi << 32) | (uint32_t)lo;
+}
+
 template <bool STREAM>
 __device__ __forceinline__ void mac_store(u64 *acc0, u64 *acc1, size_t w, const ulonglong2 &r0, const ulonglong2 &r1)
 {
@@ -529,11 +610,18 @@ __device__ __forceinline__ void mac_store(u64 *acc0, u64 *acc1, size_t w, const 
 // NI consecutive items that share `key`.  own[e] / own_elt[e]: item e's input row for digit jj's own prime and its
 // Galois element (1: no rotation), used when jj < L; xrow(e, i): digit i's transformed row for this modulus in scratch x;
 // acc0 / acc1: the two accumulator rows of item e.
+// CUT: the rows of x hold the parity classes [E | O] before the last forward stage (ntt_digit_row) and this thread, owner
+// of pair w, makes that stage itself: x.(x, y) = E[w] +- tw[N/2 + w] O[w] in the target prime's forward policy, reduced to
+// what P::mac takes (P::xin_cut, with the range argument of each policy).  Memory instructions per thread, item and digit
+// stay what they are for a finished row -- one 16-byte load of x, two of the key: the lanes of a pair fetch (E[w], E[w+1])
+// and (O[w-1], O[w]) and swap a word each through DPP -- plus ONE twiddle load per thread for all digits and items.  The
+// own-prime term is a finished row of the source either way.  The transform kernels issue VALU back to back while this one
+// waits for HBM two thirds of its wave time: the stage costs less here than there.
 // Shape of the loop (round 3, after reading the ISA): the own-prime term is peeled out in front, so the body over the
 // other digits has no conditional loads -- the old form tested i == jj per digit, re-read the item descriptor from
 // memory inside that branch and closed every conditional block with s_waitcnt vmcnt(0): 52 full drains and not one
 // counted wait in the kernel -- and the operands of digit i+1 are requested before digit i is accumulated.
-template <class P, int NI, bool STREAM, class XR>
+template <class P, int NI, bool STREAM, bool CUT, class XR>
 __device__ __forceinline__ void mac_items(const DevTables &T, const u64 *key, int L, int jj, int m, size_t n, size_t w,
                                           const u64 *const (&own)[NI], const uint32_t (&own_elt)[NI], const XR &xrow,
                                           u64 *const (&acc0)[NI], u64 *const (&acc1)[NI])
@@ -547,12 +635,29 @@ __device__ __forceinline__ void mac_items(const DevTables &T, const u64 *key, in
         k0 = gld16(kb + 2 * w);
         k1 = gld16(kb + kpoly + 2 * w);
     };
+    // CUT: an even lane fetches the record (E[w], E[w+1]), its odd neighbour (O[w-1], O[w]) -- per wave instruction two
+    // dense 512-byte runs, one 16-byte load per thread, item and digit as for a finished row
+    const bool odd = (w & 1) != 0;
+    const size_t xoff = CUT ? (odd ? n / 2 + w - 1 : w) : 2 * w;
     auto load_x = [&](int i, ulonglong2 (&xb)[NI]) {
 #pragma unroll
         for (int e = 0; e < NI; ++e) {
-            const u64 *xp = xrow(e, i) + 2 * w;
+            const u64 *xp = xrow(e, i) + xoff;
             xb[e] = STREAM ? nt_load16(xp) : gld16(xp);  // read exactly once
         }
+    };
+    // the last-stage twiddle w_w = tw[N/2 + w] of the target modulus: one load for all digits and items
+    typename P::LTW lw = {};
+    if constexpr (CUT) lw = P::ltw(ntt_tables(T, m), n / 2 + w);
+    const int slack = CUT ? mac_x_slack(T.mods[m], T.modsf[m], L) : 0;
+    // a non-own digit's MAC operand: the finished pair as it lies in scratch, or (CUT) the last stage on (E[w], O[w]) once
+    // the lane pair has swapped the words it fetched for each other
+    auto x_of = [&](const ulonglong2 &b) {
+        if constexpr (CUT) {
+            const u64 sx = lane_pair_swap(b.x), sy = lane_pair_swap(b.y);
+            return P::xin_cut(odd ? sy : b.x, odd ? b.y : sx, lw, cx, slack);
+        } else
+            return P::xin(b, false, cx);
     };
     if (jj < L) {  // the digit in NTT form modulo its own prime: the (rotated) input row itself, gathered
         ulonglong2 xb[NI], k0, k1;
@@ -583,7 +688,7 @@ __device__ __forceinline__ void mac_items(const DevTables &T, const u64 *key, in
         for (int g = 0; g < G; ++g) {
             const typename P::K k = P::kin(k0[g], k1[g], cx);
 #pragma unroll
-            for (int e = 0; e < NI; ++e) A[e].mac(P::xin(xb[g][e], false, cx), k, cx);
+            for (int e = 0; e < NI; ++e) A[e].mac(x_of(xb[g][e]), k, cx);
         }
     }
     for (; r0 < nd; ++r0) {  // remainder, one digit at a time
@@ -592,7 +697,7 @@ __device__ __forceinline__ void mac_items(const DevTables &T, const u64 *key, in
         load_k(digit_at(r0), k0, k1);
         const typename P::K k = P::kin(k0, k1, cx);
 #pragma unroll
-        for (int e = 0; e < NI; ++e) A[e].mac(P::xin(xb[e], false, cx), k, cx);
+        for (int e = 0; e < NI; ++e) A[e].mac(x_of(xb[e]), k, cx);
     }
 #pragma unroll
     for (int e = 0; e < NI; ++e) {
@@ -606,7 +711,7 @@ __device__ __forceinline__ void mac_items(const DevTables &T, const u64 *key, in
 }
 
 // one MAC unit: target slot jj, the item pair (bl0, bl0 + 1) of the chunk, pair index w of the row
-template <bool STREAM>
+template <bool STREAM, bool CUT>
 __device__ __forceinline__ void mac_unit(const DevTables &T, const KsItem *__restrict__ items, int L, int relin, int count,
                                          const KsScratch &S, int jj, int bl0, size_t w)
 {
@@ -625,20 +730,21 @@ __device__ __forceinline__ void mac_unit(const DevTables &T, const KsItem *__res
     mac_dispatch(T, m, L, [&](auto pol) {
         using P = decltype(pol);
         if (two && it1.key == it0.key) {
-            mac_items<P, 2, STREAM>(T, it0.key, L, jj, m, n, w, own, own_elt, xrow2, acc0, acc1);
+            mac_items<P, 2, STREAM, CUT>(T, it0.key, L, jj, m, n, w, own, own_elt, xrow2, acc0, acc1);
         } else {
             const u64 *const o0[1] = {own[0]}, *const o1[1] = {own[1]};
             const uint32_t e0[1] = {own_elt[0]}, e1[1] = {own_elt[1]};
             u64 *const a00[1] = {acc0[0]}, *const a01[1] = {acc1[0]}, *const a10[1] = {acc0[1]}, *const a11[1] = {acc1[1]};
-            mac_items<P, 1, STREAM>(T, it0.key, L, jj, m, n, w, o0, e0, [&](int, int i) { return xrow2(0, i); }, a00, a01);
+            mac_items<P, 1, STREAM, CUT>(T, it0.key, L, jj, m, n, w, o0, e0, [&](int, int i) { return xrow2(0, i); }, a00, a01);
             if (two)
-                mac_items<P, 1, STREAM>(T, it1.key, L, jj, m, n, w, o1, e1, [&](int, int i) { return xrow2(1, i); }, a10, a11);
+                mac_items<P, 1, STREAM, CUT>(T, it1.key, L, jj, m, n, w, o1, e1, [&](int, int i) { return xrow2(1, i); }, a10, a11);
         }
     });
 }
 
-template <bool STREAM>
-__global__ __launch_bounds__(256) void ks_mac_kernel(DevTables T, const KsItem *__restrict__ items, int L, int relin,
+constexpr int KS_MAC_THREADS = 256;  // workgroup size of ks_mac_kernel (its launches: dim3(256))
+template <bool STREAM, bool CUT = false>
+__global__ __launch_bounds__(KS_MAC_THREADS) void ks_mac_kernel(DevTables T, const KsItem *__restrict__ items, int L, int relin,
                                                      int count, KsScratch S)
 {
     if (S.gate_mode == 2 && ks_gated_out(S)) return;
@@ -647,7 +753,10 @@ __global__ __launch_bounds__(256) void ks_mac_kernel(DevTables T, const KsItem *
     const int wg = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
     if (threadIdx.x == 0 && wg < 1024) hefx_stamp_buf[((size_t)2 * 1024 + wg) * 16] = wall_clock64();
 #endif
-    mac_unit<STREAM>(T, items, L, relin, count, S, jj, 2 * blockIdx.z, (size_t)blockIdx.x * blockDim.x + threadIdx.x);
+    // (CUT: the lanes 2v, 2v+1 of a wave must own the pairs w, w+1 with w even -- lane_pair_swap, the record loads of
+    // mac_items -- which holds for this mapping because the workgroup size is even and the grid covers the row exactly)
+    static_assert(KS_MAC_THREADS % 64 == 0, "the parity cut pairs lane 2v with lane 2v+1: w and the lane share their parity");
+    mac_unit<STREAM, CUT>(T, items, L, relin, count, S, jj, 2 * blockIdx.z, (size_t)blockIdx.x * KS_MAC_THREADS + threadIdx.x);
 #ifdef HEFX_STAMP
     if (HEFX_STAMP > 1) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     if (threadIdx.x == 0 && wg < 1024) hefx_stamp_buf[((size_t)2 * 1024 + wg) * 16 + 15] = wall_clock64();
@@ -655,14 +764,14 @@ __global__ __launch_bounds__(256) void ks_mac_kernel(DevTables T, const KsItem *
 }
 
 // (2) as a launch
-template <int LOGN>
+template <int LOGN, bool CUT = false>
 __global__ __launch_bounds__(SplitCfg<LOGN>::T, KsWaves<LOGN>::FWD) void ks_ntt_digits_kernel(DevTables T, int L, int rows,
                                                                              int stream_x, KsScratch S)
 {
     extern __shared__ __align__(16) u64 lds[];
     HEFX_STAMP_KERNEL(1);
     HEFX_STAMP_AT(0);
-    ntt_digit_row<LOGN>(T, L, rows, stream_x, S, lds);
+    ntt_digit_row<LOGN, CUT>(T, L, rows, stream_x, S, lds);
     HEFX_STAMP_AT(15);
 }
 
@@ -1694,6 +1803,30 @@ static void set_lds(K kernel, size_t bytes)
                               (int)bytes);
 }
 
+// Launches (2) and (3) of an ordinary chunk: split-2 digit transforms into scratch x, then the regular key MAC.  The two
+// agree on what a row of x holds -- finished rows, or the two parity classes before the last stage -- through the ONE flag
+// chosen here.  Every other writer or reader of x (quarter rows, the pair path, exact and double hoisting and the
+// fallback launches of an exactly hoisted chunk) keeps finished rows.
+template <int LOGN, class MARK>
+static void launch_digits_and_mac(const DevTables &T, int L, int n, const KsItem *batch, int rl, int order_flags,
+                                  bool may_stream, const KsScratch &scr, hipStream_t s, const MARK &mark)
+{
+    using SC = SplitCfg<LOGN>;
+    constexpr bool CUT = KsWaves<LOGN>::PARITY_CUT;
+    // the chunk's digit x modulus products against the 256 MB Infinity Cache: beyond it, stream them (may_stream: the
+    // small-batch launches never did and do not)
+    const int stream_x = may_stream && (size_t)n * L * (L + 1) * SC::N * 8 > ((size_t)256 << 20) ? 1 : 0;
+    mark(2);
+    hipLaunchKernelGGL((ks_ntt_digits_kernel<LOGN, CUT>), dim3(group_grid(n * L, L)), dim3(SC::T), SC::LDS_BYTES, s, T, L,
+                       n * L, stream_x | order_flags, scr);
+    mark(3);
+    const dim3 grid(SC::N / 2 / 256, L + 1, (n + 1) / 2);
+    if (stream_x)
+        hipLaunchKernelGGL((ks_mac_kernel<true, CUT>), grid, dim3(256), 0, s, T, batch, L, rl, n, scr);
+    else
+        hipLaunchKernelGGL((ks_mac_kernel<false, CUT>), grid, dim3(256), 0, s, T, batch, L, rl, n, scr);
+}
+
 template <int LOGN>
 static hipError_t launch_keyswitch_chunk_t(const DevTables &T, int L, int n, const KsItem *batch, bool relin,
                                            const KsScratch &scr, bool alias, const KsSmallItems *small, int quarter,
@@ -1706,13 +1839,15 @@ static hipError_t launch_keyswitch_chunk_t(const DevTables &T, int L, int n, con
         set_lds(ks_intt_digits_kernel<LOGN>, lds);
         set_lds(ks_intt_digits_small_kernel<LOGN>, lds);
         set_lds(ks_ntt_digits_kernel<LOGN>, lds);
+        set_lds(ks_ntt_digits_kernel<LOGN, KsWaves<LOGN>::PARITY_CUT>, lds);
         set_lds(ks_moddown_intt_kernel<LOGN>, lds);
         set_lds(ks_moddown_finish_kernel<LOGN>, lds);
         if (getenv("HEFX_DEBUG")) {
             int nb = -1;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ks_ntt_digits_kernel<LOGN>, SC::T, lds);
-            fprintf(stderr, "[hefx] ks_ntt_digits_kernel<%d>: %d threads, %zu B LDS -> %d workgroups/CU\n", LOGN, SC::T,
-                    lds, nb);
+            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ks_ntt_digits_kernel<LOGN, KsWaves<LOGN>::PARITY_CUT>,
+                                                               SC::T, lds);
+            fprintf(stderr, "[hefx] ks_ntt_digits_kernel<%d, %d>: %d threads, %zu B LDS -> %d workgroups/CU\n", LOGN,
+                    (int)KsWaves<LOGN>::PARITY_CUT, SC::T, lds, nb);
         }
     }
     const int rl = relin ? 1 : 0;
@@ -1802,16 +1937,15 @@ static hipError_t launch_keyswitch_chunk_t(const DevTables &T, int L, int n, con
         else
             hipLaunchKernelGGL((ks_intt_digits_small_kernel<LOGN>), dim3(split_grid(n * L)), dim3(SC::T), lds, s, T, *small,
                                const_cast<KsItem *>(batch), n, L, rl, n * L, scr);
-        mark(2);
-        if (quarter & KS_Q_NTT)
+        if (quarter & KS_Q_NTT) {
+            mark(2);
             hipLaunchKernelGGL((ks_ntt_digits_q_kernel<LOGN>), fan_grid(n * L, 4 * L), dim3(TQ), ldsq, s, T, L,
                                n * L, scr);
-        else
-            hipLaunchKernelGGL((ks_ntt_digits_kernel<LOGN>), dim3(group_grid(n * L, L)), dim3(SC::T), lds, s, T, L,
-                               n * L, heavy_order, scr);
-        mark(3);
-        hipLaunchKernelGGL(ks_mac_kernel<false>, dim3(SC::N / 2 / 256, L + 1, (n + 1) / 2), dim3(256), 0, s, T, batch, L, rl, n,
-                           scr);
+            mark(3);
+            hipLaunchKernelGGL(ks_mac_kernel<false>, dim3(SC::N / 2 / 256, L + 1, (n + 1) / 2), dim3(256), 0, s, T, batch, L,
+                               rl, n, scr);
+        } else
+            launch_digits_and_mac<LOGN>(T, L, n, batch, rl, heavy_order, false, scr, s, mark);
         mark(4);
         if (quarter & KS_Q_MDI)
             hipLaunchKernelGGL((ks_moddown_intt_q_kernel<LOGN>), dim3(quarter_grid(n * 2)), dim3(TQ), ldsq, s, T, L, n * 2,
@@ -1840,18 +1974,7 @@ static hipError_t launch_keyswitch_chunk_t(const DevTables &T, int L, int n, con
     else
         hipLaunchKernelGGL((ks_intt_digits_kernel<LOGN>), dim3(split_grid(n * L)), dim3(SC::T), lds, s, T, batch, L, rl, 0,
                            n * L, scr);
-    mark(2);
-    // the chunk's digit x modulus products against the 256 MB Infinity Cache: beyond it, stream them
-    const int stream_x = (size_t)n * L * (L + 1) * SC::N * 8 > ((size_t)256 << 20) ? 1 : 0;
-    hipLaunchKernelGGL((ks_ntt_digits_kernel<LOGN>), dim3(group_grid(n * L, L)), dim3(SC::T), lds, s, T, L, n * L,
-                       stream_x | heavy_order, scr);
-    mark(3);
-    if (stream_x)
-        hipLaunchKernelGGL(ks_mac_kernel<true>, dim3(SC::N / 2 / 256, L + 1, (n + 1) / 2), dim3(256), 0, s, T, batch, L, rl, n,
-                           scr);
-    else
-        hipLaunchKernelGGL(ks_mac_kernel<false>, dim3(SC::N / 2 / 256, L + 1, (n + 1) / 2), dim3(256), 0, s, T, batch, L, rl, n,
-                           scr);
+    launch_digits_and_mac<LOGN>(T, L, n, batch, rl, heavy_order, true, scr, s, mark);
     mark(4);
     hipLaunchKernelGGL((ks_moddown_intt_kernel<LOGN>), dim3(split_grid(n * 2)), dim3(SC::T), lds, s, T, L, n * 2, scr);
     mark(5);

@@ -823,6 +823,80 @@ __device__ __forceinline__ void split_fwd(u64 (&v)[16], const LD &ld, const InMo
         split_fwd_a<LOGN, ArithU64, LD, NB, MACOP>(v, ld, mode, mc, lds, nt.tw, ArithU64::make(mc), t, h, t0);
 }
 
+// ---- forward transform cut by coefficient parity (the digit transforms of the key switch) ------------------------------
+// Stages 0 .. LOGN-2 of the size-2^LOGN transform have even gaps: they never leave a parity class of positions, and on the
+// class {2k + h} they are a whole transform of size 2^(LOGN-1) over the first N/2 entries of the same twiddle table
+// (ntt_fwd_core<LOGN-1>, pre = 1).  A workgroup that owns class h therefore loads its OWN N/2 coefficients -- with the
+// split by output half (split_fwd_raw) both workgroups of a row load and convert all N words and both compute the first
+// stage -- and leaves out the LAST stage, which pairs positions (2k, 2k+1) = (E[k], O[k]) of the two classes:
+//     row[2k] = E[k] + w_k O[k],   row[2k+1] = E[k] - w_k O[k],   w_k = tw[N/2 + k].
+// That butterfly is the reader's (the key MAC owns exactly such a pair per thread, hefx_keyswitch.hip mac_items).
+// ld(r) delivers the raw word of the class's coefficient idx_nat(t,r); on return f[r] is the UNFINISHED class value at
+// position idx_io(t,r) of the class (its size-N/2 transform's bit-reversed order).
+// Ranges on return: FP64 |f| < 2^41 + (LOGN-1) * 0.52q (the word itself rides the sum path; a reduced one starts below
+// 0.52q + 2^32); integer [0,8q), L16 [0,16q) -- the cores' own bounds, entered with words below q.
+template <int LOGN, class A, class LD>
+__device__ __forceinline__ void parity_fwd_raw(typename A::V (&f)[16], const LD &ld, const InMode &mode,
+                                               const ModConst &mc, u64 *lds, const typename A::TW *__restrict__ tw,
+                                               const typename A::Ctx &cx, int t)
+{
+    u64 x[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) x[r] = ld(r);
+    if (A::IS_F64 ? mode.red_f64 : mode.red_int) {  // uniform per workgroup, as in split_fwd_raw
+#pragma unroll
+        for (int r = 0; r < 16; ++r) f[r] = A::template input<1>(x[r], mode, cx, mc);
+    } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) f[r] = A::template input<0>(x[r], mode, cx, mc);
+    }
+    ntt_fwd_core<LOGN - 1, A>(f, reinterpret_cast<typename A::V *>(lds), tw, cx, t, 1);
+    using C = NttCfg<LOGN - 1>;
+    if constexpr (C::R == 0) {  // idx_out -> idx_io through LDS, as in split_fwd_raw
+        typename A::V *lf = reinterpret_cast<typename A::V *>(lds);
+        const int pw = 17 * t, pr = 2 * t + (t >> 3);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) lf[pw + r] = f[r];
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < 16; ++r) f[r] = lf[pr + (2 * C::T + C::T / 8) * (r >> 1) + (r & 1)];  // phys(idx_io(t, r))
+    }
+}
+
+// What the cut's producer hands the key MAC for a target modulus, by the MAC's arithmetic policy (hefx_keyswitch.hip
+// mac_kind): the consumer runs the last stage in the SAME forward policy and reduces once, after it.
+//   MAC_F  FP64 rows: the unfinished doubles, as the finished rows are handed over today
+//   MAC_L  limb MAC (prime below 2^60, hence the L16 transform): the unfinished words, below 16q -- no reduction here at all
+//   MAC_W  wide MAC: canonical words (the consumer's [0,8q) butterfly takes them whatever the prime)
+enum { MAC_F = 0, MAC_L = 1, MAC_W = 2 };
+template <int LOGN, class A, class LD>
+__device__ __forceinline__ void parity_fwd_a(u64 (&v)[16], const LD &ld, const InMode &mode, const ModConst &mc, u64 *lds,
+                                             const typename A::TW *__restrict__ tw, const typename A::Ctx &cx, int t,
+                                             int kind)
+{
+    typename A::V f[16];
+    parity_fwd_raw<LOGN, A, LD>(f, ld, mode, mc, lds, tw, cx, t);
+    if (A::IS_F64 || kind == MAC_L) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) v[r] = A::raw(f[r]);
+    } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) v[r] = A::fwd_finish(f[r], cx);
+    }
+}
+template <int LOGN, class LD>
+__device__ __forceinline__ void parity_fwd(u64 (&v)[16], const LD &ld, const InMode &mode, u64 *lds, const NttTables &nt,
+                                           const ModConst &mc, const ModConstF &mf, int t, int kind)
+{
+    if (mf.q != 0.0)
+        parity_fwd_a<LOGN, ArithF64, LD>(v, ld, mode, mc, lds, nt.twf, ArithF64::make(mf), t, kind);
+    else
+        fwd_int_dispatch(mc, [&](auto pol) {
+            using A = decltype(pol);
+            parity_fwd_a<LOGN, A, LD>(v, ld, mode, mc, lds, nt.tw, A::make(mc), t, kind);
+        });
+}
+
 // Inverse split: a0[r], a1[r] = canonical NTT values at positions 2j, 2j+1 with j = idx_out(t,r) of the
 // sub-transform (fetched as lane-adjacent records and exchanged through LDS when R == 0); on return v[r] = coefficient 2*idx_nat(t,r) + h, canonical.
 // `ldp(j)` delivers the row's (value[2j], value[2j+1]) record -- a plain 16-byte load, or a Galois-gathered one
