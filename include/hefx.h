@@ -164,6 +164,20 @@ int hefx_square(hefx_context *ctx, int L, const uint64_t *d_a, uint64_t *d_out3,
  * pointers; d_b may repeat one ciphertext; outputs must not alias inputs. */
 int hefx_multiply_batch(hefx_context *ctx, int L, int n, const uint64_t *const *d_a, const uint64_t *const *d_b,
                         uint64_t *const *d_out3, void *stream);
+/* Sums of size 2 x size 2 products in one pass -- the product loop and add_many of Linear_Transform_Cipher
+ * (helper.h:222,228,231) and sum_k A_k * B_k of CC_Matrix_Multiplication (matrix_multiplication.cpp:123-129):
+ * for g in [0, ceil(n/group)):
+ *   d_out3[g] = sum_{i in [g*group, min(n,(g+1)*group))} d_a[i] * d_b[i]      (not relinearised; mod q_j per row)
+ * d_a[i], d_b[i]: [2][L][N]; d_out3[g]: [3][L][N] = (sum a0 b0, sum (a0 b1 + a1 b0), sum a1 b1).  The canonical residues of
+ * the sums, i.e. the bits of n multiply calls followed by add_many per group.  Host arrays of device pointers.  Inputs
+ * are only read: d_a[i] == d_b[i] (a square) and operands repeated across terms are fine.  No output may overlap, in
+ * BYTES (views of one allocation included), an input of the call or another output: HEFX_ERR_INVALID before anything is
+ * submitted.  A group is one pass of one launch as long as its 2 * group + 1 pointers fit a descriptor-ring slot (10240
+ * pointers: groups of up to 5119 terms); a longer group is summed in slot-sized parts into the context's scratch buffer and
+ * the parts are added with hefx_add_many (size 3) -- same words -- for up to 96 parts; beyond that (more than 491 424
+ * terms in one group) the call returns HEFX_ERR_UNSUPPORTED "group too long" before anything is submitted. */
+int hefx_multiply_sum(hefx_context *ctx, int L, int n, int group, const uint64_t *const *d_a,
+                      const uint64_t *const *d_b, uint64_t *const *d_out3, void *stream);
 
 /* ---- K5/K6/K7: Evaluator::apply_galois_inplace = Galois permutation + key switch (one term of
  *      rotate_vector; helper.h:216,227,244,255,316,352,455,474; 5_rotation.cpp:215).
@@ -294,6 +308,17 @@ int hefx_linear_transform_plain(hefx_context *ctx, int L, const uint64_t *d_ct, 
 int hefx_linear_transform_plain_many(hefx_context *ctx, int L, int count, const uint64_t *const *d_cts, int d,
                                      const uint64_t *const *d_diag_pts, int nkeys, const uint32_t *key_elts,
                                      const uint64_t *const *d_keys, uint64_t *const *d_outs, void *stream);
+/* Linear_Transform_Cipher(ct, U_diagonals[d], gal_keys) (helper.h:212-234; linear_transformation.cpp's "C_vec . C_mat")
+ * as one call: ct_new = ct + rotate(ct, -d) (:216-219); d_out3 = sum_l rotate(ct_new, l) * d_diag_cts[l] (:222-231), the
+ * products NOT relinearised.  d_ct, d_diag_cts[l]: [2][L][N]; d_out3: [3][L][N], overlapping (in bytes) neither d_ct nor a
+ * diagonal -- HEFX_ERR_INVALID before anything is submitted otherwise.  Rotation semantics, the missing-key and
+ * step-range errors and their texts are those of hefx_linear_transform_plain, and so are the two lanes of a large
+ * forest and the exact hoisting of wide one-source depths; with no plaintext to fuse, a rotation shared by several steps
+ * (a NAF prefix that is itself a step) is computed once.  The d products and their sum are one hefx_multiply_sum.
+ * Bit-identical to the op-by-op sequence. */
+int hefx_linear_transform_cipher(hefx_context *ctx, int L, const uint64_t *d_ct, int d,
+                                 const uint64_t *const *d_diag_cts, int nkeys, const uint32_t *key_elts,
+                                 const uint64_t *const *d_keys, uint64_t *d_out3, void *stream);
 
 /* ---- A FOREST of rotations in one call: node i rotates the result of node parent[i] (parent[i] < 0: the ciphertext
  *      d_ext_in[i]) by galois_elts[i] with d_keys[i] into d_out[i]; a non-NULL d_pts[i] multiplies the rotated ciphertext

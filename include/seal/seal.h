@@ -3065,6 +3065,39 @@ public:
         dest.set(out, c0.size(), c0.rows, c0.parms_id(), ns);
     }
 
+    // ---- EXTENSION: add_many(multiply(as[i], bs[i])) in one pass over the operands (hefx_multiply_sum) -- the product
+    // loop and sum of Linear_Transform_Cipher (helper.h:222-231) and sum_k A_k * B_k (matrix_multiplication.cpp:123-129),
+    // not relinearised (dest has size 3), with the checks, exceptions and result bits of the op-by-op form: every
+    // multiply first, then add_many over the products.
+    void hefx_multiply_sum(const std::vector<Ciphertext> &as, const std::vector<Ciphertext> &bs, Ciphertext &dest) const
+    {
+        if (as.empty()) throw std::invalid_argument("encrypteds cannot be empty");
+        if (as.size() != bs.size()) throw std::invalid_argument("hefx_multiply_sum: need as many second operands as first operands");
+        if (!ctx_->is_ckks()) throw std::invalid_argument("unsupported scheme");
+        std::vector<const std::uint64_t *> ap, bp;
+        for (std::size_t i = 0; i < as.size(); ++i) {  // Evaluator::multiply, term by term
+            check_ct(as[i]);
+            check_ct(bs[i]);
+            if (as[i].parms_id() != bs[i].parms_id()) throw std::invalid_argument("encrypted1 and encrypted2 parameter mismatch");
+            if (as[i].size() != 2 || bs[i].size() != 2)
+                throw std::invalid_argument("multiply: only size-2 operands are built (every reference call site)");
+            check_scale(as[i].scale() * bs[i].scale(), as[i].parms_id());
+            ap.push_back(as[i].buf->p);
+            bp.push_back(bs[i].buf->p);
+        }
+        const Ciphertext &a0 = as[0];
+        const double ns = a0.scale() * bs[0].scale();
+        for (std::size_t i = 1; i < as.size(); ++i) {  // Evaluator::add_many over the products
+            if (as[i].parms_id() != a0.parms_id()) throw std::invalid_argument("encrypted1 and encrypted2 parameter mismatch");
+            if (!close(as[i].scale() * bs[i].scale(), ns)) throw std::invalid_argument("scale mismatch");
+        }
+        auto out = shim::new_buf(eng(), words(3, a0.rows));
+        std::uint64_t *op = out->p;
+        shim::check(::hefx_multiply_sum(eng()->live(), a0.rows, (int)ap.size(), (int)ap.size(), ap.data(), bp.data(), &op,
+                                        nullptr));
+        dest.set(out, 3, a0.rows, a0.parms_id(), ns);
+    }
+
     // ---- EXTENSION: Linear_Transform_Plain in baby-step / giant-step form (hefx_linear_transform_plain_bsgs):
     // `shifted_diags[l]` encodes diagonal l shifted right by (l / n1) * n1 slots; gk holds direct keys for -d (or its
     // NAF terms), 1..n1-1 and n1, 2*n1, ...  n1 + ceil(d/n1) - 2 key switches instead of d - 1; a fast mode like the

@@ -357,11 +357,42 @@ def linear_transform_cipher(ev: Evaluator, ct: Ciphertext, U_diagonals: Sequence
                             gal_keys: KSwitchKeys) -> Ciphertext:
     """Linear_Transform_Cipher, helper.h:212-234: ct x ct products are NOT relinearized (size-3 sum)."""
     d = len(U_diagonals)
+    native = getattr(ev.be, "linear_transform_cipher", None)
+    if native is not None and d:  # the HIP engine: the whole composition behind one C-ABI call, same bits as below
+        return _linear_transform_cipher_native(ev, native, ct, U_diagonals, gal_keys)
     ct_new = ev.add(ct, ev.rotate_vector(ct, -d, gal_keys))          # :216-219
     rots = _rotations_batched(ev, ct_new, list(range(1, d)), gal_keys)
     res = [ev.multiply(ct_new, U_diagonals[0])]                      # :222
     res += [ev.multiply(r, U_diagonals[l + 1]) for l, r in enumerate(rots)]   # :227-228
     return ev.add_many(res)                                          # :231
+
+
+def _linear_transform_cipher_native(ev: Evaluator, native, ct: Ciphertext, U_diagonals: Sequence[Ciphertext],
+                                    gal_keys: KSwitchKeys) -> Ciphertext:
+    """The checks of the op-by-op path (SEAL's exceptions: rotate_vector, multiply per diagonal, add_many), arithmetic in
+    hefx_linear_transform_cipher; missing keys / too large steps come back from the engine with SEAL's messages.
+    One difference in ORDER, as in _linear_transform_plain_native: the operand checks run here, before the engine plans
+    the rotations, so an input with two faults -- say a missing Galois key AND a diagonal at another scale -- raises the
+    operand's exception where the loop, which rotates first, raises the key's.  Every single fault raises what the loop
+    raises."""
+    L = ct.parms_id()
+    if ct.size() != 2:
+        raise ValueError("encrypted size must be 2")
+    for u in U_diagonals:                                            # Evaluator::multiply(rotation, diagonal)
+        ev._check_same(ct, u)
+        if u.size() != 2:
+            raise ValueError("multiply: only size-2 operands are supported (all reference call sites)")
+        ev._check_scale(ct.scale * u.scale, L)
+    scale = ct.scale * U_diagonals[0].scale
+    for u in U_diagonals[1:]:                                        # Evaluator::add_many over the products
+        if not ev._close(scale, ct.scale * u.scale):
+            raise ValueError("scale mismatch")
+    elts, keys = _native_key_args(gal_keys)
+    diag = [u.data for u in U_diagonals]
+    if hasattr(diag[0], "ptr"):
+        from . import capi
+        diag = capi.ptr_array([x.ptr for x in diag])
+    return Ciphertext()._set(native(L, ct.data, diag, elts, keys), 3, L, scale)
 
 
 def linear_transform_ciphermatrix_plainvector(ev: Evaluator, pt_rotations: Sequence[Plaintext],
@@ -434,9 +465,10 @@ def compute_all_powers(ev: Evaluator, ct: Ciphertext, degree: int, relin_keys: K
 
 def _matmul_step3(ev: Evaluator, ctA0: Ciphertext, ctB0: Ciphertext, ctAk: List[Ciphertext],
                   ctBk: List[Ciphertext]) -> Ciphertext:
-    """matrix_multiplication.cpp:69-129: rescale the 2(n-1) transforms, A0*B0 + sum_k A_k*B_k.  The rescales and the
-    products of the n-1 pairs are independent, so each kind is one launch over its list; the chain of add_inplace
-    (:128) is one n-way sum -- canonical residues of the same integers, hence the same bits."""
+    """matrix_multiplication.cpp:69-129: rescale the 2(n-1) transforms, A0*B0 + sum_k A_k*B_k.  The rescales are
+    independent, so they are one launch over their list; the n-1 products and the chain of add_inplace (:127-128) are
+    one fused sum (Evaluator.multiply_sum: no product is written) to which ctAB is added -- canonical residues of the
+    same integers, hence the same bits."""
     ev.rescale_to_next_many_inplace(list(ctAk) + list(ctBk))         # :69-73 (one launch pair over both families)
     ctAB = ev.multiply(ctA0, ctB0)                                   # :104
     ev.mod_switch_to_next_inplace(ctAB)                              # :112
@@ -444,7 +476,7 @@ def _matmul_step3(ev: Evaluator, ctA0: Ciphertext, ctB0: Ciphertext, ctAk: List[
         c.scale = 2.0 ** int(np.log2(c.scale))                       # :117-121 "manual rescale"
     if not ctAk:
         return ctAB
-    return ev.add_many([ctAB] + ev.multiply_many(ctAk, ctBk))        # :123-129
+    return ev.add(ctAB, ev.multiply_sum(ctAk, ctBk)[0])              # :123-129 (products and their sum in one pass)
 
 
 def _linear_transforms_of_one_input(ev: Evaluator, ct: Ciphertext, diag_sets: Sequence[Sequence[Plaintext]],

@@ -66,6 +66,7 @@ _SIGS = {
     "hefx_multiply": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "hefx_square": (_i, [_vp, _i, _vp, _vp, _vp]),
     "hefx_multiply_batch": (_i, [_vp, _i, _i, _pp, _pp, _pp, _vp]),
+    "hefx_multiply_sum": (_i, [_vp, _i, _i, _i, _pp, _pp, _pp, _vp]),
     "hefx_apply_galois": (_i, [_vp, _i, _vp, _u32, _vp, _vp, _vp]),
     "hefx_apply_galois_batch": (_i, [_vp, _i, _i, _pp, C.POINTER(_u32), _pp, _pp, _vp]),
     "hefx_rotate_multiply_plain_batch": (_i, [_vp, _i, _i, _pp, C.POINTER(_u32), _pp, _pp, _pp, _vp]),
@@ -92,6 +93,7 @@ _SIGS = {
     "hefx_allreduce_sum": (_i, [_vp, _i, _i, _vp, _vp]),
     "hefx_linear_transform_plain": (_i, [_vp, _i, _vp, _i, _pp, _i, C.POINTER(_u32), _pp, _vp, _vp]),
     "hefx_linear_transform_plain_many": (_i, [_vp, _i, _i, _pp, _i, _pp, _i, C.POINTER(_u32), _pp, _pp, _vp]),
+    "hefx_linear_transform_cipher": (_i, [_vp, _i, _vp, _i, _pp, _i, C.POINTER(_u32), _pp, _vp, _vp]),
     "hefx_rotate_hoisted_batch": (_i, [_vp, _i, _vp, _i, C.POINTER(_u32), _pp, _pp, _pp, _vp]),
     "hefx_linear_transform_plain_hoisted": (_i, [_vp, _i, _vp, _i, _pp, _i, C.POINTER(_u32), _pp, _vp, _vp]),
     "hefx_linear_transform_plain_hoisted2": (_i, [_vp, _i, _vp, _i, _pp, _i, C.POINTER(_u32), _pp, _vp, _vp]),

@@ -1005,6 +1005,85 @@ extern "C" int hefx_square(hefx_context *c, int L, const uint64_t *a, uint64_t *
     return hefx_multiply(c, L, a, a, out3, stream);
 }
 
+// the launches of hefx_multiply_sum for validated arguments whose groups fit a table slice (2 * group + 1 pointers): the
+// pointer table travels through a ring slot of the key-switch descriptors, whole groups per slice
+static int mul_sum_submit(hefx_context *c, int L, int n, int group, const uint64_t *const *a, const uint64_t *const *b,
+                          uint64_t *const *outs, hipStream_t s)
+{
+    constexpr int TABLE_MAX = (int)(sizeof(KsItem) * KS_MAX_CHUNK / sizeof(void *));
+    const int groups = (n + group - 1) / group;
+    const int gps = TABLE_MAX / (2 * group + 1);  // groups per slice
+    for (int g0 = 0; g0 < groups; g0 += gps) {
+        const int ng = groups - g0 < gps ? groups - g0 : gps;
+        const int i0 = g0 * group, cnt = (n - i0 < ng * group) ? n - i0 : ng * group;
+        const unsigned slot = c->ring_next++ % KS_RING;
+        if (c->ring_busy[slot]) HIPCHK(hipEventSynchronize(c->ring_ev[slot]));
+        const uint64_t **hp = reinterpret_cast<const uint64_t **>(c->h_items + (size_t)slot * KS_MAX_CHUNK);
+        const u64 *const *dp = reinterpret_cast<const u64 *const *>(c->d_items + (size_t)slot * KS_MAX_CHUNK);
+        for (int i = 0; i < cnt; ++i) {
+            hp[i] = a[i0 + i];
+            hp[cnt + i] = b[i0 + i];
+        }
+        for (int g = 0; g < ng; ++g) hp[2 * cnt + g] = outs[g0 + g];
+        HIPCHK(hipMemcpyAsync((void *)dp, hp, sizeof(void *) * (2 * (size_t)cnt + ng), hipMemcpyHostToDevice, s));
+        HIPCHK(launch_mul_sum(c->T, L, dp, cnt, group, s));
+        HIPCHK(hipEventRecord(c->ring_ev[slot], s));
+        c->ring_busy[slot] = true;
+    }
+    return HEFX_OK;
+}
+
+extern "C" int hefx_multiply_sum(hefx_context *c, int L, int n, int group, const uint64_t *const *a,
+                                 const uint64_t *const *b, uint64_t *const *outs, void *stream)
+{
+    CTXCHK(c);
+    if (int rc = check_level(c, L)) return rc;
+    if (n < 1 || group < 1 || !a || !b || !outs) return fail(HEFX_ERR_INVALID, "bad multiply_sum arguments");
+    if (group > n) group = n;
+    const int groups = (n + group - 1) / group;
+    for (int i = 0; i < n; ++i)
+        if (!a[i] || !b[i]) return fail(HEFX_ERR_INVALID, "null operand in multiply_sum");
+    for (int g = 0; g < groups; ++g)
+        if (!outs[g]) return fail(HEFX_ERR_INVALID, "null output in multiply_sum");
+    // The groups of one launch run side by side and a lane writes its words of a sum after reading every term, so no
+    // output may reach into an input (of any group) or into another output.  Checked on BYTE RANGES, like the key-switch
+    // batches (callers hand out views of one allocation), before anything is submitted.
+    {
+        const size_t row = (size_t)c->n * sizeof(u64), out_b = 3 * (size_t)L * row, in_b = 2 * (size_t)L * row;
+        std::vector<uintptr_t> o((size_t)groups);
+        for (int g = 0; g < groups; ++g) o[(size_t)g] = (uintptr_t)outs[g];
+        std::sort(o.begin(), o.end());
+        for (int g = 1; g < groups; ++g)
+            if (o[(size_t)g - 1] + out_b > o[(size_t)g]) return fail(HEFX_ERR_INVALID, "multiply_sum: two outputs overlap");
+        auto hits = [&](const void *p) {
+            const uintptr_t x = (uintptr_t)p;
+            auto it = std::upper_bound(o.begin(), o.end(), x);
+            if (it != o.begin() && *(it - 1) + out_b > x) return true;
+            return it != o.end() && *it < x + in_b;
+        };
+        for (int i = 0; i < n; ++i)
+            if (hits(a[i]) || hits(b[i])) return fail(HEFX_ERR_INVALID, "multiply_sum: an output overlaps an input");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    constexpr int TABLE_MAX = (int)(sizeof(KsItem) * KS_MAX_CHUNK / sizeof(void *));
+    // A group longer than one table slice (2 * group + 1 pointers): slice-sized parts' sums land in scratch and
+    // hefx_add_many (size 3) adds them, as hefx_multiply_plain_sum does -- canonical residues of the same integer sums.
+    // At most 2 * ADD_MANY_GROUP parts per group: the sums hefx_add_many forms without a scratch level of its own.
+    const int part = 2 * group + 1 > TABLE_MAX ? (TABLE_MAX - 1) / 2 : group;
+    if (part >= group) return mul_sum_submit(c, L, n, group, a, b, outs, s);
+    if ((group + part - 1) / part > 2 * ADD_MANY_GROUP) return fail(HEFX_ERR_UNSUPPORTED, "multiply_sum: group too long");
+    const size_t words = 3 * (size_t)L * c->n;
+    for (int g = 0; g < groups; ++g) {
+        const int i0 = g * group, len = (n - i0 < group) ? n - i0 : group, nparts = (len + part - 1) / part;
+        if (int rc = ensure_scratch(c, words * nparts)) return rc;
+        std::vector<uint64_t *> pp((size_t)nparts);
+        for (int t = 0; t < nparts; ++t) pp[(size_t)t] = reinterpret_cast<uint64_t *>(c->scratch + (size_t)t * words);
+        if (int rc = mul_sum_submit(c, L, len, part, a + i0, b + i0, pp.data(), s)) return rc;
+        if (int rc = hefx_add_many(c, L, 3, nparts, pp.data(), outs[g], stream)) return rc;
+    }
+    return HEFX_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Galois tables: out[i] = in[ bitrev(((elt*(2*bitrev(i)+1)) mod 2N - 1)/2) ]
 // ---------------------------------------------------------------------------------------------
@@ -2332,6 +2411,74 @@ static int run_forest(hefx_context *c, int L, const std::vector<ForestNode> &nod
     return lane_rc;
 }
 
+// Parts shared by lt_impl and hefx_linear_transform_cipher.
+// ct_new(t) = cts[t] + rotate(cts[t], -d) for `count` inputs in lockstep (helper.h:216-219 / :244-247): `first` is the plan of
+// the -d rotation; input t owns head + t * stride: ping at +0, pong at +ctw, ct_new at +2 ctw.  The sum rides in the epilogue
+// of the chain's last key switch (acc_out = acc_in + rotation, the kernels of hefx_apply_galois_add_batch): one launch
+// less than rotate + add
+static int lt_ct_new(hefx_context *c, int L, int count, const uint64_t *const *cts, const std::vector<uint32_t> &first, const LtKeys &K,
+                     uint64_t *head, size_t stride, size_t ctw, void *stream)
+{
+    std::vector<const uint64_t *> src((size_t)count), kk((size_t)count), ain((size_t)count);
+    std::vector<uint64_t *> dst((size_t)count), aout((size_t)count);
+    std::vector<uint32_t> ee((size_t)count);
+    for (int t = 0; t < count; ++t) src[(size_t)t] = cts[t], ain[(size_t)t] = cts[t], aout[(size_t)t] = head + (size_t)t * stride + 2 * ctw;
+    for (size_t s = 0; s < first.size(); ++s) {
+        const bool last = s + 1 == first.size();
+        for (int t = 0; t < count; ++t) {
+            dst[(size_t)t] = head + (size_t)t * stride + ((s & 1) ? ctw : 0);
+            kk[(size_t)t] = K.at(first[s]);
+            ee[(size_t)t] = first[s];
+        }
+        if (int rc = ks_run(c, L, count, false, src.data(), ee.data(), kk.data(), nullptr, nullptr, dst.data(), stream, false,
+                            last ? ain.data() : nullptr, last ? aout.data() : nullptr))
+            return rc;
+        for (int t = 0; t < count; ++t) src[(size_t)t] = dst[(size_t)t];
+    }
+    if (first.empty())  // d == 0 mod N/2 cannot happen (lt_plan refuses it); kept for completeness: ct_new = ct + ct
+        for (int t = 0; t < count; ++t)
+            if (int rc = hefx_add(c, L, 2, 1, cts[t], cts[t], aout[(size_t)t], stream)) return rc;
+    return HEFX_OK;
+}
+// plans[1..d) -> a forest of key-switch nodes rooted at ct_new; leaf[l] = the node that holds rotate(ct_new, l).
+// fuse_diagonals (the plain transform): a plan's last node carries diagonal l's product, so nodes de-duplicate per
+// (parent, element, fused diagonal); without (the cipher transform) per (parent, element) alone, and the leaf of one
+// step may be the prefix of another.  Returns the forest's depth.
+struct LtNode {
+    int parent;  // -1: ct_new
+    uint32_t elt;
+    int fused;   // diagonal index whose plaintext multiplies this node's output, or -1
+    int depth;
+};
+static int lt_forest(const std::vector<std::vector<uint32_t>> &plans, int d, bool fuse_diagonals, std::vector<LtNode> &nodes,
+                     std::vector<int> &leaf)
+{
+    // (parent node + 1, element, fused diagonal + 1) packed into 64 bits: parent < 2^22 nodes, element < 2^16 (N <= 32768),
+    // diagonal < 2^22
+    std::unordered_map<uint64_t, int> index;
+    index.reserve((size_t)d * 2);
+    nodes.reserve((size_t)d * 2);
+    leaf.assign((size_t)d, -1);
+    int max_depth = 0;
+    for (int l = 1; l < d; ++l) {
+        const std::vector<uint32_t> &plan = plans[(size_t)l];
+        int cur = -1;
+        for (size_t t = 0; t < plan.size(); ++t) {
+            const int fused = fuse_diagonals && t + 1 == plan.size() ? l : -1;
+            const uint64_t key = ((uint64_t)(cur + 1) << 42) | ((uint64_t)plan[t] << 24) | (uint64_t)(fused + 1);
+            auto it = index.find(key);
+            if (it == index.end()) {
+                nodes.push_back(LtNode{cur, plan[t], fused, (int)t});
+                it = index.emplace(key, (int)nodes.size() - 1).first;
+                if ((int)t + 1 > max_depth) max_depth = (int)t + 1;
+            }
+            cur = it->second;
+        }
+        leaf[(size_t)l] = cur;
+    }
+    return max_depth;
+}
+
 // `count` transforms with the same dimension and key set in lockstep (count = 1: hefx_linear_transform_plain): transform t
 // maps cts[t] with the diagonals diag_pts[t * d .. t * d + d) to outs[t].  The rotation plans are those of ONE transform;
 // every launch sequence -- the -d rotation, each depth of the rotation forest -- carries the items of all `count` inputs
@@ -2377,33 +2524,11 @@ static int lt_impl(hefx_context *c, int L, int count, const uint64_t *const *cts
     if (int rc = grow_retiring(c, &c->lt_head, &c->lt_head_cap, (size_t)count * 4 * ctw, 0, "linear-transform head")) return rc;
     uint64_t *head = reinterpret_cast<uint64_t *>(c->lt_head);
     auto ping = [&](int t) { return head + (size_t)t * 4 * ctw; };
-    auto pong = [&](int t) { return ping(t) + ctw; };
     auto ct_new = [&](int t) { return ping(t) + 2 * ctw; };
     auto prod0 = [&](int t) { return ping(t) + 3 * ctw; };
     // ---- ct_new = ct + rotate(ct, -d)      (helper.h:244-247): launched FIRST, so that the planning below (0.1 ms of host
-    // time at d = 512) runs beside it instead of in front of it.  The sum rides in the epilogue of the chain's last key
-    // switch (acc_out = acc_in + rotation, the kernels of hefx_apply_galois_add_batch): one launch less than rotate + add
-    {
-        std::vector<const uint64_t *> src((size_t)count), kk((size_t)count), ain((size_t)count);
-        std::vector<uint64_t *> dst((size_t)count), aout((size_t)count);
-        std::vector<uint32_t> ee((size_t)count);
-        for (int t = 0; t < count; ++t) src[(size_t)t] = cts[t], ain[(size_t)t] = cts[t], aout[(size_t)t] = ct_new(t);
-        for (size_t s = 0; s < first.size(); ++s) {
-            const bool last = s + 1 == first.size();
-            for (int t = 0; t < count; ++t) {
-                dst[(size_t)t] = (s & 1) ? pong(t) : ping(t);
-                kk[(size_t)t] = K.at(first[s]);
-                ee[(size_t)t] = first[s];
-            }
-            if (int rc = ks_run(c, L, count, false, src.data(), ee.data(), kk.data(), nullptr, nullptr, dst.data(), stream, false,
-                                last ? ain.data() : nullptr, last ? aout.data() : nullptr))
-                return rc;
-            for (int t = 0; t < count; ++t) src[(size_t)t] = dst[(size_t)t];
-        }
-        if (first.empty())  // d == 0 mod N/2 cannot happen (lt_plan refuses it); kept for completeness: ct_new = ct + ct
-            for (int t = 0; t < count; ++t)
-                if (int rc = hefx_add(c, L, 2, 1, cts[t], cts[t], ct_new(t), stream)) return rc;
-    }
+    // time at d = 512) runs beside it instead of in front of it (lt_ct_new)
+    if (int rc = lt_ct_new(c, L, count, cts, first, K, head, 4 * ctw, ctw, stream)) return rc;
     // ---- res[0] = ct_new * diag[0]         (helper.h:250): up to 96 diagonals the product is formed inside the final sum
     // (add_many_impl's pt0: one launch and the transparency bookkeeping of hefx_multiply_plain -- 15 us between the -d
     // rotation and the forest at d = 16, profiles/r06/lt_naf_d16_timeline_before.txt -- off the critical path); wider
@@ -2413,36 +2538,9 @@ static int lt_impl(hefx_context *c, int L, int count, const uint64_t *const *cts
         if (int rc = hefx_multiply_plain(c, L, 2, 1, ct_new(t), diag_pts[(size_t)t * d], prod0(t), stream)) return rc;
     lap("head submitted (rotate -d + add, product 0)");
     // ---- plans -> a forest of key-switch nodes rooted at ct_new, deduplicated per (parent, element, fused diagonal)
-    struct Node {
-        int parent;  // -1: ct_new
-        uint32_t elt;
-        int fused;   // diagonal index whose plaintext multiplies this node's output, or -1
-        int depth;
-    };
-    std::vector<Node> nodes;
-    // (parent node + 1, element, fused diagonal + 1) packed into 64 bits: parent < 2^22 nodes, element < 2^16 (N <= 32768),
-    // diagonal < 2^22
-    std::unordered_map<uint64_t, int> index;
-    index.reserve((size_t)d * 2);
-    nodes.reserve((size_t)d * 2);
-    std::vector<int> leaf(d, -1);
-    int max_depth = 0;
-    for (int l = 1; l < d; ++l) {
-        const std::vector<uint32_t> &plan = plans[(size_t)l];
-        int cur = -1;
-        for (size_t t = 0; t < plan.size(); ++t) {
-            const int fused = t + 1 == plan.size() ? l : -1;
-            const uint64_t key = ((uint64_t)(cur + 1) << 42) | ((uint64_t)plan[t] << 24) | (uint64_t)(fused + 1);
-            auto it = index.find(key);
-            if (it == index.end()) {
-                nodes.push_back(Node{cur, plan[t], fused, (int)t});
-                it = index.emplace(key, (int)nodes.size() - 1).first;
-                if ((int)t + 1 > max_depth) max_depth = (int)t + 1;
-            }
-            cur = it->second;
-        }
-        leaf[l] = cur;
-    }
+    std::vector<LtNode> nodes;
+    std::vector<int> leaf;
+    const int max_depth = lt_forest(plans, d, true, nodes, leaf);
     lap("forest");
     // ---- workspace, part 2: one ciphertext per node and input
     const size_t nn = nodes.size();
@@ -2456,7 +2554,7 @@ static int lt_impl(hefx_context *c, int L, int count, const uint64_t *const *cts
         std::vector<ForestNode> fn(nn * (size_t)count);
         for (int t = 0; t < count; ++t)
             for (size_t i = 0; i < nn; ++i) {
-                const Node &nd = nodes[i];
+                const LtNode &nd = nodes[i];
                 fn[(size_t)t * nn + i] = ForestNode{nd.parent < 0 ? -1 : (int)((size_t)t * nn) + nd.parent, nd.elt, nd.depth, ct_new(t),
                                                     K.at(nd.elt), nd.fused >= 0 ? diag_pts[(size_t)t * d + nd.fused] : nullptr,
                                                     node_ptr(t, (int)i)};
@@ -2536,6 +2634,66 @@ extern "C" int hefx_linear_transform_plain_hoisted(hefx_context *c, int L, const
 {
     return lt_impl(c, L, 1, &ct, d, diag_pts, nkeys, key_elts, keys, &out, stream, true);
 }
+// Linear_Transform_Cipher (helper.h:212-234) as one call, from the parts of lt_impl: the rotation plans, ct_new with its
+// sum in the last key switch's epilogue, the rotation forest on run_forest (two lanes for large forests, wide one-source
+// depths exactly hoisted) and the lt workspaces.  The diagonals are ciphertexts here, so no product rides in a key
+// switch's epilogue: the forest's nodes carry no plaintext and de-duplicate on (parent, element) alone -- the leaf of
+// one step may be the prefix of another -- and the d products and their sum (:222-231) are ONE hefx_multiply_sum over
+// (ct_new, leaves) x diagonals.  Every key switch is deterministic and the sum is the canonical residue of the same
+// integers: the bits of the reference's rotate_vector / multiply / add_many sequence.
+extern "C" int hefx_linear_transform_cipher(hefx_context *c, int L, const uint64_t *ct, int d, const uint64_t *const *diag_cts,
+                                            int nkeys, const uint32_t *key_elts, const uint64_t *const *keys, uint64_t *out3,
+                                            void *stream)
+{
+    CTXCHK(c);
+    if (int rc = check_ks_level(c, L)) return rc;
+    if (!ct || !out3 || d < 1 || !diag_cts || nkeys < 0 || (nkeys && (!key_elts || !keys)))
+        return fail(HEFX_ERR_INVALID, "bad linear-transform arguments");
+    for (int i = 0; i < d; ++i)
+        if (!diag_cts[i]) return fail(HEFX_ERR_INVALID, "null diagonal ciphertext");
+    LtKeys K;
+    for (int i = 0; i < nkeys; ++i)
+        if (!keys[i]) return fail(HEFX_ERR_INVALID, "null Galois key");
+    K.set(nkeys, key_elts, keys);
+    const size_t N = c->n, ctw = 2 * (size_t)L * N;
+    {  // the result may reach into no operand (byte ranges; refused before anything is submitted)
+        const uintptr_t o = (uintptr_t)out3, out_b = 3 * (size_t)L * N * sizeof(u64), in_b = ctw * sizeof(u64);
+        auto hits = [&](const void *p) { return (uintptr_t)p < o + out_b && o < (uintptr_t)p + in_b; };
+        if (hits(ct)) return fail(HEFX_ERR_INVALID, "linear transform: the output overlaps the input");
+        for (int i = 0; i < d; ++i)
+            if (hits(diag_cts[i])) return fail(HEFX_ERR_INVALID, "linear transform: the output overlaps a diagonal");
+    }
+    // plans of every step first: a missing key or a step too large is reported before anything runs, with SEAL's text
+    std::vector<uint32_t> first;
+    if (const char *err = lt_plan(-d, N, K, first)) return fail(HEFX_ERR_INVALID, err);
+    std::vector<std::vector<uint32_t>> plans((size_t)d);
+    for (int l = 1; l < d; ++l)
+        if (const char *err = lt_plan(l, N, K, plans[(size_t)l])) return fail(HEFX_ERR_INVALID, err);
+    // ---- ct_new = ct + rotate(ct, -d)      (helper.h:216-219), the sum in the epilogue of the chain's last key switch
+    if (int rc = grow_retiring(c, &c->lt_head, &c->lt_head_cap, 3 * ctw, 0, "linear-transform head")) return rc;
+    uint64_t *ct_new = reinterpret_cast<uint64_t *>(c->lt_head) + 2 * ctw;
+    if (int rc = lt_ct_new(c, L, 1, &ct, first, K, reinterpret_cast<uint64_t *>(c->lt_head), 3 * ctw, ctw, stream)) return rc;
+    // ---- plans -> a forest of key-switch nodes rooted at ct_new, one node per (parent, element): no diagonal is fused
+    std::vector<LtNode> nodes;
+    std::vector<int> leaf;
+    const int max_depth = lt_forest(plans, d, false, nodes, leaf);
+    std::vector<ForestNode> fn(nodes.size());
+    for (size_t i = 0; i < nodes.size(); ++i)
+        fn[i] = ForestNode{nodes[i].parent, nodes[i].elt, nodes[i].depth, ct_new, K.at(nodes[i].elt), nullptr, nullptr};
+    // ---- rotate(ct_new, l), l = 1..d-1     (helper.h:227), one workspace ciphertext per node
+    if (!fn.empty()) {
+        if (int rc = grow_retiring(c, &c->lt_ws, &c->lt_cap, ctw * fn.size(), 0, "linear-transform nodes")) return rc;
+        uint64_t *node0 = reinterpret_cast<uint64_t *>(c->lt_ws);
+        for (size_t i = 0; i < fn.size(); ++i) fn[i].out = node0 + i * ctw;
+        if (int rc = run_forest(c, L, fn, max_depth, stream, false)) return rc;
+    }
+    // ---- out = add_many(rotation_l * diag_l)   (helper.h:222,228,231) in one pass
+    std::vector<const uint64_t *> rot((size_t)d);
+    rot[0] = ct_new;
+    for (int l = 1; l < d; ++l) rot[(size_t)l] = leaf[(size_t)l] < 0 ? ct_new : fn[(size_t)leaf[(size_t)l]].out;
+    return hefx_multiply_sum(c, L, d, d, rot.data(), diag_cts, &out3, stream);
+}
+
 // Baby-step / giant-step Linear_Transform_Plain: with l = j*n1 + i,
 //   sum_l diag_l (.) rot_l(ct_new) = sum_j rot_(j*n1)( sum_i diag'_l (.) rot_i(ct_new) ),  diag'_l = diag_l shifted
 // right by j*n1 slots in the clear (the caller encodes them that way).  n1-1 baby rotations of ct_new (one hoisted

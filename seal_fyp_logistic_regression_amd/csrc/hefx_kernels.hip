@@ -323,6 +323,105 @@ hipError_t launch_mulplain_sum(const DevTables &T, int L, int size, const u64 *c
     return hipGetLastError();
 }
 
+// Grouped sum of size-2 x size-2 products, the ciphertext twin of mulplain_sum_kernel: group gi forms
+//   out3[gi] = sum_i a_i (x) b_i :  c0 = sum a0 b0,  c1 = sum (a0 b1 + a1 b0),  c2 = sum a1 b1
+// over its slice [gi*group, min(n,(gi+1)*group)) of a DEVICE pointer table laid out as  n a-pointers | n b-pointers |
+// groups outputs ([3][L][N] each).  The body of Linear_Transform_Cipher's product loop and sum (helper.h:222-231) and
+// of sum_k A_k (x) B_k (matrix_multiplication.cpp:123-129) in one pass: the 4 L N operand words of a term are read
+// once and only the sums are written, where n multiply + add_many write and re-read 3 L N words per term on top.
+// A lane owns 16 B of each output poly: six 128-bit accumulators.  a_i == b_i (a square) and operands repeated across
+// terms are fine: inputs are only read.
+// FOLD INTERVALS.  hefx_context_create refuses primes of 2^61 and above, so a residue is at most q - 1 < 2^61 and a
+// product below 2^122; an accumulator that was just folded holds a residue below 2^61.  P products on top of it stay
+// below P 2^122 + 2^61 <= 2^128 as long as P <= 63 (barrett128's quotient estimate is short by at most one for ANY
+// 128-bit value: the error of r = floor(2^128/q) costs x/2^128 < 1).  c0 and c2 take one product per term, c1 two, so c0
+// / c2 could go 63 terms and c1 31; the loop folds at the largest powers of two below that, where the test is a mask:
+// c0 / c2 every 32 terms, c1 every 16.  The loop advances four terms at a time and the tail adds at most three more
+// terms AFTER a group of fewer than 16 (32) unfolded ones, so no accumulator ever holds more than 32 products.  One final
+// Barrett per word gives the canonical residue of the integer sum -- the bits of the op-by-op sequence.
+__global__ __launch_bounds__(256) void mul_sum_kernel(DevTables T, int L, const u64 *const *__restrict__ tab, int n, int group)
+{
+    const int logn = T.logn;
+    const size_t poly_pairs = ((size_t)1 << (logn - 1)) * (size_t)L;
+    const int gi = blockIdx.y;
+    const int first = gi * group, last = first + group < n ? first + group : n;
+    ulonglong2 *__restrict__ out = reinterpret_cast<ulonglong2 *>((const_cast<u64 *>(tab[2 * n + gi])));
+    for (size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x; w < poly_pairs; w += (size_t)gridDim.x * blockDim.x) {
+        const ModConst mc = T.mods[(int)(w >> (logn - 1))];
+        const size_t w0 = 2 * w, w1 = 2 * (w + poly_pairs);  // word offsets of this lane's pair in poly 0 / poly 1
+        u64 c0xl = 0, c0xh = 0, c0yl = 0, c0yh = 0, c1xl = 0, c1xh = 0, c1yl = 0, c1yh = 0, c2xl = 0, c2xh = 0, c2yl = 0,
+            c2yh = 0;
+        int i = first;
+        for (; i + 4 <= last; i += 4) {  // sixteen independent 16-byte loads in flight per lane
+            ulonglong2 a0[4], a1[4], b0[4], b1[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const u64 *pa = tab[i + u], *pb = tab[n + i + u];
+                a0[u] = gld16(pa + w0);
+                a1[u] = gld16(pa + w1);
+                b0[u] = gld16(pb + w0);
+                b1[u] = gld16(pb + w1);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                mac128(c0xl, c0xh, a0[u].x, b0[u].x);
+                mac128(c0yl, c0yh, a0[u].y, b0[u].y);
+                mac128(c1xl, c1xh, a0[u].x, b1[u].x);
+                mac128(c1xl, c1xh, a1[u].x, b0[u].x);
+                mac128(c1yl, c1yh, a0[u].y, b1[u].y);
+                mac128(c1yl, c1yh, a1[u].y, b0[u].y);
+                mac128(c2xl, c2xh, a1[u].x, b1[u].x);
+                mac128(c2yl, c2yh, a1[u].y, b1[u].y);
+            }
+            const int done = i - first;
+            if ((done & 15) == 12) {  // 16 terms = 32 products in c1
+                c1xl = barrett128(c1xl, c1xh, mc);
+                c1yl = barrett128(c1yl, c1yh, mc);
+                c1xh = c1yh = 0;
+                if ((done & 31) == 28) {  // 32 terms = 32 products in c0 and in c2
+                    c0xl = barrett128(c0xl, c0xh, mc);
+                    c0yl = barrett128(c0yl, c0yh, mc);
+                    c2xl = barrett128(c2xl, c2xh, mc);
+                    c2yl = barrett128(c2yl, c2yh, mc);
+                    c0xh = c0yh = c2xh = c2yh = 0;
+                }
+            }
+        }
+        for (; i < last; ++i) {
+            const u64 *pa = tab[i], *pb = tab[n + i];
+            const ulonglong2 a0 = gld16(pa + w0), a1 = gld16(pa + w1), b0 = gld16(pb + w0), b1 = gld16(pb + w1);
+            mac128(c0xl, c0xh, a0.x, b0.x);
+            mac128(c0yl, c0yh, a0.y, b0.y);
+            mac128(c1xl, c1xh, a0.x, b1.x);
+            mac128(c1xl, c1xh, a1.x, b0.x);
+            mac128(c1yl, c1yh, a0.y, b1.y);
+            mac128(c1yl, c1yh, a1.y, b0.y);
+            mac128(c2xl, c2xh, a1.x, b1.x);
+            mac128(c2yl, c2yh, a1.y, b1.y);
+        }
+        ulonglong2 r0, r1, r2;
+        r0.x = barrett128(c0xl, c0xh, mc);
+        r0.y = barrett128(c0yl, c0yh, mc);
+        r1.x = barrett128(c1xl, c1xh, mc);
+        r1.y = barrett128(c1yl, c1yh, mc);
+        r2.x = barrett128(c2xl, c2xh, mc);
+        r2.y = barrett128(c2yl, c2yh, mc);
+        gst16(out + w, r0);
+        gst16(out + w + poly_pairs, r1);
+        gst16(out + w + 2 * poly_pairs, r2);
+    }
+}
+
+hipError_t launch_mul_sum(const DevTables &T, int L, const u64 *const *d_tab, int n, int group, hipStream_t s)
+{
+    const size_t poly_pairs = (size_t)L * ((size_t)1 << T.logn) / 2;
+    int blocks = (int)((poly_pairs + 255) / 256);
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    const int groups = (n + group - 1) / group;
+    hipLaunchKernelGGL(mul_sum_kernel, dim3(blocks, groups), dim3(256), 0, s, T, L, d_tab, n, group);
+    return hipGetLastError();
+}
+
 hipError_t launch_add_many(const DevTables &T, int L, int size, const PtrGroup &g, int n, bool accumulate,
                            u64 *out, hipStream_t s, const u64 *pt0)
 {

@@ -140,7 +140,10 @@ __device__ __forceinline__ u64 negmod(u64 a, u64 q) { return a ? q - a : 0; }
 // any 64-bit x -> [0,q); r1 = floor(2^64/q)
 __device__ __forceinline__ u64 barrett64(u64 x, u64 q, u64 r1) { return csub(x - mulhi64(x, r1) * q, q); }
 
-// (hi:lo) < q*2^64 -> [0,2q): the quotient estimate is short by at most one
+// ANY 128-bit (hi:lo) -> [0,2q): with r = floor(2^128/q) the estimate floor(x r / 2^128) is short of floor(x/q) by at most
+// one (the error is below x/2^128 < 1), and it is only needed mod 2^64 -- x - qhat q < 2q < 2^64 whatever the size of the
+// true quotient.  (Callers that stay below q*2^64 have a quotient that fits a word; the lazy sums of mulplain_sum_kernel
+// and mul_sum_kernel do not, and need not.)
 __device__ __forceinline__ u64 barrett128_lt2q(u64 lo, u64 hi, const ModConst &m)
 {
     u64 carry = mulhi64(lo, m.r0);
@@ -153,7 +156,7 @@ __device__ __forceinline__ u64 barrett128_lt2q(u64 lo, u64 hi, const ModConst &m
     u64 qhat = hi * m.r1 + tmp3 + carry2;
     return lo - qhat * m.q;
 }
-// (hi:lo) < q*2^64 -> [0,q)
+// any 128-bit (hi:lo) -> [0,q)
 __device__ __forceinline__ u64 barrett128(u64 lo, u64 hi, const ModConst &m) { return csub(barrett128_lt2q(lo, hi, m), m.q); }
 
 __device__ __forceinline__ u64 mulmod(u64 a, u64 b, const ModConst &m)

@@ -219,6 +219,18 @@ class Engine:
                                                   capi.ptr_array([o.ptr for o in outs]), stream))
         return outs
 
+    def multiply_sum(self, L, As, Bs, group=None, outs=None, stream=None):
+        """outs[g] = sum over group g of As[i] * Bs[i] (size 2 x 2 -> 3, hefx_multiply_sum); group=None: one sum of all n"""
+        n = len(As)
+        group = n if group is None else int(group)
+        groups = (n + group - 1) // group if n > 0 and group > 0 else 0
+        if outs is None:
+            outs = self.empty_many(groups, (3, L, self.N))
+        capi.check(capi.lib().hefx_multiply_sum(self._h, L, n, group, capi.ptr_array([a.ptr for a in As]),
+                                                capi.ptr_array([b.ptr for b in Bs]),
+                                                capi.ptr_array([o.ptr for o in outs]), stream))
+        return outs
+
     @staticmethod
     def contiguous(arrs) -> bool:
         """equally sized buffers laid out back to back (views of one slab, in order)"""
@@ -431,6 +443,15 @@ class Engine:
         karr = keys if isinstance(keys, C.Array) else capi.ptr_array([k.ptr for k in keys])
         darr = diag_pts if isinstance(diag_pts, C.Array) else capi.ptr_array([p.ptr for p in diag_pts])
         capi.check(f(
+            self._h, L, ct.ptr, len(darr), darr, len(karr), capi.u32_array(key_elts), karr, out.ptr, stream))
+        return out
+
+    def linear_transform_cipher(self, L, ct, diag_cts, key_elts, keys, out=None, stream=None):
+        """Linear_Transform_Cipher in one native call (hefx_linear_transform_cipher); the result has size 3"""
+        out = out if out is not None else DeviceArray(self, (3, L, self.N))
+        karr = keys if isinstance(keys, C.Array) else capi.ptr_array([k.ptr for k in keys])
+        darr = diag_cts if isinstance(diag_cts, C.Array) else capi.ptr_array([p.ptr for p in diag_cts])
+        capi.check(capi.lib().hefx_linear_transform_cipher(
             self._h, L, ct.ptr, len(darr), darr, len(karr), capi.u32_array(key_elts), karr, out.ptr, stream))
         return out
 

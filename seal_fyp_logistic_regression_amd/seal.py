@@ -158,6 +158,9 @@ class GpuBackend:
     def multiply_batch(self, L, As, Bs):
         return self.engine.multiply_batch(L, As, Bs)
 
+    def multiply_sum(self, L, As, Bs, group=None):
+        return self.engine.multiply_sum(L, As, Bs, group)
+
     def add_batch(self, L, size, As, Bs):
         return self.engine.add_batch(L, size, As, Bs)
 
@@ -218,6 +221,9 @@ class GpuBackend:
 
     def linear_transform_plain_many(self, L, cts, diag_pts, key_elts, keys):
         return self.engine.linear_transform_plain_many(L, cts, diag_pts, key_elts, keys)
+
+    def linear_transform_cipher(self, L, ct, diag_cts, key_elts, keys):
+        return self.engine.linear_transform_cipher(L, ct, diag_cts, key_elts, keys)
 
     def rotate_hoisted_batch(self, L, ct, elts, keys, pts=None):
         return self.engine.rotate_hoisted_batch(L, ct, elts, keys, pts)
@@ -869,6 +875,41 @@ class Evaluator:
                 raise RuntimeError("result ciphertext is transparent")
         outs = self.be.multiply_plain_sum(L, size, [a.data for a in cts], [p.data for p in pts], group)
         return [Ciphertext()._set(o, size, L, scale) for o in outs]
+
+    def multiply_sum(self, As: Sequence[Ciphertext], Bs: Sequence[Ciphertext], group: Optional[int] = None):
+        """add_many(multiply(As[i], Bs[i])) per group of `group` consecutive terms (None: one group) in one pass over
+        the operands (hefx_multiply_sum): the products and the sum of Linear_Transform_Cipher (helper.h:222-231) and
+        sum_k A_k * B_k (matrix_multiplication.cpp:123-129).  The size-3 sums are not relinearised.  Checks, messages and
+        their order are those of the op-by-op sequence -- per group every multiply, then add_many -- and so are the bits.
+        Returns the list of group sums."""
+        if not As or len(As) != len(Bs):
+            raise ValueError("multiply_sum: need as many second operands as first operands")
+        n = len(As)
+        group = n if group is None else int(group)
+        if group < 1:
+            raise ValueError("multiply_sum: group must be positive")
+        heads = []
+        for g0 in range(0, n, group):
+            terms = list(zip(As[g0:g0 + group], Bs[g0:g0 + group]))
+            for a, b in terms:                                       # Evaluator::multiply, term by term
+                self._check_same(a, b)
+                if a.size() != 2 or b.size() != 2:
+                    raise ValueError("multiply: only size-2 operands are supported (all reference call sites)")
+                self._check_scale(a.scale * b.scale, a.parms_id())
+            a0, b0 = terms[0]
+            for a, b in terms[1:]:                                   # Evaluator::add_many over the group's products
+                if a.parms_id() != a0.parms_id():
+                    raise ValueError("encrypted1 and encrypted2 parameter mismatch")
+                if not self._close(a0.scale * b0.scale, a.scale * b.scale):
+                    raise ValueError("scale mismatch")
+            heads.append((a0.parms_id(), a0.scale * b0.scale))
+        f = getattr(self.be, "multiply_sum", None)
+        if f is None or any(L != heads[0][0] for L, _ in heads):     # no fused sum (or groups at different levels)
+            return [self.add_many([self.multiply(a, b) for a, b in zip(As[g0:g0 + group], Bs[g0:g0 + group])])
+                    for g0 in range(0, n, group)]
+        L = heads[0][0]
+        outs = f(L, [a.data for a in As], [b.data for b in Bs], group)
+        return [Ciphertext()._set(o, 3, L, s) for o, (_, s) in zip(outs, heads)]
 
     def multiply(self, a: Ciphertext, b: Ciphertext, destination=None):
         self._check_same(a, b)

@@ -1,0 +1,289 @@
+"""GPU parity of the fused ciphertext product sum (hefx_multiply_sum, mul_sum_kernel) and of the native
+Linear_Transform_Cipher (hefx_linear_transform_cipher).  Bar: bit-exact uint64 RNS words, no tolerance."""
+import ctypes as C
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "appendix_b.json")))
+SETS = {s["name"]: s for s in GOLD["sets"]}
+
+
+def _table_slice():
+    """pointers in one descriptor-ring slot, read from the engine's sources (sizeof(KsItem) * KS_MAX_CHUNK / 8): the struct
+    is rebuilt with ctypes from its declaration in hefx_internal.h, so a change there moves the long-group test with it"""
+    import re
+    src = open(os.path.join(ROOT, "seal_fyp_logistic_regression_amd", "csrc", "hefx_internal.h")).read()
+    body = re.search(r"struct KsItem \{(.*?)\n\};", src, re.S).group(1)
+    body = re.sub(r"//[^\n]*", "", body)
+    fields = []
+    for i, decl in enumerate(x.strip() for x in body.split(";") if x.strip()):
+        names = decl.split(",")
+        ctype = C.c_void_p if "*" in decl else {"uint32_t": C.c_uint32, "u64": C.c_uint64, "uint64_t": C.c_uint64}[decl.split()[0]]
+        fields += [(f"f{i}_{j}", ctype) for j in range(len(names))]
+    item = type("KsItem", (C.Structure,), {"_fields_": fields})
+    chunk = int(re.search(r"constexpr int KS_MAX_CHUNK = (\d+);", src).group(1))
+    return C.sizeof(item) * chunk // 8
+
+
+_made = {}
+
+
+def _mk(name):
+    """(oracle, engine, L) of a golden set at its top data level, or of a policy set over ALL its primes (the
+    element-wise kernels take any L <= k; the special prime is where several sets keep their 61-bit prime)"""
+    if name not in _made:
+        from oracle import oracle as O
+        from seal_fyp_logistic_regression_amd import Engine
+        if name in SETS:
+            N, primes = SETS[name]["N"], [int(p, 16) for p in SETS[name]["primes"]]
+            L = len(primes) - 1
+        else:
+            from tests import policy_sets
+            s = policy_sets.sets()[name]
+            N, primes, L = s.N, s.primes, s.k
+        _made[name] = (O.Oracle(N, primes), Engine(N, primes), L)
+    return _made[name]
+
+
+def _big_prime_sets():
+    from tests import policy_sets
+    return [n for n, s in policy_sets.sets().items() if any(p >= 1 << 60 for p in s.primes)]
+
+
+assert set(_big_prime_sets()) >= {"straddle60", "small_p", "p_min61", "mixed2048", "mixed16384"}  # (at collection)
+
+
+@pytest.mark.parametrize("name", ["C2", "C3", "C5"] + _big_prime_sets())
+def test_multiply_sum_parity_with_the_oracle(name):
+    """Engine.multiply_sum == the oracle's multiply per term summed with its add: uniform residues; n = 1, 2, 7, 64, 257
+    in one group, a ragged grouping, square terms (a_i is b_i) and operands repeated across terms"""
+    o, e, L = _mk(name)
+    A = [o.uniform(L, 2, 5000 + i) for i in range(9)]
+    B = [o.uniform(L, 2, 5100 + i) for i in range(7)]
+    dA, dB = [e.to_device(x) for x in A], [e.to_device(x) for x in B]
+    prod = {}
+
+    def term(i):
+        """(a, b) of term i as (list tag, index): every seventh term a square, b repeating with period 7"""
+        ai = i % 9
+        return (("A", ai), ("A", ai)) if i % 7 == 3 else (("A", ai), ("B", (3 * i + 1) % 7))
+
+    def host(t):
+        return (A if t[0] == "A" else B)[t[1]]
+
+    def dev(t):
+        return (dA if t[0] == "A" else dB)[t[1]]
+
+    def want(idx):
+        acc = None
+        for i in idx:
+            a, b = term(i)
+            if (a, b) not in prod:
+                prod[(a, b)] = o.multiply(host(a), host(b))
+            acc = prod[(a, b)] if acc is None else o.add(acc, prod[(a, b)])
+        return acc
+
+    for n, group in ((1, None), (2, None), (7, None), (64, None), (257, None), (10, 3), (64, 16), (40, 1)):
+        g = n if group is None else group
+        As, Bs = [dev(term(i)[0]) for i in range(n)], [dev(term(i)[1]) for i in range(n)]
+        assert all((x is y) == (term(i)[0] == term(i)[1]) for i, (x, y) in enumerate(zip(As, Bs)))
+        outs = e.multiply_sum(L, As, Bs, group)
+        assert len(outs) == (n + g - 1) // g
+        for k, out in enumerate(outs):
+            assert out.shape == (3, L, o.N)
+            assert (out.download() == want(range(k * g, min(n, (k + 1) * g)))).all(), (name, n, group, k)
+
+
+@pytest.mark.parametrize("name", ["p_min61", "straddle60"])
+def test_fold_intervals_hold_at_the_largest_residues(name):
+    """every input word q_j - 1, the largest a canonical residue can be: (q-1)^2 = 1 mod q, so every word of c0 and c2
+    must be n mod q_j and every word of c1 2n mod q_j -- Python integers, no backend.  n on both sides of the c1 fold
+    (16 terms) and of the c0 / c2 fold (32 terms), and long sums: a lane walks all n terms of its group and folds on
+    the way.  Once as one group and once as eight groups side by side."""
+    o, e, L = _mk(name)
+    assert any(p > 1 << 60 for p in o.primes[:L])
+    top = np.zeros((2, L, o.N), dtype=np.uint64)
+    for j in range(L):
+        top[:, j, :] = o.primes[j] - 1
+    da, db = e.to_device(top), e.to_device(top)
+    for n in (15, 16, 17, 31, 32, 33, 64, 65, 200):
+        for groups in (1, 8):
+            outs = e.multiply_sum(L, [da if i % 3 else db for i in range(n * groups)], [db] * (n * groups), n)
+            assert len(outs) == groups
+            for out in outs:
+                got = out.download()
+                for j in range(L):
+                    q = o.primes[j]
+                    assert (got[0, j] == n % q).all() and (got[2, j] == n % q).all(), (n, groups, j)
+                    assert (got[1, j] == (2 * n) % q).all(), (n, groups, j)
+
+
+def test_a_group_longer_than_one_table_slice_equals_two_half_sums_added():
+    """a group that needs more pointers than a descriptor-ring slot holds: partial sums in scratch + add_many (size 3)"""
+    o, e, _ = _mk("C2")
+    slice_ = _table_slice()
+    assert slice_ == 10240  # what include/hefx.h documents for hefx_multiply_sum
+    L, n = 3, (slice_ // 2 + 40) // 20 * 20 + 20          # a multiple of 20 just past half a slice
+    assert 2 * n + 1 > slice_ >= 2 * (n // 2) + 1
+    dA = [e.to_device(o.uniform(L, 2, 5200 + i)) for i in range(5)]
+    dB = [e.to_device(o.uniform(L, 2, 5300 + i)) for i in range(4)]
+    As, Bs = [dA[i % 5] for i in range(n)], [dB[(3 * i) % 4] for i in range(n)]
+    whole = e.multiply_sum(L, As, Bs)[0].download()
+    h = n // 2
+    lo, hi = e.multiply_sum(L, As[:h], Bs[:h])[0], e.multiply_sum(L, As[h:], Bs[h:])[0]
+    assert (whole == e.add(L, 3, lo, hi).download()).all()
+    # and against the oracle: the 20 distinct products weighted by how often they occur
+    acc = None
+    for i in range(20):
+        p = o.multiply(dA[i % 5].download(), dB[(3 * i) % 4].download())
+        for _ in range(n // 20):
+            acc = p if acc is None else o.add(acc, p)
+    assert (whole == acc).all()
+
+
+def test_refusals_come_before_anything_is_written():
+    from seal_fyp_logistic_regression_amd import capi
+    o, e, L = _mk("C2")
+    lib, words2, words3 = capi.lib(), 2 * L * o.N, 3 * L * o.N
+    a, b = e.to_device(o.uniform(L, 2, 1)), e.to_device(o.uniform(L, 2, 2))
+    canary = o.uniform(L, 6, 3).reshape(-1)                     # one allocation: views below reach into it
+    big = e.to_device(canary)
+    arr = capi.ptr_array
+
+    def refused(Lx, n, group, As, Bs, outs):
+        rc = lib.hefx_multiply_sum(e._h, Lx, n, group, As, Bs, outs, None)
+        e.sync()
+        assert rc == capi.HEFX_ERR_INVALID, rc
+        assert (big.download() == canary).all()
+
+    in_view = big.view(0, (2, L, o.N))                          # bytes [0, 2LN)
+    out_inside = big.view(words2 - o.N, (3, L, o.N))            # starts in the input's last row: overlaps by a byte range
+    refused(L, 2, 2, arr([a.ptr, in_view.ptr]), arr([b.ptr, b.ptr]), arr([out_inside.ptr]))
+    refused(L, 2, 2, arr([a.ptr, a.ptr]), arr([b.ptr, in_view.ptr]), arr([out_inside.ptr]))
+    # an output that starts BEFORE an input and runs into it
+    in_late = big.view(words3 - o.N, (2, L, o.N))
+    refused(L, 1, 1, arr([in_late.ptr]), arr([b.ptr]), arr([big.view(0, (3, L, o.N)).ptr]))
+    # two outputs that overlap
+    refused(L, 2, 1, arr([a.ptr, a.ptr]), arr([b.ptr, b.ptr]),
+            arr([big.view(0, (3, L, o.N)).ptr, big.view(words3 - 2, (3, L, o.N)).ptr]))
+    # null pointers: an operand, an output, a table
+    good = big.view(0, (3, L, o.N))
+    refused(L, 2, 2, arr([a.ptr, None]), arr([b.ptr, b.ptr]), arr([good.ptr]))
+    refused(L, 2, 2, arr([a.ptr, a.ptr]), arr([None, b.ptr]), arr([good.ptr]))
+    refused(L, 1, 1, arr([a.ptr]), arr([b.ptr]), arr([None]))
+    refused(L, 1, 1, None, arr([b.ptr]), arr([good.ptr]))
+    # n = 0, group = 0, levels out of range
+    refused(L, 0, 1, arr([a.ptr]), arr([b.ptr]), arr([good.ptr]))
+    refused(L, 1, 0, arr([a.ptr]), arr([b.ptr]), arr([good.ptr]))
+    refused(0, 1, 1, arr([a.ptr]), arr([b.ptr]), arr([good.ptr]))
+    refused(o.k + 1, 1, 1, arr([a.ptr]), arr([b.ptr]), arr([good.ptr]))
+    # the Python layer turns the refusal into SEAL's exception type
+    with pytest.raises(ValueError, match="overlaps"):
+        e.multiply_sum(L, [a, in_view], [b, b], outs=[out_inside])
+    # and adjacent views are NOT an overlap
+    out_after = big.view(words2, (3, L, o.N))
+    got = e.multiply_sum(L, [in_view], [b], outs=[out_after])[0].download()
+    assert (got == o.multiply(canary[:words2].reshape(2, L, o.N), b.download())).all()
+
+
+# ---- hefx_linear_transform_cipher ---------------------------------------------------------------------------------
+def _lt_cipher_both(N, bits_, d, seed, galois_steps=None):
+    from seal_fyp_logistic_regression_amd import algorithms as alg
+    from tests.test_gpu_composites import both, bits, decode
+    rng = np.random.default_rng(seed)
+    M, v = rng.standard_normal((d, d)), rng.standard_normal(d)
+
+    def run(e):
+        scale = 2.0 ** 40
+        diags = [e["enc"].encrypt(e["encoder"].encode(x, scale)) for x in alg.get_all_diagonals(M)]
+        ct = e["enc"].encrypt(e["encoder"].encode(v, scale))
+        return alg.linear_transform_cipher(e["ev"], ct, diags, e["gk"])
+
+    r = both(N, bits_, run, seed=seed, galois_steps=galois_steps)
+    (eg, cg), (eo, co) = r["gpu"], r["oracle"]
+    assert hasattr(eg["ctx"].backend, "linear_transform_cipher") and not hasattr(eo["ctx"].backend, "linear_transform_cipher")
+    assert cg.size() == co.size() == 3 and cg.parms_id() == co.parms_id() and cg.scale == co.scale
+    assert (bits(eg, cg) == bits(eo, co)).all()
+    assert np.allclose(decode(eg, cg, d), M @ v, atol=1e-4)
+    return eg
+
+
+def test_linear_transform_cipher_d4_c3_bit_exact():
+    _lt_cipher_both(16384, [60, 40, 40, 40, 40, 60], 4, seed=21)
+
+
+def test_linear_transform_cipher_d16_c2_default_keys_bit_exact():
+    """power-of-two keys: every rotation a NAF chain, the chains share prefixes, and some steps are prefixes of others"""
+    eg = _lt_cipher_both(8192, [60, 40, 40, 60], 16, seed=22)
+    stats = (C.c_uint64 * 4)()
+    from seal_fyp_logistic_regression_amd import capi
+    capi.check(capi.lib().hefx_ks_stats(eg["ctx"].backend.engine._h, stats))
+    # 29 key switches step by step (golden naf_keyswitch_counts: rotate(-16) + the chains of 1..15); fewer once shared
+    # (parent, element) pairs are computed once, and at least one per step
+    assert 16 <= stats[0] < GOLD["naf_keyswitch_counts"]["16"], list(stats)
+
+
+def test_linear_transform_cipher_d40_c2_direct_keys_bit_exact():
+    """a direct key per step: 39 rotations of one ciphertext in one depth, more than 32 items -> exactly hoisted"""
+    d = 40
+    eg = _lt_cipher_both(8192, [60, 40, 40, 60], d, seed=23, galois_steps=[-d] + list(range(1, d)))
+    stats = (C.c_uint64 * 4)()
+    from seal_fyp_logistic_regression_amd import capi
+    capi.check(capi.lib().hefx_ks_stats(eg["ctx"].backend.engine._h, stats))
+    assert stats[1] >= d - 1, list(stats)  # the forest's depth ran on the hoisted path
+
+
+def test_linear_transform_cipher_missing_key_and_aliasing_errors():
+    from seal_fyp_logistic_regression_amd import algorithms as alg
+    from seal_fyp_logistic_regression_amd import seal as S
+    from tests.test_gpu_composites import make
+    d = 6
+    e = make(8192, [60, 40, 40, 60], "gpu", seed=3, galois_steps=[1, 2, 3])  # 4, 5 = NAF (4, 1): no key for 4; -6 neither
+    scale = 2.0 ** 40
+    pts = [e["encoder"].encode(np.arange(d) + l, scale) for l in range(d)]
+    ct = e["enc"].encrypt(e["encoder"].encode(np.arange(d), scale))
+    cts = [e["enc"].encrypt(p) for p in pts]
+    with pytest.raises(ValueError) as plain_err:
+        alg.linear_transform_plain(e["ev"], ct, pts, e["gk"])
+    with pytest.raises(ValueError) as cipher_err:
+        alg.linear_transform_cipher(e["ev"], ct, cts, e["gk"])
+    assert str(cipher_err.value) == str(plain_err.value) and "Galois key not present" in str(cipher_err.value)
+    half = S.KSwitchKeys()
+    with pytest.raises(ValueError, match="Galois key not present"):
+        alg.linear_transform_cipher(e["ev"], ct, cts, half)
+    # a step beyond the slot count: the plain transform's message
+    be = e["ctx"].backend
+    L = ct.parms_id()
+    many = [cts[0].data] * (e["ctx"].N // 2)
+    elts = sorted(e["gk"].keys)
+    keys = [e["gk"].key(x) for x in elts]
+    with pytest.raises(ValueError, match="step count too large"):
+        be.engine.linear_transform_cipher(L, ct.data, many, elts, keys)
+    # the result may not reach into an operand: a diagonal and the output as overlapping views of one allocation
+    N = e["ctx"].N
+    slab = be.engine.empty(5 * L * N)
+    diag = slab.view(0, (2, L, N))
+    be.engine.copy_raw(diag.ptr, cts[1].data.ptr, diag.nbytes)
+    with pytest.raises(ValueError, match="overlaps"):
+        be.engine.linear_transform_cipher(L, ct.data, [cts[0].data, diag, cts[2].data], elts, keys,
+                                          out=slab.view(2 * L * N - N, (3, L, N)))
+
+
+def test_multiply_sum_selftest_driver():
+    """drivers/multiply_sum_selftest.cpp: Evaluator::hefx_multiply_sum against multiply + add_many at d = 4 and 40, and
+    the loop of helper.h:212-234 against hefx_linear_transform_cipher's words, through include/seal/seal.h"""
+    exe = os.path.join(ROOT, "drivers", "_ref", "multiply_sum_selftest")
+    if not os.path.exists(exe):  # our own source: build it where it is missing
+        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "drivers"), "_ref/multiply_sum_selftest"], check=False)
+    if not os.path.exists(exe):
+        pytest.skip("drivers/_ref/multiply_sum_selftest could not be built (make -C drivers _ref/multiply_sum_selftest)")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "SELFTEST PASSED" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+    assert "FAIL" not in r.stdout
