@@ -17,7 +17,37 @@
  *  - All `d_*` pointers are DEVICE pointers (hefx_malloc or any hipMalloc'd memory of the same
  *    device).  Pointer ARRAYS (`const uint64_t *const *`) are HOST arrays of device pointers.
  *  - `stream` is a hipStream_t passed as void* (NULL = default stream).  Calls are asynchronous on
- *    that stream; only hefx_download / hefx_stream_sync / hefx_check_* block.
+ *    that stream: they return once the work is submitted and do not wait for what the stream still
+ *    holds.  The entries that DO wait on the host, every one of them (tests/test_gpu_streams.py holds
+ *    every other entry to returning while its stream is still held shut):
+ *      always, by their purpose:   hefx_upload, hefx_download, hefx_stream_sync, hefx_check_transparent,
+ *                                  hefx_ckks_decode, hefx_event_elapsed_ms, hefx_ks_fallback_count,
+ *                                  hefx_profile_begin, hefx_profile_end, hefx_context_destroy
+ *      on the FIRST USE of a Galois element on the exactly hoisted path (its flip-mask table is built
+ *      with one hipMalloc and one hipStreamSynchronize on the caller's stream; later calls find the
+ *      table -- see hefx_rotate_hoisted_batch):
+ *                                  hefx_rotate_hoisted_batch, hefx_apply_galois_batch,
+ *                                  hefx_rotate_multiply_plain_batch, hefx_apply_galois_add_batch,
+ *                                  hefx_rotate_add_chain, hefx_apply_galois_forest,
+ *                                  hefx_linear_transform_plain, hefx_linear_transform_plain_many,
+ *                                  hefx_linear_transform_plain_hoisted, hefx_linear_transform_plain_bsgs,
+ *                                  hefx_linear_transform_cipher
+ *      when a call outgrows a buffer that cannot be retired while in use:
+ *                                  hefx_multiply_plain (a first `count` above 4096: the per-ciphertext
+ *                                  transparency marks move), hefx_ckks_encode / hefx_ckks_encode_batch (a
+ *                                  call of more than one vector that outgrows its pinned staging buffer),
+ *                                  hefx_free (a block that is not the pool's goes to hipFree)
+ *    Besides these, an entry waits only for ITSELF: for a descriptor-ring slot or an encode staging
+ *    buffer that one of the context's own earlier calls still owns -- 32 table- or chunk-carrying
+ *    submissions, 8 one-vector encodes, 2 larger encodes may be in flight before the host waits for the
+ *    oldest -- and for the device when memory runs out (the pool and the retired scratch are given back).
+ *  - One context, one order.  The scratch buffer, the descriptor ring, the encode staging and the
+ *    transparent flag belong to the CONTEXT, not to the stream.  Consecutive calls on one context must
+ *    therefore be ordered on the device: submitted on the same stream, or on streams the caller has
+ *    ordered with events (record on the first after the earlier call, make the second wait for it
+ *    before the later call).  Calls of one context on UNORDERED streams race for these buffers and give
+ *    undefined words; work that is to overlap needs a context per stream.  The internal streams an entry
+ *    uses are forked from and joined back to the caller's stream inside the call.
  *  - Return value: 0 = HEFX_OK, negative = error; hefx_last_error() gives the thread-local message.
  *  - Level/scale/parms_id bookkeeping, NAF decomposition of rotation steps and SEAL's validity checks
  *    live ABOVE this ABI (in the shim); this layer is pure uint64 RNS arithmetic.
@@ -347,8 +377,9 @@ int hefx_apply_galois_forest(hefx_context *ctx, int L, int n, const int32_t *par
  *      d_pts may be NULL (no fused multiply_plain).
  *      FIRST USE of a Galois element on this path builds its flip-mask table (k rows of N words, kept for the context's
  *      life within HEFX_FLIPW_MB, default 8 GiB; beyond it the batch runs unhoisted, same words): one hipMalloc and one
- *      hipStreamSynchronize on the caller's stream -- the one place where an asynchronous entry waits on the host, and a
- *      reason not to capture the first call of a new element into a graph.  Later calls find the table. */
+ *      hipStreamSynchronize on the caller's stream -- a wait on the host inside an asynchronous entry (the conventions at
+ *      the top list every entry that has one), and a reason not to capture the first call of a new element into a graph.
+ *      Later calls find the table. */
 int hefx_rotate_hoisted_batch(hefx_context *ctx, int L, const uint64_t *d_ct_in, int n, const uint32_t *galois_elts,
                               const uint64_t *const *d_keys, const uint64_t *const *d_pts, uint64_t *const *d_ct_out,
                               void *stream);
@@ -401,7 +432,8 @@ int hefx_linear_transform_plain_bsgs(hefx_context *ctx, int L, const uint64_t *d
  *      returns HEFX_ERR_INVALID before any work is queued; wider coefficients need an exact host encoder followed by
  *      hefx_ntt_forward.
  *      The host arrays are copied into pinned staging memory before the call returns (they may be transient); the call
- *      does not wait for the stream -- at most for an earlier encode that still owns the staging buffer it wants. */
+ *      does not wait for the stream -- at most for an earlier encode that still owns the staging buffer it wants (and,
+ *      for a call of more than one vector, for the device when its pinned buffer has to grow: conventions at the top). */
 int hefx_ckks_encode(hefx_context *ctx, int L, const double *h_re, const double *h_im, int nvalues, int count,
                      double scale, uint64_t *d_out, void *stream);
 /* the same for `count` vectors whose plaintexts are separately allocated: d_outs[i] receives vector i (host arrays as

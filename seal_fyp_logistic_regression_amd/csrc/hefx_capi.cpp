@@ -2109,14 +2109,10 @@ extern "C" int hefx_ckks_encode(hefx_context *c, int L, const double *h_re, cons
     const size_t nv = (size_t)nvalues * count, need = nv * (h_im ? 2 : 1);
     if (!encode_values_in_range(h_re, h_im, nv, scale))  // before the values go into staging
         return fail(HEFX_ERR_INVALID, "values out of range: every |value| * scale must be finite and below 2^62");
-    if (c->vals_cap < need) {
-        if (c->d_vals) {
-            HIPCHK(hipDeviceSynchronize());
-            HIPCHK(hipFree(c->d_vals));
-        }
-        HIPCHK(hipMalloc((void **)&c->d_vals, need * sizeof(double)));
-        c->vals_cap = need;
-    }
+    // (an outgrown value buffer is retired, not freed: an earlier encode may still be reading it, and waiting for the
+    // device here would make the call wait for the caller's stream)
+    static_assert(sizeof(double) == sizeof(u64), "the value buffer grows like the scratch");
+    if (int rc = grow_retiring(c, reinterpret_cast<u64 **>(&c->d_vals), &c->vals_cap, need, 0, "encode values")) return rc;
     hipStream_t s = (hipStream_t)stream;
     const size_t slot_doubles = c->n;  // one vector of N/2 complex values
     if (need <= slot_doubles) {  // small: through the pinned ring, no wait for the copy
@@ -2867,8 +2863,18 @@ static int lt2_impl(hefx_context *c, int L, const uint64_t *ct, int d, int nterm
     S.x = S.u + (size_t)2 * N;
     S.alias = nullptr;
     hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipMemcpyAsync(d_items, items.data(), sizeof(KsItem) * items.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));  // `items` is a local
+    // `items` is a local: the descriptors travel through the pinned mirror of a descriptor-ring slot (a slot's worth at a
+    // time) into the workspace, the slot owned until its copy has run -- no wait for the stream
+    for (size_t i0 = 0; i0 < items.size(); i0 += KS_MAX_CHUNK) {
+        const size_t cnt = std::min<size_t>(KS_MAX_CHUNK, items.size() - i0);
+        const unsigned slot = c->ring_next++ % KS_RING;
+        if (c->ring_busy[slot]) HIPCHK(hipEventSynchronize(c->ring_ev[slot]));
+        KsItem *hb = c->h_items + (size_t)slot * KS_MAX_CHUNK;
+        memcpy(hb, items.data() + i0, sizeof(KsItem) * cnt);
+        HIPCHK(hipMemcpyAsync(d_items + i0, hb, sizeof(KsItem) * cnt, hipMemcpyHostToDevice, s));
+        HIPCHK(hipEventRecord(c->ring_ev[slot], s));
+        c->ring_busy[slot] = true;
+    }
     HIPCHK(launch_lt2_decompose(c->T, L, d_items, d_items + 1, nrot, S, (const u64 *)ct_new, partial_s, partial_c0,
                                 (u64 *)cbuf, s));
     HIPCHK(launch_lt2_moddown(c->T, L, d_items + nterms, S, s));
