@@ -209,6 +209,25 @@ int hefx_multiply_batch(hefx_context *ctx, int L, int n, const uint64_t *const *
 int hefx_multiply_sum(hefx_context *ctx, int L, int n, int group, const uint64_t *const *d_a,
                       const uint64_t *const *d_b, uint64_t *const *d_out3, void *stream);
 
+/* The most polynomials a ciphertext may have in this engine -- an engine limit: the general product below sums at most
+ * min(size_a, size_b) <= 8 products per word under it, far inside the 63 its 128-bit accumulator holds. */
+#define HEFX_CT_SIZE_MAX 16
+/* Evaluator::multiply / square for ciphertexts of ANY size (the size-3 results of hefx_multiply_sum,
+ * hefx_linear_transform_cipher and step 3 of the matrix product multiplied again; x*y*z with one chain of key switches
+ * at the end): d_a: [size_a][L][N], d_b: [size_b][L][N], d_out: [size_a + size_b - 1][L][N],
+ *   d_out[k] = sum_{i+j=k} d_a[i] (.) d_b[j]   (mod q_j per row), the canonical residue of the integer sum -- the bits of
+ * SEAL's dyadic-product-and-add loop.  2 <= size_a, size_b and size_a + size_b - 1 <= HEFX_CT_SIZE_MAX, otherwise
+ * HEFX_ERR_INVALID with a message that names the limit.  Inputs are only read: d_a == d_b is a square.  The output may
+ * overlap no input in BYTES (views of one allocation included): HEFX_ERR_INVALID before anything is submitted.
+ * size_a = size_b = 2 is hefx_multiply. */
+int hefx_multiply_sizes(hefx_context *ctx, int L, int size_a, const uint64_t *d_a, int size_b, const uint64_t *d_b,
+                        uint64_t *d_out, void *stream);
+/* n independent products of one shape (size_a, size_b) in one launch per pointer-table slice: d_out[i] = d_a[i] * d_b[i].
+ * Host arrays of device pointers; operands may repeat; no output may overlap, in bytes, an input of the call or another
+ * output.  size_a = size_b = 2 is hefx_multiply_batch. */
+int hefx_multiply_sizes_batch(hefx_context *ctx, int L, int n, int size_a, const uint64_t *const *d_a, int size_b,
+                              const uint64_t *const *d_b, uint64_t *const *d_out, void *stream);
+
 /* ---- K5/K6/K7: Evaluator::apply_galois_inplace = Galois permutation + key switch (one term of
  *      rotate_vector; helper.h:216,227,244,255,316,352,455,474; 5_rotation.cpp:215).
  *      d_key is the Galois key of `galois_elt` (the shim picks it: GaloisKeys index (elt-1)/2).
@@ -266,6 +285,25 @@ int hefx_relinearize(hefx_context *ctx, int L, const uint64_t *d_ct3, const uint
                      uint64_t *d_ct2, void *stream);
 int hefx_relinearize_batch(hefx_context *ctx, int L, int n, const uint64_t *const *d_ct3,
                            const uint64_t *d_relin_key, uint64_t *const *d_ct2, void *stream);
+/* Evaluator::relinearize_inplace from ANY size: size_in -> size_out polynomials, 2 <= size_out < size_in <=
+ * HEFX_CT_SIZE_MAX, in the order of SEAL's relinearize_internal -- from the top: for t = size_in - 1 down to size_out,
+ * polynomial t is key-switched with the key of s^t and the result added into (c0, c1); polynomials 2 .. size_out - 1
+ * pass through unchanged.  d_relin_keys is a HOST array of device pointers in which entry p - 2 is the key of s^p
+ * (RelinKeys::get_index(p)); the entries of the powers used, size_out - 2 .. size_in - 3, must be non-null (HEFX_ERR_INVALID otherwise).
+ * d_ct: [size_in][L][N], d_out: [size_out][L][N], not overlapping in bytes.  Each step is the key switch of
+ * hefx_relinearize on a staged block (c0, c1, c_t): 3 L N copied words for the first step and L N for each later one (a
+ * step writes its (c0, c1) straight into the next step's block), beside a VALU-bound key switch; one device copy per item
+ * and step.  The blocks -- two of [3][L][N] per item -- are engine workspace, shared with the linear transforms (one
+ * context, one order) and grown on first use like theirs (one hipMalloc, no wait for the device).  A batch is staged in
+ * groups of floor(1 GiB / (6 L N 8 B)) items (at least one; 273 at N = 16384, L = 5), group after group through the same
+ * blocks, so the workspace stays within 1 GiB whatever n is.  For size_in = 3 nothing is staged: the words AND the
+ * launches of hefx_relinearize.  The batch form uses one key array for all items; outputs pairwise disjoint and disjoint
+ * from every input. */
+int hefx_relinearize_sizes(hefx_context *ctx, int L, int size_in, int size_out, const uint64_t *d_ct,
+                           const uint64_t *const *d_relin_keys, uint64_t *d_out, void *stream);
+int hefx_relinearize_sizes_batch(hefx_context *ctx, int L, int n, int size_in, int size_out,
+                                 const uint64_t *const *d_ct, const uint64_t *const *d_relin_keys,
+                                 uint64_t *const *d_out, void *stream);
 
 /* ---- K8: Evaluator::rescale_to_next_inplace (matrix_multiplication.cpp:71-72; helper.h:441,543; polynomial.cpp:93,
  *      195,333; logistic_regression_ckks.cpp:119,189,239,321): L rows -> L-1 rows per poly, `count` contiguous cts.

@@ -1825,21 +1825,23 @@ class KSwitchKeys {
 public:
     virtual ~KSwitchKeys() = default;
     bool has_key(std::uint32_t elt) const { return keys.count(elt) != 0; }
-    std::map<std::uint32_t, shim::BufPtr> keys;  // Galois element -> [k-1][2][k][N]; relin key under element 0
+    std::map<std::uint32_t, shim::BufPtr> keys;  // Galois element -> [k-1][2][k][N]; the relin key of s^p under p - 2
     std::size_t size() const { return keys.size(); }
     parms_id_type &parms_id() { return id_; }
     const parms_id_type &parms_id() const { return id_; }
     // ---- SEAL 3.4.5 KSwitchKeys::save: parms_id, the outer dimension, then per index its component count followed by that
     // many PublicKeys (key-level size-2 ciphertexts: component i = digit i = [2][k][N]).  RelinKeys: index = key_power - 2
-    // (one index); GaloisKeys: index = (galois_elt - 1) / 2 over N indices, absent elements with zero components.
+    // (as many indices as relin_keys(count) made); GaloisKeys: index = (galois_elt - 1) / 2 over N indices, absent elements with zero components.
     void save(std::ostream &stream) const
     {
         shim::StreamGuard g(stream);
         shim::put_id(stream, id_);
-        const std::uint64_t dim1 = keys.empty() ? 0 : (galois_indexing() ? (std::uint64_t)keys.begin()->second->eng->n : 1);
+        const std::uint64_t dim1 = keys.empty() ? 0
+                                   : (galois_indexing() ? (std::uint64_t)keys.begin()->second->eng->n
+                                                        : (std::uint64_t)keys.rbegin()->first + 1);
         shim::put_u64(stream, dim1);
         for (std::uint64_t index = 0; index < dim1; ++index) {
-            const std::uint32_t elt = galois_indexing() ? (std::uint32_t)(2 * index + 1) : 0u;
+            const std::uint32_t elt = galois_indexing() ? (std::uint32_t)(2 * index + 1) : (std::uint32_t)index;
             if (!has_key(elt)) {
                 shim::put_u64(stream, 0);
                 continue;
@@ -1872,7 +1874,8 @@ protected:
         const parms_id_type id = shim::get_id(stream);
         const std::uint64_t dim1 = shim::get_u64(stream);
         const std::size_t n = ctx.n(), k = (std::size_t)ctx.k(), slice = 2 * k * n;
-        if (dim1 > (galois_indexing() ? (std::uint64_t)n : 1) || (validate && id != ctx.key_parms_id()))
+        if (dim1 > (galois_indexing() ? (std::uint64_t)n : (std::uint64_t)(HEFX_CT_SIZE_MAX - 2)) ||
+            (validate && id != ctx.key_parms_id()))
             throw std::invalid_argument("KSwitchKeys data is invalid");
         std::map<std::uint32_t, shim::BufPtr> loaded;
         auto ctxp = std::make_shared<SEALContext>(ctx);
@@ -1890,7 +1893,7 @@ protected:
                 if (c.size() != 2 || (std::size_t)c.rows != k || !c.buf) throw std::invalid_argument("KSwitchKeys data is invalid");
                 std::memcpy(words.data() + i * slice, c.data(), slice * 8);
             }
-            loaded[galois_indexing() ? (std::uint32_t)(2 * index + 1) : 0u] = shim::upload(ctx.engine(), words);
+            loaded[galois_indexing() ? (std::uint32_t)(2 * index + 1) : (std::uint32_t)index] = shim::upload(ctx.engine(), words);
         }
         keys = std::move(loaded);
         views_.clear();
@@ -1923,14 +1926,18 @@ protected:
     bool galois_indexing() const override { return false; }
 
 public:
-    static std::size_t get_index(std::size_t key_power) { return key_power - 2; }
-    // shim-internal lookups use has_key(0u) (the relinearisation key is stored under element 0); SEAL's has_key(key_power)
-    // is has_power
-    bool has_power(std::size_t key_power) const { return key_power == 2 && keys.count(0) != 0; }
+    static std::size_t get_index(std::size_t key_power)
+    {
+        if (key_power < 2) throw std::invalid_argument("key_power cannot be less than 2");
+        return key_power - 2;
+    }
+    // shim-internal lookups use has_key(get_index(p)) (the key of s^p is stored under p - 2: s^2, what a size-3 ciphertext
+    // needs, under 0); SEAL's has_key(key_power) is has_power
+    bool has_power(std::size_t key_power) const { return key_power >= 2 && keys.count((std::uint32_t)(key_power - 2)) != 0; }
     const std::vector<PublicKey> &key(std::size_t key_power) const
     {
-        if (key_power != 2) throw std::invalid_argument("key_power is not valid");
-        return components(0);
+        if (!has_power(key_power)) throw std::invalid_argument("key_power is not valid");
+        return components((std::uint32_t)get_index(key_power));
     }
 };
 class GaloisKeys : public KSwitchKeys {
@@ -2015,14 +2022,21 @@ public:
     }
     void create_public_key(PublicKey &pk) { pk = public_key(); }
 
-    RelinKeys relin_keys(std::size_t = 1)
+    // the keys of s^2 .. s^(count + 1): what relinearising a ciphertext of up to count + 2 polynomials needs.  The powers
+    // are formed on the device; sampler streams are taken in increasing power, so relin_keys(1) is the key it always was.
+    RelinKeys relin_keys(std::size_t count = 1)
     {
+        if (count < 1 || count > HEFX_CT_SIZE_MAX - 2) throw std::invalid_argument("invalid count");
         RelinKeys rk;
         const int k = ctx_->k();
         auto &e = ctx_->engine();
-        auto s2 = shim::new_buf(e, (std::size_t)k * ctx_->n());
-        shim::check(hefx_multiply_plain(e->ready({}), k, 1, 1, sk_.buf->p, sk_.buf->p, s2->p, nullptr));
-        rk.keys[0] = kswitch_key(s2);
+        shim::BufPtr power = sk_.buf;
+        for (std::size_t p = 2; p < count + 2; ++p) {
+            auto next = shim::new_buf(e, (std::size_t)k * ctx_->n());
+            shim::check(hefx_multiply_plain(e->ready({}), k, 1, 1, power->p, sk_.buf->p, next->p, nullptr));
+            rk.keys[(std::uint32_t)(p - 2)] = kswitch_key(next);
+            power = next;
+        }
         rk.parms_id() = ctx_->key_parms_id();
         return rk;
     }
@@ -2729,9 +2743,16 @@ public:
         check_ct(b);
         if (a.parms_id() != b.parms_id()) throw std::invalid_argument("encrypted1 and encrypted2 parameter mismatch");
         if (!ctx_->is_ckks()) return multiply_bfv(a, b, dest);  // any sizes (1_bfv.cpp:132 multiplies two size-3 ciphertexts)
-        if (a.size() != 2 || b.size() != 2)
-            throw std::invalid_argument("multiply: only size-2 operands are built (every reference call site)");
         const double ns = a.scale() * b.scale();
+        if (a.size() != 2 || b.size() != 2) {  // any other legal shape: hefx_multiply_sizes, live (the recorder flushes first)
+            const std::size_t sz = a.size() + b.size() - 1;
+            if (a.size() < 2 || b.size() < 2 || sz > HEFX_CT_SIZE_MAX) throw std::invalid_argument("invalid size");  // Ciphertext::resize
+            check_scale(ns, a.parms_id());
+            auto out = shim::new_buf(eng(), words(sz, a.rows));
+            shim::check(hefx_multiply_sizes(eng()->live(), a.rows, (int)a.size(), a.buf->p, (int)b.size(), b.buf->p, out->p, nullptr));
+            dest.set(out, sz, a.rows, a.parms_id(), ns);
+            return;
+        }
         check_scale(ns, a.parms_id());
         if (eng()->lazy) {  // recorded (helper.h:227-228, 432): the products of all rows / diagonals go out as one batch
             const int rows = a.rows;
@@ -2756,7 +2777,19 @@ public:
     {
         check_ct(a);
         if (a.size() == 2) return;  // SEAL: nothing to do
-        if (a.size() != 3) throw std::invalid_argument("encrypted size must be 2 or 3");
+        if (a.size() > 3) {  // SEAL's relinearize_internal from any size: hefx_relinearize_sizes, live
+            if (!ctx_->is_ckks()) throw std::invalid_argument("encrypted size must be 2 or 3");  // (the BFV path is built for 3)
+            if (a.size() > HEFX_CT_SIZE_MAX) throw std::invalid_argument("encrypted is not valid for encryption parameters");
+            std::vector<const std::uint64_t *> kp(a.size() - 2, nullptr);
+            for (std::size_t p = 2; p < a.size(); ++p) {
+                if (!rk.has_power(p)) throw std::invalid_argument("not enough relinearization keys");
+                kp[p - 2] = rk.keys.at((std::uint32_t)(p - 2))->p;
+            }
+            auto out = shim::new_buf(eng(), words(2, a.rows));
+            shim::check(hefx_relinearize_sizes(eng()->live(), a.rows, (int)a.size(), 2, a.buf->p, kp.data(), out->p, nullptr));
+            a.set(out, 2, a.rows, a.parms_id(), a.scale());
+            return;
+        }
         if (!rk.has_key(0)) throw std::invalid_argument("not enough relinearization keys");
         if (!ctx_->is_ckks()) {  // BFV: the same key switch, bracketed by NTTs (the ciphertext is in coefficient form)
             auto &e = eng();

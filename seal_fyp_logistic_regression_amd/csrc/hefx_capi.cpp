@@ -1005,6 +1005,80 @@ extern "C" int hefx_square(hefx_context *c, int L, const uint64_t *a, uint64_t *
     return hefx_multiply(c, L, a, a, out3, stream);
 }
 
+// Byte-range independence of a call's outputs (n blocks of out_b bytes) and inputs (blocks of in_b bytes each, several
+// lists): no two outputs may overlap and no input may reach into an output -- views of one allocation included.  The
+// rule hefx_multiply_sum applies (which keeps its own statement of it: its outputs are per group, not per item), here for
+// the general-size entries, one output per item.  nullptr when the call is fine, else what is wrong.
+static const char *outputs_overlap(int n, uint64_t *const *outs, size_t out_b,
+                                   std::initializer_list<std::pair<const uint64_t *const *, size_t>> ins)
+{
+    std::vector<uintptr_t> o((size_t)n);
+    for (int i = 0; i < n; ++i) o[(size_t)i] = (uintptr_t)outs[i];
+    std::sort(o.begin(), o.end());
+    for (int i = 1; i < n; ++i)
+        if (o[(size_t)i - 1] + out_b > o[(size_t)i]) return "two outputs overlap";
+    for (const auto &in : ins)
+        for (int i = 0; i < n; ++i) {
+            const uintptr_t x = (uintptr_t)in.first[i];
+            auto it = std::upper_bound(o.begin(), o.end(), x);
+            if ((it != o.begin() && *(it - 1) + out_b > x) || (it != o.end() && *it < x + in.second))
+                return "an output overlaps an input";
+        }
+    return nullptr;
+}
+
+template <class Fill, class Run>
+static int table_slices(hefx_context *c, int n, int ptrs_per_item, hipStream_t s, Fill fill, Run run, int max_slice = 0);
+
+static int check_ct_sizes(int sa, int sb)
+{
+    if (sa < 2 || sb < 2)
+        return fail(HEFX_ERR_INVALID, "multiply: every operand needs at least 2 polynomials");
+    if (sa + sb - 1 > HEFX_CT_SIZE_MAX)
+        return fail(HEFX_ERR_INVALID, "multiply: the result would have more than HEFX_CT_SIZE_MAX = " +
+                                          std::to_string(HEFX_CT_SIZE_MAX) + " polynomials");
+    return HEFX_OK;
+}
+
+extern "C" int hefx_multiply_sizes_batch(hefx_context *c, int L, int n, int sa, const uint64_t *const *a, int sb,
+                                         const uint64_t *const *b, uint64_t *const *out, void *stream)
+{
+    CTXCHK(c);
+    if (int rc = check_level(c, L)) return rc;
+    if (int rc = check_ct_sizes(sa, sb)) return rc;
+    if (n < 1 || !a || !b || !out) return fail(HEFX_ERR_INVALID, "bad multiply batch arguments");
+    for (int i = 0; i < n; ++i)
+        if (!a[i] || !b[i] || !out[i]) return fail(HEFX_ERR_INVALID, "null operand in multiply batch");
+    const size_t poly_b = (size_t)L * c->n * sizeof(u64);
+    if (const char *why = outputs_overlap(n, out, (size_t)(sa + sb - 1) * poly_b, {{a, sa * poly_b}, {b, sb * poly_b}}))
+        return fail(HEFX_ERR_INVALID, std::string("multiply: ") + why);
+    if (sa == 2 && sb == 2) return hefx_multiply_batch(c, L, n, a, b, out, stream);
+    hipStream_t s = (hipStream_t)stream;
+    return table_slices(
+        c, n, 3, s,
+        [&](const uint64_t **hp, int i0, int cnt) {
+            for (int i = 0; i < cnt; ++i) hp[i] = a[i0 + i], hp[cnt + i] = b[i0 + i], hp[2 * cnt + i] = out[i0 + i];
+        },
+        [&](const u64 *const *dp, int, int cnt) {
+            return launch_multiply_sizes(c->T, L, sa, sb, nullptr, nullptr, nullptr, dp, cnt, s);
+        });
+}
+
+extern "C" int hefx_multiply_sizes(hefx_context *c, int L, int sa, const uint64_t *a, int sb, const uint64_t *b,
+                                   uint64_t *out, void *stream)
+{
+    CTXCHK(c);
+    if (int rc = check_level(c, L)) return rc;
+    if (int rc = check_ct_sizes(sa, sb)) return rc;
+    if (!a || !b || !out) return fail(HEFX_ERR_INVALID, "null operand");
+    const size_t poly_b = (size_t)L * c->n * sizeof(u64);
+    if (const char *why = outputs_overlap(1, &out, (size_t)(sa + sb - 1) * poly_b, {{&a, sa * poly_b}, {&b, sb * poly_b}}))
+        return fail(HEFX_ERR_INVALID, std::string("multiply: ") + why);
+    if (sa == 2 && sb == 2) return hefx_multiply(c, L, a, b, out, stream);
+    HIPCHK(launch_multiply_sizes(c->T, L, sa, sb, (const u64 *)a, (const u64 *)b, (u64 *)out, nullptr, 1, (hipStream_t)stream));
+    return HEFX_OK;
+}
+
 // the launches of hefx_multiply_sum for validated arguments whose groups fit a table slice (2 * group + 1 pointers): the
 // pointer table travels through a ring slot of the key-switch descriptors, whole groups per slice
 static int mul_sum_submit(hefx_context *c, int L, int n, int group, const uint64_t *const *a, const uint64_t *const *b,
@@ -1719,6 +1793,75 @@ extern "C" int hefx_relinearize_batch(hefx_context *c, int L, int n, const uint6
     return ks_run(c, L, n, true, ct3, nullptr, nullptr, key, nullptr, ct2, stream);
 }
 
+// SEAL's relinearize_internal for any size: from the top, polynomial t is key-switched with the key of s^t into (c0, c1).
+// The key-switch kernels read their source at polynomial 2 and their add-in at polynomials 0 and 1 of ONE [3][L][N] block,
+// so every step runs the relinearisation of ks_run on a staged block (c0, c1, c_t).  Two blocks per item, used
+// alternately: step s reads block s & 1 and writes its (c0, c1) into the other block, where the next step only has to
+// place its c_t -- 3 L N copied words for the first step, L N for each later one; the last step writes the caller's output.
+// The blocks live in the linear transforms' workspace (lt_ws: grown without waiting for the device, never the scratch
+// ks_run itself uses); everything is ordered on the caller's stream, and every argument is checked before the first copy.
+// A batch is staged in groups of at most relin_stage_group() items -- 1 GiB of blocks -- one group after the other through
+// the same blocks (the stream orders them), so the workspace does not grow with n.
+static int relin_stage_group(const hefx_context *c, int L)
+{
+    const size_t per_item = 6 * (size_t)L * c->n * sizeof(u64);  // two blocks of [3][L][N]
+    const size_t g = ((size_t)1 << 30) / per_item;
+    return g < 1 ? 1 : (g > (size_t)INT32_MAX ? INT32_MAX : (int)g);
+}
+extern "C" int hefx_relinearize_sizes_batch(hefx_context *c, int L, int n, int size_in, int size_out,
+                                            const uint64_t *const *ct, const uint64_t *const *keys, uint64_t *const *out,
+                                            void *stream)
+{
+    CTXCHK(c);
+    if (int rc = check_ks_level(c, L)) return rc;
+    if (size_out < 2 || size_out >= size_in || size_in > HEFX_CT_SIZE_MAX)
+        return fail(HEFX_ERR_INVALID, "relinearize: sizes must satisfy 2 <= size_out < size_in <= HEFX_CT_SIZE_MAX = " +
+                                          std::to_string(HEFX_CT_SIZE_MAX));
+    if (n < 1 || !ct || !keys || !out) return fail(HEFX_ERR_INVALID, "bad relinearize arguments");
+    for (int t = size_out; t < size_in; ++t)
+        if (!keys[t - 2]) return fail(HEFX_ERR_INVALID, "relinearize: the key of a needed power of the secret key is missing");
+    for (int i = 0; i < n; ++i)
+        if (!ct[i] || !out[i]) return fail(HEFX_ERR_INVALID, "null ciphertext pointer in batch");
+    const size_t pw = (size_t)L * c->n;  // words of one polynomial
+    if (const char *why = outputs_overlap(n, out, size_out * pw * sizeof(u64), {{ct, size_in * pw * sizeof(u64)}}))
+        return fail(HEFX_ERR_INVALID, std::string("relinearize: ") + why);
+    if (size_in == 3) return ks_run(c, L, n, true, ct, nullptr, nullptr, keys[0], nullptr, out, stream);
+    const int group = std::min(n, relin_stage_group(c, L));
+    if (int rc = grow_retiring(c, &c->lt_ws, &c->lt_cap, 6 * pw * (size_t)group, 0, "relinearize staging")) return rc;
+    uint64_t *ws = reinterpret_cast<uint64_t *>(c->lt_ws);
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<const uint64_t *> src((size_t)group);
+    std::vector<uint64_t *> dst((size_t)group);
+    for (int i0 = 0; i0 < n; i0 += group) {
+        const int cnt = n - i0 < group ? n - i0 : group;
+        int step = 0;
+        for (int t = size_in - 1; t >= size_out; --t, ++step) {
+            for (int i = 0; i < cnt; ++i) {
+                const uint64_t *in = ct[i0 + i];
+                uint64_t *blk = ws + ((size_t)(step & 1) * group + i) * 3 * pw;
+                if (step == 0) HIPCHK(hipMemcpyAsync(blk, in, 2 * pw * sizeof(u64), hipMemcpyDeviceToDevice, s));
+                HIPCHK(hipMemcpyAsync(blk + 2 * pw, in + (size_t)t * pw, pw * sizeof(u64), hipMemcpyDeviceToDevice, s));
+                src[(size_t)i] = blk;
+                dst[(size_t)i] = t == size_out ? out[i0 + i] : ws + ((size_t)((step + 1) & 1) * group + i) * 3 * pw;
+            }
+            // (trusted: the blocks are disjoint by construction and the caller's buffers were checked above)
+            if (int rc = ks_run(c, L, cnt, true, src.data(), nullptr, nullptr, keys[t - 2], nullptr, dst.data(), stream, false,
+                                nullptr, nullptr, true))
+                return rc;
+        }
+    }
+    if (size_out > 2)
+        for (int i = 0; i < n; ++i)
+            HIPCHK(hipMemcpyAsync(out[i] + 2 * pw, ct[i] + 2 * pw, (size_t)(size_out - 2) * pw * sizeof(u64),
+                                  hipMemcpyDeviceToDevice, s));
+    return HEFX_OK;
+}
+extern "C" int hefx_relinearize_sizes(hefx_context *c, int L, int size_in, int size_out, const uint64_t *ct,
+                                      const uint64_t *const *keys, uint64_t *out, void *stream)
+{
+    return hefx_relinearize_sizes_batch(c, L, 1, size_in, size_out, &ct, keys, &out, stream);
+}
+
 // ---------------------------------------------------------------------------------------------
 // rescale / mod drop
 // ---------------------------------------------------------------------------------------------
@@ -1741,7 +1884,7 @@ static int rescale_common(hefx_context *c, int L, int size, int count, const uin
 // Pointer tables of the *_batch entries travel through a ring slot of the key-switch descriptors (pinned host mirror
 // -> device copy, one async copy per slice).  fill(hp, i0, cnt) writes the slice's table; run(dp, cnt) launches on it.
 template <class Fill, class Run>
-static int table_slices(hefx_context *c, int n, int ptrs_per_item, hipStream_t s, Fill fill, Run run, int max_slice = 0)
+static int table_slices(hefx_context *c, int n, int ptrs_per_item, hipStream_t s, Fill fill, Run run, int max_slice)
 {
     int SLICE = (int)(sizeof(KsItem) * KS_MAX_CHUNK / sizeof(void *)) / ptrs_per_item;
     if (max_slice > 0 && SLICE > max_slice) SLICE = max_slice;

@@ -576,6 +576,123 @@ hipError_t launch_addsub_table(const DevTables &T, bool sub, int L, int size, co
     return hipGetLastError();
 }
 
+// General tensor product of ciphertexts of sa and sb polynomials (Evaluator::multiply beyond size 2 x size 2):
+//   out[k] = sum_{i+j=k} a_i (.) b_j  mod q_row,   k = 0 .. sa+sb-2.
+// A lane owns one 16-byte record of a row in every polynomial.  sa + sb - 1 <= HEFX_CT_SIZE_MAX = 16, so an output word
+// sums at most min(sa, sb) <= 8 products below 2^122 each: far inside the 63 products a 128-bit accumulator holds (FOLD
+// INTERVALS at mul_sum_kernel).  mac128 per term, ONE barrett128 per output word, no intermediate fold: the canonical
+// residue of the integer sum, hence the bits of SEAL's dyadic-product-and-add loop in any order.  Inputs are only read
+// (a == b is a square); every output word is written once.
+// Two forms of the body, chosen from the resource report (DESIGN.md kernel table):
+//   SA, SB > 0  sizes 2..4 on either side at compile time: the sa + sb operand records are loaded once into registers and
+//               the k loop is unrolled over them -- every operand word leaves HBM and the caches once;
+//   SA == 0     any other legal shape: a loop over k whose inner loop re-reads the records it needs.  A lane re-reads its
+//               OWN records (the same addresses from the same lane within a few hundred instructions), so the repeats are
+//               cache hits and HBM still sees each operand word once; holding up to 17 records under a run-time index
+//               would put them in scratch memory.
+template <int SA, int SB>
+__device__ __forceinline__ void multiply_sizes_body(const DevTables &T, size_t pairs_per_poly, int sa, int sb,
+                                                    const ulonglong2 *__restrict__ a, const ulonglong2 *__restrict__ b,
+                                                    ulonglong2 *__restrict__ out)
+{
+    const int logn = T.logn;
+    for (size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x; w < pairs_per_poly;
+         w += (size_t)gridDim.x * blockDim.x) {
+        const ModConst mc = T.mods[(int)(w >> (logn - 1))];
+        if constexpr (SA > 0) {
+            ulonglong2 ra[SA], rb[SB];
+#pragma unroll
+            for (int i = 0; i < SA; ++i) ra[i] = gld16(a + w + (size_t)i * pairs_per_poly);
+#pragma unroll
+            for (int j = 0; j < SB; ++j) rb[j] = gld16(b + w + (size_t)j * pairs_per_poly);
+#pragma unroll
+            for (int k = 0; k < SA + SB - 1; ++k) {
+                u64 xl = 0, xh = 0, yl = 0, yh = 0;
+#pragma unroll
+                for (int i = 0; i < SA; ++i) {
+                    const int j = k - i;
+                    if (j >= 0 && j < SB) {
+                        mac128(xl, xh, ra[i].x, rb[j].x);
+                        mac128(yl, yh, ra[i].y, rb[j].y);
+                    }
+                }
+                ulonglong2 r;
+                r.x = barrett128(xl, xh, mc);
+                r.y = barrett128(yl, yh, mc);
+                gst16(out + w + (size_t)k * pairs_per_poly, r);
+            }
+        } else {
+            for (int k = 0; k < sa + sb - 1; ++k) {
+                const int i0 = k - (sb - 1) > 0 ? k - (sb - 1) : 0, i1 = k < sa - 1 ? k : sa - 1;
+                u64 xl = 0, xh = 0, yl = 0, yh = 0;
+                for (int i = i0; i <= i1; ++i) {
+                    const ulonglong2 x = gld16(a + w + (size_t)i * pairs_per_poly);
+                    const ulonglong2 y = gld16(b + w + (size_t)(k - i) * pairs_per_poly);
+                    mac128(xl, xh, x.x, y.x);
+                    mac128(yl, yh, x.y, y.y);
+                }
+                ulonglong2 r;
+                r.x = barrett128(xl, xh, mc);
+                r.y = barrett128(yl, yh, mc);
+                gst16(out + w + (size_t)k * pairs_per_poly, r);
+            }
+        }
+    }
+}
+
+template <int SA, int SB>
+__global__ __launch_bounds__(256) void multiply_sizes_kernel(DevTables T, size_t pairs_per_poly, int sa, int sb,
+                                                             const ulonglong2 *__restrict__ a,
+                                                             const ulonglong2 *__restrict__ b, ulonglong2 *__restrict__ out)
+{
+    multiply_sizes_body<SA, SB>(T, pairs_per_poly, sa, sb, a, b, out);
+}
+
+// the pointer-table twin (a[0..n) | b[0..n) | out[0..n), one (sa, sb) for all items), item = blockIdx.y
+template <int SA, int SB>
+__global__ __launch_bounds__(256) void multiply_sizes_table_kernel(DevTables T, size_t pairs_per_poly, int sa, int sb,
+                                                                   const u64 *const *__restrict__ tab, int n)
+{
+    const int item = blockIdx.y;
+    multiply_sizes_body<SA, SB>(T, pairs_per_poly, sa, sb, reinterpret_cast<const ulonglong2 *>(tab[item]),
+                                reinterpret_cast<const ulonglong2 *>(tab[n + item]),
+                                reinterpret_cast<ulonglong2 *>(const_cast<u64 *>(tab[2 * n + item])));
+}
+
+// d_tab == nullptr: one product a x b -> out; otherwise n products through the table (a, b, out unused)
+hipError_t launch_multiply_sizes(const DevTables &T, int L, int sa, int sb, const u64 *a, const u64 *b, u64 *out,
+                                 const u64 *const *d_tab, int n, hipStream_t s)
+{
+    const size_t pairs = (size_t)L * ((size_t)1 << T.logn) / 2;
+    int blocks = (int)((pairs + 255) / 256);
+    const int cap = d_tab ? 64 : 256 * 8;  // n items in grid.y fill the chip
+    if (blocks > cap) blocks = cap;
+    const ulonglong2 *pa = reinterpret_cast<const ulonglong2 *>(a), *pb = reinterpret_cast<const ulonglong2 *>(b);
+    ulonglong2 *po = reinterpret_cast<ulonglong2 *>(out);
+#define LAUNCH(SA, SB)                                                                                                    \
+    do {                                                                                                                  \
+        if (d_tab)                                                                                                        \
+            hipLaunchKernelGGL((multiply_sizes_table_kernel<SA, SB>), dim3(blocks, n), dim3(256), 0, s, T, pairs, sa, sb, \
+                               d_tab, n);                                                                                 \
+        else                                                                                                              \
+            hipLaunchKernelGGL((multiply_sizes_kernel<SA, SB>), dim3(blocks), dim3(256), 0, s, T, pairs, sa, sb, pa, pb,  \
+                               po);                                                                                       \
+    } while (0)
+    switch (sa >= 2 && sa <= 4 && sb >= 2 && sb <= 4 ? sa * 8 + sb : 0) {
+        case 2 * 8 + 3: LAUNCH(2, 3); break;
+        case 2 * 8 + 4: LAUNCH(2, 4); break;
+        case 3 * 8 + 2: LAUNCH(3, 2); break;
+        case 3 * 8 + 3: LAUNCH(3, 3); break;
+        case 3 * 8 + 4: LAUNCH(3, 4); break;
+        case 4 * 8 + 2: LAUNCH(4, 2); break;
+        case 4 * 8 + 3: LAUNCH(4, 3); break;
+        case 4 * 8 + 4: LAUNCH(4, 4); break;
+        default: LAUNCH(0, 0); break;
+    }
+#undef LAUNCH
+    return hipGetLastError();
+}
+
 // HIP loads a translation unit's code object at its first kernel launch (milliseconds); hefx_context_create pays
 // that once, up front, instead of the first encode / rotation / encryption of a program.
 __global__ void warm_kernels_kernel() {}

@@ -219,6 +219,43 @@ class Engine:
                                                   capi.ptr_array([o.ptr for o in outs]), stream))
         return outs
 
+    def multiply_sizes(self, L, size_a, a, size_b, b, out=None, stream=None):
+        """a [size_a][L][N] * b [size_b][L][N] -> [size_a + size_b - 1][L][N] (hefx_multiply_sizes); a is b: a square"""
+        out = out if out is not None else DeviceArray(self, (size_a + size_b - 1, L, self.N))
+        capi.check(capi.lib().hefx_multiply_sizes(self._h, L, size_a, a.ptr, size_b, b.ptr, out.ptr, stream))
+        return out
+
+    def multiply_sizes_batch(self, L, size_a, As, size_b, Bs, outs=None, stream=None):
+        """outs[i] = As[i] * Bs[i] for one shape (size_a, size_b), one launch per table slice (hefx_multiply_sizes_batch)"""
+        n = len(As)
+        outs = outs if outs is not None else self.empty_many(n, (size_a + size_b - 1, L, self.N))
+        capi.check(capi.lib().hefx_multiply_sizes_batch(self._h, L, n, size_a, capi.ptr_array([a.ptr for a in As]), size_b,
+                                                        capi.ptr_array([b.ptr for b in Bs]),
+                                                        capi.ptr_array([o.ptr for o in outs]), stream))
+        return outs
+
+    @staticmethod
+    def _key_array(keys, size_in):
+        """keys[p - 2] = key of s^p as the C array hefx_relinearize_sizes reads: entries up to size_in - 3, NULL where absent"""
+        keys = list(keys) + [None] * max(0, int(size_in) - 2 - len(keys))
+        return capi.ptr_array([k.ptr if k is not None else None for k in keys])
+
+    def relinearize_sizes(self, L, size_in, size_out, ct, keys, out=None, stream=None):
+        """size_in -> size_out polynomials in the order of SEAL's relinearize_internal (hefx_relinearize_sizes); keys[p - 2]
+        is the key of s^p, None where a power is not held"""
+        out = out if out is not None else DeviceArray(self, (size_out, L, self.N))
+        capi.check(capi.lib().hefx_relinearize_sizes(self._h, L, size_in, size_out, ct.ptr, self._key_array(keys, size_in),
+                                                     out.ptr, stream))
+        return out
+
+    def relinearize_sizes_batch(self, L, size_in, size_out, cts, keys, outs=None, stream=None):
+        n = len(cts)
+        outs = outs if outs is not None else self.empty_many(n, (size_out, L, self.N))
+        capi.check(capi.lib().hefx_relinearize_sizes_batch(
+            self._h, L, n, size_in, size_out, capi.ptr_array([c.ptr for c in cts]), self._key_array(keys, size_in),
+            capi.ptr_array([o.ptr for o in outs]), stream))
+        return outs
+
     def multiply_sum(self, L, As, Bs, group=None, outs=None, stream=None):
         """outs[g] = sum over group g of As[i] * Bs[i] (size 2 x 2 -> 3, hefx_multiply_sum); group=None: one sum of all n"""
         n = len(As)

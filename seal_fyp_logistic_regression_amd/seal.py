@@ -176,6 +176,32 @@ class GpuBackend:
     def square(self, L, a):
         return self.engine.square(L, a)
 
+    def multiply_sizes(self, L, size_a, a, size_b, b):
+        return self.engine.multiply_sizes(L, size_a, a, size_b, b)
+
+    def multiply_sizes_batch(self, L, size_a, As, size_b, Bs):
+        return self.engine.multiply_sizes_batch(L, size_a, As, size_b, Bs)
+
+    def relinearize_sizes(self, L, size_in, size_out, ct, keys):
+        """keys[p - 2]: the key of s^p (None where the set does not hold that power)"""
+        return self.engine.relinearize_sizes(L, size_in, size_out, ct, keys)
+
+    def addsub_unequal(self, L, size_a, a, size_b, b, sub):
+        """a +/- b for ciphertexts of different sizes, on the device: the sum / difference of the leading min(size)
+        polynomials goes into the result and the longer operand's tail is copied behind it -- negated when it is the
+        subtrahend's.  The words of the operation on the shorter operand padded with zero polynomials."""
+        e, N = self.engine, self.N
+        lo, hi = min(size_a, size_b), max(size_a, size_b)
+        out = e.empty(hi, L, N)
+        (e.sub if sub else e.add)(L, lo, a, b, out=out.view(0, (lo, L, N)))
+        big = a if size_a > size_b else b
+        tail, dst = big.view(lo * L * N, (hi - lo, L, N)), out.view(lo * L * N, (hi - lo, L, N))
+        if sub and big is b:
+            e.negate(L, hi - lo, tail, out=dst)
+        else:
+            e.copy_raw(dst.ptr, tail.ptr, tail.nbytes)
+        return out
+
     def apply_galois(self, L, ct, elt, key):
         return self.engine.apply_galois(L, ct, elt, key)
 
@@ -393,7 +419,9 @@ class SecretKey:
 
 
 class KSwitchKeys:
-    """GaloisKeys / RelinKeys: galois element (or 0 for the relin key) -> device key [k-1][2][k][N]."""
+    """GaloisKeys / RelinKeys: index -> device key [k-1][2][k][N].  A Galois key sits under its Galois element, the
+    relinearisation key of s^p under p - 2 (SEAL's RelinKeys::get_index; s^2, the only power a size-3 ciphertext needs,
+    under 0)."""
 
     def __init__(self):
         self.keys: Dict[int, object] = {}
@@ -404,9 +432,24 @@ class KSwitchKeys:
     def key(self, elt: int):
         return self.keys[elt]
 
+    # RelinKeys by power of the secret key
+    @staticmethod
+    def get_index(key_power: int) -> int:
+        if key_power < 2:
+            raise ValueError("key_power cannot be less than 2")
+        return key_power - 2
+
+    def has_power(self, key_power: int) -> bool:
+        return key_power >= 2 and (key_power - 2) in self.keys
+
+    def power_key(self, key_power: int):
+        return self.keys[self.get_index(key_power)]
+
 
 GaloisKeys = KSwitchKeys
 RelinKeys = KSwitchKeys
+
+CT_SIZE_MAX = 16  # HEFX_CT_SIZE_MAX (hefx.h): the most polynomials a ciphertext may have in this engine
 
 
 def _c_round(x):
@@ -497,11 +540,18 @@ class KeyGenerator:
         key = np.stack([c0, c1], axis=1)  # [k-1][2][k][N]
         return be.from_host(key)
 
-    def relin_keys(self) -> KSwitchKeys:
+    def relin_keys(self, count: int = 1) -> KSwitchKeys:
+        """keys of s^2 .. s^(count + 1) (KeyGenerator::relin_keys(count)): what relinearising a ciphertext of up to
+        count + 2 polynomials needs.  The powers are formed on the device; the sampler stream ids are taken in increasing
+        power, so relin_keys(1) is the key relin_keys() always gave."""
+        if count < 1 or count > CT_SIZE_MAX - 2:
+            raise ValueError("invalid count")
         be, sk = self.ctx.backend, self._sk
-        s2 = be.multiply_plain(self.ctx.k, 1, be.from_host(sk.host[None]), sk.data)
         rk = KSwitchKeys()
-        rk.keys[0] = self._kswitch_key(None, s2)
+        power = be.from_host(sk.host[None])
+        for p in range(2, count + 2):
+            power = be.multiply_plain(self.ctx.k, 1, power, sk.data)
+            rk.keys[p - 2] = self._kswitch_key(None, power)
         return rk
 
     def default_galois_elts(self) -> List[int]:
@@ -718,7 +768,11 @@ class Evaluator:
         if not self._close(a.scale, b.scale):
             raise ValueError("scale mismatch")
         L = a.parms_id()
-        if a.size() != b.size():  # result size = max; the extra polys are copied (negated for b in sub)
+        native = getattr(self.be, "addsub_unequal", None)
+        if a.size() != b.size() and native is not None:  # result size = max; the extra polys are copied (negated for b in sub)
+            size = max(a.size(), b.size())
+            return Ciphertext()._set(native(L, a.size(), a.data, b.size(), b.data, sub), size, L, a.scale)
+        if a.size() != b.size():  # the same through the host, for a backend without that route
             big, small = (a, b) if a.size() > b.size() else (b, a)
             hb = self.be.to_host(big.data)
             pad = np.zeros_like(hb)
@@ -912,15 +966,24 @@ class Evaluator:
         return [Ciphertext()._set(o, 3, L, s) for o, (_, s) in zip(outs, heads)]
 
     def multiply(self, a: Ciphertext, b: Ciphertext, destination=None):
+        """Evaluator::multiply for ciphertexts of any size: the result has size(a) + size(b) - 1 polynomials and is not
+        relinearised.  Size 2 x size 2 goes to the engine's dedicated kernels, any other shape to hefx_multiply_sizes."""
         self._check_same(a, b)
-        if a.size() != 2 or b.size() != 2:
+        sa, sb = a.size(), b.size()
+        general = getattr(self.be, "multiply_sizes", None) if (sa, sb) != (2, 2) else None
+        if (sa, sb) != (2, 2) and general is None:
             raise ValueError("multiply: only size-2 operands are supported (all reference call sites)")
+        if sa < 2 or sb < 2 or sa + sb - 1 > CT_SIZE_MAX:
+            raise ValueError("invalid size")  # SEAL: Ciphertext::resize refuses the destination
         new_scale = a.scale * b.scale
         self._check_scale(new_scale, a.parms_id())
         L = a.parms_id()
-        data = self.be.square(L, a.data) if a.data is b.data else self.be.multiply(L, a.data, b.data)
+        if general is not None:
+            data = general(L, sa, a.data, sb, b.data)
+        else:
+            data = self.be.square(L, a.data) if a.data is b.data else self.be.multiply(L, a.data, b.data)
         out = destination if destination is not None else Ciphertext()
-        return out._set(data, 3, L, new_scale)
+        return out._set(data, sa + sb - 1, L, new_scale)
 
     def multiply_inplace(self, a, b):
         return self.multiply(a, b, a)
@@ -935,9 +998,20 @@ class Evaluator:
     def relinearize_inplace(self, a: Ciphertext, relin_keys: KSwitchKeys):
         if a.size() == 2:
             return a  # SEAL: nothing to do (true at logistic_regression_ckks.cpp:237,319)
-        if a.size() != 3:
+        if a.size() == 3:
+            if not relin_keys.has_key(0):
+                raise ValueError("not enough relinearization keys")
+            return a._set(self.be.relinearize(a.parms_id(), a.data, relin_keys.key(0)), 2, a.parms_id(), a.scale)
+        # any larger size: SEAL's relinearize_internal -- from the top, polynomial t with the key of s^t into (c0, c1)
+        general = getattr(self.be, "relinearize_sizes", None)
+        if general is None or a.size() < 2:
             raise ValueError("relinearize: encrypted size must be 2 or 3")
-        return a._set(self.be.relinearize(a.parms_id(), a.data, relin_keys.key(0)), 2, a.parms_id(), a.scale)
+        if a.size() > CT_SIZE_MAX:
+            raise ValueError("encrypted is not valid for encryption parameters")
+        if not all(relin_keys.has_power(p) for p in range(2, a.size())):
+            raise ValueError("not enough relinearization keys")
+        keys = [relin_keys.power_key(p) for p in range(2, a.size())]
+        return a._set(general(a.parms_id(), a.size(), 2, a.data, keys), 2, a.parms_id(), a.scale)
 
     def rescale_to_next_inplace(self, a: Ciphertext):
         L = a.parms_id()
