@@ -1,4 +1,4 @@
-// xcheck_lr.cpp -- the reference's OWN logistic-regression composites (SURVEY 8a rows a9, a10) as known answers, for
+// xcheck_lr.cpp -- the reference's OWN logistic-regression composites (SURVEY 8a rows a9, a10, a11) as known answers, for
 // tests/test_gpu_xcheck.py.  Companion of tools/gen_composite_vectors.cpp (rows a1-a8), same file format; this one is
 // for THIS repository's shim only, because Tree_cipher, Horner_cipher and predict_cipher_weights encrypt a constant
 // INSIDE the function (logistic_regression_ckks.cpp:102, :162): the result is a function of recordable inputs only if
@@ -16,7 +16,15 @@
 //   poly_ct; tree = Tree_cipher(poly_ct, 3, ...)   [Encryptor 1, stream 1]
 //            horner = Horner_cipher(poly_ct, 3, ...) [Encryptor 2, stream 1]
 //   feat[6], weights; predict = predict_cipher_weights(feat, weights, 8, ...)   [Encryptor 3, stream 1]
-// Sampler-key order under SEAL_SHIM_SEED: draw 0 KeyGenerator, 1 the Encryptor of the inputs, 2..4 Encryptors 1..3.
+//   then, after all of the above (nothing before it moves): featT[8] and labels (encrypted by the Encryptor of the inputs,
+//   after its earlier streams), gk for step 2 (the window rotation -6 of the gradient's dot products is the NAF plan 2, -8
+//   under the default key set), and row a11: the reference's update_weights(feat, featT, labels, weights, ...) [Encryptor 4,
+//   stream 1].  SEAL refuses it at logistic_regression_ckks.cpp:336 (scale out of bounds); an observer of that refusal
+//   (Evaluator::hefx_on_refused) records the operand as `gradient` -- everything the step computed -- and the program fails
+//   unless the invalid_argument arrives and the observer ran exactly once.
+//   after_throw = rotate_vector(add(feat[0], feat[1]), 1), evaluated after the catch: the Evaluator and the live
+//   ciphertexts are still usable.
+// Sampler-key order under SEAL_SHIM_SEED: draw 0 KeyGenerator, 1 the Encryptor of the inputs, 2..5 Encryptors 1..4.
 #include <unistd.h>
 
 #include <cmath>
@@ -95,8 +103,10 @@ int main(int argc, char **argv)
                 s = s * 6364136223846793005ull + 1442695040888963407ull;
                 return (double)((s >> 11) & ((1ull << 40) - 1)) / (double)(1ull << 39) - 1.0;
             };
+            std::vector<std::vector<double>> fvals(rows);
             for (int i = 0; i < rows; ++i) {
-                std::vector<double> f(nw);
+                std::vector<double> &f = fvals[i];
+                f.resize(nw);
                 for (double &x : f) x = next();
                 Plaintext p;
                 encoder.encode(f, scale, p);
@@ -112,6 +122,50 @@ int main(int argc, char **argv)
             put_ct(w, "weights", cw);
             Encryptor e3(context, pk);  // draw 4
             put_ct(w, "predict", predict_cipher_weights(features, cw, nw, scale, evaluator, encoder, gk, rk, e3, params));
+
+            // ---- row a11: update_weights up to where SEAL stops it
+            std::vector<Ciphertext> features_T(nw);
+            for (int j = 0; j < nw; ++j) {
+                std::vector<double> col(rows);
+                for (int i = 0; i < rows; ++i) col[i] = fvals[i][j];
+                Plaintext p;
+                encoder.encode(col, scale, p);
+                enc_inputs.encrypt(p, features_T[j]);
+                put_ct(w, "featT", features_T[j], (std::uint32_t)j);
+            }
+            std::vector<double> yv(rows);
+            for (double &x : yv) x = next() < 0 ? 0.0 : 1.0;
+            Plaintext py;
+            encoder.encode(yv, scale, py);
+            Ciphertext cy;
+            enc_inputs.encrypt(py, cy);
+            put_ct(w, "labels", cy);
+            for (int step : shim::naf(-rows)) {  // the window rotation of the gradient's dot products: 2, -8
+                if (step == 1 || step == -8) continue;  // (recorded above)
+                const std::uint32_t e = elt_from_step(step, n);
+                put_key(w, "gk", gk.key(e), e);
+            }
+            Encryptor e4(context, pk);  // draw 5
+            int observed = 0;
+            evaluator.hefx_on_refused([&](const char *call, const Ciphertext &operand) {
+                if (std::string(call) != "multiply_plain_inplace") throw std::logic_error(std::string("refused call is ") + call);
+                ++observed;
+                put_ct(w, "gradient", operand);
+            });
+            bool refused = false;
+            try {
+                (void)update_weights(features, features_T, cy, cw, 0.1f, evaluator, encoder, gk, rk, e4, scale, params);
+            } catch (const std::invalid_argument &ex) {
+                refused = std::string(ex.what()).find("scale out of bounds") != std::string::npos;
+                if (!refused) throw;
+            }
+            evaluator.hefx_on_refused(nullptr);
+            if (!refused) throw std::logic_error("update_weights was not refused at its multiply_plain_inplace (:336)");
+            if (observed != 1) throw std::logic_error("the refusal was observed " + std::to_string(observed) + " times, not once");
+            Ciphertext sum01, after;
+            evaluator.add(features[0], features[1], sum01);
+            evaluator.rotate_vector(sum01, 1, gk, after);
+            put_ct(w, "after_throw", after);
         }
         std::printf("%s/lr_c4.bin written\n", argv[1]);
     } catch (const std::exception &ex) {

@@ -2720,6 +2720,7 @@ public:
         }
         check_pt(a, p);
         const double ns = a.scale() * p.scale();
+        if (on_refused_ && !scale_in_bounds(ns, a.parms_id())) on_refused_(&a == &dest ? "multiply_plain_inplace" : "multiply_plain", a);
         check_scale(ns, a.parms_id());
         // a valid ciphertext's c1 is uniformly random, so the product is transparent exactly when the plaintext
         // is zero -- known on the host since encode time; no device sync needed (why the reference adds 1e-8).
@@ -2737,6 +2738,15 @@ public:
         dest.set(out, a.size(), a.rows, a.parms_id(), ns);
     }
     void multiply_plain_inplace(Ciphertext &a, const Plaintext &p) const { multiply_plain(a, p, a); }
+    // ---- EXTENSION: an observer of refused products, unset by default (then one test of an empty std::function per
+    // multiply_plain).  When multiply_plain / multiply_plain_inplace is about to throw "scale out of bounds", the observer
+    // is called first with the ciphertext operand as it stands: nothing of the refused call has been recorded, the operand's
+    // own recorded producers are still pending, and reading its words (Ciphertext::data(), a decrypt) submits them like any
+    // other observation -- what a call-by-call run holds there.  The exception follows when the observer returns; afterwards
+    // the Evaluator, the recorded graph and every live ciphertext are as usable as before the call.  This is how
+    // drivers/xcheck_lr.cpp reads the gradient the reference's update_weights holds when SEAL stops it
+    // (logistic_regression_ckks.cpp:336).
+    void hefx_on_refused(std::function<void(const char *call, const Ciphertext &operand)> observer) { on_refused_ = std::move(observer); }
     void multiply(const Ciphertext &a, const Ciphertext &b, Ciphertext &dest) const
     {
         check_ct(a);
@@ -3260,10 +3270,13 @@ private:
         if (!p.buf) throw std::invalid_argument("plain is not valid for encryption parameters");
         if (c.parms_id() != p.parms_id()) throw std::invalid_argument("encrypted_ntt and plain_ntt parameter mismatch");
     }
+    bool scale_in_bounds(double s, const parms_id_type &id) const
+    {
+        return s > 0 && (int)std::log2(s) < ctx_->get_context_data(id)->total_coeff_modulus_bit_count();
+    }
     void check_scale(double s, const parms_id_type &id) const
     {
-        if (s <= 0 || (int)std::log2(s) >= ctx_->get_context_data(id)->total_coeff_modulus_bit_count())
-            throw std::invalid_argument("scale out of bounds");
+        if (!scale_in_bounds(s, id)) throw std::invalid_argument("scale out of bounds");
     }
     int target_rows(int rows, const parms_id_type &id) const
     {
@@ -3310,6 +3323,7 @@ private:
     }
 
     std::shared_ptr<SEALContext> ctx_;
+    std::function<void(const char *, const Ciphertext &)> on_refused_;
 };
 
 }  // namespace seal

@@ -885,13 +885,17 @@ def predict_cipher_weights(ev: Evaluator, encoder: CKKSEncoder, encryptor, featu
     return horner_cipher(ev, encoder, encryptor, lin, len(coeffs) - 1, coeffs, scale, relin_keys)         # :264
 
 
-def update_weights(ev: Evaluator, encoder: CKKSEncoder, encryptor, features: Sequence[Ciphertext],
-                   features_T: Sequence[Ciphertext], labels: Ciphertext, weights: Ciphertext, learning_rate: float,
-                   gal_keys: KSwitchKeys, relin_keys: KSwitchKeys, scale: float, degree: int = 3) -> Ciphertext:
-    """update_weights, /root/reference/logistic_regression_ckks.cpp:269-345.  As committed, the reference cannot
-    get past :336 with its own parameters: the gradient is at the last level (one 60-bit prime left) and the
-    multiply_plain pushes the scale to 2^80 -> SEAL throws invalid_argument("scale out of bounds").  The mirror
-    keeps that behaviour (ValueError from Evaluator._check_scale)."""
+def lr_gradient(ev: Evaluator, encoder: CKKSEncoder, encryptor, features: Sequence[Ciphertext],
+                features_T: Sequence[Ciphertext], labels: Ciphertext, weights: Ciphertext, gal_keys: KSwitchKeys,
+                relin_keys: KSwitchKeys, scale: float, degree: int = 3):
+    """update_weights up to its manual rescale, /root/reference/logistic_regression_ckks.cpp:269-323: everything the
+    training step computes before SEAL refuses it at :336.  Returns (gradient, pred_labels): the gradient after :323
+    (size 2, one prime left, scale snapped to a power of two) and the operand of the sub at :288.
+
+    Slot j < num_weights of the gradient is sum_i X[i, j] * (sigmoid(z_i) - y_i).  z_i is the dot product the
+    reference's window sum leaves in slot i of row i (helper.h:455-476, masked at :222-229): all of X[i] . w for
+    i <= num_weights, the terms k >= i - num_weights for the rows after that, nothing from row 2 * num_weights on --
+    reproduced, not fixed."""
     num_obs, num_weights = len(features), len(features_T)
     pred = predict_cipher_weights(ev, encoder, encryptor, features, weights, num_weights, scale, gal_keys,
                                   relin_keys, degree)                                                       # :282
@@ -906,7 +910,20 @@ def update_weights(ev: Evaluator, encoder: CKKSEncoder, encryptor, features: Seq
     gradient = ev.multiply_plain_sum(grads, masks)[0]                                                      # :310, :316
     ev.relinearize_inplace(gradient, relin_keys)                                                           # :319
     ev.rescale_to_next_inplace(gradient)                                                                   # :321
-    gradient.scale = 2.0 ** int(np.log2(gradient.scale))                                                   # :324
+    gradient.scale = 2.0 ** int(np.log2(gradient.scale))                                                   # :323
+    return gradient, pred_labels
+
+
+def update_weights(ev: Evaluator, encoder: CKKSEncoder, encryptor, features: Sequence[Ciphertext],
+                   features_T: Sequence[Ciphertext], labels: Ciphertext, weights: Ciphertext, learning_rate: float,
+                   gal_keys: KSwitchKeys, relin_keys: KSwitchKeys, scale: float, degree: int = 3) -> Ciphertext:
+    """update_weights, /root/reference/logistic_regression_ckks.cpp:269-345.  As committed, the reference cannot
+    get past :336 with its own parameters: the gradient is at the last level (one 60-bit prime left) and the
+    multiply_plain pushes the scale to 2^80 -> SEAL throws invalid_argument("scale out of bounds").  The mirror
+    keeps that behaviour (ValueError from Evaluator._check_scale)."""
+    num_obs = len(features)
+    gradient, _ = lr_gradient(ev, encoder, encryptor, features, features_T, labels, weights, gal_keys, relin_keys,
+                              scale, degree)                                                                # :275-323
     n_pt = encoder.encode(float(learning_rate) / num_obs, scale)                                           # :330-331
     ev.mod_switch_to_inplace(n_pt, gradient.parms_id())                                                    # :333
     ev.multiply_plain_inplace(gradient, n_pt)                                                              # :336  <- SEAL throws here

@@ -271,7 +271,8 @@ def test_matrix_encode_decode_and_ciphermatrix_plainvector_bit_exact():
 
 def test_logistic_regression_step_bit_exact(rescale_mode):
     """rows a9-a11 on the reference's LR chain {60,40x7,60}: Tree/Horner sigmoid, predict_cipher_weights (dot products
-    of all rows advanced in lockstep as batched key switches), update_weights raising where SEAL raises (:336)."""
+    of all rows advanced in lockstep as batched key switches), update_weights raising where SEAL raises (:336) -- what it
+    computes before that is held to the twin and to plaintext math in tests/test_gpu_lr_gradient.py."""
     from seal_fyp_logistic_regression_amd import algorithms as alg
     X = np.array([[0.5, -1.0, 0.2, 0.1], [1.5, 0.25, -0.3, 0.4], [-0.75, 0.5, 0.6, -0.2]])
     w = np.array([0.3, -0.6, 0.5, 0.25])

@@ -265,7 +265,8 @@ def test_composites_a2_a4_a5_a7_a8_at_n16384_c3_chain():
 
 def test_logistic_regression_step_at_n16384_c4_chain(rescale_mode):
     """rows a9-a11 at config 4's FULL parameter set (N=16384, {60,40x7,60}, L=8): Tree sigmoid, predict_cipher_weights
-    over 3 rows x 4 weights (row-batched key switches at L=8 ... 4), update_weights raising where SEAL raises."""
+    over 3 rows x 4 weights (row-batched key switches at L=8 ... 4), update_weights raising where SEAL raises (what it
+    computes before that: test_lr_gradient_at_n16384_c4_chain below)."""
     from seal_fyp_logistic_regression_amd import algorithms as alg
     from tests.test_gpu_composites import both, bits, decode
     X = np.array([[0.5, -1.0, 0.2, 0.1], [1.5, 0.25, -0.3, 0.4], [-0.75, 0.5, 0.6, -0.2]])
@@ -292,6 +293,16 @@ def test_logistic_regression_step_at_n16384_c4_chain(rescale_mode):
     assert pg.parms_id() == po.parms_id() and (bits(eg, pg) == bits(eo, po)).all()
     z = X @ w
     assert np.allclose(decode(eg, pg, 3), c[0] + c[1] * z + c[2] * z ** 2 + c[3] * z ** 3, atol=5e-3)
+
+
+def test_lr_gradient_at_n16384_c4_chain(rescale_mode):
+    """row a11 before its exception at config 4's FULL parameter set: algorithms.lr_gradient (update_weights up to its manual
+    rescale, logistic_regression_ckks.cpp:269-323) over the 3 x 4 inputs above -- pred_labels and gradient the twin's words,
+    gradient at the last level with scale 2^40, its slots the plaintext gradient within 8x the twin's own decode error
+    (figures and derivation: tests/test_gpu_lr_gradient.py), and update_weights still raising afterwards."""
+    from tests import lr_gradient_cases as C
+    from tests.test_gpu_lr_gradient import check_gradient_against_twin_and_plain_math
+    check_gradient_against_twin_and_plain_math((3, 4), rescale_mode, 16384, C.ALLOWANCE["c4"])
 
 
 # ---------------------------------------------------------------------------------------------------------------

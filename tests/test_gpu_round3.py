@@ -124,7 +124,8 @@ def test_reference_lr_driver_unchanged_runs_to_the_scale_exception(tmp_path, dev
     """The reference's logistic_regression_ckks.cpp, compiled unchanged against include/seal/seal.h, on 400 pulsar rows:
     it encrypts, runs predict_cipher_weights (:282 -> 3600 recorded key switches), the eight gradient dot products
     (:295-300, 400-long rotate-by-1 chains) and the masks, and stops where SEAL itself stops -- evaluator.multiply_plain
-    at :336 throws std::invalid_argument("scale out of bounds") at the last level (SURVEY 3.3).
+    at :336 throws std::invalid_argument("scale out of bounds") at the last level (SURVEY 3.3; rows a9-a11 -- the words of
+    the gradient the reference's update_weights holds at that throw are checked by tests/test_gpu_xcheck.py).
     devices = 2: the same unchanged binary with SEAL_SHIM_DEVICES=2 -- the recorded rows are dealt over two engine
     contexts (both on this box's one GPU; on a node: one per GPU) -- must behave identically (the bit-for-bit comparison
     of that path is drivers/shim_selftest.cpp's)."""

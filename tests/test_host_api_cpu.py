@@ -14,14 +14,14 @@ from tests.oracle_backend import OracleBackend
 GOLD = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "appendix_b.json")))
 
 
-def make(N, bits, seed=1):
+def make(N, bits, seed=1, galois_steps=None):
     parms = S.EncryptionParameters("ckks")
     parms.set_poly_modulus_degree(N)
     parms.set_coeff_modulus(S.CoeffModulus.Create(N, bits))
     ctx = S.SEALContext.Create(parms, backend=OracleBackend(N, parms.coeff_modulus()))
     kg = S.KeyGenerator(ctx, seed)
     return dict(ctx=ctx, kg=kg, enc=S.Encryptor(ctx, kg.public_key(), seed + 1), dec=S.Decryptor(ctx, kg.secret_key()),
-                encoder=S.CKKSEncoder(ctx), ev=S.Evaluator(ctx), rk=kg.relin_keys(), gk=kg.galois_keys())
+                encoder=S.CKKSEncoder(ctx), ev=S.Evaluator(ctx), rk=kg.relin_keys(), gk=kg.galois_keys(galois_steps))
 
 
 @pytest.fixture(scope="module")
@@ -156,7 +156,8 @@ def test_matrix_encode_decode(env):
 
 
 def test_polynomial_and_logistic_regression_step():
-    """rows a9-a11: Tree/Horner sigmoid, predict_cipher_weights, and update_weights stopping where SEAL stops."""
+    """rows a9-a11: Tree/Horner sigmoid, predict_cipher_weights, and update_weights stopping where SEAL stops (the gradient
+    it holds by then: test_lr_gradient_on_the_oracle_twin below)."""
     e = make(2048, [60, 40, 40, 40, 40, 40, 40, 40, 60], seed=4)  # the reference's LR chain (logistic_regression_ckks.cpp:420)
     ev, scale = e["ev"], 2.0 ** 40
     x = np.array([0.8, -0.3, 0.1])
@@ -181,6 +182,57 @@ def test_polynomial_and_logistic_regression_step():
     assert np.allclose(dec(e, pred, 3).real, c[0] + c[1] * z + c[2] * z ** 2 + c[3] * z ** 3, atol=5e-3)
     with pytest.raises(ValueError, match="scale out of bounds"):  # reference stops at :336
         alg.update_weights(ev, e["encoder"], e["enc"], feats, featsT, cy, cw, 0.1, e["gk"], e["rk"], scale)
+
+
+@pytest.mark.parametrize("shape", [(3, 4), (5, 3), (8, 8), (40, 8)])
+def test_lr_gradient_on_the_oracle_twin(shape, rescale_mode, capsys):
+    """row a11, the part before the exception: algorithms.lr_gradient on the twin alone, at the parameters and inputs of
+    tests/test_gpu_lr_gradient.py, against the float64 expectation of tests/lr_gradient_cases.py.  Prints the largest decode
+    error -- the figure the GPU tests' allowance (8x) is derived from -- and holds the recorded figure and the allowance to
+    their conditions: the error of this run within twice the recorded one, the allowance at most a tenth of the smallest
+    |g_j|.  ((40, 8) is here for its figure; its update_weights re-run is left to the smaller shapes.)"""
+    from tests import lr_gradient_cases as C
+    e = make(4096, C.LR_BITS, seed=C.KEY_SEED, galois_steps=[1, -8] if shape == (8, 8) else None)
+    X, w, y = C.inputs(*shape)
+    want = C.expected_gradient(X, w, y, alg.SIGMOID_COEFFS[3])
+    gradient, pred_labels = C.run_gradient(e, X, w, y, then_update=shape != (40, 8))
+    C.check_shape_of_results(gradient, pred_labels)
+    err = C.decode_error(e, gradient, want)
+    pl_want, _ = C.expected_pred_labels(X, w, y, alg.SIGMOID_COEFFS[3])
+    pl_err = float(np.abs(dec(e, pred_labels, shape[0]).real - pl_want).max())
+    with capsys.disabled():
+        print(f"\nlr_gradient {shape} {rescale_mode}: max |decoded - g_j| = {err:.3e} (pred_labels: {pl_err:.3e}), "
+              f"min |g_j| = {np.abs(want).min():.4f}, allowance {C.ALLOWANCE[shape]:.3e}")
+    assert C.ALLOWANCE[shape] == 8 * C.TWIN_ERROR[shape] and C.ALLOWANCE[shape] <= 0.1 * np.abs(want).min()
+    assert err <= 2 * C.TWIN_ERROR[shape]   # the recorded figure is this run's (round), the other division's within 2x
+    assert pl_err < 1e-4                    # three Horner levels at scale 2^40 over |z| < 4: far above CKKS noise, far below a term
+    if shape[0] == shape[1]:                # every sum whole: the closed form g = X^T (sigmoid(X w) - y) itself
+        assert np.abs(want - C.closed_form_gradient(X, w, y, alg.SIGMOID_COEFFS[3])).max() < 1e-12
+
+
+def test_lr_gradient_masks_encoded_at_level_2_are_the_references_route():
+    """logistic_regression_ckks.cpp:302-308 encodes each one-hot mask at the top level and mod-switches it to the level of
+    the dot products (2 on the LR chain); algorithms.lr_gradient encodes them at level 2 directly, in one batch.  CKKS
+    mod-switching of a plaintext drops RNS rows, so the words must be the same -- by one mod_switch_to as the reference does,
+    and level by level."""
+    from tests import lr_gradient_cases as C
+    e = make(4096, C.LR_BITS, seed=C.KEY_SEED)
+    ev, encoder = e["ev"], e["encoder"]
+    for num_weights in (3, 4, 8):
+        direct = encoder.encode_many(list(np.eye(num_weights)), C.SCALE, parms_id=2)
+        for i, d in enumerate(direct):
+            mask = np.zeros(num_weights)
+            mask[i] = 1
+            top = encoder.encode(mask, C.SCALE)
+            assert top.parms_id() == e["ctx"].first_parms_id() == 8 and d.parms_id() == 2 and d.scale == top.scale
+            stepwise = encoder.encode(mask, C.SCALE)
+            while stepwise.parms_id() > 2:
+                ev.mod_switch_to_next_inplace(stepwise)
+            ev.mod_switch_to_inplace(top, 2)                                                               # :308
+            for other in (top, stepwise):
+                assert other.parms_id() == 2 and np.array_equal(np.asarray(other.data).reshape(2, -1),
+                                                                np.asarray(d.data).reshape(2, -1))
+            assert not d.is_zero and np.asarray(d.data).reshape(2, -1).any()
 
 
 def test_hoisted_rotation_is_the_regular_key_switch(env):

@@ -69,3 +69,32 @@ def test_sha3_parms_id_and_parameter_stream_against_hashlib(tmp_path):
     assert tuple(int(x, 16) for x in (a, b, c, d)) == want_id
     assert bytes.fromhex(stream) == struct.pack("<BQQ", 2, 8192, 4) + struct.pack("<4Q", *primes) + struct.pack("<Q", 0)
     assert out[2] == "roundtrip 1"
+
+
+def test_refused_product_observer_on_the_symbolic_engine_under_asan_and_ubsan():
+    """drivers/shim_selftest.cpp --refused-only without a GPU: the case of Evaluator::hefx_on_refused (a multiply_plain_inplace
+    that SEAL refuses with recorded rotations pending on its operand, logistic_regression_ckks.cpp:336) linked against the
+    symbolic engine of drivers/hefx_symbolic.cpp, everything built with -fsanitize=address,undefined as the stand-alone program
+    it is.  The symbolic engine's words are digests of the dataflow, so "the observer reads the words of the call-by-call run"
+    and "add + rotate_vector afterwards give the same words" are checked for what the recorder submits; the GPU suite runs
+    the whole selftest, this case included, on real arithmetic."""
+    import shutil
+    out = os.path.join(ROOT, "build", "symbolic_san")
+    try:
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "make_symbolic_libhefx.py"), "--sanitize"], capture_output=True,
+                           text=True, timeout=900)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        exe = os.path.join(out, "shim_selftest")
+        r = subprocess.run(["g++", "-O0", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+                            "-std=c++17", "-w", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "drivers", "shim_selftest.cpp"),
+                            "-o", exe, "-L" + out, "-lhefx", "-Wl,-rpath,$ORIGIN"], capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-4000:]
+        env = {k: v for k, v in os.environ.items() if not k.startswith(("SEAL_SHIM_", "HEFX_"))}
+        env.update(ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+        r = subprocess.run([exe, "--refused-only"], capture_output=True, text=True, timeout=600, env=env)
+    finally:  # the stand-in library never outlives the test (it is named like the real one)
+        shutil.rmtree(out, ignore_errors=True)
+    assert r.returncode == 0 and "REFUSED-ONLY PASSED (0 failures)" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "FAIL" not in r.stdout and r.stdout.count("ok:   ") >= 9
+    assert "hefx-symbolic-error" not in r.stderr and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr \
+        and "LeakSanitizer" not in r.stderr, r.stderr[-4000:]
