@@ -35,7 +35,8 @@
  *      when a call outgrows a buffer that cannot be retired while in use:
  *                                  hefx_multiply_plain (a first `count` above 4096: the per-ciphertext
  *                                  transparency marks move), hefx_ckks_encode / hefx_ckks_encode_batch (a
- *                                  call of more than one vector that outgrows its pinned staging buffer),
+ *                                  call of more than one vector that outgrows its pinned staging buffer; their
+ *                                  _wide forms and the scalar form share that staging and wait the same way),
  *                                  hefx_free (a block that is not the pool's goes to hipFree)
  *    Besides these, an entry waits only for ITSELF: for a descriptor-ring slot or an encode staging
  *    buffer that one of the context's own earlier calls still owns -- 32 table- or chunk-carrying
@@ -467,8 +468,7 @@ int hefx_linear_transform_plain_bsgs(hefx_context *ctx, int L, const uint64_t *d
  *      another correct encoder that is +-1 where p_k * scale lies next to a half-integer, not bit for bit.
  *      Range: every |value| * scale must be finite and below 2^62 (|p_k| <= max |value|, and the kernel holds
  *      |round(p_k * scale)| in one 64-bit word).  Anything else -- a NaN or an infinity among the values included --
- *      returns HEFX_ERR_INVALID before any work is queued; wider coefficients need an exact host encoder followed by
- *      hefx_ntt_forward.
+ *      returns HEFX_ERR_INVALID before any work is queued; wider coefficients go through hefx_ckks_encode_wide.
  *      The host arrays are copied into pinned staging memory before the call returns (they may be transient); the call
  *      does not wait for the stream -- at most for an earlier encode that still owns the staging buffer it wants (and,
  *      for a call of more than one vector, for the device when its pinned buffer has to grow: conventions at the top). */
@@ -479,6 +479,27 @@ int hefx_ckks_encode(hefx_context *ctx, int L, const double *h_re, const double 
  * hefx_ckks_encode writes. */
 int hefx_ckks_encode_batch(hefx_context *ctx, int L, const double *h_re, const double *h_im, int nvalues, int count,
                            double scale, uint64_t *const *d_outs, void *stream);
+/* ---- the same encoder at any scale: encode(v, ct.scale(), pt) after an unrescaled product (2^80, 2^120), plaintexts
+ *      for add_plain onto hefx_multiply_sum / hefx_linear_transform_cipher results.  Arguments, staging, the out-of-place
+ *      path at N = 32768 and asynchrony as hefx_ckks_encode / hefx_ckks_encode_batch; on input those accept, the same
+ *      words.  A rounded coefficient of 2^63 or more is a float64 without fraction bits, m * 2^e with m < 2^53: row j
+ *      receives (m mod q_j) * (2^e mod q_j) mod q_j, negated for a negative coefficient -- the integer encoded is exactly
+ *      the double the transform produced (nothing is rounded twice; SEAL decomposes the same integer), the same integer
+ *      in every row, within 0.5 + (FFT rounding error, relative to max |value| * scale) of the exact p_k * scale.
+ *      Range: with bc the bit length of q_0 * ... * q_(L-1), every |value| * scale must be finite and below
+ *      2^max(62, min(bc - 3, 1000)).  bc - 3: |p_k * scale| <= max |value| * scale and the float64 error is below 2^-40
+ *      of that, so every coefficient stays below 2^(bc-2) <= Q/2 and the centred integer is unambiguous; 1000 keeps the
+ *      transform's intermediate sums finite.  Anything else returns HEFX_ERR_INVALID before any work is queued. */
+int hefx_ckks_encode_wide(hefx_context *ctx, int L, const double *h_re, const double *h_im, int nvalues, int count,
+                          double scale, uint64_t *d_out, void *stream);
+int hefx_ckks_encode_wide_batch(hefx_context *ctx, int L, const double *h_re, const double *h_im, int nvalues, int count,
+                                double scale, uint64_t *const *d_outs, void *stream);
+/* CKKSEncoder::encode(double, scale, plain) for `count` scalars (host array) -> `count` contiguous plaintexts at d_out:
+ * every word of row j of plaintext i is round_half_away(h_values[i] * scale) mod q_j, the float64 product reduced like
+ * a wide coefficient (the NTT of a constant is that constant in every slot: no transform).  Range and staging as
+ * hefx_ckks_encode_wide. */
+int hefx_ckks_encode_scalar(hefx_context *ctx, int L, const double *h_values, int count, double scale, uint64_t *d_out,
+                            void *stream);
 
 /* ---- randomness, Encryptor::encrypt, Decryptor::decrypt on the GPU (call sites
  *      linear_transformation2.cpp:344-350, logistic_regression_ckks.cpp:362-381, matrix_multiplication.cpp:419).

@@ -678,8 +678,12 @@ inline void submit_nodes(hefx_context *cx, Engine::Stats &stats, const std::vect
                             std::memcpy(vals.data() + t * nv, K[bs.second[t]].host->data(), nv * sizeof(double));
                             outs.push_back(out(bs.second[t]));
                         }
-                        check(hefx_ckks_encode_batch(cx, L, vals.data(), nullptr, size, (int)bs.second.size(), bs.first,
-                                                     outs.data(), nullptr));
+                        // (a group with a coefficient bound of 2^62 or more goes through the wide entry: on vectors
+                        // the narrow entry accepts it writes the narrow entry's words)
+                        double mx = 0;
+                        for (double v : vals) mx = std::max(mx, std::fabs(v));
+                        check((mx * bs.first >= 4611686018427387904.0 ? hefx_ckks_encode_wide_batch : hefx_ckks_encode_batch)(
+                            cx, L, vals.data(), nullptr, size, (int)bs.second.size(), bs.first, outs.data(), nullptr));
                     }
                     break;
                 }
@@ -2250,7 +2254,8 @@ private:
 
 // ------------------------------------------------------------------------------------------------
 // CKKSEncoder (App. A.12): canonical embedding, slot i <-> root zeta^(3^i); encode and decode run on the GPU
-// (hefx_ckks_encode / hefx_ckks_decode); the host FFT below remains for wide coefficients and SEAL_SHIM_HOST_ENCODE=1
+// (hefx_ckks_encode, hefx_ckks_encode_wide from max|v| * scale = 2^62 up to 2^(bit count - 3), hefx_ckks_encode_scalar /
+// hefx_ckks_decode); the host FFT below remains for what lies beyond and for SEAL_SHIM_HOST_ENCODE=1
 // ------------------------------------------------------------------------------------------------
 class CKKSEncoder {
 public:
@@ -2277,14 +2282,83 @@ public:
 
     void encode(const std::vector<double> &values, parms_id_type id, double scale, Plaintext &dest) const
     {
-        const std::size_t n = ctx_->n();
-        if (values.size() > n / 2) throw std::invalid_argument("values has invalid size");
-        const int L = rows_checked(id, scale);
-        if (encode_on_device(values, L, id, scale, dest)) return;
-        std::vector<std::complex<double>> A(n, 0.0);
+        encode_vector(values.data(), nullptr, values.size(), id, scale, dest);
+    }
+    void encode(const std::vector<double> &values, double scale, Plaintext &dest) const
+    {
+        encode(values, ctx_->first_parms_id(), scale, dest);
+    }
+    void encode(const std::vector<std::complex<double>> &values, parms_id_type id, double scale, Plaintext &dest) const
+    {
+        std::vector<double> re(values.size()), im(values.size());
         for (std::size_t i = 0; i < values.size(); ++i) {
-            A[r1_[i]] = values[i];
-            A[r2_[i]] = values[i];
+            re[i] = values[i].real();
+            im[i] = values[i].imag();
+        }
+        encode_vector(re.data(), im.data(), values.size(), id, scale, dest);
+    }
+    void encode(const std::vector<std::complex<double>> &values, double scale, Plaintext &dest) const
+    {
+        encode(values, ctx_->first_parms_id(), scale, dest);
+    }
+    // every NTT slot = round(value*scale): no FFT (hefx_ckks_encode_scalar; the host loop beyond its range)
+    void encode(double value, parms_id_type id, double scale, Plaintext &dest) const
+    {
+        const std::size_t n = ctx_->n();
+        const int L = rows_checked(id, scale);
+        const double co = std::round(value * scale);
+        auto &e = ctx_->engine();
+        if (!host_only() && std::fabs(value * scale) < wide_bound(id)) {
+            dest.buf = shim::new_buf(e, (std::size_t)L * n);
+            shim::check(hefx_ckks_encode_scalar(e->ready({}), L, &value, 1, scale, dest.buf->p, nullptr));
+            finish(dest, L, id, scale, co == 0.0);
+            return;
+        }
+        std::vector<std::uint64_t> rows((std::size_t)L * n);
+        std::vector<std::uint64_t> tmp((std::size_t)L * n, 0);
+        put(tmp, 0, co, L);  // residue of the constant per row
+        for (int j = 0; j < L; ++j) std::fill(rows.begin() + (std::size_t)j * n, rows.begin() + (std::size_t)(j + 1) * n, tmp[(std::size_t)j * n]);
+        dest.buf = shim::upload(e, rows);
+        finish(dest, L, id, scale, co == 0.0);
+    }
+    void encode(double value, double scale, Plaintext &dest) const { encode(value, ctx_->first_parms_id(), scale, dest); }
+
+    void decode(const Plaintext &plain, std::vector<std::complex<double>> &dest) const
+    {
+        std::vector<double> re, im;
+        decode_slots(plain, re, &im);
+        dest.resize(re.size());
+        for (std::size_t i = 0; i < re.size(); ++i) dest[i] = std::complex<double>(re[i], im[i]);
+    }
+    void decode(const Plaintext &plain, std::vector<double> &dest) const { decode_slots(plain, dest, nullptr); }
+
+private:
+    static bool host_only()
+    {
+        static const bool on = [] {
+            const char *s = std::getenv("SEAL_SHIM_HOST_ENCODE");
+            return s && *s && *s != '0';
+        }();
+        return on;
+    }
+    // the bound of hefx_ckks_encode_wide / hefx_ckks_encode_scalar at this level: 2^max(62, min(bit count - 3, 1000))
+    double wide_bound(const parms_id_type &id) const
+    {
+        const int bc = ctx_->get_context_data(id)->total_coeff_modulus_bit_count();
+        return std::ldexp(1.0, std::max(62, std::min(bc - 3, 1000)));
+    }
+    // slot values re (+ i im, im may be null) -> plaintext: on the device when it can, else the host FFT
+    void encode_vector(const double *re, const double *im, std::size_t count, parms_id_type id, double scale, Plaintext &dest) const
+    {
+        const std::size_t n = ctx_->n();
+        if (count > n / 2) throw std::invalid_argument("values has invalid size");
+        const int L = rows_checked(id, scale);
+        if (encode_on_device(re, im, count, L, id, scale, dest)) return;
+        std::vector<std::complex<double>> A(n, 0.0);
+        for (std::size_t i = 0; i < count; ++i) {
+            const std::complex<double> v(re[i], im ? im[i] : 0.0);
+            A[r1_[i]] = v;
+            A[r2_[i]] = std::conj(v);
         }
         fft(A, false);  // a_k = (1/N) sum_r A_r e^{-2 pi i r k / N}
         std::vector<std::uint64_t> rows((std::size_t)L * n);
@@ -2299,38 +2373,17 @@ public:
         shim::check(hefx_ntt_forward(e->ready({}), dest.buf->p, 1, L, 0, nullptr));
         finish(dest, L, id, scale, !any);
     }
-    void encode(const std::vector<double> &values, double scale, Plaintext &dest) const
-    {
-        encode(values, ctx_->first_parms_id(), scale, dest);
-    }
-    // every NTT slot = round(value*scale): no FFT
-    void encode(double value, parms_id_type id, double scale, Plaintext &dest) const
-    {
-        const std::size_t n = ctx_->n();
-        const int L = rows_checked(id, scale);
-        const double co = std::round(value * scale);
-        std::vector<std::uint64_t> one((std::size_t)L), rows((std::size_t)L * n);
-        std::vector<std::uint64_t> tmp((std::size_t)L * n, 0);
-        put(tmp, 0, co, L);  // residue of the constant per row
-        for (int j = 0; j < L; ++j) std::fill(rows.begin() + (std::size_t)j * n, rows.begin() + (std::size_t)(j + 1) * n, tmp[(std::size_t)j * n]);
-        dest.buf = shim::upload(ctx_->engine(), rows);
-        finish(dest, L, id, scale, co == 0.0);
-    }
-    void encode(double value, double scale, Plaintext &dest) const { encode(value, ctx_->first_parms_id(), scale, dest); }
-
-    void decode(const Plaintext &plain, std::vector<double> &dest) const
+    void decode_slots(const Plaintext &plain, std::vector<double> &dest, std::vector<double> *dest_im) const
     {
         if (!plain.buf) throw std::invalid_argument("plain is not valid for encryption parameters");
         auto &e = ctx_->engine();
         const std::size_t n = ctx_->n();
         const int L = plain.rows;
-        static const bool host_only = [] {
-            const char *s = std::getenv("SEAL_SHIM_HOST_ENCODE");
-            return s && *s && *s != '0';
-        }();
-        if (!host_only && L <= 16 && n >= 1024) {  // inverse NTT, CRT, centring and the slot-root FFT on the GPU
+        if (!host_only() && L <= 16 && n >= 1024) {  // inverse NTT, CRT, centring and the slot-root FFT on the GPU
             dest.resize(n / 2);
-            shim::check(hefx_ckks_decode(e->ready({plain.buf.get()}), L, plain.buf->p, 1, plain.scale(), dest.data(), nullptr, nullptr));
+            if (dest_im) dest_im->resize(n / 2);
+            shim::check(hefx_ckks_decode(e->ready({plain.buf.get()}), L, plain.buf->p, 1, plain.scale(), dest.data(),
+                                         dest_im ? dest_im->data() : nullptr, nullptr));
             return;
         }
         auto tmp = shim::new_buf(e, (std::size_t)L * n);
@@ -2372,9 +2425,11 @@ public:
         fft(A, true);  // P(zeta^(2r+1)) = sum_k p_k zeta^k e^{+2 pi i r k / N}
         dest.resize(n / 2);
         for (std::size_t i = 0; i < n / 2; ++i) dest[i] = A[r1_[i]].real();
+        if (dest_im) {
+            dest_im->resize(n / 2);
+            for (std::size_t i = 0; i < n / 2; ++i) (*dest_im)[i] = A[r1_[i]].imag();
+        }
     }
-
-private:
     int rows_checked(const parms_id_type &id, double scale) const
     {
         const int L = ctx_->rows_of(id);
@@ -2385,41 +2440,42 @@ private:
     }
     // hefx_ckks_encode (FFT + rounding + RNS + NTT on the GPU) when N is in the kernel's range, every coefficient
     // provably fits 62 bits (|p_k| <= max|v|) and zero-ness follows from norms (Parseval: max|p_k| >=
-    // sqrt(2 sum v^2)/N); otherwise the host FFT below.  SEAL_SHIM_HOST_ENCODE=1 forces the host path.
-    bool encode_on_device(const std::vector<double> &values, int L, const parms_id_type &id, double scale,
+    // sqrt(2 sum |v|^2)/N); hefx_ckks_encode_wide from there up to its bound (never zero: the same inequality); otherwise
+    // the host FFT.  SEAL_SHIM_HOST_ENCODE=1 forces the host path.
+    bool encode_on_device(const double *re, const double *im, std::size_t count, int L, const parms_id_type &id, double scale,
                           Plaintext &dest) const
     {
         const std::size_t n = ctx_->n();
-        if (n < 1024 || n > 32768 || values.empty()) return false;
-        static const bool host_only = [] {
-            const char *s = std::getenv("SEAL_SHIM_HOST_ENCODE");
-            return s && *s && *s != '0';
-        }();
-        if (host_only) return false;
+        if (n < 1024 || n > 32768 || count == 0) return false;
+        if (host_only()) return false;
         double mx = 0, ss = 0;
-        for (double v : values) {
-            if (!std::isfinite(v)) return false;
-            mx = std::max(mx, std::fabs(v));
-            ss += v * v;
+        for (std::size_t i = 0; i < count; ++i) {
+            const double a = im ? std::hypot(re[i], im[i]) : std::fabs(re[i]);
+            if (!std::isfinite(a)) return false;
+            mx = std::max(mx, a);
+            ss += a * a;
         }
-        if (mx * scale >= 4611686018427387904.0) return false;
+        const bool wide = mx * scale >= 4611686018427387904.0;
+        if (wide && !(mx * scale < std::ldexp(1.0, std::min(ctx_->get_context_data(id)->total_coeff_modulus_bit_count() - 3, 1000))))
+            return false;
         const bool zero = mx * scale < 0.499, nonzero = std::sqrt(2.0 * ss) / (double)n * scale > 0.501;
         if (!zero && !nonzero) return false;
         auto &e = ctx_->engine();
-        if (e->lazy && !shim::sync_mode()) {
+        if (!im && e->lazy && !shim::sync_mode()) {
             // recorded: the encodes of a loop (2000 one-hot masks in logistic_regression_ckks.cpp:222-225, 4018 vectors in
             // front of the training loop) go to the device as one hefx_ckks_encode_batch per (level, length, scale)
             shim::Engine::Node x{};
-            x.host = std::make_shared<std::vector<double>>(values);
+            x.host = std::make_shared<std::vector<double>>(re, re + count);
             x.scale = scale;
-            dest.buf = e->record(shim::Engine::Node::ENCODE, nullptr, nullptr, 0, L, (int)values.size(), (std::size_t)L * n, e, &x);
+            dest.buf = e->record(shim::Engine::Node::ENCODE, nullptr, nullptr, 0, L, (int)count, (std::size_t)L * n, e, &x);
             dest.view_words_ = 0;
             finish(dest, L, id, scale, zero);
             return true;
         }
+        // (complex vectors are encoded at the call: they read nothing recorded, and the stream orders them)
         dest.buf = shim::new_buf(e, (std::size_t)L * n);
         dest.view_words_ = 0;
-        shim::check(hefx_ckks_encode(e->ready({}), L, values.data(), nullptr, (int)values.size(), 1, scale, dest.buf->p, nullptr));
+        shim::check((wide ? hefx_ckks_encode_wide : hefx_ckks_encode)(e->ready({}), L, re, im, (int)count, 1, scale, dest.buf->p, nullptr));
         finish(dest, L, id, scale, zero);
         return true;
     }
@@ -2435,9 +2491,15 @@ private:
     {
         const std::size_t n = ctx_->n();
         const bool neg = co < 0;
-        const shim::u128 mag = (shim::u128)std::fabs(co);
+        // an integer-valued double is m * 2^ex with m < 2^53: (m mod q) * (2^ex mod q) mod q, right at every magnitude
+        // (what hefx_ckks_encode_wide computes)
+        int ex = 0;
+        const double fr = std::frexp(std::fabs(co), &ex);  // |co| = fr * 2^ex, fr in [0.5, 1)
+        const int sh = ex > 53 ? ex - 53 : 0;
+        const std::uint64_t m = (std::uint64_t)std::ldexp(fr, ex - sh);
         for (int j = 0; j < L; ++j) {
-            const std::uint64_t q = ctx_->primes()[j], r = (std::uint64_t)(mag % q);
+            const std::uint64_t q = ctx_->primes()[j];
+            const std::uint64_t r = shim::mulmod(m % q, shim::powmod(2 % q, (std::uint64_t)sh, q), q);
             rows[(std::size_t)j * n + i] = neg ? (r ? q - r : 0) : r;
         }
     }

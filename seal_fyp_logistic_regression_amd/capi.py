@@ -106,6 +106,9 @@ _SIGS = {
     "hefx_linear_transform_plain_bsgs": (_i, [_vp, _i, _vp, _i, _i, _pp, _i, C.POINTER(_u32), _pp, _i, _vp, _vp]),
     "hefx_ckks_encode": (_i, [_vp, _i, _vp, _vp, _i, _i, C.c_double, _vp, _vp]),
     "hefx_ckks_encode_batch": (_i, [_vp, _i, _vp, _vp, _i, _i, C.c_double, _pp, _vp]),
+    "hefx_ckks_encode_wide": (_i, [_vp, _i, _vp, _vp, _i, _i, C.c_double, _vp, _vp]),
+    "hefx_ckks_encode_wide_batch": (_i, [_vp, _i, _vp, _vp, _i, _i, C.c_double, _pp, _vp]),
+    "hefx_ckks_encode_scalar": (_i, [_vp, _i, _vp, _i, C.c_double, _vp, _vp]),
     "hefx_sample_uniform": (_i, [_vp, C.c_char_p, _u64, _i, _i, _i, _vp, _vp]),
     "hefx_sample_ternary": (_i, [_vp, C.c_char_p, _u64, _i, _i, _i, _vp, _vp]),
     "hefx_sample_noise": (_i, [_vp, C.c_char_p, _u64, _i, _i, _i, _vp, _vp]),

@@ -174,6 +174,7 @@ struct hefx_context {
     EncodeTables E{};
     double *d_vals = nullptr;
     size_t vals_cap = 0;
+    std::vector<int> enc_wide_bits;  // [L] log2 of the wide entries' bound (encode_wide_bits), 0 = not computed yet
     // pinned staging ring for small encodes (one vector): the caller's array is copied here and the call returns
     // without waiting for the H2D copy
     static constexpr int STAGE_SLOTS = 8;
@@ -2224,39 +2225,59 @@ static int ensure_encode_tables(hefx_context *c)
     return HEFX_OK;
 }
 
-// every |v_i| * scale < 2^62 and finite?  |p_k| <= max|v_i|, and the kernel converts |round(p_k * scale)| to a 64-bit
-// word: beyond the range that conversion is undefined, not an error.  One vectorisable pass over the components
-// (max(|re|, |im|) * scale < 2^61 implies |v| * scale < 2^62); the exact modulus only where that does not decide.
-static bool encode_values_in_range(const double *re, const double *im, size_t n, double scale)
+// every |v_i| * scale < bound (2^62 for the narrow entries) and finite?  |p_k| <= max|v_i|, and the narrow kernel converts
+// |round(p_k * scale)| to a 64-bit word: beyond the range that conversion is undefined, not an error.  One vectorisable
+// pass over the components (max(|re|, |im|) * scale < bound/2 implies |v| * scale < bound); the exact modulus only where
+// that does not decide.
+static bool encode_values_in_range(const double *re, const double *im, size_t n, double scale, double bound = 0x1p62)
 {
+    const double half = bound * 0.5;
     bool undecided = false;
-    for (size_t i = 0; i < n; ++i) undecided |= !(fabs(re[i]) * scale < 0x1p61);
+    for (size_t i = 0; i < n; ++i) undecided |= !(fabs(re[i]) * scale < half);
     if (im)
-        for (size_t i = 0; i < n; ++i) undecided |= !(fabs(im[i]) * scale < 0x1p61);
+        for (size_t i = 0; i < n; ++i) undecided |= !(fabs(im[i]) * scale < half);
     if (!undecided) return true;
     for (size_t i = 0; i < n; ++i)
-        if (!((im ? hypot(re[i], im[i]) : fabs(re[i])) * scale < 0x1p62)) return false;  // NaN and inf fail too
+        if (!((im ? hypot(re[i], im[i]) : fabs(re[i])) * scale < bound)) return false;  // NaN and inf fail too
     return true;
 }
 
-extern "C" int hefx_ckks_encode(hefx_context *c, int L, const double *h_re, const double *h_im, int nvalues,
-                                int count, double scale, uint64_t *d_out, void *stream)
+// log2 of the bound of the wide entries at level L: max(62, min(bc - 3, 1000)), bc = bit length of q_0 ... q_(L-1).
+// Every exact coefficient has |x_k| <= max|v| * scale < 2^(bc-3) and the float64 transform adds less than 2^-40 of
+// that, so |c_k| < 2^(bc-2) <= Q/2: the centred integer a decoder composes is the one encoded.  1000: the transform's
+// intermediate sums (up to N/2 times the values, times the scale) stay finite.
+static int encode_wide_bits(hefx_context *c, int L)
 {
-    CTXCHK(c);
-    if (int rc = check_level(c, L)) return rc;
-    if (c->logn < 10 || c->logn > 15) return fail(HEFX_ERR_UNSUPPORTED, "GPU encode is built for poly_degree in [1024, 32768]");
-    if (!h_re || !d_out || count < 1 || nvalues < 1 || (size_t)nvalues > c->n / 2)
-        return fail(HEFX_ERR_INVALID, "values has invalid size");
-    if (!(scale > 0)) return fail(HEFX_ERR_INVALID, "scale out of bounds");
-    if (int rc = ensure_encode_tables(c)) return rc;
-    const size_t nv = (size_t)nvalues * count, need = nv * (h_im ? 2 : 1);
-    if (!encode_values_in_range(h_re, h_im, nv, scale))  // before the values go into staging
-        return fail(HEFX_ERR_INVALID, "values out of range: every |value| * scale must be finite and below 2^62");
+    if (c->enc_wide_bits.size() != (size_t)c->k + 1) c->enc_wide_bits.assign((size_t)c->k + 1, 0);
+    int &b = c->enc_wide_bits[(size_t)L];
+    if (b) return b;
+    std::vector<u64> Q{1};
+    for (int j = 0; j < L; ++j) {  // Q *= q_j
+        u128 carry = 0;
+        for (auto &limb : Q) {
+            const u128 t = (u128)limb * c->primes[j] + carry;
+            limb = (u64)t;
+            carry = t >> 64;
+        }
+        if (carry) Q.push_back((u64)carry);
+    }
+    int bc = (int)(Q.size() - 1) * 64;
+    for (u64 top = Q.back(); top; top >>= 1) ++bc;
+    return b = std::max(62, std::min(bc - 3, 1000));
+}
+static int encode_range_fail(int bits)
+{
+    return fail(HEFX_ERR_INVALID, "values out of range: every |value| * scale must be finite and below 2^" + std::to_string(bits));
+}
+
+// `need` doubles (h_a, then h_b when it is given) into c->d_vals through pinned memory, asynchronous on s
+static int stage_encode_values(hefx_context *c, const double *h_a, const double *h_b, size_t na, hipStream_t s)
+{
+    const size_t need = na * (h_b ? 2 : 1);
     // (an outgrown value buffer is retired, not freed: an earlier encode may still be reading it, and waiting for the
     // device here would make the call wait for the caller's stream)
     static_assert(sizeof(double) == sizeof(u64), "the value buffer grows like the scratch");
     if (int rc = grow_retiring(c, reinterpret_cast<u64 **>(&c->d_vals), &c->vals_cap, need, 0, "encode values")) return rc;
-    hipStream_t s = (hipStream_t)stream;
     const size_t slot_doubles = c->n;  // one vector of N/2 complex values
     if (need <= slot_doubles) {  // small: through the pinned ring, no wait for the copy
         if (!c->h_stage) {
@@ -2267,8 +2288,8 @@ extern "C" int hefx_ckks_encode(hefx_context *c, int L, const double *h_re, cons
         const unsigned slot = c->stage_next++ % hefx_context::STAGE_SLOTS;
         if (c->stage_busy[slot]) HIPCHK(hipEventSynchronize(c->stage_ev[slot]));
         double *h = c->h_stage + (size_t)slot * slot_doubles;
-        memcpy(h, h_re, nv * sizeof(double));
-        if (h_im) memcpy(h + nv, h_im, nv * sizeof(double));
+        memcpy(h, h_a, na * sizeof(double));
+        if (h_b) memcpy(h + na, h_b, na * sizeof(double));
         HIPCHK(hipMemcpyAsync(c->d_vals, h, need * sizeof(double), hipMemcpyHostToDevice, s));
         HIPCHK(hipEventRecord(c->stage_ev[slot], s));
         c->stage_busy[slot] = true;
@@ -2290,40 +2311,72 @@ extern "C" int hefx_ckks_encode(hefx_context *c, int L, const double *h_re, cons
         }
         if (!c->big_ev[b]) HIPCHK(hipEventCreateWithFlags(&c->big_ev[b], hipEventDisableTiming));
         double *h = c->h_big[b];
-        memcpy(h, h_re, nv * sizeof(double));
-        if (h_im) memcpy(h + nv, h_im, nv * sizeof(double));
+        memcpy(h, h_a, na * sizeof(double));
+        if (h_b) memcpy(h + na, h_b, na * sizeof(double));
         HIPCHK(hipMemcpyAsync(c->d_vals, h, need * sizeof(double), hipMemcpyHostToDevice, s));
         HIPCHK(hipEventRecord(c->big_ev[b], s));
         c->big_busy[b] = true;
     }
+    return HEFX_OK;
+}
+
+// hefx_ckks_encode (wide == false) and hefx_ckks_encode_wide: one body, two bounds, two kernel instantiations
+static int encode_impl(hefx_context *c, int L, const double *h_re, const double *h_im, int nvalues, int count,
+                       double scale, uint64_t *d_out, void *stream, bool wide)
+{
+    if (int rc = check_level(c, L)) return rc;
+    if (c->logn < 10 || c->logn > 15) return fail(HEFX_ERR_UNSUPPORTED, "GPU encode is built for poly_degree in [1024, 32768]");
+    if (!h_re || !d_out || count < 1 || nvalues < 1 || (size_t)nvalues > c->n / 2)
+        return fail(HEFX_ERR_INVALID, "values has invalid size");
+    if (!(scale > 0)) return fail(HEFX_ERR_INVALID, "scale out of bounds");
+    if (int rc = ensure_encode_tables(c)) return rc;
+    const size_t nv = (size_t)nvalues * count;
+    const int bits = wide ? encode_wide_bits(c, L) : 62;
+    if (!encode_values_in_range(h_re, h_im, nv, scale, ldexp(1.0, bits)))  // before the values go into staging
+        return encode_range_fail(bits);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = stage_encode_values(c, h_re, h_im, nv, s)) return rc;
     if (c->logn == 15) {  // the N = 32768 transform is out of place: coefficients into scratch, NTT into d_out
         const size_t words = (size_t)count * L * c->n;
         if (int rc = ensure_scratch(c, words)) return rc;
-        HIPCHK(launch_encode(c->T, c->E, c->d_vals, h_im ? c->d_vals + nv : nullptr, nvalues, count, scale, L, c->scratch, s));
+        HIPCHK(launch_encode(c->T, c->E, c->d_vals, h_im ? c->d_vals + nv : nullptr, nvalues, count, scale, L, c->scratch, wide, s));
         HIPCHK(launch_ntt_split15(c->T, false, c->scratch, (u64 *)d_out, count, L, 0, s));
         return HEFX_OK;
     }
-    HIPCHK(launch_encode(c->T, c->E, c->d_vals, h_im ? c->d_vals + nv : nullptr, nvalues, count, scale, L, (u64 *)d_out, s));
+    HIPCHK(launch_encode(c->T, c->E, c->d_vals, h_im ? c->d_vals + nv : nullptr, nvalues, count, scale, L, (u64 *)d_out, wide, s));
     HIPCHK(launch_ntt(c->T, false, (u64 *)d_out, count, L, 0, s));
     return HEFX_OK;
+}
+
+extern "C" int hefx_ckks_encode(hefx_context *c, int L, const double *h_re, const double *h_im, int nvalues,
+                                int count, double scale, uint64_t *d_out, void *stream)
+{
+    CTXCHK(c);
+    return encode_impl(c, L, h_re, h_im, nvalues, count, scale, d_out, stream, false);
+}
+extern "C" int hefx_ckks_encode_wide(hefx_context *c, int L, const double *h_re, const double *h_im, int nvalues,
+                                     int count, double scale, uint64_t *d_out, void *stream)
+{
+    CTXCHK(c);
+    return encode_impl(c, L, h_re, h_im, nvalues, count, scale, d_out, stream, true);
 }
 
 // the same for `count` vectors whose plaintexts are separately allocated (pointer table): slices of vectors are encoded
 // into engine scratch in one pass each and handed to their owners by one scatter launch -- the words hefx_ckks_encode
 // writes for each vector.  What the shim's recorder calls for the encodes it has collected (2000 one-hot masks inside the
 // reference's prediction loop, logistic_regression_ckks.cpp:222-225; 4018 in front of it).
-extern "C" int hefx_ckks_encode_batch(hefx_context *c, int L, const double *h_re, const double *h_im, int nvalues,
-                                      int count, double scale, uint64_t *const *d_outs, void *stream)
+static int encode_batch_impl(hefx_context *c, int L, const double *h_re, const double *h_im, int nvalues, int count,
+                             double scale, uint64_t *const *d_outs, void *stream, bool wide)
 {
-    CTXCHK(c);
     if (int rc = check_level(c, L)) return rc;
     if (!d_outs || count < 1) return fail(HEFX_ERR_INVALID, "values has invalid size");
-    if (h_re && nvalues >= 1 && scale > 0 && !encode_values_in_range(h_re, h_im, (size_t)nvalues * count, scale))
-        return fail(HEFX_ERR_INVALID, "values out of range: every |value| * scale must be finite and below 2^62");
+    const int bits = wide ? encode_wide_bits(c, L) : 62;
+    if (h_re && nvalues >= 1 && scale > 0 && !encode_values_in_range(h_re, h_im, (size_t)nvalues * count, scale, ldexp(1.0, bits)))
+        return encode_range_fail(bits);
     if (c->logn == 15) {  // out-of-place transform: vector by vector
         for (int i = 0; i < count; ++i)
-            if (int rc = hefx_ckks_encode(c, L, h_re + (size_t)i * nvalues, h_im ? h_im + (size_t)i * nvalues : nullptr, nvalues, 1,
-                                          scale, d_outs[i], stream))
+            if (int rc = encode_impl(c, L, h_re + (size_t)i * nvalues, h_im ? h_im + (size_t)i * nvalues : nullptr, nvalues, 1,
+                                     scale, d_outs[i], stream, wide))
                 return rc;
         return HEFX_OK;
     }
@@ -2335,14 +2388,43 @@ extern "C" int hefx_ckks_encode_batch(hefx_context *c, int L, const double *h_re
     return table_slices(
         c, count, 1, s, [&](const uint64_t **hp, int i0, int cnt) { for (int i = 0; i < cnt; ++i) hp[i] = d_outs[i0 + i]; },
         [&](const u64 *const *dp, int i0, int cnt) -> hipError_t {
-            // (hefx_ckks_encode sizes its own staging; the scratch region is only this call's output area)
+            // (the encode sizes its own staging; the scratch region is only this call's output area)
             if (ensure_scratch(c, words * (size_t)cnt) != HEFX_OK) return hipErrorOutOfMemory;
-            if (hefx_ckks_encode(c, L, h_re + (size_t)i0 * nvalues, h_im ? h_im + (size_t)i0 * nvalues : nullptr, nvalues, cnt, scale,
-                                 (uint64_t *)c->scratch, s) != HEFX_OK)
+            if (encode_impl(c, L, h_re + (size_t)i0 * nvalues, h_im ? h_im + (size_t)i0 * nvalues : nullptr, nvalues, cnt, scale,
+                            (uint64_t *)c->scratch, s, wide) != HEFX_OK)
                 return hipErrorUnknown;
             return launch_scatter_rows(c->scratch, dp, cnt, words, s);
         },
         cap);
+}
+extern "C" int hefx_ckks_encode_batch(hefx_context *c, int L, const double *h_re, const double *h_im, int nvalues,
+                                      int count, double scale, uint64_t *const *d_outs, void *stream)
+{
+    CTXCHK(c);
+    return encode_batch_impl(c, L, h_re, h_im, nvalues, count, scale, d_outs, stream, false);
+}
+extern "C" int hefx_ckks_encode_wide_batch(hefx_context *c, int L, const double *h_re, const double *h_im, int nvalues,
+                                           int count, double scale, uint64_t *const *d_outs, void *stream)
+{
+    CTXCHK(c);
+    return encode_batch_impl(c, L, h_re, h_im, nvalues, count, scale, d_outs, stream, true);
+}
+
+// CKKSEncoder::encode(double, scale, plain) for `count` scalars: plaintext i holds round_half_away(h_values[i] * scale)
+// mod q_j in every word of row j (the NTT of a constant is that constant in every slot).  Staged like a vector encode.
+extern "C" int hefx_ckks_encode_scalar(hefx_context *c, int L, const double *h_values, int count, double scale,
+                                       uint64_t *d_out, void *stream)
+{
+    CTXCHK(c);
+    if (int rc = check_level(c, L)) return rc;
+    if (!h_values || !d_out || count < 1) return fail(HEFX_ERR_INVALID, "values has invalid size");
+    if (!(scale > 0)) return fail(HEFX_ERR_INVALID, "scale out of bounds");
+    const int bits = encode_wide_bits(c, L);
+    if (!encode_values_in_range(h_values, nullptr, (size_t)count, scale, ldexp(1.0, bits))) return encode_range_fail(bits);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = stage_encode_values(c, h_values, nullptr, (size_t)count, s)) return rc;
+    HIPCHK(launch_encode_scalar(c->T, c->d_vals, count, scale, L, (u64 *)d_out, s));
+    return HEFX_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

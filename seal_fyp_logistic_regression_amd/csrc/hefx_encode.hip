@@ -22,6 +22,32 @@ __device__ __forceinline__ double2 cmul(double2 a, double2 b)
     return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
 
+// Wide coefficients (hefx_ckks_encode_wide, hefx_ckks_encode_scalar).  A rounded coefficient of 2^63 or more is already
+// an integer of the form m * 2^e with m < 2^53 (a float64 that large has no fraction bits), so its residue is
+// (m mod q) * (2^e mod q) mod q -- the integer encoded is exactly the double the FFT produced, nothing is rounded twice.
+// 2^e mod q (11 <= e <= 971) as (2^64 mod q)^(e / 64) * (2^(e % 64) mod q): below e = 64 -- every scale up to 2^116 -- one
+// word reduction, beyond it square-and-multiply over the four bits of e / 64.  No table to build or keep resident.
+// Below 2^63 the conversion of the narrow kernel.
+__device__ __forceinline__ u64 pow2mod(int e, const ModConst &mc)
+{
+    u64 r = barrett64(1ull << (e & 63), mc.q, mc.r1);
+    u64 b = barrett64(mc.nq, mc.q, mc.r1);  // nq = 2^64 - q
+    for (e >>= 6; e; e >>= 1) {
+        if (e & 1) r = mulmod(r, b, mc);
+        b = mulmod(b, b, mc);
+    }
+    return r;
+}
+// |co| mod q for an integer-valued double co of any magnitude; canonical in [0, q)
+__device__ __forceinline__ u64 wide_residue(double a /* = |co| */, const ModConst &mc)
+{
+    if (a < 0x1p63) return barrett64((u64)a, mc.q, mc.r1);
+    const u64 bits = (u64)__double_as_longlong(a);
+    const int e = (int)(bits >> 52) - 1075;  // a = m * 2^e, e >= 11
+    const u64 m = (bits & ((1ull << 52) - 1)) | (1ull << 52);
+    return mulmod(barrett64(m, mc.q, mc.r1), pow2mod(e, mc), mc);
+}
+
 template <int LM>  // M = 2^LM = N/2 complex points
 struct FftCfg {
     static constexpr int M = 1 << LM;
@@ -43,7 +69,8 @@ __device__ __forceinline__ void dif(double2 &u, double2 &v, const double2 *__res
 // SPLIT (N = 32768: 16384 complex points do not fit LDS): the first DIF stage is applied while loading -- half h of
 // an FFT of FM = 2*M points keeps a0 + a1 (h = 0: even frequencies) or (a0 - a1) * w_FM^r (h = 1: odd frequencies) --
 // and the workgroup runs the remaining M-point transform; blockIdx.x = 2*kappa + h.
-template <int LM, bool SPLIT>
+// WIDE: the output stage alone differs (wide_residue above); the narrow instantiation is the kernel it always was.
+template <int LM, bool SPLIT, bool WIDE>
 __global__ __launch_bounds__(FftCfg<LM>::T) void ckks_encode_kernel(DevTables T, EncodeTables E, const double *re,
                                                                    const double *im, int nvalues, double scale, int L,
                                                                    u64 *out /* [count][L][N] coefficient form */)
@@ -140,13 +167,37 @@ __global__ __launch_bounds__(FftCfg<LM>::T) void ckks_encode_kernel(DevTables T,
         const double2 z = cmul(v[e], E.post[k]);
         const double co = __builtin_round(z.x * (2.0 / (double)N) * scale);
         const bool neg = co < 0.0;
-        const u64 mag = (u64)__builtin_fabs(co);
-        for (int j = 0; j < L; ++j) {
-            const ModConst mc = T.mods[j];
-            const u64 r = barrett64(mag, mc.q, mc.r1);
-            out[((size_t)vec * L + j) * N + k] = neg ? (r ? mc.q - r : 0) : r;
+        if (WIDE) {
+            const double a = __builtin_fabs(co);
+            for (int j = 0; j < L; ++j) {
+                const ModConst mc = T.mods[j];
+                const u64 r = wide_residue(a, mc);
+                out[((size_t)vec * L + j) * N + k] = neg ? (r ? mc.q - r : 0) : r;
+            }
+        } else {
+            const u64 mag = (u64)__builtin_fabs(co);
+            for (int j = 0; j < L; ++j) {
+                const ModConst mc = T.mods[j];
+                const u64 r = barrett64(mag, mc.q, mc.r1);
+                out[((size_t)vec * L + j) * N + k] = neg ? (r ? mc.q - r : 0) : r;
+            }
         }
     }
+}
+
+// CKKSEncoder::encode(double, scale, plain): the NTT of a constant is that constant in every slot, so plaintext i is
+// round_half_away(value_i * scale) mod q_j in every word of row j -- no transform.  One workgroup row per (j, i).
+__global__ __launch_bounds__(256) void ckks_encode_scalar_kernel(DevTables T, const double *__restrict__ vals, double scale,
+                                                                 int L, u64 *__restrict__ out /* [count][L][N] */)
+{
+    const size_t n = (size_t)1 << T.logn;
+    const size_t a = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = blockIdx.y, i = blockIdx.z;
+    if (a >= n) return;
+    const double co = __builtin_round(vals[i] * scale);
+    const ModConst mc = T.mods[j];
+    const u64 r = wide_residue(__builtin_fabs(co), mc);
+    out[((size_t)i * L + j) * n + a] = co < 0.0 ? (r ? mc.q - r : 0) : r;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -327,17 +378,22 @@ hipError_t launch_decode(const DevTables &T, const EncodeTables &E, const Decode
 }
 
 hipError_t launch_encode(const DevTables &T, const EncodeTables &E, const double *re, const double *im, int nvalues,
-                         int count, double scale, int L, u64 *out, hipStream_t s)
+                         int count, double scale, int L, u64 *out, bool wide, hipStream_t s)
 {
     const int lm = T.logn - 1;
-#define LAUNCH(LMV, SPL)                                                                                         \
+#define LAUNCH1(LMV, SPL, W)                                                                                     \
     {                                                                                                            \
         const size_t lds = sizeof(double2) * (size_t)FftCfg<LMV>::M;                                             \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ckks_encode_kernel<LMV, SPL>),                  \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ckks_encode_kernel<LMV, SPL, W>),               \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
-        hipLaunchKernelGGL((ckks_encode_kernel<LMV, SPL>), dim3(SPL ? 4 : 2, count), dim3(FftCfg<LMV>::T), lds, s, T, \
-                           E, re, im, nvalues, scale, L, out);                                                   \
+        hipLaunchKernelGGL((ckks_encode_kernel<LMV, SPL, W>), dim3(SPL ? 4 : 2, count), dim3(FftCfg<LMV>::T), lds, s, \
+                           T, E, re, im, nvalues, scale, L, out);                                                \
     }
+#define LAUNCH(LMV, SPL)                                                                                         \
+    if (wide)                                                                                                    \
+        LAUNCH1(LMV, SPL, true)                                                                                  \
+    else                                                                                                         \
+        LAUNCH1(LMV, SPL, false)
     switch (lm) {
         case 9: LAUNCH(9, false) break;
         case 10: LAUNCH(10, false) break;
@@ -348,6 +404,19 @@ hipError_t launch_encode(const DevTables &T, const EncodeTables &E, const double
         default: return hipErrorInvalidValue;
     }
 #undef LAUNCH
+#undef LAUNCH1
+    return hipGetLastError();
+}
+
+hipError_t launch_encode_scalar(const DevTables &T, const double *vals, int count, double scale, int L, u64 *out,
+                                hipStream_t s)
+{
+    const int n = 1 << T.logn;
+    for (int i0 = 0; i0 < count; i0 += 32768) {  // (the grid's z extent ends at 65535)
+        const int cnt = count - i0 < 32768 ? count - i0 : 32768;
+        hipLaunchKernelGGL(ckks_encode_scalar_kernel, dim3((n + 255) / 256, L, cnt), dim3(256), 0, s, T, vals + i0, scale, L,
+                           out + (size_t)i0 * L * n);
+    }
     return hipGetLastError();
 }
 

@@ -185,7 +185,10 @@ struct DecodeTables {
 hipError_t launch_decode(const DevTables &T, const EncodeTables &E, const DecodeTables &D, int L, const u64 *coef,
                          int count, double scale, double *p, double *re, double *im, hipStream_t s);
 hipError_t launch_encode(const DevTables &T, const EncodeTables &E, const double *re, const double *im, int nvalues,
-                         int count, double scale, int L, u64 *out, hipStream_t s);
+                         int count, double scale, int L, u64 *out, bool wide, hipStream_t s);
+// plaintext i = round(vals[i] * scale) in every word of its rows ([count][L][N])
+hipError_t launch_encode_scalar(const DevTables &T, const double *vals, int count, double scale, int L, u64 *out,
+                                hipStream_t s);
 // sampling + encrypt/decrypt arithmetic (hefx_sample.hip)
 struct SampleKey {
     uint32_t w[8];  // ChaCha20 key, little-endian words of the 32 key bytes

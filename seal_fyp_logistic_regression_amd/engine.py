@@ -579,28 +579,49 @@ class Engine:
         return out
 
     # ---- CKKS encode on the GPU
-    def ckks_encode(self, L, values, scale, out=None, stream=None):
-        """values: [count][nvalues] (or [nvalues]) real or complex -> [count][L][N] NTT-form plaintexts"""
+    @staticmethod
+    def _encode_args(values):
         v = np.atleast_2d(np.asarray(values))
-        count, nvalues = v.shape
         re = np.ascontiguousarray(v.real, dtype=np.float64)
         im = np.ascontiguousarray(v.imag, dtype=np.float64) if np.iscomplexobj(v) else None
+        return v.shape, re, im
+
+    def _ckks_encode(self, entry, L, values, scale, out, stream):
+        (count, nvalues), re, im = self._encode_args(values)
         out = out if out is not None else DeviceArray(self, (count, L, self.N))
-        capi.check(capi.lib().hefx_ckks_encode(self._h, L, re.ctypes.data, im.ctypes.data if im is not None else None,
-                                               nvalues, count, float(scale), out.ptr, stream))
+        capi.check(entry(self._h, L, re.ctypes.data, im.ctypes.data if im is not None else None,
+                         nvalues, count, float(scale), out.ptr, stream))
         return out
+
+    def _ckks_encode_batch(self, entry, L, values, scale, outs, stream):
+        (count, nvalues), re, im = self._encode_args(values)
+        outs = outs if outs is not None else self.empty_many(count, (L, self.N))
+        capi.check(entry(self._h, L, re.ctypes.data, im.ctypes.data if im is not None else None, nvalues, count,
+                         float(scale), capi.ptr_array([o.ptr for o in outs]), stream))
+        return outs
+
+    def ckks_encode(self, L, values, scale, out=None, stream=None):
+        """values: [count][nvalues] (or [nvalues]) real or complex -> [count][L][N] NTT-form plaintexts"""
+        return self._ckks_encode(capi.lib().hefx_ckks_encode, L, values, scale, out, stream)
 
     def ckks_encode_batch(self, L, values, scale, outs=None, stream=None):
         """values: [count][nvalues] -> `count` separately allocated [L][N] plaintexts (hefx_ckks_encode_batch)"""
-        v = np.atleast_2d(np.asarray(values))
-        count, nvalues = v.shape
-        re = np.ascontiguousarray(v.real, dtype=np.float64)
-        im = np.ascontiguousarray(v.imag, dtype=np.float64) if np.iscomplexobj(v) else None
-        outs = outs if outs is not None else self.empty_many(count, (L, self.N))
-        capi.check(capi.lib().hefx_ckks_encode_batch(
-            self._h, L, re.ctypes.data, im.ctypes.data if im is not None else None, nvalues, count, float(scale),
-            capi.ptr_array([o.ptr for o in outs]), stream))
-        return outs
+        return self._ckks_encode_batch(capi.lib().hefx_ckks_encode_batch, L, values, scale, outs, stream)
+
+    def ckks_encode_wide(self, L, values, scale, out=None, stream=None):
+        """ckks_encode at any scale: |value| * scale below 2^max(62, min(bc - 3, 1000)) (hefx_ckks_encode_wide)"""
+        return self._ckks_encode(capi.lib().hefx_ckks_encode_wide, L, values, scale, out, stream)
+
+    def ckks_encode_wide_batch(self, L, values, scale, outs=None, stream=None):
+        """ckks_encode_batch at any scale (hefx_ckks_encode_wide_batch)"""
+        return self._ckks_encode_batch(capi.lib().hefx_ckks_encode_wide_batch, L, values, scale, outs, stream)
+
+    def ckks_encode_scalar(self, L, values, scale, out=None, stream=None):
+        """values: [count] (or one) real scalars -> [count][L][N] plaintexts, round(v * scale) mod q_j in every word"""
+        v = np.ascontiguousarray(np.atleast_1d(np.asarray(values, dtype=np.float64)))
+        out = out if out is not None else DeviceArray(self, (v.size, L, self.N))
+        capi.check(capi.lib().hefx_ckks_encode_scalar(self._h, L, v.ctypes.data, int(v.size), float(scale), out.ptr, stream))
+        return out
 
     def ckks_decode(self, L, pt, scale, count=1, complex_out=True, stream=None):
         """[count][L][N] NTT-form plaintexts -> [count][N/2] slot values (complex, or real if complex_out=False)"""

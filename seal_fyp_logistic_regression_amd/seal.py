@@ -284,6 +284,16 @@ class GpuBackend:
             return None
         return self.engine.ckks_encode(L, values, scale)
 
+    def ckks_encode_wide(self, L, values, scale):
+        """ckks_encode for 2^62 <= max|v| * scale < 2^(bc-3) (hefx_ckks_encode_wide); None outside the kernel's range of N"""
+        if not 1024 <= self.N <= 32768:
+            return None
+        return self.engine.ckks_encode_wide(L, values, scale)
+
+    def ckks_encode_scalar(self, L, value, scale):
+        """one scalar -> [L][N] plaintext with round(value * scale) mod q_j in every word (hefx_ckks_encode_scalar)"""
+        return self.engine.ckks_encode_scalar(L, [value], scale).view(0, (L, self.N))
+
 
 # ----------------------------------------------------------------------------------------------
 # SEAL-shaped objects
@@ -612,9 +622,10 @@ class Decryptor:
 
 class CKKSEncoder:
     """Canonical embedding with slot i <-> root zeta^(3^i) (App. A.12).  encode runs on the GPU
-    (hefx_ckks_encode: FFT + rounding + RNS + NTT in two launches) when the backend offers it; decode, scalars and
-    coefficients wider than 62 bits use the host FFT + the backend NTT.  device_encode=False forces
-    the host FFT (bit-identical across backends -- what the evaluator parity tests use)."""
+    (hefx_ckks_encode: FFT + rounding + RNS + NTT in two launches; hefx_ckks_encode_wide from max|v| * scale = 2^62 up to
+    2^(bc-3), bc the bit count of the level's modulus; hefx_ckks_encode_scalar for scalars) when the backend offers it;
+    anything beyond uses the host FFT + the backend NTT.  device_encode=False forces the host path (bit-identical across
+    backends -- what the evaluator parity tests use)."""
 
     def __init__(self, context: SEALContext, device_encode: bool = True):
         self.ctx = context
@@ -651,11 +662,18 @@ class CKKSEncoder:
         L = parms_id if parms_id is not None else ctx.first_parms_id()
         out = destination if destination is not None else Plaintext()
         if np.isscalar(values):  # encode(double, scale, pt): every NTT slot = round(v*scale) mod q
-            c = _c_round(float(values) * float(scale))
-            rows = np.empty((L, N), dtype=np.uint64)
-            for j in range(L):
-                rows[j, :] = c % ctx.primes[j]
-            out.data, out.is_zero = be.from_host(rows), c == 0
+            x = float(values) * float(scale)
+            c = _c_round(x) if math.isfinite(x) else None
+            bc = ContextData(ctx, L).total_coeff_modulus_bit_count()
+            dev = getattr(be, "ckks_encode_scalar", None) if self.device_encode else None
+            if dev is not None and c is not None and scale > 0 and abs(x) < 2.0 ** max(62, min(bc - 3, 1000)):
+                out.data, out.is_zero = dev(L, float(values), float(scale)), c == 0
+            else:
+                c = _c_round(x)  # (a non-finite product raises here, as it always did)
+                rows = np.empty((L, N), dtype=np.uint64)
+                for j in range(L):
+                    rows[j, :] = c % ctx.primes[j]
+                out.data, out.is_zero = be.from_host(rows), c == 0
         else:
             v = np.asarray(values)
             if v.size > N // 2:
@@ -680,15 +698,28 @@ class CKKSEncoder:
         return out
 
     def _encode_device(self, v2d: np.ndarray, scale: float, L: int):
-        """GPU encode (hefx_ckks_encode) when the backend has it and every coefficient provably fits 62 bits and
-        zero-ness is decidable from norms; returns (slab [count][L][N], is_zero[count]) or None -> host path."""
+        """GPU encode when the backend has it: hefx_ckks_encode when every coefficient provably fits 62 bits and
+        zero-ness is decidable from norms, hefx_ckks_encode_wide for 2^62 <= max|v| * scale < 2^(bc-3) (never zero);
+        returns (slab [count][L][N], is_zero[count]) or None -> host path."""
         be, N = self.ctx.backend, self.ctx.N
         enc = getattr(be, "ckks_encode", None) if self.device_encode else None
-        if enc is None or not (scale > 0) or math.log2(scale) >= ContextData(self.ctx, L).total_coeff_modulus_bit_count():
+        bc = ContextData(self.ctx, L).total_coeff_modulus_bit_count()
+        if enc is None or not (scale > 0) or math.log2(scale) >= bc:
             return None
         mag = np.abs(v2d)
-        if not np.all(np.isfinite(mag)) or float(mag.max(initial=0.0)) * scale >= 2.0 ** 62:
-            return None  # |p_k| <= max|v|: wide coefficients take the exact big-int host path
+        if not np.all(np.isfinite(mag)):
+            return None
+        top = float(mag.max(initial=0.0)) * scale
+        if top >= 2.0 ** 62:  # |p_k| <= max|v|: wide coefficients
+            wide = getattr(be, "ckks_encode_wide", None)
+            if wide is None or not top < 2.0 ** min(bc - 3, 1000):
+                return None  # beyond the wide entry's bound: the exact big-int host path
+            # Parseval as below: some row may still be (near) zero; only rows with a provably nonzero coefficient go
+            lo = np.sqrt(2.0 * (mag.astype(np.float64) ** 2).sum(axis=1)) / N * scale
+            if not np.all(lo > 0.501):
+                return None
+            slab = wide(L, v2d, scale)
+            return None if slab is None else (slab, [False] * v2d.shape[0])
         # Parseval: sum p_k^2 = (2/N) sum |v_i|^2, so max|p_k| >= sqrt(2 sum|v|^2)/N; and max|p_k| <= max|v|
         hi = mag.max(axis=1) * scale
         lo = np.sqrt(2.0 * (mag.astype(np.float64) ** 2).sum(axis=1)) / N * scale
