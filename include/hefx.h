@@ -145,7 +145,11 @@ int hefx_ntt_forward(hefx_context *ctx, uint64_t *d_data, int npoly, int nrows, 
 int hefx_ntt_inverse(hefx_context *ctx, uint64_t *d_data, int npoly, int nrows, int mod_first, void *stream);
 
 /* ---- K4/K10: Evaluator::add / sub / negate / add_plain (helper.h:219,231,247,259,275,319,464,475;
- *      logistic_regression_ckks.cpp:288,341-342; polynomial.cpp:210).  `count` contiguous ciphertexts. */
+ *      logistic_regression_ckks.cpp:288,341-342; polynomial.cpp:210).  `count` contiguous ciphertexts.
+ *      Aliasing: exact in place is served -- d_out may BE d_a (or, for add / sub, d_b; add(a, a, a) included): same first
+ *      byte, over the whole count * size * L * N words.  Any other overlap of d_out with an operand, in BYTES (views of one
+ *      allocation included), the plaintext d_pt among them, is HEFX_ERR_INVALID before anything is submitted.  Inputs may
+ *      overlap each other freely. */
 int hefx_add(hefx_context *ctx, int L, int size, int count, const uint64_t *d_a, const uint64_t *d_b,
              uint64_t *d_out, void *stream);
 int hefx_sub(hefx_context *ctx, int L, int size, int count, const uint64_t *d_a, const uint64_t *d_b,
@@ -155,12 +159,18 @@ int hefx_negate(hefx_context *ctx, int L, int size, int count, const uint64_t *d
 int hefx_add_plain(hefx_context *ctx, int L, int size, const uint64_t *d_ct, const uint64_t *d_pt,
                    uint64_t *d_out, void *stream);
 /* n independent pairs in one launch: d_out[i] = d_a[i] +/- d_b[i] (the add / add_inplace of n dot-product chains in
- * lockstep, helper.h:464,475).  Host arrays of device pointers; d_out[i] may alias d_a[i] or d_b[i]. */
+ * lockstep, helper.h:464,475).  Host arrays of device pointers.  Aliasing: d_out[i] may BE d_a[i] or d_b[i] (exact in place,
+ * per item), and operands may repeat (one read-only d_b for all items); d_out[i] may overlap, in bytes, no other operand or
+ * output of the call -- another item's included: HEFX_ERR_INVALID before anything is submitted. */
 int hefx_add_batch(hefx_context *ctx, int L, int size, int n, const uint64_t *const *d_a, const uint64_t *const *d_b,
                    uint64_t *const *d_out, void *stream);
 int hefx_sub_batch(hefx_context *ctx, int L, int size, int n, const uint64_t *const *d_a, const uint64_t *const *d_b,
                    uint64_t *const *d_out, void *stream);
-/* Evaluator::add_many (helper.h:231,259,275,319): out = sum of n ciphertexts (one n-way reduction). */
+/* Evaluator::add_many (helper.h:231,259,275,319): out = sum of n ciphertexts (one n-way reduction).
+ * Aliasing: exact in place is served -- d_out may BE d_in[i] for any i, repeated pointers included (add_many(v, out = v[k]),
+ * the accumulate idiom), and the sum is the same for every n and i: when more than one launch would read the inputs they
+ * are first reduced into the context's scratch, so that d_out is written only by launches that read no caller input.  A
+ * d_out that overlaps an input in bytes without being it is HEFX_ERR_INVALID before anything is submitted. */
 int hefx_add_many(hefx_context *ctx, int L, int size, int n, const uint64_t *const *d_in, uint64_t *d_out,
                   void *stream);
 
@@ -168,31 +178,38 @@ int hefx_add_many(hefx_context *ctx, int L, int size, int n, const uint64_t *con
  *      matrix_multiplication.cpp:104,127), square (vector_ops.cpp:269; 4_ckks.cpp:114).
  *      multiply_plain records "transparent" (all polys beyond c0 zero) in a device flag; read it with
  *      hefx_check_transparent (blocks), which returns HEFX_ERR_TRANSPARENT if any call since the last
- *      check produced a transparent result. */
+ *      check produced a transparent result.
+ *      Aliasing (hefx_multiply_plain): d_out may BE d_ct, exactly (in place); any other overlap of d_out with d_ct or with
+ *      d_pt, in bytes, is HEFX_ERR_INVALID before anything is submitted. */
 int hefx_multiply_plain(hefx_context *ctx, int L, int size, int count, const uint64_t *d_ct,
                         const uint64_t *d_pt, uint64_t *d_out, void *stream);
 int hefx_check_transparent(hefx_context *ctx, void *stream);
 /* n independent products in one launch: d_outs[i] = d_cts[i] (.) d_pts[i] (the mask products of
- * logistic_regression_ckks.cpp:229 over all rows).  Host arrays of device pointers; no output may alias its input;
+ * logistic_regression_ckks.cpp:229 over all rows).  Host arrays of device pointers; no output may overlap, in BYTES, an
+ * input of the call (any item's ciphertext or plaintext) or another output: HEFX_ERR_INVALID before anything is submitted;
  * transparency is the caller's check (the plaintexts' zero flags), as for hefx_multiply_plain_sum. */
 int hefx_multiply_plain_batch(hefx_context *ctx, int L, int size, int n, const uint64_t *const *d_cts,
                               const uint64_t *const *d_pts, uint64_t *const *d_outs, void *stream);
 /* Linear_Transform_CipherMatrix_PlainVector (helper.h:265-278: add_many of multiply_plain results, :271,:275) and the
  * inner sums of a baby-step/giant-step transform, in one pass: for g in [0, ceil(n/group)):
  *   d_outs[g] = sum_{i in [g*group, min(n,(g+1)*group))} d_cts[i] (.) d_pts[i]   (mod q_j per row)
- * d_cts[i]: [size][L][N], d_pts[i]: [L][N], d_outs[g]: [size][L][N], none of a group's inputs aliasing its output.
+ * d_cts[i]: [size][L][N], d_pts[i]: [L][N], d_outs[g]: [size][L][N].  No output may overlap, in BYTES (views of one
+ * allocation included), an input of the call -- ciphertext or plaintext, of ANY group -- or another output:
+ * HEFX_ERR_INVALID before anything is submitted (the groups are parallel workgroups of one launch).
  * The canonical residues of the sums, i.e. the bits of n multiply_plain calls followed by add_many.  The pointer
  * arrays are host arrays of device pointers.  Transparency is the caller's check (the plaintexts' zero flags). */
 int hefx_multiply_plain_sum(hefx_context *ctx, int L, int size, int n, int group, const uint64_t *const *d_cts,
                             const uint64_t *const *d_pts, uint64_t *const *d_outs, void *stream);
 
-/* size 2 x size 2 -> size 3 */
+/* size 2 x size 2 -> size 3.  Inputs are only read (d_a == d_b is fine; hefx_square is that).  d_out3 may overlap no input
+ * in BYTES, the exact alias d_out3 == d_a included: HEFX_ERR_INVALID before anything is submitted. */
 int hefx_multiply(hefx_context *ctx, int L, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out3,
                   void *stream);
 int hefx_square(hefx_context *ctx, int L, const uint64_t *d_a, uint64_t *d_out3, void *stream);
 /* n independent size 2 x size 2 products in one launch: d_out3[i] = d_a[i] * d_b[i] (the loop of cipher_dot_product
  * over the rows of a data set, logistic_regression_ckks.cpp:217-220 -> helper.h:432).  Host arrays of device
- * pointers; d_b may repeat one ciphertext; outputs must not alias inputs. */
+ * pointers; d_b may repeat one ciphertext; no output may overlap, in BYTES, an input of the call (another item's
+ * included) or another output: HEFX_ERR_INVALID before anything is submitted. */
 int hefx_multiply_batch(hefx_context *ctx, int L, int n, const uint64_t *const *d_a, const uint64_t *const *d_b,
                         uint64_t *const *d_out3, void *stream);
 /* Sums of size 2 x size 2 products in one pass -- the product loop and add_many of Linear_Transform_Cipher
@@ -246,7 +263,8 @@ int hefx_apply_galois(hefx_context *ctx, int L, const uint64_t *d_ct_in, uint32_
 int hefx_apply_galois_batch(hefx_context *ctx, int L, int n, const uint64_t *const *d_ct_in,
                             const uint32_t *galois_elts, const uint64_t *const *d_keys,
                             uint64_t *const *d_ct_out, void *stream);
-/* the hot-loop body of Linear_Transform_Plain (helper.h:255-256): out_i = rotate(ct_i, elt_i) (.) pt_i with
+/* (aliasing: the independence rule of hefx_apply_galois_batch above, plaintexts included)
+ * the hot-loop body of Linear_Transform_Plain (helper.h:255-256): out_i = rotate(ct_i, elt_i) (.) pt_i with
  * a directly keyed element, multiply_plain fused into the key-switch epilogue.  This is the unit
  * BASELINE.json's metric counts.  A NULL d_pts[i] makes item i a plain rotation (no product): the rotations of one
  * dependency depth of a NAF forest -- some end in a diagonal product, some only feed deeper rotations -- go out as ONE
@@ -318,7 +336,9 @@ int hefx_relinearize_sizes_batch(hefx_context *ctx, int L, int n, int size_in, i
  *                            reviews recall Evaluator::mod_switch_scale_to_next calling it, and SEAL >= 3.5's
  *                            RNSTool::divide_and_round_q_last_ntt_inplace.  The default since round 6.
  *      hefx_rescale_to_next uses the context's mode (hefx_set_rescale_mode; environment HEFX_RESCALE=floor|round
- *      presets it at hefx_context_create); hefx_rescale_to_next_mode names it per call. */
+ *      presets it at hefx_context_create); hefx_rescale_to_next_mode names it per call.
+ *      Aliasing: d_in is [count][size][L][N] and d_out [count][size][L-1][N]; they may not overlap in BYTES -- d_out == d_in
+ *      and a d_out that starts inside d_in included: HEFX_ERR_INVALID before anything is submitted. */
 #define HEFX_RESCALE_FLOOR 0
 #define HEFX_RESCALE_ROUND 1
 int hefx_rescale_to_next(hefx_context *ctx, int L, int size, int count, const uint64_t *d_in, uint64_t *d_out,
@@ -326,13 +346,15 @@ int hefx_rescale_to_next(hefx_context *ctx, int L, int size, int count, const ui
 int hefx_rescale_to_next_mode(hefx_context *ctx, int L, int size, int count, const uint64_t *d_in, uint64_t *d_out,
                               int mode, void *stream);
 /* n independent ciphertexts through host arrays of device pointers (the rescales of n dot products advancing in
- * lockstep, helper.h:441 over logistic_regression_ckks.cpp:217); uses the context's mode; d_out[i] != d_in[i]. */
+ * lockstep, helper.h:441 over logistic_regression_ckks.cpp:217); uses the context's mode.  No output may overlap, in
+ * BYTES, an input of the call (another item's included) or another output: HEFX_ERR_INVALID before anything is submitted. */
 int hefx_rescale_to_next_batch(hefx_context *ctx, int L, int size, int n, const uint64_t *const *d_in,
                                uint64_t *const *d_out, void *stream);
 int hefx_set_rescale_mode(hefx_context *ctx, int mode);
 int hefx_get_rescale_mode(const hefx_context *ctx);
 /* ---- K9: Evaluator::mod_switch_to_next / mod_switch_to for CKKS ct and pt (matrix_multiplication.cpp:112):
- *      drop trailing RNS rows, L_in -> L_out, npoly polys. */
+ *      drop trailing RNS rows, L_in -> L_out, npoly polys.  One strided device copy: d_out may not overlap d_in in BYTES
+ *      (d_out == d_in included): HEFX_ERR_INVALID before anything is submitted. */
 int hefx_mod_drop(hefx_context *ctx, int L_in, int L_out, int npoly, const uint64_t *d_in, uint64_t *d_out,
                   void *stream);
 
@@ -364,7 +386,9 @@ int hefx_reduce_canonical(hefx_context *ctx, int L, int size, uint64_t *d_data, 
  *      A forest of 96 or more key switches below ct_new (the reference's default keys from d ~ 70 on) is dealt onto TWO
  *      lanes -- the subtrees of about half the nodes each, every depth of a lane one batch on a stream of its own, the
  *      second lane in the back half of the scratch buffer -- joined before the final sum; same words (HEFX_LT_LANES=0: one
- *      lane). */
+ *      lane).
+ *      Aliasing (this and every plain transform below): an output may overlap, in BYTES, neither d_ct nor a diagonal nor
+ *      another output -- HEFX_ERR_INVALID before anything is submitted. */
 int hefx_linear_transform_plain(hefx_context *ctx, int L, const uint64_t *d_ct, int d,
                                 const uint64_t *const *d_diag_pts, int nkeys, const uint32_t *key_elts,
                                 const uint64_t *const *d_keys, uint64_t *d_out, void *stream);
@@ -373,7 +397,8 @@ int hefx_linear_transform_plain(hefx_context *ctx, int L, const uint64_t *d_ct, 
  * transforms of ctA and ctB in CC_Matrix_Multiplication (matrix_multiplication.cpp:22-25), the n independent products of
  * matrix_mult_benchmark.cpp -- share every launch sequence (the -d rotations, each depth of the rotation forest): the same
  * number of dependent sequences as ONE transform, each `count` times as wide.  Per input the operations and their order
- * are those of hefx_linear_transform_plain: same words.  Outputs pairwise distinct and distinct from the inputs. */
+ * are those of hefx_linear_transform_plain: same words.  No output may overlap, in BYTES, an input, a diagonal or another
+ * output: HEFX_ERR_INVALID before anything is submitted. */
 int hefx_linear_transform_plain_many(hefx_context *ctx, int L, int count, const uint64_t *const *d_cts, int d,
                                      const uint64_t *const *d_diag_pts, int nkeys, const uint32_t *key_elts,
                                      const uint64_t *const *d_keys, uint64_t *const *d_outs, void *stream);
@@ -397,7 +422,8 @@ int hefx_linear_transform_cipher(hefx_context *ctx, int L, const uint64_t *d_ct,
  *      batch per depth and lane, the subtrees of a forest of 96 nodes or more on two lanes, wide one-source depths
  *      exactly hoisted -- the schedule hefx_linear_transform_plain uses behind its own planner.  Every node's words are
  *      those of hefx_apply_galois / hefx_rotate_multiply_plain_batch on the same operands.  Outputs must be pairwise
- *      disjoint and disjoint from every external input and plaintext (HEFX_ERR_INVALID before anything runs). */
+ *      disjoint and disjoint from every external input and plaintext -- no overlap in bytes (HEFX_ERR_INVALID before
+ *      anything runs). */
 int hefx_apply_galois_forest(hefx_context *ctx, int L, int n, const int32_t *parent, const uint64_t *const *d_ext_in,
                              const uint32_t *galois_elts, const uint64_t *const *d_keys, const uint64_t *const *d_pts,
                              uint64_t *const *d_out, void *stream);
@@ -418,13 +444,16 @@ int hefx_apply_galois_forest(hefx_context *ctx, int L, int n, const int32_t *par
  *      life within HEFX_FLIPW_MB, default 8 GiB; beyond it the batch runs unhoisted, same words): one hipMalloc and one
  *      hipStreamSynchronize on the caller's stream -- a wait on the host inside an asynchronous entry (the conventions at
  *      the top list every entry that has one), and a reason not to capture the first call of a new element into a graph.
- *      Later calls find the table. */
+ *      Later calls find the table.
+ *      Aliasing: no output may overlap, in BYTES, d_ct_in, a plaintext or another output, for every n: HEFX_ERR_INVALID
+ *      before anything is submitted. */
 int hefx_rotate_hoisted_batch(hefx_context *ctx, int L, const uint64_t *d_ct_in, int n, const uint32_t *galois_elts,
                               const uint64_t *const *d_keys, const uint64_t *const *d_pts, uint64_t *const *d_ct_out,
                               void *stream);
 /* Linear_Transform_Plain with the d-1 rotations of ct_new hoisted; needs a DIRECT Galois key for every step 1..d-1
  * (keygen.galois_keys(steps)); the -d rotation is a regular one.  Same words as hefx_linear_transform_plain with those
- * keys (which hoists by itself from d = 34 on); refuses key sets without the direct keys. */
+ * keys (which hoists by itself from d = 34 on); refuses key sets without the direct keys.  d_out may overlap neither d_ct
+ * nor a diagonal, in bytes. */
 int hefx_linear_transform_plain_hoisted(hefx_context *ctx, int L, const uint64_t *d_ct, int d,
                                         const uint64_t *const *d_diag_pts, int nkeys, const uint32_t *key_elts,
                                         const uint64_t *const *d_keys, uint64_t *d_out, void *stream);
@@ -433,7 +462,8 @@ int hefx_linear_transform_plain_hoisted(hefx_context *ctx, int L, const uint64_t
  * extended basis (data primes + special prime) and modded down ONCE: per rotation only a gathered key MAC remains.
  * d_diag_pts_keylevel[l] are KEY-LEVEL plaintexts ([k][N]: encode with parms_id = key level); L must be the top data
  * level (k-1); direct Galois keys for 1..d-1.  One rounding instead of d-1: not the bits of the rotation-by-rotation
- * sum (nor SEAL's); bit-exact against the oracle's statement of this algorithm (orc_lt_double_hoisted). */
+ * sum (nor SEAL's); bit-exact against the oracle's statement of this algorithm (orc_lt_double_hoisted).  d_out may overlap
+ * neither d_ct nor a diagonal ([k][N] each), in bytes. */
 int hefx_linear_transform_plain_hoisted2(hefx_context *ctx, int L, const uint64_t *d_ct, int d,
                                          const uint64_t *const *d_diag_pts_keylevel, int nkeys,
                                          const uint32_t *key_elts, const uint64_t *const *d_keys, uint64_t *d_out,
@@ -441,7 +471,7 @@ int hefx_linear_transform_plain_hoisted2(hefx_context *ctx, int L, const uint64_
 /* Double hoisting over a SUBSET of the diagonals (the permutation matrices of the matrix product have 2n-1 or n
  * non-zero diagonals out of n^2, matrix_multiplication.cpp:239-297): term i multiplies rotate(ct_new, steps[i]) by
  * d_diag_pts_keylevel[i]; steps[0] must be 0, every other step non-zero with a direct Galois key; d only fixes the
- * duplication rotate(ct, -d) of helper.h:244. */
+ * duplication rotate(ct, -d) of helper.h:244.  d_out may overlap neither d_ct nor a diagonal, in bytes. */
 int hefx_linear_transform_plain_hoisted2_sparse(hefx_context *ctx, int L, const uint64_t *d_ct, int d, int nterms,
                                                 const int *steps, const uint64_t *const *d_diag_pts_keylevel,
                                                 int nkeys, const uint32_t *key_elts, const uint64_t *const *d_keys,
@@ -454,7 +484,7 @@ int hefx_linear_transform_plain_hoisted2_sparse(hefx_context *ctx, int L, const 
  * use a NAF chain.  d + n1*n2 <= N/2.  hoisted_baby: the baby rotations go through hefx_rotate_hoisted_batch (same
  * words either way).  A different operation sequence than the reference's loop -- every primitive in it is one of SEAL's
  * bit for bit -- so the same plaintext result with different noise bits than Linear_Transform_Plain; the checker is the
- * same composition over the oracle. */
+ * same composition over the oracle.  d_out may overlap neither d_ct nor a diagonal, in bytes. */
 int hefx_linear_transform_plain_bsgs(hefx_context *ctx, int L, const uint64_t *d_ct, int d, int n1,
                                      const uint64_t *const *d_shifted_diag_pts, int nkeys, const uint32_t *key_elts,
                                      const uint64_t *const *d_keys, int hoisted_baby, uint64_t *d_out, void *stream);
@@ -518,23 +548,27 @@ int hefx_sample_noise(hefx_context *ctx, const uint8_t *key32, uint64_t stream_i
 /* KeyGenerator's key-switching keys (relin_keys, galois_keys; App. A.11) entirely on the device:
  * out[k-1][2][k][N] (SEAL's layout) = for digit i: (-(a_i*sk + e_i) + [row i] (P mod q_i)*new_sk, a_i), a_i uniform from
  * sub-stream 2*stream_id, e_i noise from 2*stream_id+1.  d_sk, d_new_sk: [k][N] NTT form (new_sk = sk^2 for the
- * relinearisation key, hefx_galois_permute(sk) for a Galois key). */
+ * relinearisation key, hefx_galois_permute(sk) for a Galois key).  d_out may overlap neither secret key, in bytes. */
 int hefx_keygen_kswitch(hefx_context *ctx, const uint64_t *d_sk, const uint64_t *d_new_sk, const uint8_t *key32,
                         uint64_t stream_id, uint64_t *d_out, void *stream);
 /* out[r][w] = in[r][perm_g[w]] for `rows` rows of N words: the NTT-domain automorphism X -> X^g of plain
- * polynomials (SEAL apply_galois_ntt); in != out */
+ * polynomials (SEAL apply_galois_ntt).  A gather: d_out may not overlap d_in in BYTES (d_out == d_in included):
+ * HEFX_ERR_INVALID before anything is submitted. */
 int hefx_galois_permute(hefx_context *ctx, uint32_t galois_elt, const uint64_t *d_in, int rows, uint64_t *d_out,
                         void *stream);
 /* out[2][L][N] = (pk0*u + e0 + plain, pk1*u + e1), NTT form; d_pk = [2][k][N] (key-level public key), d_plain may be
- * NULL (encryption of zero); u ternary from sub-stream 4*stream_id, e0 / e1 noise from 4*stream_id+1 / +2. */
+ * NULL (encryption of zero); u ternary from sub-stream 4*stream_id, e0 / e1 noise from 4*stream_id+1 / +2.  d_out may
+ * overlap neither d_pk nor d_plain, in BYTES (d_out == d_plain included): HEFX_ERR_INVALID before anything is submitted. */
 int hefx_encrypt(hefx_context *ctx, int L, const uint64_t *d_pk, const uint64_t *d_plain, const uint8_t *key32,
                  uint64_t stream_id, uint64_t *d_out, void *stream);
 /* n encryptions under one public key and one sampler key, item i with stream id first_stream_id + i: the words n
  * hefx_encrypt calls with those ids produce, from five launches per 256 items instead of five per item.  d_plains may be
- * NULL, and so may any d_plains[i] (encryption of zero). */
+ * NULL, and so may any d_plains[i] (encryption of zero).  No output may overlap, in BYTES, d_pk, a plaintext (any item's) or
+ * another output: HEFX_ERR_INVALID before anything is submitted. */
 int hefx_encrypt_batch(hefx_context *ctx, int L, int n, const uint64_t *d_pk, const uint64_t *const *d_plains,
                        const uint8_t *key32, uint64_t first_stream_id, uint64_t *const *d_outs, void *stream);
-/* out[L][N] = c0 + c1*s + ... + c_(size-1)*s^(size-1), NTT form; d_sk = NTT-form secret key rows [>=L][N] */
+/* out[L][N] = c0 + c1*s + ... + c_(size-1)*s^(size-1), NTT form; d_sk = NTT-form secret key rows [>=L][N].  d_out may overlap
+ * neither d_ct nor the L rows of d_sk, in BYTES (d_out == d_ct included): HEFX_ERR_INVALID before anything is submitted. */
 int hefx_decrypt(hefx_context *ctx, int L, int size, const uint64_t *d_ct, const uint64_t *d_sk, uint64_t *d_out,
                  void *stream);
 

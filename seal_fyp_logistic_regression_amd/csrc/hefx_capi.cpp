@@ -22,6 +22,7 @@
 #include <link.h>
 
 #include "hefx_internal.h"
+#include "hefx_ranges.h"
 
 using namespace hefx;
 typedef unsigned __int128 u128;
@@ -35,6 +36,21 @@ static int fail(int code, const std::string &msg)
 static int hipfail(hipError_t e, const char *what)
 {
     return fail(HEFX_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// The aliasing rule of include/hefx.h (stated per entry there, as a table in INTEGRATION.md), applied before anything is
+// submitted: n outputs of out_b bytes against the call's input lists (hefx_ranges.h).  `names` are the arguments the lists
+// came from, for the message.  Engine-internal calls on disjoint workspace skip it (the `trusted` arguments below).
+static int check_ranges(const char *entry, size_t n, uint64_t *const *outs, size_t out_b,
+                        std::initializer_list<hefx_ranges::In> ins, std::initializer_list<const char *> names)
+{
+    std::pair<size_t, size_t> which{0, 0};
+    const hefx_ranges::Verdict v = hefx_ranges::check(n, outs, out_b, ins, &which);
+    if (v == hefx_ranges::FINE) return HEFX_OK;
+    std::string msg = std::string(entry) + ": " + hefx_ranges::text(v);
+    if (v == hefx_ranges::OUTPUT_OVERLAPS_INPUT && which.first < names.size())
+        msg += std::string(" (") + names.begin()[which.first] + ", entry " + std::to_string(which.second) + ")";
+    return fail(HEFX_ERR_INVALID, msg);
 }
 #define HIPCHK(expr)                                  \
     do {                                              \
@@ -771,14 +787,34 @@ extern "C" int hefx_ntt_inverse(hefx_context *c, uint64_t *d, int npoly, int nro
 // ---------------------------------------------------------------------------------------------
 // element-wise
 // ---------------------------------------------------------------------------------------------
-static int ew_common(hefx_context *c, EwOp op, int L, int size, int count, const uint64_t *a, const uint64_t *b,
-                     uint64_t *out, void *stream)
+// trusted: engine-internal calls on workspace that is disjoint by construction (and the in-place reduction) skip the
+// aliasing check.  The rule: out may be a (or, for add / sub, b) exactly, over the whole range; any other overlap of out
+// with an operand, the plaintext included, is refused.
+// (the checks alone, for hefx_multiply_plain, which has to make them before it grows its marks)
+static int ew_validate(hefx_context *c, EwOp op, int L, int size, int count, const uint64_t *a, const uint64_t *b,
+                       uint64_t *out, bool trusted)
 {
-    CTXCHK(c);
     if (int rc = check_level(c, L)) return rc;
     if (size < 1 || count < 1 || !a || !out) return fail(HEFX_ERR_INVALID, "bad element-wise arguments");
     if ((op == EW_ADD || op == EW_SUB || op == EW_MULPLAIN || op == EW_ADDPLAIN) && !b)
         return fail(HEFX_ERR_INVALID, "missing second operand");
+    if (!trusted) {
+        static const char *const entry[] = {"add", "sub", "negate", "multiply_plain", "add_plain", "reduce_canonical"};
+        const size_t pt_b = (size_t)L * c->n * sizeof(u64), all_b = pt_b * size * count;
+        const bool plain = op == EW_MULPLAIN || op == EW_ADDPLAIN;
+        if (int rc = check_ranges(entry[op], 1, &out, all_b, {{&a, 1, all_b, true}, {&b, (size_t)(b ? 1 : 0), plain ? pt_b : all_b, !plain}},
+                                  {plain ? "d_ct" : "d_a", plain ? "d_pt" : "d_b"}))
+            return rc;
+    }
+    return HEFX_OK;
+}
+// validated: the caller has run ew_validate on these arguments already
+static int ew_common(hefx_context *c, EwOp op, int L, int size, int count, const uint64_t *a, const uint64_t *b,
+                     uint64_t *out, void *stream, bool trusted = false, bool validated = false)
+{
+    CTXCHK(c);
+    if (!validated)
+        if (int rc = ew_validate(c, op, L, size, count, a, b, out, trusted)) return rc;
     HIPCHK(launch_elementwise(c->T, op, L, size, count, (const u64 *)a, (const u64 *)b, (u64 *)out, c->d_flag,
                               (hipStream_t)stream));
     return HEFX_OK;
@@ -806,7 +842,7 @@ extern "C" int hefx_add_plain(hefx_context *c, int L, int size, const uint64_t *
 extern "C" int hefx_reduce_canonical(hefx_context *c, int L, int size, uint64_t *d, int addends, void *stream)
 {
     (void)addends;  // barrett64 handles any 64-bit word; callers guarantee the sum did not wrap
-    return ew_common(c, EW_REDUCE, L, size, 1, d, nullptr, d, stream);
+    return ew_common(c, EW_REDUCE, L, size, 1, d, nullptr, d, stream, true);
 }
 
 // flag[1 + i] == 0 after a multiply_plain over `count` ciphertexts means nothing beyond c0 of ciphertext i was
@@ -821,10 +857,13 @@ __global__ void transparent_finalize_kernel(int *flag, int count)
     if (zeros) atomicAdd(&flag[0], zeros);
 }
 
-extern "C" int hefx_multiply_plain(hefx_context *c, int L, int size, int count, const uint64_t *ct,
-                                   const uint64_t *pt, uint64_t *out, void *stream)
+static int multiply_plain_impl(hefx_context *c, int L, int size, int count, const uint64_t *ct, const uint64_t *pt,
+                               uint64_t *out, void *stream, bool trusted)
 {
     CTXCHK(c);
+    // every argument check, the aliasing rule included, BEFORE the marks grow: growing them submits copies and waits for the
+    // stream, and a refused call submits nothing
+    if (int rc = ew_validate(c, EW_MULPLAIN, L, size, count, ct, pt, out, trusted)) return rc;
     if (count >= 1 && size > 1 && c->flag_cap < 1 + count) {  // [0] transparent count, [1..] one mark per ciphertext
         int *nf = nullptr;
         HIPCHK(hipMalloc((void **)&nf, sizeof(int) * (size_t)(1 + count)));
@@ -835,13 +874,19 @@ extern "C" int hefx_multiply_plain(hefx_context *c, int L, int size, int count, 
         c->d_flag = nf;
         c->flag_cap = 1 + count;
     }
-    int rc = ew_common(c, EW_MULPLAIN, L, size, count, ct, pt, out, stream);
+    int rc = ew_common(c, EW_MULPLAIN, L, size, count, ct, pt, out, stream, trusted, true);
     if (rc) return rc;
     if (size > 1) {
         hipLaunchKernelGGL(transparent_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, c->d_flag, count);
         HIPCHK(hipGetLastError());
     }
     return HEFX_OK;
+}
+
+extern "C" int hefx_multiply_plain(hefx_context *c, int L, int size, int count, const uint64_t *ct,
+                                   const uint64_t *pt, uint64_t *out, void *stream)
+{
+    return multiply_plain_impl(c, L, size, count, ct, pt, out, stream, false);
 }
 
 extern "C" int hefx_check_transparent(hefx_context *c, void *stream)
@@ -859,59 +904,96 @@ extern "C" int hefx_check_transparent(hefx_context *c, void *stream)
 
 // pt0 (engine-internal; only for n <= 2 * ADD_MANY_GROUP, the sums that skip the table level): in[0] enters the sum
 // multiplied by that plaintext
+// The aliasing rule (include/hefx.h): out may BE one of the inputs, repeated pointers included -- add_many(v, out = v[k]),
+// the accumulate idiom -- and the sum is the same for every n and k; any other overlap of out with an input is refused.
+// What makes it hold: a launch that reads caller inputs writes out only when it is the ONLY such launch (n <=
+// ADD_MANY_GROUP: every lane reads its word of every input before it writes that word).  Otherwise, when out is an input,
+// the inputs are first reduced into scratch partials (the table level) and out is written by launches that read scratch
+// alone.  trusted (engine-internal callers: inputs in engine workspace, out checked by the caller) skips the check.
 static int add_many_impl(hefx_context *c, int L, int size, int n, const uint64_t *const *in, const uint64_t *pt0, uint64_t *out,
-                         void *stream)
+                         void *stream, bool trusted)
 {
     CTXCHK(c);
     if (int rc = check_level(c, L)) return rc;
     if (n < 1 || size < 1 || !in || !out) return fail(HEFX_ERR_INVALID, "bad add_many arguments");
     if (pt0 && n > 2 * ADD_MANY_GROUP) return fail(HEFX_ERR_INVALID, "internal: a fused first product needs a direct sum");
+    for (int i = 0; i < n; ++i)
+        if (!in[i]) return fail(HEFX_ERR_INVALID, "null ciphertext in add_many");
+    const size_t words = (size_t)size * L * c->n;
+    bool in_place = false;
+    if (!trusted) {
+        if (int rc = check_ranges("add_many", 1, &out, words * sizeof(u64), {{in, (size_t)n, words * sizeof(u64), true, (size_t)n}}, {"d_in"}))
+            return rc;
+        for (int i = 0; i < n && !in_place; ++i) in_place = in[i] == out;
+    }
     // wide sums: one launch reduces groups of 16 through a device pointer table (a ring slot of the key-switch
     // descriptors doubles as the table), then the partials are summed below
     constexpr int TABLE_GROUP = 16;
     constexpr int TABLE_MAX = (int)(sizeof(KsItem) * KS_MAX_CHUNK / sizeof(void *));
+    hipStream_t s = (hipStream_t)stream;
     std::vector<const uint64_t *> partial_ptrs;
-    if (n > 2 * ADD_MANY_GROUP && n <= TABLE_MAX) {
-        for (int i = 0; i < n; ++i)
-            if (!in[i]) return fail(HEFX_ERR_INVALID, "null ciphertext in add_many");
-        const int groups = (n + TABLE_GROUP - 1) / TABLE_GROUP;
-        const size_t words = (size_t)size * L * c->n;
-        if (int rc = ensure_scratch(c, words * groups)) return rc;
+    // inputs [i0, i0 + cnt) -> ceil(cnt / TABLE_GROUP) partial sums at dst (scratch), cnt <= TABLE_MAX
+    auto table_level = [&](int i0, int cnt, u64 *dst) -> int {
         const unsigned slot = c->ring_next++ % KS_RING;
         if (c->ring_busy[slot]) HIPCHK(hipEventSynchronize(c->ring_ev[slot]));
         const uint64_t **hp = reinterpret_cast<const uint64_t **>(c->h_items + (size_t)slot * KS_MAX_CHUNK);
         const u64 *const *dp = reinterpret_cast<const u64 *const *>(c->d_items + (size_t)slot * KS_MAX_CHUNK);
-        for (int i = 0; i < n; ++i) hp[i] = in[i];
-        hipStream_t s = (hipStream_t)stream;
-        HIPCHK(hipMemcpyAsync((void *)dp, hp, sizeof(void *) * n, hipMemcpyHostToDevice, s));
-        HIPCHK(launch_add_many_table(c->T, L, size, dp, n, TABLE_GROUP, c->scratch, s));
+        for (int i = 0; i < cnt; ++i) hp[i] = in[i0 + i];
+        HIPCHK(hipMemcpyAsync((void *)dp, hp, sizeof(void *) * cnt, hipMemcpyHostToDevice, s));
+        HIPCHK(launch_add_many_table(c->T, L, size, dp, cnt, TABLE_GROUP, dst, s));
         HIPCHK(hipEventRecord(c->ring_ev[slot], s));
         c->ring_busy[slot] = true;
+        return HEFX_OK;
+    };
+    // out (accumulate: += ) the sum of m blocks of `words` words each, by launches of up to ADD_MANY_GROUP pointers
+    auto direct = [&](const uint64_t *const *p, int m, u64 *dst, const uint64_t *first_pt) -> int {
+        for (int base = 0; base < m; base += ADD_MANY_GROUP) {
+            PtrGroup g{};
+            const int cnt = (m - base < ADD_MANY_GROUP) ? m - base : ADD_MANY_GROUP;
+            for (int i = 0; i < cnt; ++i) g.p[i] = (const u64 *)p[base + i];
+            HIPCHK(launch_add_many(c->T, L, size, g, cnt, base > 0, dst, s, base == 0 ? (const u64 *)first_pt : nullptr));
+        }
+        return HEFX_OK;
+    };
+    if (n <= TABLE_MAX && (n > 2 * ADD_MANY_GROUP || (in_place && n > ADD_MANY_GROUP))) {
+        const int groups = (n + TABLE_GROUP - 1) / TABLE_GROUP;
+        if (int rc = ensure_scratch(c, words * groups)) return rc;
+        if (int rc = table_level(0, n, c->scratch)) return rc;
         partial_ptrs.resize(groups);
         for (int g = 0; g < groups; ++g) partial_ptrs[g] = reinterpret_cast<const uint64_t *>(c->scratch + (size_t)g * words);
-        in = partial_ptrs.data();
-        n = groups;
+        return direct(partial_ptrs.data(), groups, (u64 *)out, nullptr);
     }
-    for (int base = 0; base < n; base += ADD_MANY_GROUP) {
-        PtrGroup g{};
-        const int cnt = (n - base < ADD_MANY_GROUP) ? n - base : ADD_MANY_GROUP;
-        for (int i = 0; i < cnt; ++i) {
-            if (!in[base + i]) return fail(HEFX_ERR_INVALID, "null ciphertext in add_many");
-            g.p[i] = (const u64 *)in[base + i];
+    if (in_place && n > TABLE_MAX) {
+        // more inputs than a pointer table holds, and out among them: slice by slice through the table level into one
+        // partial per slice (scratch: the slice sums first, behind them the table level's partials of the slice in
+        // flight), then out = the sum of the slice sums
+        const int slices = (n + TABLE_MAX - 1) / TABLE_MAX, gmax = (TABLE_MAX + TABLE_GROUP - 1) / TABLE_GROUP;  // partials of a full slice
+        if (int rc = ensure_scratch(c, words * ((size_t)slices + gmax))) return rc;
+        u64 *level = c->scratch + (size_t)slices * words;
+        partial_ptrs.resize(gmax);
+        for (int g = 0; g < gmax; ++g) partial_ptrs[g] = reinterpret_cast<const uint64_t *>(level + (size_t)g * words);
+        std::vector<const uint64_t *> slice_ptrs((size_t)slices);
+        for (int t = 0; t < slices; ++t) {
+            const int i0 = t * TABLE_MAX, cnt = n - i0 < TABLE_MAX ? n - i0 : TABLE_MAX;
+            if (int rc = table_level(i0, cnt, level)) return rc;
+            u64 *sum = c->scratch + (size_t)t * words;
+            if (int rc = direct(partial_ptrs.data(), (cnt + TABLE_GROUP - 1) / TABLE_GROUP, sum, nullptr)) return rc;
+            slice_ptrs[(size_t)t] = reinterpret_cast<const uint64_t *>(sum);
         }
-        HIPCHK(launch_add_many(c->T, L, size, g, cnt, base > 0, (u64 *)out, (hipStream_t)stream, base == 0 ? (const u64 *)pt0 : nullptr));
+        return direct(slice_ptrs.data(), slices, (u64 *)out, nullptr);
     }
-    return HEFX_OK;
+    return direct(in, n, (u64 *)out, pt0);
 }
 extern "C" int hefx_add_many(hefx_context *c, int L, int size, int n, const uint64_t *const *in, uint64_t *out,
                              void *stream)
 {
-    return add_many_impl(c, L, size, n, in, nullptr, out, stream);
+    return add_many_impl(c, L, size, n, in, nullptr, out, stream, false);
 }
 
-extern "C" int hefx_multiply_plain_sum(hefx_context *c, int L, int size, int n, int group,
-                                       const uint64_t *const *cts, const uint64_t *const *pts, uint64_t *const *outs,
-                                       void *stream)
+// entry: the C-ABI entry the call came through (for the message), or nullptr for an engine-internal call on disjoint
+// workspace, which skips the aliasing check (the inner sums of the baby-step/giant-step transform, the parts of a long group)
+static int mulplain_sum_impl(hefx_context *c, int L, int size, int n, int group, const uint64_t *const *cts,
+                             const uint64_t *const *pts, uint64_t *const *outs, void *stream, const char *entry)
 {
     CTXCHK(c);
     if (int rc = check_level(c, L)) return rc;
@@ -921,10 +1003,14 @@ extern "C" int hefx_multiply_plain_sum(hefx_context *c, int L, int size, int n, 
     const int groups = (n + group - 1) / group;
     for (int i = 0; i < n; ++i)
         if (!cts[i] || !pts[i]) return fail(HEFX_ERR_INVALID, "null operand in multiply_plain_sum");
-    for (int g = 0; g < groups; ++g) {
+    for (int g = 0; g < groups; ++g)
         if (!outs[g]) return fail(HEFX_ERR_INVALID, "null output in multiply_plain_sum");
-        for (int i = g * group; i < n && i < (g + 1) * group; ++i)
-            if (cts[i] == outs[g]) return fail(HEFX_ERR_INVALID, "multiply_plain_sum output aliases an input");
+    // the groups of one launch run side by side: no output may share a byte with an operand of ANY group or with another output
+    if (entry) {
+        const size_t pt_b = (size_t)L * c->n * sizeof(u64);
+        if (int rc = check_ranges(entry, (size_t)groups, outs, size * pt_b, {{cts, (size_t)n, size * pt_b}, {pts, (size_t)n, pt_b}},
+                                  {"d_cts", "d_pts"}))
+            return rc;
     }
     // the pointer table travels through a ring slot of the key-switch descriptors; whole groups per slice
     constexpr int TABLE_MAX = (int)(sizeof(KsItem) * KS_MAX_CHUNK / sizeof(void *));
@@ -936,8 +1022,8 @@ extern "C" int hefx_multiply_plain_sum(hefx_context *c, int L, int size, int n, 
             if (int rc = ensure_scratch(c, words * nparts)) return rc;
             std::vector<uint64_t *> pp(nparts);
             for (int t = 0; t < nparts; ++t) pp[t] = reinterpret_cast<uint64_t *>(c->scratch + (size_t)t * words);
-            if (int rc = hefx_multiply_plain_sum(c, L, size, len, part, cts + i0, pts + i0, pp.data(), stream)) return rc;
-            if (int rc = hefx_add_many(c, L, size, nparts, pp.data(), outs[g], stream)) return rc;
+            if (int rc = mulplain_sum_impl(c, L, size, len, part, cts + i0, pts + i0, pp.data(), stream, nullptr)) return rc;
+            if (int rc = add_many_impl(c, L, size, nparts, pp.data(), nullptr, outs[g], stream, true)) return rc;
         }
         return HEFX_OK;
     }
@@ -963,24 +1049,49 @@ extern "C" int hefx_multiply_plain_sum(hefx_context *c, int L, int size, int n, 
     return HEFX_OK;
 }
 
-extern "C" int hefx_multiply(hefx_context *c, int L, const uint64_t *a, const uint64_t *b, uint64_t *out3,
-                             void *stream)
+extern "C" int hefx_multiply_plain_sum(hefx_context *c, int L, int size, int n, int group,
+                                       const uint64_t *const *cts, const uint64_t *const *pts, uint64_t *const *outs,
+                                       void *stream)
+{
+    return mulplain_sum_impl(c, L, size, n, group, cts, pts, outs, stream, "multiply_plain_sum");
+}
+
+// (the product kernels read every operand word a lane needs before the lane writes, but a lane's three output words lie in
+// three polynomials and its reads in two: an output that shares bytes with an operand is read by other lanes after it is
+// written.  Refused, the exact alias included.)
+static int multiply_impl(hefx_context *c, int L, const uint64_t *a, const uint64_t *b, uint64_t *out3, void *stream,
+                         const char *entry)
 {
     CTXCHK(c);
     if (int rc = check_level(c, L)) return rc;
     if (!a || !b || !out3) return fail(HEFX_ERR_INVALID, "null operand");
+    if (entry) {
+        const size_t poly_b = (size_t)L * c->n * sizeof(u64);
+        if (int rc = check_ranges(entry, 1, &out3, 3 * poly_b, {{&a, 1, 2 * poly_b}, {&b, 1, 2 * poly_b}}, {"d_a", "d_b"})) return rc;
+    }
     HIPCHK(launch_multiply(c->T, L, (const u64 *)a, (const u64 *)b, (u64 *)out3, (hipStream_t)stream));
     return HEFX_OK;
 }
-extern "C" int hefx_multiply_batch(hefx_context *c, int L, int n, const uint64_t *const *a, const uint64_t *const *b,
-                                   uint64_t *const *out3, void *stream)
+extern "C" int hefx_multiply(hefx_context *c, int L, const uint64_t *a, const uint64_t *b, uint64_t *out3,
+                             void *stream)
+{
+    return multiply_impl(c, L, a, b, out3, stream, "multiply");
+}
+// check: false when hefx_multiply_sizes_batch has already held the same buffers to the same rule
+static int multiply_batch_impl(hefx_context *c, int L, int n, const uint64_t *const *a, const uint64_t *const *b,
+                               uint64_t *const *out3, void *stream, bool check)
 {
     CTXCHK(c);
     if (int rc = check_level(c, L)) return rc;
     if (n < 1 || !a || !b || !out3) return fail(HEFX_ERR_INVALID, "bad multiply batch arguments");
     for (int i = 0; i < n; ++i)
-        if (!a[i] || !b[i] || !out3[i] || out3[i] == a[i] || out3[i] == b[i])
-            return fail(HEFX_ERR_INVALID, "null or aliasing operand in multiply batch");
+        if (!a[i] || !b[i] || !out3[i]) return fail(HEFX_ERR_INVALID, "null operand in multiply batch");
+    if (check) {
+        const size_t poly_b = (size_t)L * c->n * sizeof(u64);
+        if (int rc = check_ranges("multiply_batch", (size_t)n, out3, 3 * poly_b, {{a, (size_t)n, 2 * poly_b}, {b, (size_t)n, 2 * poly_b}},
+                                  {"d_a", "d_b"}))
+            return rc;
+    }
     constexpr int SLICE = (int)(sizeof(KsItem) * KS_MAX_CHUNK / sizeof(void *)) / 3;  // pointer-table ring slot
     hipStream_t s = (hipStream_t)stream;
     for (int i0 = 0; i0 < n; i0 += SLICE) {
@@ -1001,31 +1112,14 @@ extern "C" int hefx_multiply_batch(hefx_context *c, int L, int n, const uint64_t
     }
     return HEFX_OK;
 }
+extern "C" int hefx_multiply_batch(hefx_context *c, int L, int n, const uint64_t *const *a, const uint64_t *const *b,
+                                   uint64_t *const *out3, void *stream)
+{
+    return multiply_batch_impl(c, L, n, a, b, out3, stream, true);
+}
 extern "C" int hefx_square(hefx_context *c, int L, const uint64_t *a, uint64_t *out3, void *stream)
 {
-    return hefx_multiply(c, L, a, a, out3, stream);
-}
-
-// Byte-range independence of a call's outputs (n blocks of out_b bytes) and inputs (blocks of in_b bytes each, several
-// lists): no two outputs may overlap and no input may reach into an output -- views of one allocation included.  The
-// rule hefx_multiply_sum applies (which keeps its own statement of it: its outputs are per group, not per item), here for
-// the general-size entries, one output per item.  nullptr when the call is fine, else what is wrong.
-static const char *outputs_overlap(int n, uint64_t *const *outs, size_t out_b,
-                                   std::initializer_list<std::pair<const uint64_t *const *, size_t>> ins)
-{
-    std::vector<uintptr_t> o((size_t)n);
-    for (int i = 0; i < n; ++i) o[(size_t)i] = (uintptr_t)outs[i];
-    std::sort(o.begin(), o.end());
-    for (int i = 1; i < n; ++i)
-        if (o[(size_t)i - 1] + out_b > o[(size_t)i]) return "two outputs overlap";
-    for (const auto &in : ins)
-        for (int i = 0; i < n; ++i) {
-            const uintptr_t x = (uintptr_t)in.first[i];
-            auto it = std::upper_bound(o.begin(), o.end(), x);
-            if ((it != o.begin() && *(it - 1) + out_b > x) || (it != o.end() && *it < x + in.second))
-                return "an output overlaps an input";
-        }
-    return nullptr;
+    return multiply_impl(c, L, a, a, out3, stream, "square");
 }
 
 template <class Fill, class Run>
@@ -1051,9 +1145,10 @@ extern "C" int hefx_multiply_sizes_batch(hefx_context *c, int L, int n, int sa, 
     for (int i = 0; i < n; ++i)
         if (!a[i] || !b[i] || !out[i]) return fail(HEFX_ERR_INVALID, "null operand in multiply batch");
     const size_t poly_b = (size_t)L * c->n * sizeof(u64);
-    if (const char *why = outputs_overlap(n, out, (size_t)(sa + sb - 1) * poly_b, {{a, sa * poly_b}, {b, sb * poly_b}}))
-        return fail(HEFX_ERR_INVALID, std::string("multiply: ") + why);
-    if (sa == 2 && sb == 2) return hefx_multiply_batch(c, L, n, a, b, out, stream);
+    if (int rc = check_ranges("multiply", (size_t)n, out, (size_t)(sa + sb - 1) * poly_b, {{a, (size_t)n, sa * poly_b}, {b, (size_t)n, sb * poly_b}},
+                              {"d_a", "d_b"}))
+        return rc;
+    if (sa == 2 && sb == 2) return multiply_batch_impl(c, L, n, a, b, out, stream, false);
     hipStream_t s = (hipStream_t)stream;
     return table_slices(
         c, n, 3, s,
@@ -1073,9 +1168,9 @@ extern "C" int hefx_multiply_sizes(hefx_context *c, int L, int sa, const uint64_
     if (int rc = check_ct_sizes(sa, sb)) return rc;
     if (!a || !b || !out) return fail(HEFX_ERR_INVALID, "null operand");
     const size_t poly_b = (size_t)L * c->n * sizeof(u64);
-    if (const char *why = outputs_overlap(1, &out, (size_t)(sa + sb - 1) * poly_b, {{&a, sa * poly_b}, {&b, sb * poly_b}}))
-        return fail(HEFX_ERR_INVALID, std::string("multiply: ") + why);
-    if (sa == 2 && sb == 2) return hefx_multiply(c, L, a, b, out, stream);
+    if (int rc = check_ranges("multiply", 1, &out, (size_t)(sa + sb - 1) * poly_b, {{&a, 1, sa * poly_b}, {&b, 1, sb * poly_b}}, {"d_a", "d_b"}))
+        return rc;
+    if (sa == 2 && sb == 2) return multiply_impl(c, L, a, b, out, stream, nullptr);
     HIPCHK(launch_multiply_sizes(c->T, L, sa, sb, (const u64 *)a, (const u64 *)b, (u64 *)out, nullptr, 1, (hipStream_t)stream));
     return HEFX_OK;
 }
@@ -1154,7 +1249,7 @@ extern "C" int hefx_multiply_sum(hefx_context *c, int L, int n, int group, const
         std::vector<uint64_t *> pp((size_t)nparts);
         for (int t = 0; t < nparts; ++t) pp[(size_t)t] = reinterpret_cast<uint64_t *>(c->scratch + (size_t)t * words);
         if (int rc = mul_sum_submit(c, L, len, part, a + i0, b + i0, pp.data(), s)) return rc;
-        if (int rc = hefx_add_many(c, L, 3, nparts, pp.data(), outs[g], stream)) return rc;
+        if (int rc = add_many_impl(c, L, 3, nparts, pp.data(), nullptr, outs[g], stream, true)) return rc;
     }
     return HEFX_OK;
 }
@@ -1824,8 +1919,8 @@ extern "C" int hefx_relinearize_sizes_batch(hefx_context *c, int L, int n, int s
     for (int i = 0; i < n; ++i)
         if (!ct[i] || !out[i]) return fail(HEFX_ERR_INVALID, "null ciphertext pointer in batch");
     const size_t pw = (size_t)L * c->n;  // words of one polynomial
-    if (const char *why = outputs_overlap(n, out, size_out * pw * sizeof(u64), {{ct, size_in * pw * sizeof(u64)}}))
-        return fail(HEFX_ERR_INVALID, std::string("relinearize: ") + why);
+    if (int rc = check_ranges("relinearize", (size_t)n, out, size_out * pw * sizeof(u64), {{ct, (size_t)n, size_in * pw * sizeof(u64)}}, {"d_ct"}))
+        return rc;
     if (size_in == 3) return ks_run(c, L, n, true, ct, nullptr, nullptr, keys[0], nullptr, out, stream);
     const int group = std::min(n, relin_stage_group(c, L));
     if (int rc = grow_retiring(c, &c->lt_ws, &c->lt_cap, 6 * pw * (size_t)group, 0, "relinearize staging")) return rc;
@@ -1873,9 +1968,12 @@ static int rescale_common(hefx_context *c, int L, int size, int count, const uin
     if (int rc = check_level(c, L)) return rc;
     if (L < 2) return fail(HEFX_ERR_INVALID, "cannot rescale at the last level");
     if (size < 1 || count < 1 || !in || !out) return fail(HEFX_ERR_INVALID, "bad rescale arguments");
-    if (in == out) return fail(HEFX_ERR_INVALID, "rescale input and output must not alias");
     if (mode != HEFX_RESCALE_FLOOR && mode != HEFX_RESCALE_ROUND) return fail(HEFX_ERR_INVALID, "bad rescale mode");
     if (c->logn < 11) return fail(HEFX_ERR_UNSUPPORTED, "key switching / rescale need poly_degree >= 2048");
+    {  // L rows in, L - 1 out per polynomial, the workgroups of one launch side by side: no shared byte, in == out included
+        const size_t rows_b = (size_t)count * size * c->n * sizeof(u64);
+        if (int rc = check_ranges("rescale_to_next", 1, &out, rows_b * (L - 1), {{&in, 1, rows_b * L}}, {"d_in"})) return rc;
+    }
     if (int rc = ensure_scratch(c, (size_t)c->n * size * count)) return rc;
     HIPCHK(launch_rescale(c->T, L, size, count, (const u64 *)in, (u64 *)out, nullptr, c->scratch,
                           mode == HEFX_RESCALE_ROUND, (hipStream_t)stream));
@@ -1913,8 +2011,11 @@ extern "C" int hefx_rescale_to_next_batch(hefx_context *c, int L, int size, int 
     if (size < 1 || n < 1 || !in || !out) return fail(HEFX_ERR_INVALID, "bad rescale arguments");
     if (c->logn < 11) return fail(HEFX_ERR_UNSUPPORTED, "key switching / rescale need poly_degree >= 2048");
     for (int i = 0; i < n; ++i)
-        if (!in[i] || !out[i] || in[i] == out[i])
-            return fail(HEFX_ERR_INVALID, "null or aliasing operand in rescale batch");
+        if (!in[i] || !out[i]) return fail(HEFX_ERR_INVALID, "null operand in rescale batch");
+    {
+        const size_t rows_b = (size_t)size * c->n * sizeof(u64);
+        if (int rc = check_ranges("rescale_to_next_batch", (size_t)n, out, rows_b * (L - 1), {{in, (size_t)n, rows_b * L}}, {"d_in"})) return rc;
+    }
     const int SLICE = (int)(sizeof(KsItem) * KS_MAX_CHUNK / sizeof(void *)) / 2;
     if (int rc = ensure_scratch(c, (size_t)c->n * size * (n < SLICE ? n : SLICE))) return rc;
     const bool rounded = c->rescale_mode == HEFX_RESCALE_ROUND;
@@ -1936,6 +2037,12 @@ static int addsub_batch(hefx_context *c, bool sub, int L, int size, int n, const
     if (n < 1 || size < 1 || !a || !b || !out) return fail(HEFX_ERR_INVALID, "bad element-wise batch arguments");
     for (int i = 0; i < n; ++i)
         if (!a[i] || !b[i] || !out[i]) return fail(HEFX_ERR_INVALID, "null operand in element-wise batch");
+    {  // item i may write its own d_a[i] or d_b[i] exactly; no other overlap with an operand or output of ANY item
+        const size_t ct_b = (size_t)size * L * c->n * sizeof(u64);
+        if (int rc = check_ranges(sub ? "sub_batch" : "add_batch", (size_t)n, out, ct_b, {{a, (size_t)n, ct_b, true}, {b, (size_t)n, ct_b, true}},
+                                  {"d_a", "d_b"}))
+            return rc;
+    }
     return table_slices(
         c, n, 3, (hipStream_t)stream,
         [&](const uint64_t **hp, int i0, int cnt) {
@@ -1959,7 +2066,7 @@ extern "C" int hefx_multiply_plain_batch(hefx_context *c, int L, int size, int n
                                          const uint64_t *const *pts, uint64_t *const *outs, void *stream)
 {
     // n one-term sums: the same kernel, the same canonical products (transparency is the caller's check, as there)
-    return hefx_multiply_plain_sum(c, L, size, n, 1, cts, pts, outs, stream);
+    return mulplain_sum_impl(c, L, size, n, 1, cts, pts, outs, stream, "multiply_plain_batch");
 }
 extern "C" int hefx_rescale_to_next(hefx_context *c, int L, int size, int count, const uint64_t *in, uint64_t *out,
                                     void *stream)
@@ -1988,6 +2095,8 @@ extern "C" int hefx_mod_drop(hefx_context *c, int L_in, int L_out, int npoly, co
     if (L_out < 1 || L_out > L_in || L_in > c->k || npoly < 1 || !in || !out)
         return fail(HEFX_ERR_INVALID, "bad mod_drop arguments");
     const size_t row = (size_t)c->n * sizeof(u64);
+    // one strided copy: source and destination may share no byte (the runtime leaves an overlapping copy undefined)
+    if (int rc = check_ranges("mod_drop", 1, &out, row * L_out * npoly, {{&in, 1, row * L_in * npoly}}, {"d_in"})) return rc;
     HIPCHK(hipMemcpy2DAsync(out, row * L_out, in, row * L_in, row * L_out, npoly, hipMemcpyDeviceToDevice,
                             (hipStream_t)stream));
     return HEFX_OK;
@@ -2717,6 +2826,13 @@ static int lt_impl(hefx_context *c, int L, int count, const uint64_t *const *cts
         if (!cts[t] || !outs[t]) return fail(HEFX_ERR_INVALID, "bad linear-transform arguments");
     for (int i = 0; i < count * d; ++i)
         if (!diag_pts[i]) return fail(HEFX_ERR_INVALID, "null diagonal plaintext");
+    {  // the outputs against the inputs, every diagonal and one another (count + count * d pointers; its host time at d = 512 is what
+       // tools/aliasing_ew_timing.py measures as lt_d512_host, recorded in profiles/EXPERIMENTS.md, "Aliasing rule")
+        const size_t pt_b = (size_t)L * c->n * sizeof(u64);
+        if (int rc = check_ranges("linear transform", (size_t)count, outs, 2 * pt_b,
+                                  {{cts, (size_t)count, 2 * pt_b}, {diag_pts, (size_t)count * d, pt_b}}, {"d_ct", "d_diag_pts"}))
+            return rc;
+    }
     static const bool dbg = getenv("HEFX_DEBUG") != nullptr;  // host time of the call's phases on stderr
     auto t_last = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) {
@@ -2756,7 +2872,7 @@ static int lt_impl(hefx_context *c, int L, int count, const uint64_t *const *cts
     // transforms, whose sum goes through the table level, keep the launch
     const bool fuse0 = d <= 2 * ADD_MANY_GROUP;
     for (int t = 0; t < count && !fuse0; ++t)
-        if (int rc = hefx_multiply_plain(c, L, 2, 1, ct_new(t), diag_pts[(size_t)t * d], prod0(t), stream)) return rc;
+        if (int rc = multiply_plain_impl(c, L, 2, 1, ct_new(t), diag_pts[(size_t)t * d], prod0(t), stream, true)) return rc;
     lap("head submitted (rotate -d + add, product 0)");
     // ---- plans -> a forest of key-switch nodes rooted at ct_new, deduplicated per (parent, element, fused diagonal)
     std::vector<LtNode> nodes;
@@ -2789,7 +2905,7 @@ static int lt_impl(hefx_context *c, int L, int count, const uint64_t *const *cts
     for (int t = 0; t < count && rc == HEFX_OK; ++t) {
         res[0] = fuse0 ? ct_new(t) : prod0(t);
         for (int l = 1; l < d; ++l) res[l] = node_ptr(t, leaf[l]);
-        rc = add_many_impl(c, L, 2, d, res.data(), fuse0 ? diag_pts[(size_t)t * d] : nullptr, outs[t], stream);
+        rc = add_many_impl(c, L, 2, d, res.data(), fuse0 ? diag_pts[(size_t)t * d] : nullptr, outs[t], stream, true);
     }
     lap("add_many submitted");
     return rc;
@@ -2934,6 +3050,12 @@ extern "C" int hefx_linear_transform_plain_bsgs(hefx_context *c, int L, const ui
         return fail(HEFX_ERR_INVALID, "baby-step/giant-step transform: dimension too large for the slot count");
     for (int i = 0; i < d; ++i)
         if (!shifted_diag_pts[i]) return fail(HEFX_ERR_INVALID, "null diagonal plaintext");
+    {
+        const size_t pt_b = (size_t)L * c->n * sizeof(u64);
+        if (int rc = check_ranges("linear transform", 1, &out, 2 * pt_b, {{&ct, 1, 2 * pt_b}, {shifted_diag_pts, (size_t)d, pt_b}},
+                                  {"d_ct", "d_shifted_diag_pts"}))
+            return rc;
+    }
     static const bool dbg = getenv("HEFX_DEBUG") != nullptr;  // host time of the call's phases on stderr
     auto t_last = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) {
@@ -2971,7 +3093,7 @@ extern "C" int hefx_linear_transform_plain_bsgs(hefx_context *c, int L, const ui
         if (int rc = ks_run(c, L, 1, false, &src, &first[t], &key, nullptr, nullptr, &dst, stream)) return rc;
         src = dst;
     }
-    if (int rc = hefx_add(c, L, 2, 1, ct, src, ct_new, stream)) return rc;
+    if (int rc = ew_common(c, EW_ADD, L, 2, 1, ct, src, ct_new, stream, true)) return rc;
     std::vector<const uint64_t *> in, kk;
     std::vector<uint64_t *> oo;
     // ---- baby steps: rots[i-1] = rotate(ct_new, i)
@@ -2990,7 +3112,7 @@ extern "C" int hefx_linear_transform_plain_bsgs(hefx_context *c, int L, const ui
     std::vector<uint64_t *> io(n2);
     for (int l = 0; l < d; ++l) cc[l] = (l % n1) ? rots + (size_t)(l % n1 - 1) * ctw : ct_new;
     for (int j = 0; j < n2; ++j) io[j] = inner + (size_t)j * ctw;
-    if (int rc = hefx_multiply_plain_sum(c, L, 2, d, n1, cc.data(), shifted_diag_pts, io.data(), stream)) return rc;
+    if (int rc = mulplain_sum_impl(c, L, 2, d, n1, cc.data(), shifted_diag_pts, io.data(), stream, nullptr)) return rc;
     // ---- giant steps and the final sum
     std::vector<const uint64_t *> res(n2);
     res[0] = inner;
@@ -3005,7 +3127,7 @@ extern "C" int hefx_linear_transform_plain_bsgs(hefx_context *c, int L, const ui
         if (int rc = ks_run(c, L, n2 - 1, false, in.data(), gelt.data(), kk.data(), nullptr, nullptr, oo.data(), stream))
             return rc;
     }
-    return hefx_add_many(c, L, 2, n2, res.data(), out, stream);
+    return add_many_impl(c, L, 2, n2, res.data(), nullptr, out, stream, true);
 }
 
 // Double-hoisted Linear_Transform_Plain (see lt2_mac_kernel): top data level, direct keys for 1..d-1, diagonals
@@ -3024,6 +3146,12 @@ static int lt2_impl(hefx_context *c, int L, const uint64_t *ct, int d, int nterm
         return fail(HEFX_ERR_INVALID, "bad linear-transform arguments");
     for (int i = 0; i < nterms; ++i)
         if (!diag_pts_keylevel[i]) return fail(HEFX_ERR_INVALID, "null diagonal plaintext");
+    {
+        const size_t row_b = (size_t)c->n * sizeof(u64);
+        if (int rc = check_ranges("linear transform", 1, &out, 2 * L * row_b, {{&ct, 1, 2 * L * row_b}, {diag_pts_keylevel, (size_t)nterms, c->k * row_b}},
+                                  {"d_ct", "d_diag_pts_keylevel"}))
+            return rc;
+    }
     static const bool dbg = getenv("HEFX_DEBUG") != nullptr;  // host time of the call's phases on stderr
     auto t_last = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) {
@@ -3072,8 +3200,8 @@ static int lt2_impl(hefx_context *c, int L, const uint64_t *ct, int d, int nterm
         if (int rc = ks_run(c, L, 1, false, &src, &first[t], &key, nullptr, nullptr, &dst, stream)) return rc;
         src = dst;
     }
-    if (int rc = hefx_add(c, L, 2, 1, ct, src, ct_new, stream)) return rc;
-    if (int rc = hefx_multiply_plain(c, L, 2, 1, ct_new, diag_pts_keylevel[0], cbuf, stream)) return rc;
+    if (int rc = ew_common(c, EW_ADD, L, 2, 1, ct, src, ct_new, stream, true)) return rc;
+    if (int rc = multiply_plain_impl(c, L, 2, 1, ct_new, diag_pts_keylevel[0], cbuf, stream, true)) return rc;
     if (nrot == 0) {
         HIPCHK(hipMemcpyAsync(out, cbuf, ctw * sizeof(u64), hipMemcpyDeviceToDevice, (hipStream_t)stream));
         return HEFX_OK;
@@ -3130,10 +3258,19 @@ extern "C" int hefx_rotate_hoisted_batch(hefx_context *c, int L, const uint64_t 
                                          const uint64_t *const *keys, const uint64_t *const *pts,
                                          uint64_t *const *ct_out, void *stream)
 {
-    if (n < 1 || !ct_in) return fail(HEFX_ERR_INVALID, "bad hoisted batch arguments");
-    if (pts)
-        for (int i = 0; i < n; ++i)
-            if (!pts[i]) return fail(HEFX_ERR_INVALID, "null plaintext pointer in batch");
+    CTXCHK(c);
+    if (int rc = check_ks_level(c, L)) return rc;
+    if (n < 1 || !ct_in || !ct_out) return fail(HEFX_ERR_INVALID, "bad hoisted batch arguments");
+    for (int i = 0; i < n; ++i) {
+        if (!ct_out[i]) return fail(HEFX_ERR_INVALID, "null ciphertext pointer in batch");
+        if (pts && !pts[i]) return fail(HEFX_ERR_INVALID, "null plaintext pointer in batch");
+    }
+    // the one source, the plaintexts and the outputs, for every n (ks_run's own check starts at two items or a plaintext and
+    // compares the source with the outputs for equality)
+    const size_t pt_b = (size_t)L * c->n * sizeof(u64);
+    if (int rc = check_ranges("rotate_hoisted_batch", (size_t)n, ct_out, 2 * pt_b, {{&ct_in, 1, 2 * pt_b}, {pts, (size_t)(pts ? n : 0), pt_b}},
+                              {"d_ct_in", "d_pts"}))
+        return rc;
     std::vector<const uint64_t *> in((size_t)n, ct_in);
     return ks_run(c, L, n, false, in.data(), elts, keys, nullptr, pts, ct_out, stream, true);
 }
@@ -3185,6 +3322,9 @@ extern "C" int hefx_encrypt(hefx_context *c, int L, const uint64_t *pk, const ui
     if (!pk || !key32 || !out) return fail(HEFX_ERR_INVALID, "bad encrypt arguments");
     if (stream_id >> 62) return fail(HEFX_ERR_INVALID, "stream id must be below 2^62");
     const size_t N = c->n, rowsz = (size_t)L * N;
+    if (int rc = check_ranges("encrypt", 1, &out, 2 * rowsz * sizeof(u64),
+                              {{&pk, 1, 2 * (size_t)c->k * N * sizeof(u64)}, {&plain, 1, rowsz * sizeof(u64)}}, {"d_pk", "d_plain"}))
+        return rc;
     const bool split = c->logn == 15;  // the N = 32768 transform is out of place
     if (int rc = ensure_scratch(c, (split ? 6 : 3) * rowsz)) return rc;
     u64 *u = c->scratch, *e = u + rowsz;
@@ -3220,6 +3360,12 @@ extern "C" int hefx_encrypt_batch(hefx_context *c, int L, int n, const uint64_t 
     if ((first_stream_id + (uint64_t)n) >> 62) return fail(HEFX_ERR_INVALID, "stream id must be below 2^62");
     for (int i = 0; i < n; ++i)
         if (!outs[i]) return fail(HEFX_ERR_INVALID, "null output pointer in batch");
+    {
+        const size_t pt_b = (size_t)L * c->n * sizeof(u64);
+        if (int rc = check_ranges("encrypt_batch", (size_t)n, outs, 2 * pt_b,
+                                  {{&pk, 1, 2 * (size_t)c->k * c->n * sizeof(u64)}, {plains, (size_t)(plains ? n : 0), pt_b}}, {"d_pk", "d_plains"}))
+            return rc;
+    }
     if (c->logn == 15) {  // the N = 32768 transform is out of place: item by item (no caller batches there yet)
         for (int i = 0; i < n; ++i)
             if (int rc = hefx_encrypt(c, L, pk, plains ? plains[i] : nullptr, key32, first_stream_id + (uint64_t)i, outs[i], stream))
@@ -3260,6 +3406,10 @@ extern "C" int hefx_decrypt(hefx_context *c, int L, int size, const uint64_t *ct
     CTXCHK(c);
     if (int rc = check_level(c, L)) return rc;
     if (!ct || !sk || !out || size < 1) return fail(HEFX_ERR_INVALID, "bad decrypt arguments");
+    {
+        const size_t pt_b = (size_t)L * c->n * sizeof(u64);
+        if (int rc = check_ranges("decrypt", 1, &out, pt_b, {{&ct, 1, size * pt_b}, {&sk, 1, pt_b}}, {"d_ct", "d_sk"})) return rc;
+    }
     HIPCHK(launch_decrypt(c->T, L, size, (const u64 *)ct, (const u64 *)sk, (u64 *)out, (hipStream_t)stream));
     return HEFX_OK;
 }
@@ -3273,6 +3423,9 @@ extern "C" int hefx_keygen_kswitch(hefx_context *c, const uint64_t *sk, const ui
     if (stream_id >> 62) return fail(HEFX_ERR_INVALID, "stream id must be below 2^62");
     const size_t N = c->n, words = (size_t)(c->k - 1) * c->k * N;
     const bool split = c->logn == 15;
+    if (int rc = check_ranges("keygen_kswitch", 1, &out, 2 * words * sizeof(u64),
+                              {{&sk, 1, (size_t)c->k * N * sizeof(u64)}, {&new_sk, 1, (size_t)c->k * N * sizeof(u64)}}, {"d_sk", "d_new_sk"}))
+        return rc;
     if (int rc = ensure_scratch(c, (split ? 3 : 2) * words)) return rc;
     u64 *a = c->scratch, *e = a + words;
     hipStream_t s = (hipStream_t)stream;
@@ -3294,7 +3447,11 @@ extern "C" int hefx_galois_permute(hefx_context *c, uint32_t galois_elt, const u
                                    void *stream)
 {
     CTXCHK(c);
-    if (!in || !out || rows < 1 || in == out) return fail(HEFX_ERR_INVALID, "bad permutation arguments");
+    if (!in || !out || rows < 1) return fail(HEFX_ERR_INVALID, "bad permutation arguments");
+    {  // a gather: every output word reads another word of the input
+        const size_t all_b = (size_t)rows * c->n * sizeof(u64);
+        if (int rc = check_ranges("galois_permute", 1, &out, all_b, {{&in, 1, all_b}}, {"d_in"})) return rc;
+    }
     const uint32_t *perm = nullptr;
     if (int rc = get_perm(c, galois_elt, &perm)) return rc;
     HIPCHK(launch_galois_permute(c->T, perm, (const u64 *)in, rows, (u64 *)out, (hipStream_t)stream));

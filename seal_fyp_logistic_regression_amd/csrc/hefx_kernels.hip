@@ -108,12 +108,14 @@ hipError_t launch_ntt(const DevTables &T, bool inverse, u64 *data, int npoly, in
 // ------------------------------------------------------------------------------------------------
 // K3/K4/K10: element-wise ops, two words (16 B) per lane per step, grid-stride.
 // word w of a ciphertext batch: row = w / N, modulus j = row % L.  Plaintext operand: [L][N].
+// a, b and out carry no __restrict__: the C-ABI serves out == a and out == b (include/hefx.h, "exact in place"), which
+// works because a lane reads word w of its operands before it writes word w and touches no other word.  A plaintext b
+// can never be the output (refused on the host), but a and b share one parameter list, so the qualifier is off for it too.
 // ------------------------------------------------------------------------------------------------
 template <int OP>
 __global__ __launch_bounds__(256) void elementwise_kernel(DevTables T, int L, int size, size_t total_pairs,
-                                                          const ulonglong2 *__restrict__ a,
-                                                          const ulonglong2 *__restrict__ b,
-                                                          ulonglong2 *__restrict__ out, int *flag)
+                                                          const ulonglong2 *a, const ulonglong2 *b, ulonglong2 *out,
+                                                          int *flag)
 {
     const int logn = T.logn;
     const size_t pairs_per_row = (size_t)1 << (logn - 1);
@@ -197,9 +199,11 @@ hipError_t launch_elementwise(const DevTables &T, EwOp op, int L, int size, int 
 // add_many: out = (accumulate ? out : 0) + sum_{i<n} in[i]   (n <= ADD_MANY_GROUP pointers by value)
 // pt0 != nullptr: the FIRST addend is in[0] (.) pt0 (multiply_plain, plaintext [L][N]) -- Linear_Transform_Plain's
 // res[0] = ct_new * diag[0] (helper.h:250) formed inside its final sum (:259) instead of by a launch of its own
+// out carries no __restrict__: it may be one of g.p[] (hefx_add_many's in-place form, a single launch) and is read back when
+// accumulating; a lane reads its word of every input before it writes that word.  pt0 is never the output.
 __global__ __launch_bounds__(256) void add_many_kernel(DevTables T, int L, size_t total_pairs, PtrGroup g, int n,
                                                        int accumulate, const ulonglong2 *__restrict__ pt0,
-                                                       ulonglong2 *__restrict__ out)
+                                                       ulonglong2 *out)
 {
     const int logn = T.logn;
     for (size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x; w < total_pairs;
@@ -542,7 +546,8 @@ hipError_t launch_multiply_table(const DevTables &T, int L, const u64 *const *d_
 
 // n independent element-wise sums / differences through a DEVICE pointer table  a[0..n) | b[0..n) | out[0..n): the adds
 // of n dot-product chains advancing in lockstep (helper.h:464,475 over the rows of logistic_regression_ckks.cpp:217)
-// as one launch.  out[i] may alias a[i] or b[i] (element-wise).
+// as one launch.  out[i] may be a[i] or b[i] exactly (element-wise: a lane reads word w before it writes word w), so the
+// three data pointers carry no __restrict__; the pointer table itself is only read.
 template <bool SUB>
 __global__ __launch_bounds__(256) void addsub_table_kernel(DevTables T, int L, size_t total_pairs,
                                                            const u64 *const *__restrict__ tab, int n)
