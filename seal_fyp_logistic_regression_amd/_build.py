@@ -8,8 +8,20 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libhefx.so")
 SOURCES = ["hefx_keyswitch.hip", "hefx_kernels.hip", "hefx_encode.hip", "hefx_sample.hip", "hefx_capi.cpp"]  # slowest first
-HEADERS = ["hefx_internal.h", "hefx_modarith.cuh", "hefx_ntt.cuh", "hefx_ntt8.cuh", "hefx_ranges.h", "../../include/hefx.h"]
+HEADERS = ["hefx_internal.h", "hefx_modarith.cuh", "hefx_ntt.cuh", "hefx_ntt8.cuh", "hefx_mac.cuh", "hefx_ranges.h", "../../include/hefx.h"]
 DEPS = SOURCES + HEADERS  # a change in any of them rebuilds the library (a header: every object; a source: its object)
+# The arithmetic probe (tests/test_gpu_arith_primitives.py): ONE device primitive per thread on the caller's operands.  A test
+# library of its own -- not linked into libhefx.so, not in capi.EXPORTED_SYMBOLS, not in source_sha16() -- with its own
+# staleness rule: its source and the three headers it instantiates.
+PROBE_SO = os.path.join(HERE, "libhefx_arith_probe.so")
+PROBE_SOURCE = "hefx_arith_probe.hip"
+PROBE_DEPS = [PROBE_SOURCE, "hefx_modarith.cuh", "hefx_ntt.cuh", "hefx_mac.cuh"]
+# what every device translation unit is compiled with
+# -pragma-unroll-threshold: the transforms are written as fully unrolled loops over register arrays; the inline
+# asm statements of hefx_modarith.cuh count as large in the unroller's size estimate and push the inverse
+# transforms past the default threshold (loops left rolled -> the register arrays go to scratch memory)
+DEVICE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
+                "-mllvm", "-pragma-unroll-threshold=1048576", "-x", "hip"]
 
 
 def source_sha16() -> str:
@@ -45,7 +57,26 @@ def needs_build() -> bool:
     return any(os.path.getmtime(os.path.join(CSRC, d)) > t for d in DEPS)
 
 
+def probe_needs_build() -> bool:
+    if not os.path.exists(PROBE_SO):
+        return True
+    t = os.path.getmtime(PROBE_SO)
+    return any(os.path.getmtime(os.path.join(CSRC, d)) > t for d in PROBE_DEPS)
+
+
+def build_probe(force: bool = False, verbose: bool = False) -> str:
+    """libhefx_arith_probe.so: one translation unit, the engine's flags, straight to a shared object (a few seconds)"""
+    if not force and not probe_needs_build():
+        return PROBE_SO
+    cmd = [hipcc()] + DEVICE_FLAGS + ["-shared", os.path.join(CSRC, PROBE_SOURCE), "-o", PROBE_SO]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    return PROBE_SO
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
+    build_probe(force, verbose)
     if not force and not needs_build():
         return SO
     objs, jobs = [], []
@@ -58,11 +89,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         hdr_t = max(os.path.getmtime(os.path.join(CSRC, h)) for h in hdrs)
         if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(hdr_t, os.path.getmtime(os.path.join(CSRC, src))):
             continue  # this object is newer than its source and every header it includes
-        # -pragma-unroll-threshold: the transforms are written as fully unrolled loops over register arrays; the inline
-        # asm statements of hefx_modarith.cuh count as large in the unroller's size estimate and push the inverse
-        # transforms past the default threshold (loops left rolled -> the register arrays go to scratch memory)
-        cmd = [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-               "-mllvm", "-pragma-unroll-threshold=1048576", "-x", "hip", "-c", os.path.join(CSRC, src), "-o", obj]
+        cmd = [hipcc()] + DEVICE_FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd))
         jobs.append((src, subprocess.Popen(cmd)))  # the five translation units compile side by side
