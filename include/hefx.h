@@ -577,7 +577,8 @@ int hefx_decrypt(hefx_context *ctx, int L, int size, const uint64_t *d_ct, const
  *      `count` NTT-form plaintexts of L rows -> slot values, h_re/h_im[count][N/2] (h_im may be NULL).  Inverse NTT,
  *      CRT composition (Garner, exact), centring against Q/2, division by the scale and the slot-root evaluation
  *      (two N/2-point complex FFTs) all on the device.  Floating point: agrees with a host decode to ~1e-12 relative.
- *      Blocks until the values are in the host arrays. */
+ *      Blocks until the values are in the host arrays.  (That refresh as one call, exact and without the host round
+ *      trip: hefx_refresh in hefx_refresh.h.) */
 int hefx_ckks_decode(hefx_context *ctx, int L, const uint64_t *d_pt, int count, double scale, double *h_re,
                      double *h_im, void *stream);
 

@@ -2149,6 +2149,9 @@ public:
         shim::check(hefx_encrypt(e->ready({plain.buf.get()}), L, pk_.buf->p, plain.buf->p, rnd_.key.data(), rnd_.stream(), c->p, nullptr));
         dest.set(c, 2, L, plain.parms_id(), plain.scale());
     }
+    // shim internals, read by seal/shim_refresh.h
+    const PublicKey &shim_public_key() const { return pk_; }
+    const shim::SamplerState &shim_sampler() const { return rnd_; }
 
 private:
     // BFV: (pk0*u + e0 + Delta*m, pk1*u + e1) at the first data level, coefficient form (vector_ops.cpp:155)
@@ -2211,6 +2214,9 @@ public:
         decrypt_bfv(ct, tmp, budget);
         return budget;
     }
+    // shim internals, read by seal/shim_refresh.h
+    const std::shared_ptr<SEALContext> &shim_context() const { return ctx_; }
+    const SecretKey &shim_secret_key() const { return sk_; }
 
 private:
     // BFV: x = [c0 + c1 s (+ c2 s^2)]_Q on the GPU (NTT domain), then per coefficient t*x = quo*Q + rem on the host:

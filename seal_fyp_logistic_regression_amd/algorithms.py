@@ -930,3 +930,41 @@ def update_weights(ev: Evaluator, encoder: CKKSEncoder, encryptor, features: Seq
     new_weights = ev.sub(gradient, weights)                                                                # :341
     ev.negate_inplace(new_weights)                                                                         # :342
     return new_weights
+
+
+def update_weights_refreshed(ev: Evaluator, encoder: CKKSEncoder, encryptor, decryptor, features: Sequence[Ciphertext],
+                             features_T: Sequence[Ciphertext], labels: Ciphertext, weights: Ciphertext,
+                             learning_rate: float, gal_keys: KSwitchKeys, relin_keys: KSwitchKeys, scale: float,
+                             degree: int = 3) -> Ciphertext:
+    """A training step that ends: w - (learning_rate / num_obs) * gradient, at the first level.  A COMPLETION of the
+    reference, not a mirror of it: update_weights above stops where SEAL stops (:336), because the gradient arrives with
+    one prime left.  The holder of the secret key -- the reference's train_cipher has a Decryptor for exactly this
+    (:348-385) -- refreshes the gradient (Decryptor.refresh: decrypt, exact lift, encrypt; no decode / encode), after which
+    the reference's own lines go through, plus the rescale they omit."""
+    num_obs = len(features)
+    gradient, _ = lr_gradient(ev, encoder, encryptor, features, features_T, labels, weights, gal_keys, relin_keys,
+                              scale, degree)                                                                # :275-323
+    gradient = decryptor.refresh(gradient, encryptor)                  # first level, scale 2^40: room for the product
+    n_pt = encoder.encode(float(learning_rate) / num_obs, scale)                                           # :330-331
+    ev.mod_switch_to_inplace(n_pt, gradient.parms_id())                                                    # :333
+    ev.multiply_plain_inplace(gradient, n_pt)                                                              # :336
+    ev.rescale_to_next_inplace(gradient)                               # (omitted by the reference)
+    gradient.scale = 2.0 ** int(np.log2(gradient.scale))               # its own idiom, :323
+    weights = weights.copy()
+    ev.mod_switch_to_inplace(weights, gradient.parms_id())
+    new_weights = ev.sub(gradient, weights)                                                                # :341
+    ev.negate_inplace(new_weights)                                                                         # :342
+    return decryptor.refresh(new_weights, encryptor)                   # back to the first level
+
+
+def train_cipher(ev: Evaluator, encoder: CKKSEncoder, encryptor, decryptor, features: Sequence[Ciphertext],
+                 features_T: Sequence[Ciphertext], labels: Ciphertext, weights: Ciphertext, learning_rate: float,
+                 iters: int, gal_keys: KSwitchKeys, relin_keys: KSwitchKeys, scale: float, degree: int = 3) -> Ciphertext:
+    """The loop of train_cipher, /root/reference/logistic_regression_ckks.cpp:356-382, over update_weights_refreshed.
+    The reference refreshes by decrypt / decode ... encrypt of a last-level plaintext (:362-381) and so could not start
+    a second iteration; here every step already returns first-level weights."""
+    new_weights = weights                                                                                  # :354
+    for _ in range(int(iters)):                                                                            # :356
+        new_weights = update_weights_refreshed(ev, encoder, encryptor, decryptor, features, features_T, labels,
+                                               new_weights, learning_rate, gal_keys, relin_keys, scale, degree)  # :359
+    return new_weights

@@ -129,6 +129,16 @@ _SIGS = {
 
 EXPORTED_SYMBOLS = sorted(_SIGS)
 
+# include/hefx_refresh.h: the extension header (exact mod-raise, refresh), bound beside the surface of hefx.h
+_REFRESH_SIGS = {
+    "hefx_mod_raise": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "hefx_refresh": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, C.c_char_p, _u64, _vp, _vp]),
+    "hefx_refresh_batch": (_i, [_vp, _i, _i, _i, _i, _pp, _vp, _vp, C.c_char_p, _u64, _pp, _vp]),
+}
+REFRESH_SYMBOLS = sorted(_REFRESH_SIGS)
+LIFT_MAX_LIN = 16   # HEFX_LIFT_MAX_LIN
+REFRESH_GROUP = 64  # HEFX_REFRESH_GROUP
+
 
 def library_path() -> str:
     # HEFX_LIB: development override to A/B alternative builds of the same ABI
@@ -144,7 +154,7 @@ def lib():
     if not os.path.exists(path):
         raise HefxError(f"{path} is missing: build the HIP extension first (__graft_entry__.build())")
     L = C.CDLL(path, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in _SIGS.items():
+    for name, (res, args) in list(_SIGS.items()) + list(_REFRESH_SIGS.items()):
         f = getattr(L, name)
         f.restype = res
         f.argtypes = args

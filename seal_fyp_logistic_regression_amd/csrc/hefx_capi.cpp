@@ -3,6 +3,7 @@
 // scratch management and the chunked launch sequences.  No CPU arithmetic fallback exists: every
 // compute entry point dispatches HIP kernels from hefx_kernels.hip or fails.
 #include "../../include/hefx.h"
+#include "../../include/hefx_refresh.h"
 
 #include <chrono>
 #include <cmath>
@@ -3527,4 +3528,162 @@ extern "C" int hefx_ckks_decode(hefx_context *c, int L, const uint64_t *d_pt, in
     if (h_im) HIPCHK(hipMemcpyAsync(h_im, im, sizeof(double) * count * (N / 2), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return HEFX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// mod-raise and refresh (include/hefx_refresh.h)
+// ---------------------------------------------------------------------------------------------
+// What the lift needs beyond the context's tables, per (L_in, new row): the digits of floor(Q_in / 2) and Q_in mod q_j.
+// A few hundred bytes of host arithmetic, passed in the kernel's arguments: nothing to upload, nothing to wait for.
+static LiftTables lift_tables(const hefx_context *c, int L_in, int L_out)
+{
+    const DecodeTables D = decode_tables(c, L_in);
+    LiftTables T{};
+    for (int j = 0; j < L_in; ++j) T.half[j] = D.half[j];
+    for (int j = L_in; j < L_out; ++j) {
+        const u64 q = c->primes[(size_t)j];
+        u64 r = 1;
+        for (int i = 0; i < L_in; ++i) r = h_mulmod(r, c->primes[(size_t)i] % q, q);
+        T.qin[j] = r;
+    }
+    return T;
+}
+static int data_primes(const hefx_context *c) { return c->k > 1 ? c->k - 1 : 1; }
+
+// coefficient-form rows coef[cnt][L_in][N] (consumed) -> NTT-form new rows L_in .. L_out-1 of item i at
+// dst + i * dst_stride + (j - L_in) * N.  cnt == 1: lifted and transformed where they belong; otherwise through
+// w[cnt][L_out - L_in][N], so that ONE transform launch serves the group, and one strided copy puts the rows in place.
+static hipError_t lift_rows(hefx_context *c, int L_in, int L_out, int cnt, u64 *coef, u64 *w, u64 *dst, size_t dst_stride,
+                            hipStream_t s)
+{
+    const size_t N = c->n;
+    const int Ln = L_out - L_in;
+    hipError_t e = launch_ntt(c->T, true, coef, cnt, L_in, 0, s);
+    if (e != hipSuccess) return e;
+    const LiftTables D = lift_tables(c, L_in, L_out);
+    if (cnt == 1) {
+        e = launch_lift(c->T, D, c->d_qmod, L_in, L_out, 1, coef, dst, 0, s);
+        if (e == hipSuccess) e = launch_ntt(c->T, false, dst, 1, Ln, L_in, s);
+        return e;
+    }
+    e = launch_lift(c->T, D, c->d_qmod, L_in, L_out, cnt, coef, w, (size_t)Ln * N, s);
+    if (e == hipSuccess) e = launch_ntt(c->T, false, w, cnt, Ln, L_in, s);
+    if (e == hipSuccess)
+        e = hipMemcpy2DAsync(dst, dst_stride * sizeof(u64), w, (size_t)Ln * N * sizeof(u64), (size_t)Ln * N * sizeof(u64),
+                             (size_t)cnt, hipMemcpyDeviceToDevice, s);
+    return e;
+}
+
+extern "C" int hefx_mod_raise(hefx_context *c, int L_in, int L_out, int count, const uint64_t *in, uint64_t *out,
+                              void *stream)
+{
+    CTXCHK(c);
+    if (L_in < 1 || L_in >= L_out || L_out > data_primes(c) || L_in > HEFX_LIFT_MAX_LIN || count < 1 || !in || !out)
+        return fail(HEFX_ERR_INVALID, "bad mod_raise arguments");
+    if (count > 32768) return fail(HEFX_ERR_INVALID, "too many plaintexts in one mod_raise call");  // (one grid row each)
+    if (c->logn == 15) return fail(HEFX_ERR_UNSUPPORTED, "mod_raise is built for poly_degree up to 16384");
+    const size_t N = c->n, row = N * sizeof(u64);
+    if (int rc = check_ranges("mod_raise", 1, &out, row * L_out * count, {{&in, 1, row * L_in * count}}, {"d_in"})) return rc;
+    const int Ln = L_out - L_in;
+    const size_t cw = (size_t)count * L_in * N;
+    if (int rc = ensure_scratch(c, cw + (size_t)count * Ln * N)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    u64 *coef = c->scratch, *w = coef + cw;
+    // rows below L_in: the input's words, copied; a scratch copy of them goes through the inverse transform
+    HIPCHK(hipMemcpy2DAsync(out, row * L_out, in, row * L_in, row * L_in, (size_t)count, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(coef, in, cw * sizeof(u64), hipMemcpyDeviceToDevice, s));
+    HIPCHK(lift_rows(c, L_in, L_out, count, coef, w, (u64 *)out + (size_t)L_in * N, (size_t)L_out * N, s));
+    return HEFX_OK;
+}
+
+static int refresh_args(const hefx_context *c, int L_in, int size, int L_out)
+{
+    if (L_in < 1 || L_in > L_out || L_out > data_primes(c) || size < 2) return fail(HEFX_ERR_INVALID, "bad refresh arguments");
+    if (L_in < L_out && L_in > HEFX_LIFT_MAX_LIN) return fail(HEFX_ERR_INVALID, "bad refresh arguments: the lift reads at most 16 primes");
+    if (c->logn == 15) return fail(HEFX_ERR_UNSUPPORTED, "refresh is built for poly_degree up to 16384");
+    return HEFX_OK;
+}
+
+// One group of cnt items: decrypt into the plaintext rows p[cnt][L_out][N] (and a copy for the inverse transform), lift,
+// then hefx_encrypt[_batch]'s launches on u[3 cnt][L_out][N].  d_tab == nullptr: cnt == 1, ciphertext ct -> out;
+// otherwise the device table  cnt plaintext pointers (into p) | cnt output pointers | cnt ciphertext pointers.
+static hipError_t refresh_group(hefx_context *c, int L_in, int size, int L_out, int cnt, const u64 *ct, u64 *out,
+                                const u64 *const *d_tab, const u64 *sk, const u64 *pk, const SampleKey &k, uint64_t first_id,
+                                hipStream_t s)
+{
+    const size_t N = c->n, rowsz = (size_t)L_out * N;
+    u64 *u = c->scratch, *ee = u + (size_t)cnt * rowsz, *p = u + 3 * (size_t)cnt * rowsz;
+    u64 *coef = p + (size_t)cnt * rowsz, *w = coef + (size_t)cnt * L_in * N;
+    hipError_t e = launch_decrypt_items(c->T, L_in, size, cnt, ct, d_tab ? d_tab + 2 * cnt : nullptr, sk, p, rowsz,
+                                        L_in < L_out ? coef : nullptr, s);
+    if (e == hipSuccess && L_in < L_out) e = lift_rows(c, L_in, L_out, cnt, coef, w, p + (size_t)L_in * N, rowsz, s);
+    const uint64_t sid = 4 * first_id;
+    const u64 stride = d_tab ? 4 : 0;
+    if (e == hipSuccess) e = launch_sample(c->T, SAMPLE_TERNARY, k, c->noise, sid + 0, cnt, L_out, 0, u, s, stride);
+    if (e == hipSuccess) e = launch_sample(c->T, SAMPLE_NOISE, k, c->noise, sid + 1, cnt, L_out, 0, ee, s, stride);
+    if (e == hipSuccess) e = launch_sample(c->T, SAMPLE_NOISE, k, c->noise, sid + 2, cnt, L_out, 0, ee + (size_t)cnt * rowsz, s, stride);
+    if (e == hipSuccess) e = launch_ntt(c->T, false, u, 3 * cnt, L_out, 0, s);
+    if (e == hipSuccess)
+        e = d_tab ? launch_encrypt_combine_table(c->T, L_out, cnt, pk, u, ee, d_tab, s)
+                  : launch_encrypt_combine(c->T, L_out, pk, u, ee, p, out, s);
+    return e;
+}
+// scratch words of one group: u, e0, e1, the plaintext, its coefficient copy, the lifted rows
+static size_t refresh_words(const hefx_context *c, int L_in, int L_out, int cnt)
+{
+    return (size_t)cnt * c->n * (4 * (size_t)L_out + L_in + (L_out - L_in));
+}
+
+extern "C" int hefx_refresh(hefx_context *c, int L_in, int size, int L_out, const uint64_t *ct, const uint64_t *sk,
+                            const uint64_t *pk, const uint8_t *key32, uint64_t stream_id, uint64_t *out, void *stream)
+{
+    CTXCHK(c);
+    if (int rc = refresh_args(c, L_in, size, L_out)) return rc;
+    if (!ct || !sk || !pk || !key32 || !out) return fail(HEFX_ERR_INVALID, "bad refresh arguments: null pointer");
+    if (stream_id >> 62) return fail(HEFX_ERR_INVALID, "stream id must be below 2^62");
+    const size_t row = (size_t)c->n * sizeof(u64);
+    if (int rc = check_ranges("refresh", 1, &out, 2 * row * L_out,
+                              {{&ct, 1, row * L_in * size}, {&sk, 1, row * L_in}, {&pk, 1, 2 * row * c->k}}, {"d_ct", "d_sk", "d_pk"}))
+        return rc;
+    if (int rc = ensure_scratch(c, refresh_words(c, L_in, L_out, 1))) return rc;
+    HIPCHK(refresh_group(c, L_in, size, L_out, 1, (const u64 *)ct, (u64 *)out, nullptr, (const u64 *)sk, (const u64 *)pk,
+                         sample_key(key32), stream_id, (hipStream_t)stream));
+    return HEFX_OK;
+}
+
+extern "C" int hefx_refresh_batch(hefx_context *c, int L_in, int size, int L_out, int n, const uint64_t *const *cts,
+                                  const uint64_t *sk, const uint64_t *pk, const uint8_t *key32, uint64_t first_stream_id,
+                                  uint64_t *const *outs, void *stream)
+{
+    CTXCHK(c);
+    if (int rc = refresh_args(c, L_in, size, L_out)) return rc;
+    if (!cts || !sk || !pk || !key32 || !outs || n < 1) return fail(HEFX_ERR_INVALID, "bad refresh arguments: null pointer");
+    if ((first_stream_id + (uint64_t)n) >> 62) return fail(HEFX_ERR_INVALID, "stream id must be below 2^62");
+    for (int i = 0; i < n; ++i)
+        if (!cts[i] || !outs[i]) return fail(HEFX_ERR_INVALID, "null operand in refresh batch");
+    const size_t row = (size_t)c->n * sizeof(u64);
+    if (int rc = check_ranges("refresh_batch", (size_t)n, outs, 2 * row * L_out,
+                              {{cts, (size_t)n, row * L_in * size}, {&sk, 1, row * L_in}, {&pk, 1, 2 * row * c->k}},
+                              {"d_cts", "d_sk", "d_pk"}))
+        return rc;
+    const int cap = HEFX_REFRESH_GROUP;
+    if (int rc = ensure_scratch(c, refresh_words(c, L_in, L_out, n < cap ? n : cap))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const SampleKey k = sample_key(key32);
+    const size_t rowsz = (size_t)L_out * c->n;
+    return table_slices(
+        c, n, 3, s,
+        [&](const uint64_t **hp, int i0, int cnt) {
+            const u64 *p = c->scratch + 3 * (size_t)cnt * rowsz;  // refresh_group's plaintext rows
+            for (int i = 0; i < cnt; ++i) {
+                hp[i] = reinterpret_cast<const uint64_t *>(p + (size_t)i * rowsz);
+                hp[cnt + i] = outs[i0 + i];
+                hp[2 * cnt + i] = cts[i0 + i];
+            }
+        },
+        [&](const u64 *const *dp, int i0, int cnt) -> hipError_t {
+            return refresh_group(c, L_in, size, L_out, cnt, nullptr, nullptr, dp, (const u64 *)sk, (const u64 *)pk, k,
+                                 first_stream_id + (uint64_t)i0, s);
+        },
+        cap);
 }

@@ -209,16 +209,11 @@ __global__ __launch_bounds__(256) void ckks_encode_scalar_kernel(DevTables T, co
 // slot i reads A_r at r = (3^i - 1)/2 or the conjugate of its mirror.  The positive-exponent DFT runs through the
 // same DIF passes as encode on conjugated data.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void decode_crt_kernel(DevTables T, DecodeTables D, int L, const u64 *__restrict__ coef,
-                                                         double inv_scale, double *__restrict__ p)
+// Garner mixed-radix digits of one coefficient: d_j = ((r_j - d_0) q_0^-1 - d_1) q_1^-1 ... mod q_j, from the residues
+// c[j * n] of rows j < L; x = d_0 + d_1 q_0 + d_2 q_0 q_1 + ... in [0, Q).  Exact modular arithmetic.
+__device__ __forceinline__ void garner_digits(const DevTables &T, int L, const u64 *__restrict__ c, size_t n, u64 *d)
 {
-    const size_t n = (size_t)1 << T.logn;
-    const size_t a = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t vec = blockIdx.y;
-    if (a >= n) return;
-    const u64 *__restrict__ c = coef + vec * L * n + a;
-    u64 d[16];
-    for (int j = 0; j < L; ++j) {  // Garner: d_j = ((r_j - d_0) q_0^-1 - d_1) q_1^-1 ... mod q_j
+    for (int j = 0; j < L; ++j) {
         const ModConst mc = T.mods[j];
         u64 t = c[(size_t)j * n];
         for (int i = 0; i < j; ++i) {
@@ -227,14 +222,25 @@ __global__ __launch_bounds__(256) void decode_crt_kernel(DevTables T, DecodeTabl
         }
         d[j] = t;
     }
-    // x > floor(Q/2)?  compare the mixed-radix digits from the top
-    bool neg = false;
-    for (int j = L - 1; j >= 0; --j) {
-        if (d[j] != D.half[j]) {
-            neg = d[j] > D.half[j];
-            break;
-        }
-    }
+}
+// x > floor(Q/2)?  compare the mixed-radix digits from the top (Q is odd: no tie)
+__device__ __forceinline__ bool above_half(const u64 *d, const u64 *half, int L)
+{
+    for (int j = L - 1; j >= 0; --j)
+        if (d[j] != half[j]) return d[j] > half[j];
+    return false;
+}
+
+__global__ __launch_bounds__(256) void decode_crt_kernel(DevTables T, DecodeTables D, int L, const u64 *__restrict__ coef,
+                                                         double inv_scale, double *__restrict__ p)
+{
+    const size_t n = (size_t)1 << T.logn;
+    const size_t a = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t vec = blockIdx.y;
+    if (a >= n) return;
+    u64 d[16];
+    garner_digits(T, L, coef + vec * L * n + a, n, d);
+    const bool neg = above_half(d, D.half, L);
     if (neg) {  // y = Q - x, digit-wise with borrow (Q = (0, ..., 0 | 1))
         u64 borrow = 0;
         for (int j = 0; j < L; ++j) {
@@ -251,6 +257,37 @@ __global__ __launch_bounds__(256) void decode_crt_kernel(DevTables T, DecodeTabl
     double m = (double)d[L - 1];
     for (int j = L - 2; j >= 0; --j) m = m * (double)T.mods[j].q + (double)d[j];
     p[vec * n + a] = (neg ? -m : m) * inv_scale;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Exact centred base extension (mod-raise; include/hefx_refresh.h): the integer back end of the digits above.  A
+// coefficient x in [0, Q_in) stands for x when x <= floor(Q_in / 2) and for x - Q_in otherwise -- decode's rule -- and
+// row j >= L_in of the output holds that integer mod q_j:
+//     x mod q_j = ((d_(L-1) q_(L-2) + d_(L-2)) q_(L-3) + ... + d_0) mod q_j   (Horner over the mixed-radix digits),
+// minus Q_in mod q_j for a negative one.  No floating point: every step is a canonical residue.  One thread per
+// (coefficient, item), consecutive lanes on consecutive coefficients; the new rows may be 40-bit or 60-bit primes, so
+// the arithmetic is the ModConst path that serves both.  qmod[i * k + j] = q_i mod q_j.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void lift_crt_kernel(DevTables T, LiftTables D, const u64 *__restrict__ qmod, int L_in,
+                                                       int L_out, const u64 *__restrict__ coef, u64 *__restrict__ out,
+                                                       size_t out_stride)
+{
+    const size_t n = (size_t)1 << T.logn;
+    const size_t a = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t item = blockIdx.y;
+    if (a >= n) return;
+    u64 d[16];
+    garner_digits(T, L_in, coef + item * L_in * n + a, n, d);
+    const bool neg = above_half(d, D.half, L_in);
+    u64 *__restrict__ o = out + item * out_stride + a;
+    for (int j = L_in; j < L_out; ++j) {
+        const ModConst mc = T.mods[j];
+        u64 acc = barrett64(d[L_in - 1], mc.q, mc.r1);
+        for (int i = L_in - 2; i >= 0; --i)
+            acc = addmod(mulmod(acc, qmod[(size_t)i * T.k + j], mc), barrett64(d[i], mc.q, mc.r1), mc.q);
+        if (neg) acc = submod(acc, D.qin[j], mc.q);
+        o[(size_t)(j - L_in) * n] = acc;
+    }
 }
 
 template <int LM, bool SPLIT>
@@ -374,6 +411,15 @@ hipError_t launch_decode(const DevTables &T, const EncodeTables &E, const Decode
         default: return hipErrorInvalidValue;
     }
 #undef LAUNCHD
+    return hipGetLastError();
+}
+
+hipError_t launch_lift(const DevTables &T, const LiftTables &D, const u64 *qmod, int L_in, int L_out, int count,
+                       const u64 *coef, u64 *out, size_t out_stride, hipStream_t s)
+{
+    const int n = 1 << T.logn;
+    hipLaunchKernelGGL(lift_crt_kernel, dim3((n + 255) / 256, count), dim3(256), 0, s, T, D, qmod, L_in, L_out, coef, out,
+                       out_stride);
     return hipGetLastError();
 }
 

@@ -186,6 +186,15 @@ hipError_t launch_decode(const DevTables &T, const EncodeTables &E, const Decode
                          int count, double scale, double *p, double *re, double *im, hipStream_t s);
 hipError_t launch_encode(const DevTables &T, const EncodeTables &E, const double *re, const double *im, int nvalues,
                          int count, double scale, int L, u64 *out, bool wide, hipStream_t s);
+// exact centred base extension (hefx_encode.hip, include/hefx_refresh.h): the integer back end of decode's Garner digits
+struct LiftTables {
+    u64 half[16];  // as DecodeTables::half, for Q_in = q_0 ... q_(L_in-1)
+    u64 qin[64];   // Q_in mod q_j, read at the new rows j = L_in .. L_out-1
+};
+// coef [count][L_in][N] coefficient form -> rows L_in .. L_out-1 of the same integer polynomials, coefficient form:
+// item i, new row j at out + i * out_stride + (j - L_in) * N; qmod [k][k] = q_i mod q_m (device)
+hipError_t launch_lift(const DevTables &T, const LiftTables &D, const u64 *qmod, int L_in, int L_out, int count,
+                       const u64 *coef, u64 *out, size_t out_stride, hipStream_t s);
 // plaintext i = round(vals[i] * scale) in every word of its rows ([count][L][N])
 hipError_t launch_encode_scalar(const DevTables &T, const double *vals, int count, double scale, int L, u64 *out,
                                 hipStream_t s);
@@ -207,6 +216,10 @@ hipError_t launch_encrypt_combine_table(const DevTables &T, int L, int m, const 
 // dst[i][0..words) = src + i*words for i < n (device pointer table): contiguous batch results to their owners
 hipError_t launch_scatter_rows(const u64 *src, const u64 *const *d_tab, int n, size_t words, hipStream_t s);
 hipError_t launch_decrypt(const DevTables &T, int L, int size, const u64 *ct, const u64 *sk, u64 *out, hipStream_t s);
+// m decryptions, item i of ciphertext d_tab[i] (d_tab == nullptr: m = 1, of ct), written twice: to out + i * out_stride
+// ([L][N]) and, for the inverse transform that follows in a refresh, to copy + i * L * N (copy may be null)
+hipError_t launch_decrypt_items(const DevTables &T, int L, int size, int m, const u64 *ct, const u64 *const *d_tab,
+                                const u64 *sk, u64 *out, size_t out_stride, u64 *copy, hipStream_t s);
 hipError_t launch_keygen_combine(const DevTables &T, const u64 *sk, const u64 *new_sk, const u64 *a, const u64 *e,
                                  u64 *out, hipStream_t s);
 hipError_t launch_galois_permute(const DevTables &T, const uint32_t *perm, const u64 *in, int rows, u64 *out,

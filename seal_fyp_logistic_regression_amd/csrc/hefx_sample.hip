@@ -185,6 +185,30 @@ __global__ __launch_bounds__(256) void decrypt_kernel(DevTables T, int L, int si
     *reinterpret_cast<ulonglong2 *>(out + (size_t)j * n + w) = acc;
 }
 
+// decrypt_kernel for m items in one launch (hefx_refresh[_batch]): item i of the ciphertext tab[i] (tab == nullptr: of
+// ct), the same Horner, written to out + i * out_stride and (copy != nullptr) to copy + i * L * N
+__global__ __launch_bounds__(256) void decrypt_items_kernel(DevTables T, int L, int size, const u64 *__restrict__ ct0,
+                                                            const u64 *const *__restrict__ tab,
+                                                            const u64 *__restrict__ sk, u64 *__restrict__ out,
+                                                            size_t out_stride, u64 *__restrict__ copy)
+{
+    const size_t n = (size_t)1 << T.logn;
+    const size_t w = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 2;
+    const int j = blockIdx.y;
+    const size_t item = blockIdx.z;
+    const ModConst mc = T.mods[j];
+    const u64 *ct = tab ? tab[item] : ct0;
+    const ulonglong2 s = *reinterpret_cast<const ulonglong2 *>(sk + (size_t)j * n + w);
+    ulonglong2 acc = gld16(ct + ((size_t)(size - 1) * L + j) * n + w);
+    for (int p = size - 2; p >= 0; --p) {
+        const ulonglong2 cp = gld16(ct + ((size_t)p * L + j) * n + w);
+        acc.x = addmod(mulmod(acc.x, s.x, mc), cp.x, mc.q);
+        acc.y = addmod(mulmod(acc.y, s.y, mc), cp.y, mc.q);
+    }
+    *reinterpret_cast<ulonglong2 *>(out + item * out_stride + (size_t)j * n + w) = acc;
+    if (copy) *reinterpret_cast<ulonglong2 *>(copy + (item * L + j) * n + w) = acc;
+}
+
 // Key-switching key for the secret new_sk under sk (App. A.11), digit i, key-level row m:
 //   out[i][1][m] = a_i[m] (uniform),  out[i][0][m] = -(a_i[m]*sk[m] + e_i[m]) + [m == i] (P mod q_i) * new_sk[i]
 // a: uniform [k-1][k][N]; e: noise [k-1][k][N] already in NTT form; everything NTT form, SEAL's key layout.
@@ -281,6 +305,15 @@ hipError_t launch_decrypt(const DevTables &T, int L, int size, const u64 *ct, co
 {
     const int n2 = (1 << T.logn) / 2;
     hipLaunchKernelGGL(decrypt_kernel, dim3((n2 + 255) / 256, L), dim3(256), 0, s, T, L, size, ct, sk, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_decrypt_items(const DevTables &T, int L, int size, int m, const u64 *ct, const u64 *const *d_tab,
+                                const u64 *sk, u64 *out, size_t out_stride, u64 *copy, hipStream_t s)
+{
+    const int n2 = (1 << T.logn) / 2;
+    hipLaunchKernelGGL(decrypt_items_kernel, dim3((n2 + 255) / 256, L, m), dim3(256), 0, s, T, L, size, ct, d_tab, sk, out,
+                       out_stride, copy);
     return hipGetLastError();
 }
 

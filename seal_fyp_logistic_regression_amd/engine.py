@@ -578,6 +578,37 @@ class Engine:
         capi.check(capi.lib().hefx_decrypt(self._h, L, size, ct.ptr, sk.ptr, out.ptr, stream))
         return out
 
+    # ---- exact mod-raise and refresh (include/hefx_refresh.h)
+    def mod_raise(self, L_in, L_out, x, count=1, out=None, stream=None):
+        """[count][L_in][N] NTT-form plaintexts -> the same integer polynomials (centred representatives) over L_out
+        primes, [count][L_out][N]; exact, x is left as it is (hefx_mod_raise)"""
+        if out is None:
+            out = DeviceArray(self, (L_out, self.N) if count == 1 else (count, L_out, self.N))
+        capi.check(capi.lib().hefx_mod_raise(self._h, L_in, L_out, count, x.ptr, out.ptr, stream))
+        return out
+
+    def refresh(self, L_in, size, L_out, ct, sk, pk, key32: bytes, stream_id: int, out=None, stream=None):
+        """decrypt at L_in -> lift -> encrypt at L_out in one call, the plaintext stays on the device (hefx_refresh): the
+        words of decrypt, mod_raise and encrypt with this key32 / stream_id"""
+        if len(key32) != 32:
+            raise ValueError("key32 must be 32 bytes")
+        out = out if out is not None else DeviceArray(self, (2, L_out, self.N))
+        capi.check(capi.lib().hefx_refresh(self._h, L_in, size, L_out, ct.ptr, sk.ptr, pk.ptr, key32, int(stream_id),
+                                           out.ptr, stream))
+        return out
+
+    def refresh_batch(self, L_in, size, L_out, cts, sk, pk, key32: bytes, first_stream_id: int, outs=None, stream=None):
+        """n refreshes in lockstep, item i with stream id first_stream_id + i: the words of n refresh() calls
+        (hefx_refresh_batch)"""
+        if len(key32) != 32:
+            raise ValueError("key32 must be 32 bytes")
+        n = len(cts)
+        outs = outs if outs is not None else self.empty_many(n, (2, L_out, self.N))
+        capi.check(capi.lib().hefx_refresh_batch(
+            self._h, L_in, size, L_out, n, capi.ptr_array([c.ptr for c in cts]), sk.ptr, pk.ptr, key32,
+            int(first_stream_id), capi.ptr_array([o.ptr for o in outs]), stream))
+        return outs
+
     # ---- CKKS encode on the GPU
     @staticmethod
     def _encode_args(values):

@@ -275,6 +275,17 @@ class GpuBackend:
     def decrypt(self, L, size, ct, sk):
         return self.engine.decrypt(L, size, ct, sk)
 
+    def mod_raise(self, L_in, L_out, x, count=1):
+        return self.engine.mod_raise(L_in, L_out, x, count)
+
+    def refresh(self, L_in, size, L_out, ct, sk, pk, key32, stream_id):
+        """decrypt -> exact lift -> encrypt in one engine call (hefx_refresh); the oracle-backed twin of the tests has no
+        such method and Decryptor.refresh composes the same words from its decrypt, transforms and encrypt"""
+        return self.engine.refresh(L_in, size, L_out, ct, sk, pk, key32, stream_id)
+
+    def refresh_batch(self, L_in, size, L_out, cts, sk, pk, key32, first_stream_id):
+        return self.engine.refresh_batch(L_in, size, L_out, cts, sk, pk, key32, first_stream_id)
+
     def ckks_decode(self, L, pt, scale):
         return self.engine.ckks_decode(L, pt, scale)[0]
 
@@ -618,6 +629,82 @@ class Decryptor:
         out.data = self.ctx.backend.decrypt(L, encrypted.size(), encrypted.data, self.sk.data)
         out._parms_id, out._scale = L, encrypted.scale
         return out
+
+    # ---- refresh: decrypt, lift to a higher level, encrypt.  What the reference's training loop does after every step
+    # (logistic_regression_ckks.cpp:362-381), without its decode / encode pair: at one scale that pair is the identity on
+    # the integer polynomial, so the plaintext's centred coefficients are written mod the target level's primes -- exact.
+    def _refresh_target(self, encrypted: Ciphertext, parms_id: Optional[int]) -> int:
+        L_out = parms_id if parms_id is not None else self.ctx.first_parms_id()
+        if encrypted.size() < 2:
+            raise ValueError("encrypted is not valid for encryption parameters")
+        if L_out < encrypted.parms_id() or L_out > self.ctx.first_parms_id():
+            raise ValueError("refresh: the target level must lie between the ciphertext's and the first level")
+        return L_out
+
+    def _refresh_composed(self, encrypted: Ciphertext, encryptor: "Encryptor", L_out: int, stream_id: int):
+        """the words of the engine's refresh from a backend without one: decrypt, inverse transform, lift_coefficients,
+        forward transform of the new rows, encrypt"""
+        be, N, L_in = self.ctx.backend, self.ctx.N, encrypted.parms_id()
+        pt = be.decrypt(L_in, encrypted.size(), encrypted.data, self.sk.data)
+        if L_in < L_out:
+            old = np.array(be.to_host(pt), dtype=np.uint64).reshape(L_in, N)
+            coef = np.asarray(be.to_host(be.ntt_inverse(be.from_host(old), 1, L_in, 0))).reshape(L_in, N)
+            new = be.ntt_forward(be.from_host(lift_coefficients(coef, self.ctx.primes, L_in, L_out)), 1, L_out - L_in, L_in)
+            pt = be.from_host(np.concatenate([old, np.asarray(be.to_host(new)).reshape(L_out - L_in, N)]))
+        return be.encrypt(L_out, encryptor._pk_dev, pt, encryptor._key32, stream_id)
+
+    def refresh(self, encrypted: Ciphertext, encryptor: "Encryptor", parms_id: Optional[int] = None) -> Ciphertext:
+        """A fresh size-2 encryption, at level parms_id (default: the first level), of what `encrypted` decrypts to; the
+        scale is unchanged.  The encryptor's stream counter advances as encrypt() advances it.  One engine call
+        (hefx_refresh) when the backend has it."""
+        L_out = self._refresh_target(encrypted, parms_id)
+        encryptor._stream += 1
+        native = getattr(self.ctx.backend, "refresh", None) if self.ctx.N <= 16384 else None  # (the entry's range of N)
+        if native is not None:
+            data = native(encrypted.parms_id(), encrypted.size(), L_out, encrypted.data, self.sk.data, encryptor._pk_dev,
+                          encryptor._key32, encryptor._stream)
+        else:
+            data = self._refresh_composed(encrypted, encryptor, L_out, encryptor._stream)
+        return Ciphertext()._set(data, 2, L_out, encrypted.scale)
+
+    def refresh_many(self, encrypteds: Sequence[Ciphertext], encryptor: "Encryptor",
+                     parms_id: Optional[int] = None) -> List[Ciphertext]:
+        """[refresh(c) for c in encrypteds], the same words and stream ids, as one engine call (hefx_refresh_batch) when the
+        ciphertexts share level and size and the backend has it"""
+        cts = list(encrypteds)
+        native = getattr(self.ctx.backend, "refresh_batch", None) if self.ctx.N <= 16384 else None
+        if not cts or native is None or any(c.parms_id() != cts[0].parms_id() or c.size() != cts[0].size() for c in cts):
+            return [self.refresh(c, encryptor, parms_id) for c in cts]
+        L_out = self._refresh_target(cts[0], parms_id)
+        first = encryptor._stream + 1
+        encryptor._stream += len(cts)
+        outs = native(cts[0].parms_id(), cts[0].size(), L_out, [c.data for c in cts], self.sk.data, encryptor._pk_dev,
+                      encryptor._key32, first)
+        return [Ciphertext()._set(o, 2, L_out, c.scale) for o, c in zip(outs, cts)]
+
+
+def lift_coefficients(rows: np.ndarray, primes: Sequence[int], L_in: int, L_out: int) -> np.ndarray:
+    """The centred lift on the host, in Python integers: rows [L_in][N] (coefficient form, canonical) -> the new rows
+    L_in .. L_out-1, [L_out - L_in][N].  Every coefficient x in [0, Q_in), Q_in = q_0 ... q_(L_in-1), stands for x when
+    x <= Q_in // 2 and for x - Q_in otherwise (Q_in is odd: no tie) -- the rule of CKKSEncoder.decode -- and is written
+    mod the new primes.  Composed by Garner's mixed-radix digits; the engine's kernel (hefx_mod_raise) does the same work
+    in 64-bit residues."""
+    q = [int(p) for p in primes]
+    rows = np.asarray(rows).reshape(L_in, -1)
+    digits = []
+    for j in range(L_in):  # d_j = ((r_j - d_0) q_0^-1 - d_1) q_1^-1 ... mod q_j
+        t = rows[j].astype(object)
+        for i in range(j):
+            t = (t - digits[i]) * pow(q[i], -1, q[j]) % q[j]
+        digits.append(t)
+    x, Q = digits[-1], q[L_in - 1]
+    for i in range(L_in - 2, -1, -1):  # x = d_0 + q_0 (d_1 + q_1 (d_2 + ...))
+        x, Q = x * q[i] + digits[i], Q * q[i]
+    x = np.where((x > Q // 2).astype(bool), x - Q, x)
+    out = np.empty((L_out - L_in, rows.shape[1]), dtype=np.uint64)
+    for j in range(L_in, L_out):
+        out[j - L_in] = (x % q[j]).astype(np.uint64)
+    return out
 
 
 class CKKSEncoder:
