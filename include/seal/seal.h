@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "../hefx.h"
+#include "../hefx_bfv.h"
 #include "shim_bfv.h"
 #include "shim_io.h"
 
@@ -1335,15 +1336,30 @@ public:
     struct BfvTools {
         int L = 0;                                  // data primes
         std::uint64_t t = 0;
-        shim::bfv::Basis data, aux;                 // Q-basis and the auxiliary basis of the tensor product
+        shim::bfv::Basis data;                      // Q-basis
         shim::bfv::Big delta;                       // floor(Q / t)
         std::vector<std::uint64_t> delta_mod;       // delta mod q_j
-        std::shared_ptr<shim::Engine> aux_engine;   // hefx context over the auxiliary primes (NTT + dyadic products)
         shim::bfv::PlainNtt pntt;
         bool batching = false;
+        // the engine's multiply / decrypt rounding of this level (include/hefx_bfv.h), made on first use; null after an
+        // HEFX_ERR_UNSUPPORTED: that level stays on the host path (shim_bfv.h multiply_host / decrypt_round_host)
+        mutable hefx_bfv *dev = nullptr;
+        mutable bool dev_tried = false;
+        BfvTools() = default;
+        BfvTools(const BfvTools &) = delete;
+        BfvTools &operator=(const BfvTools &) = delete;
+        ~BfvTools()
+        {
+            if (dev) hefx_bfv_destroy(dev);
+        }
+    };
+    // the auxiliary basis of the HOST path's tensor product and an engine context over it (NTT + dyadic products)
+    struct BfvHostAux {
+        shim::bfv::Basis aux;
+        std::shared_ptr<shim::Engine> engine;
     };
     int bfv_top_level() const { return k_ > 1 ? k_ - 1 : 1; }
-    // tools of the level with `L` data primes (0: the first data level); levels share the auxiliary basis and engine
+    // tools of the level with `L` data primes (0: the first data level)
     const BfvTools &bfv(int L = 0) const
     {
         if (L <= 0) L = bfv_top_level();
@@ -1359,9 +1375,25 @@ public:
         shim::bfv::Big rem;
         shim::bfv::divrem(b->data.M, shim::bfv::Big(t_), b->delta, rem);
         for (int j = 0; j < b->L; ++j) b->delta_mod.push_back(shim::bfv::mod_small(b->delta, primes_[j]));
-        // tensor-product coefficients are sums of N products of centred residues, up to three of them per output
-        // polynomial: |x| < 3 N (Q/2)^2 at the top level; one auxiliary basis of that width serves every level
-        if (bfv_.empty()) {
+        b->batching = b->pntt.init(t_, n_);
+        bfv_[L] = b;
+        return *b;
+    }
+    // the device object of a level, or null when the engine does not serve its shape (the caller takes the host path)
+    hefx_bfv *bfv_device(const BfvTools &B) const
+    {
+        if (!B.dev_tried) {
+            B.dev_tried = true;
+            const int rc = hefx_bfv_create(engine()->ready({}), B.L, B.t, &B.dev);
+            if (rc != HEFX_OK && rc != HEFX_ERR_UNSUPPORTED) shim::check(rc);
+        }
+        return B.dev;
+    }
+    // host path only: tensor-product coefficients are sums of N products of centred residues, up to three of them per
+    // output polynomial: |x| < 3 N (Q/2)^2 at the top level; one auxiliary basis of that width serves every level
+    const BfvHostAux &bfv_host_aux() const
+    {
+        if (!bfv_aux_.engine) {
             shim::bfv::Basis top;
             top.init(std::vector<std::uint64_t>(primes_.begin(), primes_.begin() + bfv_top_level()));
             int logn = 0;
@@ -1371,14 +1403,10 @@ public:
             for (std::uint64_t v = ((std::uint64_t)1 << 60) - 2 * n_ + 1; (int)aux.size() * 59 < need; v -= 2 * n_)
                 if (shim::is_prime(v) && std::find(primes_.begin(), primes_.end(), v) == primes_.end()) aux.push_back(v);
             if (aux.size() > 7) throw std::invalid_argument("coeff_modulus too large for the BFV demo path of this shim");
-            bfv_aux_.init(aux);
-            bfv_aux_engine_ = shim::get_engine((std::uint32_t)n_, aux);
+            bfv_aux_.aux.init(aux);
+            bfv_aux_.engine = shim::get_engine((std::uint32_t)n_, aux);
         }
-        b->aux = bfv_aux_;
-        b->aux_engine = bfv_aux_engine_;
-        b->batching = b->pntt.init(t_, n_);
-        bfv_[L] = b;
-        return *b;
+        return bfv_aux_;
     }
     // number of RNS rows of a level, from its parms_id (0 if unknown)
     int rows_of(const parms_id_type &id) const
@@ -1462,8 +1490,7 @@ private:
     mutable std::shared_ptr<shim::Engine> eng_;
     std::uint64_t t_ = 0;
     mutable std::map<int, std::shared_ptr<BfvTools>> bfv_;
-    mutable shim::bfv::Basis bfv_aux_;
-    mutable std::shared_ptr<shim::Engine> bfv_aux_engine_;
+    mutable BfvHostAux bfv_aux_;
 };
 
 namespace shim {
@@ -2189,8 +2216,7 @@ public:
     {
         if (!ct.buf) throw std::invalid_argument("encrypted is not valid for encryption parameters");
         if (!ctx_->is_ckks()) {
-            int budget = 0;
-            decrypt_bfv(ct, dest, budget);
+            decrypt_bfv(ct, dest, nullptr);
             return;
         }
         auto &e = ctx_->engine();
@@ -2211,17 +2237,23 @@ public:
         if (!ct.buf) throw std::invalid_argument("encrypted is not valid for encryption parameters");
         Plaintext tmp;
         int budget = 0;
-        decrypt_bfv(ct, tmp, budget);
+        decrypt_bfv(ct, tmp, &budget);
         return budget;
     }
+    // shim internals, read by drivers/bfv_selftest.cpp: the BFV decryption with its rounding on the host
+    // (shim_bfv.h decrypt_round_host) whatever the engine serves, and whether the engine serves this ciphertext's level
+    void shim_decrypt_bfv_host(const Ciphertext &ct, Plaintext &dest, int &budget) const { decrypt_bfv(ct, dest, &budget, true); }
+    bool shim_bfv_on_device(const Ciphertext &ct) const { return ctx_->bfv_device(ctx_->bfv(ct.rows)) != nullptr; }
     // shim internals, read by seal/shim_refresh.h
     const std::shared_ptr<SEALContext> &shim_context() const { return ctx_; }
     const SecretKey &shim_secret_key() const { return sk_; }
 
 private:
-    // BFV: x = [c0 + c1 s (+ c2 s^2)]_Q on the GPU (NTT domain), then per coefficient t*x = quo*Q + rem on the host:
-    // m = round(t*x/Q) mod t, and |rem centred| is the invariant noise
-    void decrypt_bfv(const Ciphertext &ct, Plaintext &dest, int &budget) const
+    // BFV: x = [c0 + c1 s (+ c2 s^2)]_Q on the GPU (NTT domain), then m = round(t*x/Q) mod t per coefficient, on the GPU
+    // as well (hefx_bfv_decrypt_round): only m comes back.  The noise budget, when asked for, is host work on x as it
+    // always was: t*x = quo*Q + rem, |rem centred| is the invariant noise.  `host`, or a level the engine does not serve:
+    // the rounding on the host too.
+    void decrypt_bfv(const Ciphertext &ct, Plaintext &dest, int *budget, bool host = false) const
     {
         namespace bf = shim::bfv;
         const auto &B = ctx_->bfv(ct.rows);
@@ -2233,24 +2265,22 @@ private:
         shim::check(hefx_ntt_forward(e->ready({}), tmp->p, (int)ct.size(), L, 0, nullptr));
         shim::check(hefx_decrypt(e->ready({}), L, (int)ct.size(), tmp->p, sk_.buf->p, acc->p, nullptr));
         shim::check(hefx_ntt_inverse(e->ready({}), acc->p, 1, L, 0, nullptr));
-        const std::vector<std::uint64_t> x = shim::download(acc);
+        hefx_bfv *dev = host ? nullptr : ctx_->bfv_device(B);
         dest = Plaintext();
-        dest.bfv.assign(n, 0);
         dest.parms_id() = parms_id_zero;
-        bf::Big worst;
-        for (std::size_t i = 0; i < n; ++i) {
-            const bf::Big xi = B.data.compose(x.data(), n, i);
-            bf::Big quo, rem;
-            bf::divrem(bf::mul_small(xi, B.t), B.data.M, quo, rem);
-            std::uint64_t m = bf::mod_small(quo, B.t);
-            if (bf::cmp(rem, B.data.half) > 0) {  // round up; the noise is the distance to the next multiple of Q
-                m = (m + 1) % B.t;
-                rem = bf::sub(B.data.M, rem);
-            }
-            dest.bfv[i] = m;
-            if (bf::cmp(rem, worst) > 0) worst = rem;
+        if (dev) {
+            auto m = shim::new_buf(e, n);
+            (void)e->ready({});
+            shim::check(hefx_bfv_decrypt_round(dev, acc->p, m->p, nullptr));
+            dest.bfv = shim::download(m);
         }
-        budget = std::max(0, B.data.M.bits() - worst.bits() - 1);
+        if (!dev || budget) {
+            const std::vector<std::uint64_t> x = shim::download(acc);
+            bf::Big worst;
+            std::vector<std::uint64_t> m = bf::decrypt_round_host(B.data, B.t, x, n, &worst);
+            if (!dev) dest.bfv.swap(m);
+            if (budget) *budget = std::max(0, B.data.M.bits() - worst.bits() - 1);
+        }
         while (dest.bfv.size() > 1 && dest.bfv.back() == 0) dest.bfv.pop_back();  // SEAL keeps the significant coefficients
     }
 
@@ -2815,6 +2845,14 @@ public:
     // drivers/xcheck_lr.cpp reads the gradient the reference's update_weights holds when SEAL stops it
     // (logistic_regression_ckks.cpp:336).
     void hefx_on_refused(std::function<void(const char *call, const Ciphertext &operand)> observer) { on_refused_ = std::move(observer); }
+    // shim internals, read by drivers/bfv_selftest.cpp: the BFV product on the host path (shim_bfv.h multiply_host)
+    // whatever the engine serves
+    void shim_multiply_bfv_host(const Ciphertext &a, const Ciphertext &b, Ciphertext &dest) const
+    {
+        check_ct(a);
+        check_ct(b);
+        multiply_bfv(a, b, dest, true);
+    }
     void multiply(const Ciphertext &a, const Ciphertext &b, Ciphertext &dest) const
     {
         check_ct(a);
@@ -3245,67 +3283,54 @@ public:
     }
 
 private:
-    // BFV tensor product scaled by t/Q (vector_ops.cpp:179 square_inplace): the exact integer products
-    // c0 = a0 b0, c1 = a0 b1 + a1 b0, c2 = a1 b1 of the centred operands are formed in an auxiliary RNS basis wide
-    // enough to hold them (dyadic products in the NTT domain on the GPU), CRT-composed on the host, multiplied by t,
-    // divided by Q with rounding and reduced into the data basis -- the textbook Fan-Vercauteren multiplication.
-    void multiply_bfv(const Ciphertext &a, const Ciphertext &b, Ciphertext &dest) const
+    // BFV tensor product scaled by t/Q (vector_ops.cpp:179 square_inplace), the textbook Fan-Vercauteren multiplication:
+    // c_k = sum_{i+j=k} a_i b_j of the centred operands as exact integers, times t, divided by Q with rounding, reduced
+    // into the data basis.  One engine call (hefx_bfv_multiply): the ciphertexts never leave the device.  `host`, or a
+    // level the engine does not serve: shim_bfv.h multiply_host -- operands downloaded, re-reduced into an auxiliary
+    // basis, the dyadic products on a second engine context, the rounding by long division on the host.
+    void multiply_bfv(const Ciphertext &a, const Ciphertext &b, Ciphertext &dest, bool host = false) const
     {
         namespace bf = shim::bfv;
         const auto &B = ctx_->bfv(a.rows);
         const std::size_t n = ctx_->n();
-        const int L = B.L, A = (int)B.aux.m.size();
+        const int L = B.L;
         const int sa = (int)a.size(), sb = (int)b.size(), sr = sa + sb - 1;
         if (sa < 2 || sb < 2 || sr > 6) throw std::invalid_argument("encrypted1 or encrypted2 has an unsupported size");
-        auto lift = [&](const Ciphertext &c) {  // [size][L][N] residues -> centred integers -> [size][A][N] residues
-            const std::vector<std::uint64_t> h = shim::download(c.buf);
-            const int sz = (int)c.size();
-            std::vector<std::uint64_t> out((std::size_t)sz * A * n);
-            for (int p = 0; p < sz; ++p)
-                for (std::size_t i = 0; i < n; ++i) {
-                    bf::Big x = B.data.compose(h.data() + (std::size_t)p * L * n, n, i);
-                    const bool neg = bf::cmp(x, B.data.half) > 0;
-                    if (neg) x = bf::sub(B.data.M, x);
-                    for (int j = 0; j < A; ++j) {
-                        const std::uint64_t r = bf::mod_small(x, B.aux.m[j]);
-                        out[((std::size_t)p * A + j) * n + i] = neg && r ? B.aux.m[j] - r : r;
-                    }
-                }
-            return out;
-        };
-        auto &ae = B.aux_engine;
-        auto da = shim::upload(ae, lift(a));
-        auto db = a.buf == b.buf ? da : shim::upload(ae, lift(b));
-        shim::check(hefx_ntt_forward(ae->ready({}), da->p, sa, A, 0, nullptr));
-        if (db != da) shim::check(hefx_ntt_forward(ae->ready({}), db->p, sb, A, 0, nullptr));
-        const std::size_t poly = (std::size_t)A * n;
-        auto prod = shim::new_buf(ae, (std::size_t)sr * poly), tmp = shim::new_buf(ae, poly);
-        if (sa == 2 && sb == 2) {
-            shim::check(hefx_multiply(ae->ready({}), A, da->p, db->p, prod->p, nullptr));
-        } else {  // c_k = sum_{i+j=k} a_i b_j, polynomial by polynomial (dyadic products in the NTT domain)
-            shim::check(hefx_memset_zero(ae->ready({}), prod->p, (std::size_t)sr * poly * 8, nullptr));
-            for (int i = 0; i < sa; ++i)
-                for (int j = 0; j < sb; ++j) {
-                    shim::check(hefx_multiply_plain(ae->ready({}), A, 1, 1, da->p + i * poly, db->p + j * poly, tmp->p, nullptr));
-                    shim::check(hefx_add(ae->ready({}), A, 1, 1, prod->p + (i + j) * poly, tmp->p, prod->p + (i + j) * poly, nullptr));
-                }
+        if (hefx_bfv *dev = host ? nullptr : ctx_->bfv_device(B)) {
+            auto out = shim::new_buf(eng(), (std::size_t)sr * L * n);
+            (void)eng()->ready({a.buf.get(), b.buf.get()});
+            shim::check(hefx_bfv_multiply(dev, sa, a.buf->p, sb, b.buf->p, out->p, nullptr));
+            dest.set(out, (std::size_t)sr, L, a.parms_id(), a.scale() * b.scale());
+            dest.ntt_form_ = false;
+            return;
         }
-        shim::check(hefx_ntt_inverse(ae->ready({}), prod->p, sr, A, 0, nullptr));
-        const std::vector<std::uint64_t> hp = shim::download(prod);
-        std::vector<std::uint64_t> res((std::size_t)sr * L * n);
-        for (int p = 0; p < sr; ++p)
-            for (std::size_t i = 0; i < n; ++i) {
-                bf::Big x = B.aux.compose(hp.data() + (std::size_t)p * A * n, n, i);
-                const bool neg = bf::cmp(x, B.aux.half) > 0;
-                if (neg) x = bf::sub(B.aux.M, x);
-                bf::Big quo, rem;
-                bf::divrem(bf::mul_small(x, B.t), B.data.M, quo, rem);  // round(t |x| / Q)
-                if (bf::cmp(rem, B.data.half) > 0) quo = bf::add(quo, bf::Big(1));
-                for (int j = 0; j < L; ++j) {
-                    const std::uint64_t q = ctx_->primes()[j], r = bf::mod_small(quo, q);
-                    res[((std::size_t)p * L + j) * n + i] = neg && r ? q - r : r;
-                }
+        const auto &H = ctx_->bfv_host_aux();
+        const int A = (int)H.aux.m.size();
+        auto &ae = H.engine;
+        auto tensor = [&](const std::vector<std::uint64_t> &la, const std::vector<std::uint64_t> *lb) {
+            auto da = shim::upload(ae, la);
+            auto db = lb ? shim::upload(ae, *lb) : da;
+            shim::check(hefx_ntt_forward(ae->ready({}), da->p, sa, A, 0, nullptr));
+            if (db != da) shim::check(hefx_ntt_forward(ae->ready({}), db->p, sb, A, 0, nullptr));
+            const std::size_t poly = (std::size_t)A * n;
+            auto prod = shim::new_buf(ae, (std::size_t)sr * poly), tmp = shim::new_buf(ae, poly);
+            if (sa == 2 && sb == 2) {
+                shim::check(hefx_multiply(ae->ready({}), A, da->p, db->p, prod->p, nullptr));
+            } else {  // c_k = sum_{i+j=k} a_i b_j, polynomial by polynomial (dyadic products in the NTT domain)
+                shim::check(hefx_memset_zero(ae->ready({}), prod->p, (std::size_t)sr * poly * 8, nullptr));
+                for (int i = 0; i < sa; ++i)
+                    for (int j = 0; j < sb; ++j) {
+                        shim::check(hefx_multiply_plain(ae->ready({}), A, 1, 1, da->p + i * poly, db->p + j * poly, tmp->p, nullptr));
+                        shim::check(hefx_add(ae->ready({}), A, 1, 1, prod->p + (i + j) * poly, tmp->p, prod->p + (i + j) * poly, nullptr));
+                    }
             }
+            shim::check(hefx_ntt_inverse(ae->ready({}), prod->p, sr, A, 0, nullptr));
+            return shim::download(prod);
+        };
+        const std::vector<std::uint64_t> ha = shim::download(a.buf);
+        std::vector<std::uint64_t> hb;
+        if (a.buf != b.buf) hb = shim::download(b.buf);
+        const std::vector<std::uint64_t> res = bf::multiply_host(B.data, H.aux, B.t, ha, sa, a.buf != b.buf ? &hb : nullptr, sb, n, tensor);
         dest.set(shim::upload(eng(), res), (std::size_t)sr, L, a.parms_id(), a.scale() * b.scale());
         dest.ntt_form_ = false;
     }

@@ -8,9 +8,10 @@
 //     same hefx_* entry points as CKKS -- a BFV ciphertext is kept in coefficient form, so those calls are bracketed
 //     by hefx_ntt_forward / hefx_ntt_inverse; NTTs are exact and linear, so the residues are the ones a
 //     coefficient-domain implementation produces;
-//   * what is specific to BFV is plain multi-precision integer work on the host: Delta*m scaling, the
-//     round(t*x/Q) of decryption, the noise budget, the tensor product scaled by t/Q (exact integers through an
-//     auxiliary RNS basis on the GPU, CRT-composed here), and BatchEncoder's NTT modulo the plain modulus.
+//   * what is specific to BFV is plain multi-precision integer work on the host: Delta*m scaling,
+//     the noise budget and BatchEncoder's NTT modulo the plain modulus.  The round(t*x/Q) of decryption and the tensor
+//     product scaled by t/Q run on the GPU (include/hefx_bfv.h); their host forms below (multiply_host,
+//     decrypt_round_host) are the fall-back for unsupported shapes and the self-test's comparison.
 // It follows the textbook BFV definition (Fan-Vercauteren with Delta = floor(Q/t)); SEAL's BEHZ RNS variant computes the
 // same rounded quantities up to its documented approximation error in the noise, so decrypted results agree while
 // ciphertext bits need not -- BFV is outside the bit-exact contract.
@@ -172,6 +173,85 @@ struct Basis {
         return x;
     }
 };
+
+// ---- the host path of the two operations that are specific to BFV.  The engine serves both on the device
+// (include/hefx_bfv.h); these remain as the fall-back for the shapes hefx_bfv_create answers HEFX_ERR_UNSUPPORTED to, and
+// as the independent computation drivers/bfv_selftest.cpp compares the device words with.
+// [size][L][n] residues of the data basis -> centred integers -> [size][A][n] residues of the auxiliary basis
+inline std::vector<std::uint64_t> lift_host(const Basis &data, const Basis &aux, const std::vector<std::uint64_t> &h, int sz,
+                                            std::size_t n)
+{
+    const int L = (int)data.m.size(), A = (int)aux.m.size();
+    std::vector<std::uint64_t> out((std::size_t)sz * A * n);
+    for (int p = 0; p < sz; ++p)
+        for (std::size_t i = 0; i < n; ++i) {
+            Big x = data.compose(h.data() + (std::size_t)p * L * n, n, i);
+            const bool neg = cmp(x, data.half) > 0;
+            if (neg) x = sub(data.M, x);
+            for (int j = 0; j < A; ++j) {
+                const std::uint64_t r = mod_small(x, aux.m[j]);
+                out[((std::size_t)p * A + j) * n + i] = neg && r ? aux.m[j] - r : r;
+            }
+        }
+    return out;
+}
+// [sr][A][n] residues of exact integer products in the auxiliary basis -> round(t x / Q) mod every data prime, [sr][L][n]
+inline std::vector<std::uint64_t> scale_round_host(const Basis &data, const Basis &aux, std::uint64_t t,
+                                                   const std::vector<std::uint64_t> &hp, int sr, std::size_t n)
+{
+    const int L = (int)data.m.size(), A = (int)aux.m.size();
+    std::vector<std::uint64_t> res((std::size_t)sr * L * n);
+    for (int p = 0; p < sr; ++p)
+        for (std::size_t i = 0; i < n; ++i) {
+            Big x = aux.compose(hp.data() + (std::size_t)p * A * n, n, i);
+            const bool neg = cmp(x, aux.half) > 0;
+            if (neg) x = sub(aux.M, x);
+            Big quo, rem;
+            divrem(mul_small(x, t), data.M, quo, rem);  // round(t |x| / Q)
+            if (cmp(rem, data.half) > 0) quo = add(quo, Big(1));
+            for (int j = 0; j < L; ++j) {
+                const std::uint64_t q = data.m[j], r = mod_small(quo, q);
+                res[((std::size_t)p * L + j) * n + i] = neg && r ? q - r : r;
+            }
+        }
+    return res;
+}
+// The BFV tensor product scaled by t/Q on the host: a [sa][L][n], b [sb][L][n] (null: a square) -> [sa + sb - 1][L][n].
+// `tensor(la, lb, A)` receives the operands in the auxiliary basis ([sa][A][n], [sb][A][n] or null) and returns the exact
+// products c_k = sum_{i+j=k} a_i b_j, [sa + sb - 1][A][n] in coefficient form (the shim runs it on an engine context over
+// the auxiliary primes).
+template <class Tensor>
+inline std::vector<std::uint64_t> multiply_host(const Basis &data, const Basis &aux, std::uint64_t t,
+                                                const std::vector<std::uint64_t> &a, int sa, const std::vector<std::uint64_t> *b,
+                                                int sb, std::size_t n, Tensor tensor)
+{
+    const std::vector<std::uint64_t> la = lift_host(data, aux, a, sa, n);
+    std::vector<std::uint64_t> lb;
+    if (b) lb = lift_host(data, aux, *b, sb, n);
+    return scale_round_host(data, aux, t, tensor(la, b ? &lb : nullptr), sa + sb - 1, n);
+}
+// x = [c0 + c1 s + ...]_Q as [L][n] residues -> m = round(t x / Q) mod t per coefficient; *worst: the largest distance of
+// t x to a multiple of Q (the invariant noise)
+inline std::vector<std::uint64_t> decrypt_round_host(const Basis &data, std::uint64_t t, const std::vector<std::uint64_t> &x,
+                                                     std::size_t n, Big *worst = nullptr)
+{
+    std::vector<std::uint64_t> out(n, 0);
+    Big w;
+    for (std::size_t i = 0; i < n; ++i) {
+        const Big xi = data.compose(x.data(), n, i);
+        Big quo, rem;
+        divrem(mul_small(xi, t), data.M, quo, rem);
+        std::uint64_t m = mod_small(quo, t);
+        if (cmp(rem, data.half) > 0) {  // round up; the noise is the distance to the next multiple of Q
+            m = (m + 1) % t;
+            rem = sub(data.M, rem);
+        }
+        out[i] = m;
+        if (cmp(rem, w) > 0) w = rem;
+    }
+    if (worst) *worst = w;
+    return out;
+}
 
 // ---- negacyclic NTT modulo the plain modulus t (BatchEncoder); same conventions as the engine's: psi minimal primitive
 // 2N-th root, forward = natural in -> bit-reversed out, out[bitrev(j)] = a(psi^(2j+1))

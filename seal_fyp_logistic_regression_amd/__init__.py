@@ -5,6 +5,6 @@ Layers: csrc/ (gfx950 HIP kernels + C-ABI, include/hefx.h) -> capi.py (ctypes) -
 buffers, one method per ABI call).  There is no CPU fallback anywhere in this package.
 """
 from . import capi  # noqa: F401
-from .engine import DeviceArray, Engine  # noqa: F401
+from .engine import BfvPlan, DeviceArray, Engine  # noqa: F401
 
 __all__ = ["capi", "Engine", "DeviceArray"]

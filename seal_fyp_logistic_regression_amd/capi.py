@@ -139,6 +139,18 @@ REFRESH_SYMBOLS = sorted(_REFRESH_SIGS)
 LIFT_MAX_LIN = 16   # HEFX_LIFT_MAX_LIN
 REFRESH_GROUP = 64  # HEFX_REFRESH_GROUP
 
+# include/hefx_bfv.h: the BFV tensor product scaled by t/Q and the rounding of decryption, exact and on the device
+_BFV_SIGS = {
+    "hefx_bfv_create": (_i, [_vp, _i, _u64, _pp]),
+    "hefx_bfv_destroy": (None, [_vp]),
+    "hefx_bfv_aux_count": (_i, [_vp]),
+    "hefx_bfv_multiply": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "hefx_bfv_decrypt_round": (_i, [_vp, _vp, _vp, _vp]),
+}
+BFV_SYMBOLS = sorted(_BFV_SIGS)
+BFV_MAX_BASIS = 16  # HEFX_BFV_MAX_BASIS
+BFV_SIZE_MAX = 6    # HEFX_BFV_SIZE_MAX
+
 
 def library_path() -> str:
     # HEFX_LIB: development override to A/B alternative builds of the same ABI
@@ -154,7 +166,7 @@ def lib():
     if not os.path.exists(path):
         raise HefxError(f"{path} is missing: build the HIP extension first (__graft_entry__.build())")
     L = C.CDLL(path, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in list(_SIGS.items()) + list(_REFRESH_SIGS.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_REFRESH_SIGS.items()) + list(_BFV_SIGS.items()):
         f = getattr(L, name)
         f.restype = res
         f.argtypes = args

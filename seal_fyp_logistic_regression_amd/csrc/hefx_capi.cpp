@@ -4,6 +4,7 @@
 // compute entry point dispatches HIP kernels from hefx_kernels.hip or fails.
 #include "../../include/hefx.h"
 #include "../../include/hefx_refresh.h"
+#include "../../include/hefx_bfv.h"
 
 #include <chrono>
 #include <cmath>
@@ -3686,4 +3687,214 @@ extern "C" int hefx_refresh_batch(hefx_context *c, int L_in, int size, int L_out
                                  first_stream_id + (uint64_t)i0, s);
         },
         cap);
+}
+
+// ---------------------------------------------------------------------------------------------
+// BFV: tensor product scaled by t/Q and the rounding of decryption (include/hefx_bfv.h, hefx_bfv.hip)
+// ---------------------------------------------------------------------------------------------
+// The object owns a context of its own over the working basis -- the L data primes, then auxiliary primes just below
+// 2^60 -- whose tables serve the lift (launch_lift), the transforms, the tensor product (launch_multiply_sizes) and the
+// Garner digits of the rounding kernel.
+struct hefx_bfv {
+    hefx_context *ctx = nullptr;  // the caller's data context
+    hefx_context *wk = nullptr;   // the working basis: rows 0 .. L-1 the data primes, L .. A-1 auxiliary
+    int L = 0, A = 0, Ad = 0;     // Ad: rows the decryption rounding uses (L + the auxiliary primes that hold 2 t + 2)
+    u64 t = 0;
+    u64 *d_tab = nullptr;   // mul [A] | add of the product [A] | add of the decryption [A] | m_i mod t [A]
+    u64 *d_work = nullptr;  // a [5][A][N] | b [5][A][N] | product [6][A][N]
+    ModConst tmod{};
+    LiftTables lift_mul{}, lift_dec{};
+};
+
+// little-endian big integers on the host, for the sizing rule only
+static void big_mul_small(std::vector<u64> &x, u64 m)
+{
+    u128 carry = 0;
+    for (auto &limb : x) {
+        const u128 v = (u128)limb * m + carry;
+        limb = (u64)v;
+        carry = v >> 64;
+    }
+    if (carry) x.push_back((u64)carry);
+}
+static bool big_greater(std::vector<u64> a, std::vector<u64> b)
+{
+    while (!a.empty() && !a.back()) a.pop_back();
+    while (!b.empty() && !b.back()) b.pop_back();
+    if (a.size() != b.size()) return a.size() > b.size();
+    for (size_t i = a.size(); i-- > 0;)
+        if (a[i] != b[i]) return a[i] > b[i];
+    return false;
+}
+static u64 h_gcd(u64 a, u64 b)
+{
+    while (b) {
+        const u64 r = a % b;
+        a = b;
+        b = r;
+    }
+    return a;
+}
+
+extern "C" int hefx_bfv_create(hefx_context *c, int L, uint64_t t, hefx_bfv **out)
+{
+    if (!out) return fail(HEFX_ERR_INVALID, "null argument");
+    *out = nullptr;
+    CTXCHK(c);
+    if (L < 1 || L > data_primes(c)) return fail(HEFX_ERR_INVALID, "bfv_create: L out of range");
+    if (t < 2 || (t >> 60)) return fail(HEFX_ERR_INVALID, "bfv_create: the plain modulus must be in [2, 2^60)");
+    for (int j = 0; j < L; ++j)
+        if (h_gcd(t, c->primes[(size_t)j]) != 1) return fail(HEFX_ERR_INVALID, "bfv_create: the plain modulus shares a factor with a prime");
+    if (c->logn == 15) return fail(HEFX_ERR_UNSUPPORTED, "bfv is built for poly_degree up to 16384");
+    // v = t (z + N Q^2) + (Q-1)/2 with |z| < 3 N (Q/2)^2 stays below (7/4) t N Q^2 + Q/2, and below M = Q P when
+    // 4 P > 7 t N Q + 2
+    std::vector<u64> need{7};
+    big_mul_small(need, t);
+    big_mul_small(need, c->n);
+    for (int j = 0; j < L; ++j) big_mul_small(need, c->primes[(size_t)j]);
+    {
+        u128 carry = 2;
+        for (auto &limb : need) {
+            carry += limb;
+            limb = (u64)carry;
+            carry >>= 64;
+        }
+        if (carry) need.push_back((u64)carry);
+    }
+    std::vector<u64> basis(c->primes.begin(), c->primes.begin() + L), P4{4};
+    const u64 two_n = 2ull * c->n;
+    for (u64 v = ((u64)1 << 60) - two_n + 1; !big_greater(P4, need); v -= two_n) {
+        if (!h_is_prime(v) || std::find(c->primes.begin(), c->primes.end(), v) != c->primes.end()) continue;
+        if ((int)basis.size() == HEFX_BFV_MAX_BASIS)
+            return fail(HEFX_ERR_UNSUPPORTED, "bfv_create: the product needs a working basis of more than " +
+                                                  std::to_string(HEFX_BFV_MAX_BASIS) + " primes");
+        basis.push_back(v);
+        big_mul_small(P4, v);
+    }
+    const int A = (int)basis.size();
+    hefx_bfv *b = new hefx_bfv();
+    b->ctx = c;
+    b->L = L;
+    b->A = A;
+    b->t = t;
+    if (int rc = hefx_context_create(c->n, reinterpret_cast<const uint64_t *>(basis.data()), A, c->device, &b->wk)) {
+        delete b;
+        return rc;
+    }
+    // decryption: v = t (x^ + Q) + (Q-1)/2 < Q (3 t / 2 + 1); auxiliary primes until their product exceeds 2 t + 2
+    {
+        u128 prod = 1;
+        b->Ad = L;
+        while (prod <= 2 * (u128)t + 2) prod *= basis[(size_t)b->Ad++];  // (the first one already exceeds 2^59; two suffice)
+    }
+    // Barrett constants of t: floor(2^128 / t) exactly, also when t divides 2^128
+    {
+        const u128 ones = ~(u128)0;
+        u128 ratio = ones / t;
+        if (ones % t == t - 1) ++ratio;
+        b->tmod.q = t;
+        b->tmod.r0 = (u64)ratio;
+        b->tmod.r1 = (u64)(ratio >> 64);
+        b->tmod.nq = 0 - t;
+    }
+    std::vector<u64> tab((size_t)4 * A);
+    for (int j = 0; j < A; ++j) {
+        const u64 m = basis[(size_t)j];
+        u64 qm = 1;  // Q mod m
+        for (int i = 0; i < L; ++i) qm = h_mulmod(qm, basis[(size_t)i] % m, m);
+        const u64 tm = t % m, half = h_mulmod((qm + m - 1) % m, (m + 1) / 2, m);  // (Q - 1) / 2 mod m, m odd
+        tab[(size_t)j] = tm;
+        tab[(size_t)A + j] = (h_mulmod(h_mulmod(tm, c->n % m, m), h_mulmod(qm, qm, m), m) + half) % m;
+        tab[(size_t)2 * A + j] = (h_mulmod(tm, qm, m) + half) % m;
+        tab[(size_t)3 * A + j] = m % t;
+    }
+    const size_t N = c->n;
+    hipError_t e = hipMalloc((void **)&b->d_tab, tab.size() * sizeof(u64));
+    if (e == hipSuccess) e = hipMemcpy(b->d_tab, tab.data(), tab.size() * sizeof(u64), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&b->d_work, (size_t)(2 * (HEFX_BFV_SIZE_MAX - 1) + HEFX_BFV_SIZE_MAX) * A * N * sizeof(u64));
+    if (e != hipSuccess) {
+        hefx_bfv_destroy(b);
+        return hipfail(e, "bfv_create");
+    }
+    b->lift_mul = lift_tables(b->wk, L, A);
+    b->lift_dec = lift_tables(b->wk, L, b->Ad);
+    *out = b;
+    return HEFX_OK;
+}
+
+extern "C" void hefx_bfv_destroy(hefx_bfv *b)
+{
+    if (!b) return;
+    if (b->wk) {
+        DevGuard devguard(b->wk->device);
+        (void)hipDeviceSynchronize();
+        if (b->d_tab) (void)hipFree(b->d_tab);
+        if (b->d_work) (void)hipFree(b->d_work);
+        hefx_context_destroy(b->wk);
+    }
+    delete b;
+}
+
+extern "C" int hefx_bfv_aux_count(const hefx_bfv *b) { return b ? b->A - b->L : 0; }
+
+// rows 0 .. L-1 of every polynomial: the caller's words (the centred integer mod a data prime is the residue itself);
+// rows L .. A_out-1: the exact centred lift
+static hipError_t bfv_extend(hefx_bfv *b, const LiftTables &D, int A_out, int size, const u64 *in, u64 *w, hipStream_t s)
+{
+    const size_t row = (size_t)b->ctx->n * sizeof(u64);
+    hipError_t e = hipMemcpy2DAsync(w, row * b->A, in, row * b->L, row * b->L, (size_t)size, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess)
+        e = launch_lift(b->wk->T, D, b->wk->d_qmod, b->L, A_out, size, in, w + (size_t)b->L * b->ctx->n, (size_t)b->A * b->ctx->n, s);
+    return e;
+}
+
+extern "C" int hefx_bfv_multiply(hefx_bfv *b, int sa, const uint64_t *a, int sb, const uint64_t *bb, uint64_t *out,
+                                 void *stream)
+{
+    if (!b) return fail(HEFX_ERR_INVALID, "null bfv object");
+    CTXCHK(b->ctx);
+    if (sa < 2 || sb < 2) return fail(HEFX_ERR_INVALID, "bfv_multiply: every operand needs at least 2 polynomials");
+    if (sa + sb - 1 > HEFX_BFV_SIZE_MAX)
+        return fail(HEFX_ERR_INVALID, "bfv_multiply: the result would have more than HEFX_BFV_SIZE_MAX = " +
+                                          std::to_string(HEFX_BFV_SIZE_MAX) + " polynomials");
+    if (!a || !bb || !out) return fail(HEFX_ERR_INVALID, "null operand");
+    const int L = b->L, A = b->A, sr = sa + sb - 1;
+    const size_t N = b->ctx->n, poly_b = (size_t)L * N * sizeof(u64);
+    if (int rc = check_ranges("bfv_multiply", 1, &out, sr * poly_b, {{&a, 1, sa * poly_b}, {&bb, 1, sb * poly_b}}, {"d_a", "d_b"}))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t wpoly = (size_t)A * N;
+    const bool square = a == bb && sa == sb;
+    u64 *wa = b->d_work, *wb = square ? wa : wa + (HEFX_BFV_SIZE_MAX - 1) * wpoly, *prod = b->d_work + 2 * (HEFX_BFV_SIZE_MAX - 1) * wpoly;
+    const DevTables &T = b->wk->T;
+    HIPCHK(bfv_extend(b, b->lift_mul, A, sa, (const u64 *)a, wa, s));
+    HIPCHK(launch_ntt(T, false, wa, sa, A, 0, s));
+    if (!square) {
+        HIPCHK(bfv_extend(b, b->lift_mul, A, sb, (const u64 *)bb, wb, s));
+        HIPCHK(launch_ntt(T, false, wb, sb, A, 0, s));
+    }
+    if (sa == 2 && sb == 2)
+        HIPCHK(launch_multiply(T, A, wa, wb, prod, s));
+    else
+        HIPCHK(launch_multiply_sizes(T, A, sa, sb, wa, wb, prod, nullptr, 1, s));
+    HIPCHK(launch_ntt(T, true, prod, sr, A, 0, s));
+    BfvRoundTables R{b->d_tab, b->d_tab + A, b->wk->d_qmod, b->tmod};
+    HIPCHK(launch_bfv_round(T, R, A, L, false, sr, prod, wpoly, (u64 *)out, s));
+    return HEFX_OK;
+}
+
+extern "C" int hefx_bfv_decrypt_round(hefx_bfv *b, const uint64_t *x, uint64_t *m, void *stream)
+{
+    if (!b) return fail(HEFX_ERR_INVALID, "null bfv object");
+    CTXCHK(b->ctx);
+    if (!x || !m) return fail(HEFX_ERR_INVALID, "null operand");
+    const int L = b->L, A = b->A;
+    const size_t N = b->ctx->n, row = N * sizeof(u64);
+    if (int rc = check_ranges("bfv_decrypt_round", 1, &m, row, {{&x, 1, row * L}}, {"d_x"})) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    u64 *w = b->d_work;
+    HIPCHK(bfv_extend(b, b->lift_dec, b->Ad, 1, (const u64 *)x, w, s));
+    BfvRoundTables R{b->d_tab, b->d_tab + 2 * (size_t)A, b->d_tab + 3 * (size_t)A, b->tmod};
+    HIPCHK(launch_bfv_round(b->wk->T, R, b->Ad, L, true, 1, w, (size_t)A * N, (u64 *)m, s));
+    return HEFX_OK;
 }

@@ -14,6 +14,7 @@
 // Parity: floating point -- not bit-exact with any other FFT; |coefficient difference| <= 1 against the CPU
 // oracle on a small fraction of coefficients (tested), decode(encode(v)) == v to ~1e-9 at scale 2^40.
 #include "hefx_internal.h"
+#include "hefx_crt.cuh"
 
 namespace hefx {
 
@@ -209,28 +210,7 @@ __global__ __launch_bounds__(256) void ckks_encode_scalar_kernel(DevTables T, co
 // slot i reads A_r at r = (3^i - 1)/2 or the conjugate of its mirror.  The positive-exponent DFT runs through the
 // same DIF passes as encode on conjugated data.
 // ------------------------------------------------------------------------------------------------
-// Garner mixed-radix digits of one coefficient: d_j = ((r_j - d_0) q_0^-1 - d_1) q_1^-1 ... mod q_j, from the residues
-// c[j * n] of rows j < L; x = d_0 + d_1 q_0 + d_2 q_0 q_1 + ... in [0, Q).  Exact modular arithmetic.
-__device__ __forceinline__ void garner_digits(const DevTables &T, int L, const u64 *__restrict__ c, size_t n, u64 *d)
-{
-    for (int j = 0; j < L; ++j) {
-        const ModConst mc = T.mods[j];
-        u64 t = c[(size_t)j * n];
-        for (int i = 0; i < j; ++i) {
-            const u64 di = barrett64(d[i], mc.q, mc.r1);
-            t = mulmod(submod(t, di, mc.q), T.invmod[(size_t)i * T.k + j].x, mc);
-        }
-        d[j] = t;
-    }
-}
-// x > floor(Q/2)?  compare the mixed-radix digits from the top (Q is odd: no tie)
-__device__ __forceinline__ bool above_half(const u64 *d, const u64 *half, int L)
-{
-    for (int j = L - 1; j >= 0; --j)
-        if (d[j] != half[j]) return d[j] > half[j];
-    return false;
-}
-
+// (garner_digits, above_half, horner_digits: hefx_crt.cuh -- shared with the BFV rounding of hefx_bfv.hip)
 __global__ __launch_bounds__(256) void decode_crt_kernel(DevTables T, DecodeTables D, int L, const u64 *__restrict__ coef,
                                                          double inv_scale, double *__restrict__ p)
 {
@@ -282,9 +262,7 @@ __global__ __launch_bounds__(256) void lift_crt_kernel(DevTables T, LiftTables D
     u64 *__restrict__ o = out + item * out_stride + a;
     for (int j = L_in; j < L_out; ++j) {
         const ModConst mc = T.mods[j];
-        u64 acc = barrett64(d[L_in - 1], mc.q, mc.r1);
-        for (int i = L_in - 2; i >= 0; --i)
-            acc = addmod(mulmod(acc, qmod[(size_t)i * T.k + j], mc), barrett64(d[i], mc.q, mc.r1), mc.q);
+        u64 acc = horner_digits(d, L_in, qmod + j, (size_t)T.k, mc);
         if (neg) acc = submod(acc, D.qin[j], mc.q);
         o[(size_t)(j - L_in) * n] = acc;
     }

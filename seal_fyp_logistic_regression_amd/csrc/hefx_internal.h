@@ -195,6 +195,18 @@ struct LiftTables {
 // item i, new row j at out + i * out_stride + (j - L_in) * N; qmod [k][k] = q_i mod q_m (device)
 hipError_t launch_lift(const DevTables &T, const LiftTables &D, const u64 *qmod, int L_in, int L_out, int count,
                        const u64 *coef, u64 *out, size_t out_stride, hipStream_t s);
+// BFV divide-and-round (hefx_bfv.hip, include/hefx_bfv.h) over the first A rows of a working basis whose first L rows are
+// the data primes: row j of the input stands for z mod m_j; v = t (z + K Q) + (Q-1)/2 has the rows  in * mul[j] + add[j],
+// and the result is floor(v / Q) mod every data prime (rad = the context's q_i mod q_m table [k][k]) or, `plain`, mod
+// out.q = t (rad[i] = m_i mod t).  All tables are device memory of the hefx_bfv object.
+struct BfvRoundTables {
+    const u64 *mul, *add;  // [A]
+    const u64 *rad;
+    ModConst out;          // q, r0, r1 of the plain modulus (any t >= 2, not only primes); unused unless `plain`
+};
+// in: npoly polynomials of >= A rows, in_stride words apart, coefficient form; out [npoly][L][N], or `plain` [npoly][N]
+hipError_t launch_bfv_round(const DevTables &T, const BfvRoundTables &R, int A, int L, bool plain, int npoly, const u64 *in,
+                            size_t in_stride, u64 *out, hipStream_t s);
 // plaintext i = round(vals[i] * scale) in every word of its rows ([count][L][N])
 hipError_t launch_encode_scalar(const DevTables &T, const double *vals, int count, double scale, int L, u64 *out,
                                 hipStream_t s);

@@ -694,3 +694,41 @@ class Engine:
                 break
             names.append(nm)
         return {nm: float(ms[k]) for k, nm in enumerate(names)}, int(n.value)
+
+
+class BfvPlan:
+    """The BFV entries of include/hefx_bfv.h for one (engine, L, t): the tensor product scaled by t/Q and the rounding of
+    decryption, exact, on device buffers in COEFFICIENT form.  Owns the working basis and scratch (hefx_bfv); calls of one
+    plan must be ordered on the device, two plans may run on two streams at once."""
+
+    def __init__(self, engine: Engine, L: int, t: int):
+        self.engine, self.L, self.t = engine, int(L), int(t)
+        self._h = None
+        h = C.c_void_p()
+        capi.check(capi.lib().hefx_bfv_create(engine._h, self.L, self.t, C.byref(h)))
+        self._h = h.value
+        self.aux = int(capi.lib().hefx_bfv_aux_count(self._h))
+
+    def close(self):
+        if self._h and self.engine._h:
+            capi.lib().hefx_bfv_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def multiply(self, a: DeviceArray, b: DeviceArray, out: Optional[DeviceArray] = None, stream=None) -> DeviceArray:
+        """a [sa][L][N] x b [sb][L][N] -> [sa + sb - 1][L][N], out[k] = round(t c_k / Q) mod every prime; b may be a"""
+        sa, sb = a.shape[0], b.shape[0]
+        out = out if out is not None else DeviceArray(self.engine, (sa + sb - 1, self.L, self.engine.N))
+        capi.check(capi.lib().hefx_bfv_multiply(self._h, sa, a.ptr, sb, b.ptr, out.ptr, stream))
+        return out
+
+    def decrypt_round(self, x: DeviceArray, out: Optional[DeviceArray] = None, stream=None) -> DeviceArray:
+        """x [L][N] -> m [N], m = round(t x^ / Q) mod t"""
+        out = out if out is not None else DeviceArray(self.engine, (self.engine.N,))
+        capi.check(capi.lib().hefx_bfv_decrypt_round(self._h, x.ptr, out.ptr, stream))
+        return out

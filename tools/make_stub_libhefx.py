@@ -1,5 +1,5 @@
 """Host-side profiling of the C++ shim WITHOUT a GPU: builds build/stub/libhefx.so, a stand-in whose every C-ABI entry
-(parsed from include/hefx.h) returns HEFX_OK at once (hefx_malloc hands out 64 host bytes, hefx_download fills ones), and
+(parsed from include/hefx.h and include/hefx_bfv.h) returns HEFX_OK at once (hefx_malloc hands out 64 host bytes, hefx_download fills ones), and
 build/stub/probe = drivers/lt_host_probe.cpp linked against it.  What remains when it runs is the recorder's own work:
     python tools/make_stub_libhefx.py && build/stub/probe 1000 30
     (add -pg by hand and run gprof for a profile; this is how recording a rotation went from 3.7 to 0.4 us in round 4)
@@ -9,10 +9,14 @@ import os, re, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def prototypes():
-    """every prototype of include/hefx.h: [(full text without the semicolon, name, parameter text)], in header order
-    (tools/make_symbolic_libhefx.py generates its loud fall-backs from the same list)"""
-    h = open(os.path.join(root, "include", "hefx.h")).read()
+# the headers include/seal/seal.h itself includes: a stand-in for the engine has to define what the shim names
+SHIM_HEADERS = ("hefx.h", "hefx_bfv.h")
+
+
+def prototypes(headers=SHIM_HEADERS):
+    """every prototype of include/hefx.h and include/hefx_bfv.h: [(full text without the semicolon, name, parameter
+    text)], in header order (tools/make_symbolic_libhefx.py generates its loud fall-backs from the same list)"""
+    h = "\n".join(open(os.path.join(root, "include", name)).read() for name in headers)
     h = re.sub(r"/\*.*?\*/", "", h, flags=re.S)
     h = re.sub(r"//.*", "", h)
     protos = re.findall(r"\n\s*((?:const\s+)?[A-Za-z_][A-Za-z0-9_ \*]*?\b(hefx_[a-z0-9_]+)\s*\(([^;{]*?)\))\s*;", h, flags=re.S)
@@ -27,7 +31,7 @@ def prototypes():
 def main():
     out = os.path.join(root, "build", "stub")
     os.makedirs(out, exist_ok=True)
-    src = ['#include "hefx.h"', "#include <cstdlib>", "#include <cstring>", 'extern "C" {']
+    src = [f'#include "{name}"' for name in SHIM_HEADERS] + ["#include <cstdlib>", "#include <cstring>", 'extern "C" {']
     special = {
         "hefx_malloc": "*d_ptr = std::calloc(1, 64); return 0;",
         "hefx_free": "std::free(d_ptr); return 0;",

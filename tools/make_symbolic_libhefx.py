@@ -1,6 +1,7 @@
 """Builds the fuzz of the C++ shim's recorder WITHOUT a GPU (tests/test_shim_fuzz_cpu.py):
     build/symbolic/libhefx.so   drivers/hefx_symbolic.cpp -- the symbolic stand-in for the engine -- plus one generated
-                                fall-back per prototype of include/hefx.h that it does not define: the fall-back fails by name
+                                fall-back per prototype of include/hefx.h and include/hefx_bfv.h (what seal.h names) that it does
+                                not define -- the BFV entries among them, fuzz programs are CKKS: the fall-back fails by name
                                 (nothing succeeds silently)
     build/symbolic/shim_fuzz    drivers/shim_fuzz.cpp linked against it
     python tools/make_symbolic_libhefx.py [--sanitize] && build/symbolic/shim_fuzz --seed 7 --dump
@@ -10,7 +11,7 @@ import os, re, subprocess, sys
 
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(root, "tools"))
-from make_stub_libhefx import prototypes  # noqa: E402
+from make_stub_libhefx import SHIM_HEADERS, prototypes  # noqa: E402
 
 
 def main():
@@ -20,7 +21,7 @@ def main():
     sym = os.path.join(root, "drivers", "hefx_symbolic.cpp")
     # its definitions start a line with the return type (the file's own helpers carry no hefx_ prefix)
     defined = set(re.findall(r"^(?:int|void|const char \*|uint32_t|uint64_t) ?(hefx_[a-z0-9_]+)\(", open(sym).read(), flags=re.M))
-    src = ['#include "hefx.h"', "#include <cstdio>", "#include <cstdlib>", 'extern "C" {']
+    src = [f'#include "{name}"' for name in SHIM_HEADERS] + ["#include <cstdio>", "#include <cstdlib>", 'extern "C" {']
     missing = []
     for full, name, _ in prototypes():
         if name in defined:
