@@ -249,7 +249,10 @@ int hefx_multiply_sizes_batch(hefx_context *ctx, int L, int n, int size_a, const
 /* ---- K5/K6/K7: Evaluator::apply_galois_inplace = Galois permutation + key switch (one term of
  *      rotate_vector; helper.h:216,227,244,255,316,352,455,474; 5_rotation.cpp:215).
  *      d_key is the Galois key of `galois_elt` (the shim picks it: GaloisKeys index (elt-1)/2).
- *      in and out may alias (rotate_vector_inplace). */
+ *      in and out may alias EXACTLY, d_ct_out == d_ct_in (rotate_vector_inplace: served in place).  Any other byte shared by
+ *      the output and the input -- views of one allocation that overlap in part -- is refused with HEFX_ERR_INVALID before
+ *      anything is submitted, like in the batches below (until this was checked for one item too, such a call returned
+ *      wrong words). */
 int hefx_apply_galois(hefx_context *ctx, int L, const uint64_t *d_ct_in, uint32_t galois_elt,
                       const uint64_t *d_key, uint64_t *d_ct_out, void *stream);
 /* n independent (ciphertext, element, key) triples in one launch sequence.  "Independent" is meant: no item may read

@@ -28,6 +28,7 @@
 
 using namespace hefx;
 typedef unsigned __int128 u128;
+#pragma clang diagnostic ignored "-Wc++20-designator"  // KsRequest's call sites name the fields they set
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg)
@@ -43,17 +44,38 @@ static int hipfail(hipError_t e, const char *what)
 // The aliasing rule of include/hefx.h (stated per entry there, as a table in INTEGRATION.md), applied before anything is
 // submitted: n outputs of out_b bytes against the call's input lists (hefx_ranges.h).  `names` are the arguments the lists
 // came from, for the message.  Engine-internal calls on disjoint workspace skip it (the `trusted` arguments below).
+// texts (optional): the entry's own words for "two outputs overlap" and "an output overlaps an input".
 static int check_ranges(const char *entry, size_t n, uint64_t *const *outs, size_t out_b,
-                        std::initializer_list<hefx_ranges::In> ins, std::initializer_list<const char *> names)
+                        std::initializer_list<hefx_ranges::In> ins, std::initializer_list<const char *> names,
+                        const char *outputs_text = nullptr, const char *input_text = nullptr)
 {
     std::pair<size_t, size_t> which{0, 0};
     const hefx_ranges::Verdict v = hefx_ranges::check(n, outs, out_b, ins, &which);
     if (v == hefx_ranges::FINE) return HEFX_OK;
-    std::string msg = std::string(entry) + ": " + hefx_ranges::text(v);
+    const char *own = v == hefx_ranges::OUTPUTS_OVERLAP ? outputs_text : input_text;
+    std::string msg = std::string(entry) + ": " + (own ? own : hefx_ranges::text(v));
     if (v == hefx_ranges::OUTPUT_OVERLAPS_INPUT && which.first < names.size())
         msg += std::string(" (") + names.begin()[which.first] + ", entry " + std::to_string(which.second) + ")";
     return fail(HEFX_ERR_INVALID, msg);
 }
+// HEFX_DEBUG: the host time since the previous lap on stderr, one line per phase of a call
+struct Lap {
+    std::string who;
+    bool ms = false;
+    const bool on = getenv("HEFX_DEBUG") != nullptr;
+    std::chrono::steady_clock::time_point t_last = std::chrono::steady_clock::now();
+    void operator()(const char *what)
+    {
+        if (!on) return;
+        const auto now = std::chrono::steady_clock::now();
+        const double us = std::chrono::duration<double, std::micro>(now - t_last).count();
+        if (ms)
+            fprintf(stderr, "[hefx] %s: %-44s %7.2f ms\n", who.c_str(), what, us / 1000);
+        else
+            fprintf(stderr, "[hefx] %s: %-36s %7.1f us\n", who.c_str(), what, us);
+        t_last = now;
+    }
+};
 #define HIPCHK(expr)                                  \
     do {                                              \
         hipError_t _e = (expr);                       \
@@ -330,14 +352,7 @@ extern "C" int hefx_context_create(uint32_t poly_degree, const uint64_t *primes,
     }
 
     // HEFX_DEBUG=1: where context creation spends its time (stderr), for tools/first_call_costs2.py
-    const bool dbg = getenv("HEFX_DEBUG") != nullptr;
-    auto t_last = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!dbg) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[hefx] context_create: %-44s %7.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-        t_last = now;
-    };
+    Lap lap{"context_create", true};
     lap("device selection (HIP runtime start-up)");
     hefx_context *c = new hefx_context();
     c->device = device;
@@ -1220,22 +1235,10 @@ extern "C" int hefx_multiply_sum(hefx_context *c, int L, int n, int group, const
     // The groups of one launch run side by side and a lane writes its words of a sum after reading every term, so no
     // output may reach into an input (of any group) or into another output.  Checked on BYTE RANGES, like the key-switch
     // batches (callers hand out views of one allocation), before anything is submitted.
-    {
-        const size_t row = (size_t)c->n * sizeof(u64), out_b = 3 * (size_t)L * row, in_b = 2 * (size_t)L * row;
-        std::vector<uintptr_t> o((size_t)groups);
-        for (int g = 0; g < groups; ++g) o[(size_t)g] = (uintptr_t)outs[g];
-        std::sort(o.begin(), o.end());
-        for (int g = 1; g < groups; ++g)
-            if (o[(size_t)g - 1] + out_b > o[(size_t)g]) return fail(HEFX_ERR_INVALID, "multiply_sum: two outputs overlap");
-        auto hits = [&](const void *p) {
-            const uintptr_t x = (uintptr_t)p;
-            auto it = std::upper_bound(o.begin(), o.end(), x);
-            if (it != o.begin() && *(it - 1) + out_b > x) return true;
-            return it != o.end() && *it < x + in_b;
-        };
-        for (int i = 0; i < n; ++i)
-            if (hits(a[i]) || hits(b[i])) return fail(HEFX_ERR_INVALID, "multiply_sum: an output overlaps an input");
-    }
+    const size_t poly_b = (size_t)L * c->n * sizeof(u64);
+    if (int rc = check_ranges("multiply_sum", (size_t)groups, outs, 3 * poly_b, {{a, (size_t)n, 2 * poly_b}, {b, (size_t)n, 2 * poly_b}},
+                              {"d_a", "d_b"}))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
     constexpr int TABLE_MAX = (int)(sizeof(KsItem) * KS_MAX_CHUNK / sizeof(void *));
     // A group longer than one table slice (2 * group + 1 pointers): slice-sized parts' sums land in scratch and
@@ -1360,6 +1363,72 @@ static size_t ks_words_per_item(const hefx_context *c, int L)
     return (size_t)c->n * ((size_t)L + 2 * (size_t)(L + 1) + 2);
 }
 static size_t ks_x_words(const hefx_context *c, int L, int items) { return (size_t)c->n * items * L * (L + 1); }
+// THE scratch layout of one chunk of `cnt` items (ks_run, the lanes of hefx_rotate_add_chain and of run_forest, lt2_impl):
+// d, acc, u, x back to back from `base`, then the scratch copies of in-place rotations (alias), which only ks_run uses and
+// only a chunk that has any needs room for.  qmod and the gate fields are the caller's to set.
+static size_t ks_chunk_words(const hefx_context *c, int L, int cnt, bool with_alias)
+{
+    return ks_words_per_item(c, L) * (size_t)cnt + ks_x_words(c, L, cnt) + (with_alias ? (size_t)cnt * 2 * L * c->n : 0);
+}
+static KsScratch ks_scratch_at(const hefx_context *c, int L, int cnt, u64 *base)
+{
+    const size_t N = c->n;
+    KsScratch S{};
+    S.d = base;
+    S.acc = S.d + (size_t)cnt * L * N;
+    S.u = S.acc + (size_t)cnt * 2 * (L + 1) * N;
+    S.x = S.u + (size_t)cnt * 2 * N;
+    S.alias = S.x + ks_x_words(c, L, cnt);
+    return S;
+}
+// items per chunk (one launch sequence): the context's setting, or auto: about 1 GiB of scratch per in-flight chunk,
+// multiple of 8, at most KS_AUTO_CHUNK
+static int ks_auto_chunk(const hefx_context *c, int L)
+{
+    if (c->chunk > 0) return c->chunk;
+    const int chunk = (int)(((size_t)1 << 30) / (ks_words_per_item(c, L) * sizeof(u64)));
+    // ... and at most 256 items from N = 16384 on (2 workgroups per CU x 256 CUs: 256 items fill the chip in whole rounds
+    // in every launch; 384 / 512 measure the same at C3 and C5 and 3 % less at C4), 512 below (N = 8192: three or four
+    // 256-thread workgroups per CU, and five launches of ~60 us each per 256 items are mostly ramp and tail: 788 k ->
+    // 921 k ops/s at C2 with 512, 904 k / 910 k with 768 / 1024; profiles/r04/chunk_size_by_ring.txt)
+    const int cap = c->logn <= 13 ? 2 * KS_AUTO_CHUNK : KS_AUTO_CHUNK;
+    return chunk > cap ? cap : (chunk < 16 ? 16 : chunk & ~7);
+}
+// one item's descriptor: not hoisted, not in place (ks_run sets dsrc / flipw / KS_ALIASED where they apply)
+static void ks_fill_item(KsItem &it, const uint64_t *c_in, uint64_t *c_out, const uint64_t *pt, const uint64_t *key,
+                         const uint32_t *perm, uint32_t elt, const uint64_t *acc_in, uint64_t *acc_out)
+{
+    it.c_in = (const u64 *)c_in;
+    it.c_out = (u64 *)c_out;
+    it.pt = (const u64 *)pt;
+    it.key = (const u64 *)key;
+    it.perm = perm;
+    it.elt = elt;
+    it.flags = 0;
+    it.acc_in = (const u64 *)acc_in;
+    it.acc_out = (u64 *)acc_out;
+    it.dsrc = it.pad_ = 0;
+    it.flipw = nullptr;
+}
+// The caller's stream forked onto the first k internal streams and joined again (the chunk pipeline of ks_run, the lanes of
+// run_forest and of hefx_rotate_add_chain).  Whoever forked joins on every path, errors included, so that whatever was
+// launched stays ordered before the caller's next work; the join's error counts only if nothing failed before it.
+static hipError_t ks_fork(hefx_context *c, hipStream_t user, int k)
+{
+    hipError_t e = k > 0 ? hipEventRecord(c->ev_fork, user) : hipSuccess;
+    for (int s = 0; s < k && e == hipSuccess; ++s) e = hipStreamWaitEvent(c->streams[s], c->ev_fork, 0);
+    return e;
+}
+static hipError_t ks_join(hefx_context *c, hipStream_t user, int k)
+{
+    hipError_t first = hipSuccess;
+    for (int s = 0; s < k; ++s) {
+        hipError_t e = hipEventRecord(c->ev_join[s], c->streams[s]);
+        if (e == hipSuccess) e = hipStreamWaitEvent(user, c->ev_join[s], 0);
+        if (first == hipSuccess) first = e;
+    }
+    return first;
+}
 
 // Workgroup shapes of a SMALL chunk (descriptors in the kernel arguments, one launch sequence; KS_Q_* mask).
 // Pair path (round 5, ks_pair_*): four launches with two transform phases instead of five with four -- taken while its
@@ -1391,18 +1460,36 @@ static int ks_small_shape(int n, int L)
 // Chunks of a batch alternate between two internal streams (each with its own scratch half) so that the
 // small tail launches of one chunk (2 workgroups per item in the mod-down INTT) overlap the wide launches of
 // the next; the caller's stream is forked before and joined after.
-// acc_in / acc_out (both or neither; rotations without a fused plaintext only): acc_out[i] = acc_in[i] + ct_out[i]
-// trusted (engine-internal callers whose inputs and outputs are engine-owned workspace, disjoint by construction --
-// hefx_linear_transform_plain's node buffers): the O(n log n) byte-range independence check is skipped (40 us of host time
-// in front of the first launch of a 511-rotation batch)
-static int ks_run(hefx_context *c, int L, int n, bool relin, const uint64_t *const *ct_in, const uint32_t *elts,
-                  const uint64_t *const *keys, const uint64_t *single_key, const uint64_t *const *pts,
-                  uint64_t *const *ct_out, void *stream, bool hoist = false, const uint64_t *const *acc_in = nullptr,
-                  uint64_t *const *acc_out = nullptr, bool trusted = false, size_t scratch_off = 0)
+struct KsRequest {
+    int n = 0;
+    bool relin = false;                          // relinearisation with single_key; else rotations by elts[i] with keys[i]
+    const uint64_t *const *ct_in = nullptr;
+    const uint32_t *elts = nullptr;
+    const uint64_t *const *keys = nullptr;
+    const uint64_t *single_key = nullptr;
+    const uint64_t *const *pts = nullptr;        // fused plaintexts; a null entry is a plain rotation
+    uint64_t *const *ct_out = nullptr;
+    // acc_in / acc_out (both or neither; rotations without a fused plaintext only): acc_out[i] = acc_in[i] + ct_out[i]
+    const uint64_t *const *acc_in = nullptr;
+    uint64_t *const *acc_out = nullptr;
+    bool hoist = false;                          // hefx_*_hoisted: one shared source, see below
+    // trusted (engine-internal callers whose inputs and outputs are engine-owned workspace, disjoint by construction --
+    // hefx_linear_transform_plain's node buffers): the O(n log n) byte-range independence check is skipped (40 us of host
+    // time in front of the first launch of a 511-rotation batch)
+    bool trusted = false;
+    // scratch_off (words; engine-internal, hefx_linear_transform_plain's second lane): this call's scratch starts there, so
+    // that it may run on another stream beside a call that uses the front of the buffer.  One chunk only (the chunk
+    // pipeline's internal streams and scratch halves are one set per context), and the caller has sized the buffer for both.
+    size_t scratch_off = 0;
+};
+static int ks_run(hefx_context *c, int L, const KsRequest &rq, void *stream)
 {
-    // scratch_off (words; engine-internal, hefx_linear_transform_plain's second lane): this call's scratch starts there, so that
-    // it may run on another stream beside a call that uses the front of the buffer.  One chunk only (the chunk pipeline's
-    // internal streams and scratch halves are one set per context), and the caller has sized the buffer for both.
+    const int n = rq.n;
+    const bool relin = rq.relin, hoist = rq.hoist;
+    const uint64_t *const *const ct_in = rq.ct_in, *const *const keys = rq.keys, *const *const pts = rq.pts, *const *const acc_in = rq.acc_in;
+    uint64_t *const *const ct_out = rq.ct_out, *const *const acc_out = rq.acc_out;
+    const uint32_t *const elts = rq.elts;
+    const size_t scratch_off = rq.scratch_off;
     CTXCHK(c);
     static const bool ksdbg = getenv("HEFX_DEBUG") && atoi(getenv("HEFX_DEBUG")) >= 2;  // host time of the call's phases
     const auto ks_t0 = std::chrono::steady_clock::now();
@@ -1411,20 +1498,10 @@ static int ks_run(hefx_context *c, int L, int n, bool relin, const uint64_t *con
     if (int rc = check_ks_level(c, L)) return rc;
     if (n < 1 || !ct_in || !ct_out) return fail(HEFX_ERR_INVALID, "bad key-switch batch arguments");
     if (!relin && (!elts || !keys)) return fail(HEFX_ERR_INVALID, "missing Galois elements / keys");
-    if (relin && !single_key) return fail(HEFX_ERR_INVALID, "missing relinearization key");
+    if (relin && !rq.single_key) return fail(HEFX_ERR_INVALID, "missing relinearization key");
     if ((acc_in != nullptr) != (acc_out != nullptr) || (acc_out && (relin || pts || hoist)))
         return fail(HEFX_ERR_INVALID, "accumulate: rotations only, input and output sums together, no fused plaintext");
-    const size_t per = ks_words_per_item(c, L);
-    int chunk = c->chunk;
-    if (chunk <= 0) {  // auto: about 1 GiB of scratch per in-flight chunk, multiple of 8, at most KS_AUTO_CHUNK
-        chunk = (int)(((size_t)1 << 30) / (per * sizeof(u64)));
-        // ... and at most 256 items from N = 16384 on (2 workgroups per CU x 256 CUs: 256 items fill the chip in whole rounds
-        // in every launch; 384 / 512 measure the same at C3 and C5 and 3 % less at C4), 512 below (N = 8192: three or four
-        // 256-thread workgroups per CU, and five launches of ~60 us each per 256 items are mostly ramp and tail: 788 k ->
-        // 921 k ops/s at C2 with 512, 904 k / 910 k with 768 / 1024; profiles/r04/chunk_size_by_ring.txt)
-        const int cap = c->logn <= 13 ? 2 * KS_AUTO_CHUNK : KS_AUTO_CHUNK;
-        chunk = chunk > cap ? cap : (chunk < 16 ? 16 : chunk & ~7);
-    }
+    const int chunk = ks_auto_chunk(c, L);
     const int nchunks = (n + chunk - 1) / chunk;
     const bool two = nchunks > 1 && c->use_streams && !c->profiling;
     // hoisting asked for explicitly (hefx_*_hoisted): every item rotates the same source, which no item may overwrite.
@@ -1436,7 +1513,7 @@ static int ks_run(hefx_context *c, int L, int n, bool relin, const uint64_t *con
         if (relin) return fail(HEFX_ERR_INVALID, "hoisting applies to rotations only");
         for (int i = 0; i < n; ++i)
             if (ct_in[i] != ct_in[0] || ct_out[i] == ct_in[0])
-                return fail(HEFX_ERR_INVALID, "hoisted batch: one shared source, never overwritten");
+                return fail(HEFX_ERR_INVALID, "hoisted batch: one shared source, which no output may alias");
     }
     // Validate the WHOLE batch and resolve every gather table before anything is submitted: an argument error must
     // leave no chunk in flight, no forked stream unjoined and no ring slot marked busy.
@@ -1451,67 +1528,24 @@ static int ks_run(hefx_context *c, int L, int n, bool relin, const uint64_t *con
             if (int rc = get_perm(c, elts[i], &perms[i])) return rc;
             any_alias |= ct_in[i] == ct_out[i];
         }
+        if (acc_out && (!acc_in[i] || !acc_out[i])) return fail(HEFX_ERR_INVALID, "null accumulator pointer in batch");
     }
     // Items run in key-grouped order on several internal streams, so no item may read another item's output: a
     // dependent chain handed over as ONE batch would silently give wrong bits.  Refused here, before anything is
-    // submitted, on BYTE RANGES (callers hand out views of one allocation: big.view(...) slices): no two outputs may
-    // overlap, and no input or plaintext may overlap another item's output -- nor its own, except the exact in-place
-    // rotation c_in == c_out, which the kernels serve from a scratch copy.  O(n log n) on the host.
-    if (!trusted && (n > 1 || pts || acc_out || relin)) {  // (a lone relinearisation too: its three input polys against its two output polys)
-        const size_t row = (size_t)c->n * sizeof(u64);
-        const size_t out_b = 2 * (size_t)L * row, in_b = (relin ? 3 : 2) * (size_t)L * row, pt_b = (size_t)L * row;
-        std::vector<std::pair<uintptr_t, int>> outs((size_t)n);
-        for (int i = 0; i < n; ++i) outs[(size_t)i] = {(uintptr_t)ct_out[i], i};
-        std::sort(outs.begin(), outs.end());
-        for (int i = 1; i < n; ++i)
-            if (outs[(size_t)i - 1].first + out_b > outs[(size_t)i].first)
-                return fail(HEFX_ERR_INVALID, "two items of a key-switch batch write overlapping outputs");
-        // the output (if any) whose range meets [p, p + bytes): outputs are disjoint, so at most two candidates
-        auto hits = [&](const void *p, size_t bytes, int self, bool inplace_ok) -> bool {
-            const uintptr_t a = (uintptr_t)p;
-            auto it = std::upper_bound(outs.begin(), outs.end(), std::make_pair(a, n));
-            for (int step = 0; step < 2; ++step) {
-                if (step == 0) {
-                    if (it == outs.begin()) continue;
-                    const auto &o = *(it - 1);  // starts at or before a
-                    if (o.first + out_b > a && !(inplace_ok && o.second == self && o.first == a)) return true;
-                } else if (it != outs.end() && it->first < a + bytes)  // starts inside the range
-                    return true;
-            }
-            return false;
-        };
-        for (int j = 0; j < n; ++j) {
-            if (hits(ct_in[j], in_b, j, !relin))
-                return fail(HEFX_ERR_INVALID, "key-switch batch items must be independent: one item's input overlaps an item's output");
-            if (pts && pts[j] && hits(pts[j], pt_b, j, false))
-                return fail(HEFX_ERR_INVALID, "key-switch batch items must be independent: a plaintext overlaps an item's output");
-            if (acc_out && (hits(acc_in[j], out_b, -1, false) || hits(acc_out[j], out_b, -1, false)))
-                return fail(HEFX_ERR_INVALID, "accumulate: a sum overlaps a rotation output of the batch");
-        }
-    }
-    if (acc_out) {  // the sums: pairwise disjoint, none overlapping any input; acc_in[i] == acc_out[i] (in place) is fine
-        const size_t out_b = 2 * (size_t)L * (size_t)c->n * sizeof(u64);
-        std::vector<std::pair<uintptr_t, int>> sums((size_t)n);
-        for (int i = 0; i < n; ++i) {
-            if (!acc_in[i] || !acc_out[i]) return fail(HEFX_ERR_INVALID, "null accumulator pointer in batch");
-            sums[(size_t)i] = {(uintptr_t)acc_out[i], i};
-        }
-        std::sort(sums.begin(), sums.end());
-        for (int i = 1; i < n; ++i)
-            if (sums[(size_t)i - 1].first + out_b > sums[(size_t)i].first)
-                return fail(HEFX_ERR_INVALID, "accumulate: two items write overlapping sums");
-        auto meets = [&](const void *p, int self, bool same_ok) {
-            const uintptr_t a = (uintptr_t)p;
-            auto it = std::upper_bound(sums.begin(), sums.end(), std::make_pair(a, n));
-            if (it != sums.begin()) {
-                const auto &o = *(it - 1);
-                if (o.first + out_b > a && !(same_ok && o.second == self && o.first == a)) return true;
-            }
-            return it != sums.end() && it->first < a + out_b;
-        };
-        for (int j = 0; j < n; ++j)
-            if (meets(ct_in[j], j, false) || meets(acc_in[j], j, true))
-                return fail(HEFX_ERR_INVALID, "accumulate: an input overlaps another item's sum");
+    // submitted, on BYTE RANGES (callers hand out views of one allocation: big.view(...) slices), whatever n is: no two
+    // outputs -- the rotations and, behind them, the sums -- may overlap, and no input, plaintext or input sum may overlap
+    // an output, except the exact in-place forms: the rotation c_in == c_out, which the kernels serve from a scratch copy
+    // (a relinearisation has none: its three input polys against its two output polys), and acc_in[i] == acc_out[i].
+    // O(n log n) on the host.
+    if (!rq.trusted) {
+        const size_t poly_b = (size_t)L * c->n * sizeof(u64), nn = (size_t)n;
+        std::vector<uint64_t *> outs(ct_out, ct_out + n);
+        if (acc_out) outs.insert(outs.end(), acc_out, acc_out + n);
+        if (int rc = check_ranges("key-switch batch", outs.size(), outs.data(), 2 * poly_b,
+                                  {{ct_in, nn, (relin ? 3 : 2) * poly_b, !relin, 1, 0}, {pts, pts ? nn : 0, poly_b}, {acc_in, acc_in ? nn : 0, 2 * poly_b, true, 1, nn}},
+                                  {"d_ct_in", "d_pts", "d_acc_in"}, "two items write overlapping outputs",
+                                  "items must be independent: an input overlaps an item's output"))
+            return rc;
     }
     t_valid = ks_us();
     // The items of a batch are independent, so they are PROCESSED grouped by key (stable order inside a group): items
@@ -1558,21 +1592,17 @@ static int ks_run(hefx_context *c, int L, int n, bool relin, const uint64_t *con
         if (int rc = ensure_flipw(c, elts, n, (hipStream_t)stream, flips)) return rc;
         if (flips.empty()) share = false;  // the tables' memory budget is spent
     }
-    const size_t half_words = per * (size_t)cmax + ks_x_words(c, L, cmax) + (any_alias ? (size_t)cmax * 2 * L * c->n : 0);
+    const size_t half_words = ks_chunk_words(c, L, cmax, any_alias);
     t_tables = ks_us();
     if (scratch_off && (two || c->scratch_words < scratch_off + half_words))
         return fail(HEFX_ERR_INVALID, "internal: a laned key-switch batch must be one chunk inside the pre-sized scratch");
     if (int rc = ensure_scratch(c, scratch_off + half_words * (size_t)ns)) return rc;
     hipStream_t user = (hipStream_t)stream;
-    if (two) {
-        HIPCHK(hipEventRecord(c->ev_fork, user));
-        for (int s = 0; s < ns; ++s) HIPCHK(hipStreamWaitEvent(c->streams[s], c->ev_fork, 0));
-    }
     const size_t N = c->n;
     // from here on only HIP runtime failures can occur; they stop the submission, and the internal streams are still
     // joined to the caller's stream below so that whatever was launched stays ordered before the caller's next work
-    hipError_t herr = hipSuccess;
-    const char *hwhat = "";
+    hipError_t herr = ks_fork(c, user, two ? ns : 0);
+    const char *hwhat = "fork onto the internal streams";
 #define KS_TRY(expr)                       \
     if (herr == hipSuccess) {              \
         herr = (expr);                     \
@@ -1588,12 +1618,7 @@ static int ks_run(hefx_context *c, int L, int n, bool relin, const uint64_t *con
             c->ring_busy[slot] = false;
         }
         KsItem *hb = c->h_items + (size_t)slot * KS_MAX_CHUNK, *db = c->d_items + (size_t)slot * KS_MAX_CHUNK;
-        KsScratch S{};
-        S.d = c->scratch + scratch_off + (two ? (size_t)(ci % ns) * half_words : 0);
-        S.acc = S.d + (size_t)cnt * L * N;
-        S.u = S.acc + (size_t)cnt * 2 * (L + 1) * N;
-        S.x = S.u + (size_t)cnt * 2 * N;
-        S.alias = S.x + ks_x_words(c, L, cnt);
+        KsScratch S = ks_scratch_at(c, L, cnt, c->scratch + scratch_off + (two ? (size_t)(ci % ns) * half_words : 0));
         S.qmod = c->d_qmod;
         S.gate = c->d_gate + slot;
         S.gate_hits = c->d_gate + KS_RING;
@@ -1614,17 +1639,8 @@ static int ks_run(hefx_context *c, int L, int n, bool relin, const uint64_t *con
         for (int i = 0; i < cnt; ++i) {
             KsItem &it = hb[i];
             const int j = src(base + i);
-            it.c_in = (const u64 *)ct_in[j];
-            it.c_out = (u64 *)ct_out[j];
-            it.pt = pts ? (const u64 *)pts[j] : nullptr;
-            it.key = relin ? (const u64 *)single_key : (const u64 *)keys[j];
-            it.perm = relin ? nullptr : perms[j];
-            it.elt = relin ? 1u : elts[j];
-            it.flags = 0;
-            it.acc_in = acc_out ? (const u64 *)acc_in[j] : nullptr;
-            it.acc_out = acc_out ? (u64 *)acc_out[j] : nullptr;
-            it.dsrc = it.pad_ = 0;
-            it.flipw = nullptr;
+            ks_fill_item(it, ct_in[j], ct_out[j], pts ? pts[j] : nullptr, relin ? rq.single_key : keys[j], relin ? nullptr : perms[j],
+                         relin ? 1u : elts[j], acc_out ? acc_in[j] : nullptr, acc_out ? acc_out[j] : nullptr);
             if (nsrc) {
                 it.dsrc = one_source ? 0u : src_of[(const void *)ct_in[j]];
                 it.flipw = flips[(size_t)j];
@@ -1676,13 +1692,8 @@ static int ks_run(hefx_context *c, int L, int n, bool relin, const uint64_t *con
         if (herr == hipSuccess && hipEventRecord(c->ring_ev[slot], cs) == hipSuccess) c->ring_busy[slot] = true;
     }
 #undef KS_TRY
-    if (two) {
-        for (int s = 0; s < ns; ++s) {
-            hipError_t e = hipEventRecord(c->ev_join[s], c->streams[s]);
-            if (e == hipSuccess) e = hipStreamWaitEvent(user, c->ev_join[s], 0);
-            if (e != hipSuccess && herr == hipSuccess) herr = e, hwhat = "join of the internal streams";
-        }
-    }
+    if (const hipError_t ej = ks_join(c, user, two ? ns : 0); ej != hipSuccess && herr == hipSuccess)
+        herr = ej, hwhat = "join of the internal streams";
     if (herr != hipSuccess) return hipfail(herr, hwhat);
     if (ksdbg)
         fprintf(stderr, "[hefx] ks_run n=%d L=%d chunks=%d share=%d: checks %.1f us, order/tables %.1f us, scratch+submit %.1f us\n", n, L,
@@ -1693,13 +1704,13 @@ static int ks_run(hefx_context *c, int L, int n, bool relin, const uint64_t *con
 extern "C" int hefx_apply_galois(hefx_context *c, int L, const uint64_t *ct_in, uint32_t elt, const uint64_t *key,
                                  uint64_t *ct_out, void *stream)
 {
-    return ks_run(c, L, 1, false, &ct_in, &elt, &key, nullptr, nullptr, &ct_out, stream);
+    return ks_run(c, L, {.n = 1, .ct_in = &ct_in, .elts = &elt, .keys = &key, .ct_out = &ct_out}, stream);
 }
 extern "C" int hefx_apply_galois_batch(hefx_context *c, int L, int n, const uint64_t *const *ct_in,
                                        const uint32_t *elts, const uint64_t *const *keys, uint64_t *const *ct_out,
                                        void *stream)
 {
-    return ks_run(c, L, n, false, ct_in, elts, keys, nullptr, nullptr, ct_out, stream);
+    return ks_run(c, L, {.n = n, .ct_in = ct_in, .elts = elts, .keys = keys, .ct_out = ct_out}, stream);
 }
 extern "C" int hefx_rotate_multiply_plain_batch(hefx_context *c, int L, int n, const uint64_t *const *ct_in,
                                                 const uint32_t *elts, const uint64_t *const *keys,
@@ -1707,7 +1718,7 @@ extern "C" int hefx_rotate_multiply_plain_batch(hefx_context *c, int L, int n, c
 {
     if (!pts) return fail(HEFX_ERR_INVALID, "missing plaintexts");
     // (a null ENTRY is a plain rotation: hefx.h)
-    return ks_run(c, L, n, false, ct_in, elts, keys, nullptr, pts, ct_out, stream);
+    return ks_run(c, L, {.n = n, .ct_in = ct_in, .elts = elts, .keys = keys, .pts = pts, .ct_out = ct_out}, stream);
 }
 extern "C" int hefx_apply_galois_add_batch(hefx_context *c, int L, int n, const uint64_t *const *ct_in,
                                            const uint32_t *elts, const uint64_t *const *keys,
@@ -1715,7 +1726,7 @@ extern "C" int hefx_apply_galois_add_batch(hefx_context *c, int L, int n, const 
                                            uint64_t *const *ct_out, void *stream)
 {
     if (!acc_in || !acc_out) return fail(HEFX_ERR_INVALID, "missing accumulators");
-    return ks_run(c, L, n, false, ct_in, elts, keys, nullptr, nullptr, ct_out, stream, false, acc_in, acc_out);
+    return ks_run(c, L, {.n = n, .ct_in = ct_in, .elts = elts, .keys = keys, .ct_out = ct_out, .acc_in = acc_in, .acc_out = acc_out}, stream);
 }
 // ---------------------------------------------------------------------------------------------
 // helper.h:472-476 as ONE call:  for (s = 1 .. steps) { rotate_vector_inplace(dup, step, gal_keys); add_inplace(mult, dup); }
@@ -1735,20 +1746,7 @@ hipError_t chain_level(hefx_context *c, int L, int n, const uint64_t *const *in,
                        KsItem *db, int quarter, hipStream_t s)
 {
     KsItem hb[64];
-    for (int i = 0; i < n; ++i) {
-        KsItem &it = hb[i];
-        it.c_in = (const u64 *)in[i];
-        it.c_out = (u64 *)out[i];
-        it.pt = nullptr;
-        it.key = (const u64 *)keys[i];
-        it.perm = perms[i];
-        it.elt = elts[i];
-        it.flags = 0;
-        it.acc_in = (const u64 *)acc_in[i];
-        it.acc_out = (u64 *)acc_out[i];
-        it.dsrc = it.pad_ = 0;
-        it.flipw = nullptr;
-    }
+    for (int i = 0; i < n; ++i) ks_fill_item(hb[i], in[i], out[i], nullptr, keys[i], perms[i], elts[i], acc_in[i], acc_out[i]);
     c->stat_ks_items += (uint64_t)n, ++c->stat_ks_chunks;
     return launch_keyswitch_chunk(c->T, L, n, db, false, S, false, hb, quarter, s, nullptr);
 }
@@ -1762,27 +1760,22 @@ extern "C" int hefx_rotate_add_chain(hefx_context *c, int L, int n, const uint64
     if (steps < 1) return fail(HEFX_ERR_INVALID, "a rotate-and-add chain needs at least one step");
     if (!acc_in || !acc_out) return fail(HEFX_ERR_INVALID, "missing accumulators");
     if (steps == 1)
-        return ks_run(c, L, n, false, ct_in, elts, keys, nullptr, nullptr, ct_out, stream, false, acc_in, acc_out);
+        return ks_run(c, L, {.n = n, .ct_in = ct_in, .elts = elts, .keys = keys, .ct_out = ct_out, .acc_in = acc_in, .acc_out = acc_out}, stream);
     if (int rc = check_ks_level(c, L)) return rc;
     if (n < 1 || !ct_in || !ct_out || !elts || !keys) return fail(HEFX_ERR_INVALID, "bad chain arguments");
     // The levels after the first are launched without ks_run's checks, so what they write is checked HERE, before anything
     // is submitted and whatever n is (the wide path's ks_run calls would refuse the same arguments, only later): every
     // final rotation and every sum non-null and all 2n of them pairwise disjoint in bytes.  (ct_out[i] == ct_in[i] is
     // fine: the inputs are read by level 1 only.)
+    for (int i = 0; i < n; ++i)
+        if (!ct_out[i] || !acc_out[i] || !acc_in[i] || !ct_in[i] || !keys[i])
+            return fail(HEFX_ERR_INVALID, "null pointer in a rotate-and-add chain");
     {
-        const size_t out_b = 2 * (size_t)L * (size_t)c->n * sizeof(u64);
-        std::vector<uintptr_t> w;
-        w.reserve(2 * (size_t)n);
-        for (int i = 0; i < n; ++i) {
-            if (!ct_out[i] || !acc_out[i] || !acc_in[i] || !ct_in[i] || !keys[i])
-                return fail(HEFX_ERR_INVALID, "null pointer in a rotate-and-add chain");
-            w.push_back((uintptr_t)ct_out[i]);
-            w.push_back((uintptr_t)acc_out[i]);
-        }
-        std::sort(w.begin(), w.end());
-        for (size_t i = 1; i < w.size(); ++i)
-            if (w[i - 1] + out_b > w[i])
-                return fail(HEFX_ERR_INVALID, "rotate-and-add chain: final rotations and sums must not overlap one another");
+        std::vector<uint64_t *> w(ct_out, ct_out + n);
+        w.insert(w.end(), acc_out, acc_out + n);
+        if (int rc = check_ranges("rotate-and-add chain", w.size(), w.data(), 2 * (size_t)L * c->n * sizeof(u64), {}, {},
+                                  "final rotations and sums must not overlap one another"))
+            return rc;
     }
     // the two intermediate buffer sets (pooled; parked again when the call returns -- later users are ordered behind
     // this call's work on the caller's stream, hefx_malloc's contract)
@@ -1800,26 +1793,25 @@ extern "C" int hefx_rotate_add_chain(hefx_context *c, int L, int n, const uint64
         B[(size_t)i] = (uint64_t *)ws + ((size_t)n + i) * ctw;
     }
     // level 1 through the validating front door: ct_in -> A, acc_in -> acc_out; from then on the sums are in place
-    if (int rc = ks_run(c, L, n, false, ct_in, elts, keys, nullptr, nullptr, A.data(), stream, false, acc_in, acc_out)) return rc;
+    if (int rc = ks_run(c, L, {.n = n, .ct_in = ct_in, .elts = elts, .keys = keys, .ct_out = A.data(), .acc_in = acc_in, .acc_out = acc_out}, stream))
+        return rc;
     const int mid = steps - 2;  // levels 2 .. steps-1 alternate A -> B, B -> A; the last level writes ct_out
     const uint64_t *const *lastsrc = (mid & 1) ? B.data() : A.data();
     hipStream_t user = (hipStream_t)stream;
     if (n > ks_small_max() || n > 64) {  // wide chains: the regular batched path per level (descriptor ring, chunks)
         for (int sidx = 0; sidx < mid; ++sidx) {
             const bool ab = (sidx & 1) == 0;
-            if (int rc = ks_run(c, L, n, false, ab ? A.data() : B.data(), elts, keys, nullptr, nullptr, ab ? B.data() : A.data(),
-                                stream, false, acc_out, acc_out))
+            if (int rc = ks_run(c, L, {.n = n, .ct_in = ab ? A.data() : B.data(), .elts = elts, .keys = keys, .ct_out = ab ? B.data() : A.data(),
+                                       .acc_in = acc_out, .acc_out = acc_out}, stream))
                 return rc;
         }
-        return ks_run(c, L, n, false, lastsrc, elts, keys, nullptr, nullptr, ct_out, stream, false, acc_out, acc_out);
+        return ks_run(c, L, {.n = n, .ct_in = lastsrc, .elts = elts, .keys = keys, .ct_out = ct_out, .acc_in = acc_out, .acc_out = acc_out}, stream);
     }
     std::vector<const uint32_t *> perms((size_t)n);
     for (int i = 0; i < n; ++i)
         if (int rc = get_perm(c, elts[i], &perms[(size_t)i])) return rc;
     // scratch as ks_run lays it out for one chunk on the caller's stream (level 1 has already sized it)
-    const size_t per = ks_words_per_item(c, L);
-    if (int rc = ensure_scratch(c, per * (size_t)n + ks_x_words(c, L, n))) return rc;
-    const size_t N = c->n;
+    if (int rc = ensure_scratch(c, ks_chunk_words(c, L, n, false))) return rc;
     // LANES (round 5).  Chains are independent of one another, so many of them can be dealt over the caller's stream and
     // the internal ones (every lane its own slice of the scratch and its own descriptor slots; internal streams forked from
     // and joined to the caller's) -- same launches per chain, same bits.  Measured (profiles/r05/chain_lanes.txt): a level
@@ -1844,22 +1836,13 @@ extern "C" int hefx_rotate_add_chain(hefx_context *c, int L, int n, const uint64
         ln.lo = (int)((long long)n * l / nl);
         ln.cnt = (int)((long long)n * (l + 1) / nl) - ln.lo;
         ln.quarter = ks_small_shape(ln.cnt, L);
-        ln.S = KsScratch{};
-        ln.S.d = c->scratch + off;
-        ln.S.acc = ln.S.d + (size_t)ln.cnt * L * N;
-        ln.S.u = ln.S.acc + (size_t)ln.cnt * 2 * (L + 1) * N;
-        ln.S.x = ln.S.u + (size_t)ln.cnt * 2 * N;
-        ln.S.alias = ln.S.x + ks_x_words(c, L, ln.cnt);
-        off += per * (size_t)ln.cnt + ks_x_words(c, L, ln.cnt);
+        ln.S = ks_scratch_at(c, L, ln.cnt, c->scratch + off);
+        off += ks_chunk_words(c, L, ln.cnt, false);
         ln.dbA = c->chain_items + (size_t)l * 128;
         ln.dbB = ln.dbA + 64;
         ln.s = l == 0 ? user : c->streams[l - 1];
     }
-    hipError_t herr = hipSuccess;
-    if (nl > 1) {
-        herr = hipEventRecord(c->ev_fork, user);
-        for (int l = 1; l < nl && herr == hipSuccess; ++l) herr = hipStreamWaitEvent(lane[l].s, c->ev_fork, 0);
-    }
+    hipError_t herr = ks_fork(c, user, nl - 1);
     auto lane_level = [&](const Lane &ln, const uint64_t *const *in, uint64_t *const *out, KsItem *db) {
         return chain_level(c, L, ln.cnt, in + ln.lo, out + ln.lo, acc_out + ln.lo, acc_out + ln.lo, elts + ln.lo, keys + ln.lo,
                            perms.data() + ln.lo, ln.S, db, ln.quarter, ln.s);
@@ -1871,11 +1854,7 @@ extern "C" int hefx_rotate_add_chain(hefx_context *c, int L, int n, const uint64
             herr = lane_level(lane[l], ab ? A.data() : B.data(), ab ? B.data() : A.data(), ab ? lane[l].dbA : lane[l].dbB);
     }
     for (int l = 0; l < nl && herr == hipSuccess; ++l) herr = lane_level(lane[l], lastsrc, ct_out, lane[l].dbA);
-    for (int l = 1; l < nl; ++l) {  // joined on every path: whatever was launched stays ordered before the caller's next work
-        hipError_t ej = hipEventRecord(c->ev_join[l - 1], lane[l].s);
-        if (ej == hipSuccess) ej = hipStreamWaitEvent(user, c->ev_join[l - 1], 0);
-        if (herr == hipSuccess) herr = ej;
-    }
+    if (const hipError_t ej = ks_join(c, user, nl - 1); herr == hipSuccess) herr = ej;  // joined on every path
     if (herr != hipSuccess) return hipfail(herr, "rotate-and-add chain");
     return HEFX_OK;
 }
@@ -1883,12 +1862,12 @@ extern "C" int hefx_rotate_add_chain(hefx_context *c, int L, int n, const uint64
 extern "C" int hefx_relinearize(hefx_context *c, int L, const uint64_t *ct3, const uint64_t *key, uint64_t *ct2,
                                 void *stream)
 {
-    return ks_run(c, L, 1, true, &ct3, nullptr, nullptr, key, nullptr, &ct2, stream);
+    return ks_run(c, L, {.n = 1, .relin = true, .ct_in = &ct3, .single_key = key, .ct_out = &ct2}, stream);
 }
 extern "C" int hefx_relinearize_batch(hefx_context *c, int L, int n, const uint64_t *const *ct3,
                                       const uint64_t *key, uint64_t *const *ct2, void *stream)
 {
-    return ks_run(c, L, n, true, ct3, nullptr, nullptr, key, nullptr, ct2, stream);
+    return ks_run(c, L, {.n = n, .relin = true, .ct_in = ct3, .single_key = key, .ct_out = ct2}, stream);
 }
 
 // SEAL's relinearize_internal for any size: from the top, polynomial t is key-switched with the key of s^t into (c0, c1).
@@ -1923,7 +1902,7 @@ extern "C" int hefx_relinearize_sizes_batch(hefx_context *c, int L, int n, int s
     const size_t pw = (size_t)L * c->n;  // words of one polynomial
     if (int rc = check_ranges("relinearize", (size_t)n, out, size_out * pw * sizeof(u64), {{ct, (size_t)n, size_in * pw * sizeof(u64)}}, {"d_ct"}))
         return rc;
-    if (size_in == 3) return ks_run(c, L, n, true, ct, nullptr, nullptr, keys[0], nullptr, out, stream);
+    if (size_in == 3) return ks_run(c, L, {.n = n, .relin = true, .ct_in = ct, .single_key = keys[0], .ct_out = out}, stream);
     const int group = std::min(n, relin_stage_group(c, L));
     if (int rc = grow_retiring(c, &c->lt_ws, &c->lt_cap, 6 * pw * (size_t)group, 0, "relinearize staging")) return rc;
     uint64_t *ws = reinterpret_cast<uint64_t *>(c->lt_ws);
@@ -1943,8 +1922,8 @@ extern "C" int hefx_relinearize_sizes_batch(hefx_context *c, int L, int n, int s
                 dst[(size_t)i] = t == size_out ? out[i0 + i] : ws + ((size_t)((step + 1) & 1) * group + i) * 3 * pw;
             }
             // (trusted: the blocks are disjoint by construction and the caller's buffers were checked above)
-            if (int rc = ks_run(c, L, cnt, true, src.data(), nullptr, nullptr, keys[t - 2], nullptr, dst.data(), stream, false,
-                                nullptr, nullptr, true))
+            if (int rc = ks_run(c, L, {.n = cnt, .relin = true, .ct_in = src.data(), .single_key = keys[t - 2], .ct_out = dst.data(), .trusted = true},
+                                stream))
                 return rc;
         }
     }
@@ -2682,14 +2661,8 @@ static int run_forest(hefx_context *c, int L, const std::vector<ForestNode> &nod
         }
         bool all_loaded = true;
         for (int q = 0; q < LANES; ++q) all_loaded = all_loaded && load[q] > 0;
-        int chunk = c->chunk;  // ks_run's rule for the items of one launch sequence
-        if (chunk <= 0) {
-            chunk = (int)(((size_t)1 << 30) / (ks_words_per_item(c, L) * sizeof(u64)));
-            const int cap = c->logn <= 13 ? 2 * KS_AUTO_CHUNK : KS_AUTO_CHUNK;
-            chunk = chunk > cap ? cap : (chunk < 16 ? 16 : chunk & ~7);
-        }
-        if (all_loaded && widest <= chunk) {
-            lane1_off = ks_words_per_item(c, L) * (size_t)widest + ks_x_words(c, L, widest);
+        if (all_loaded && widest <= ks_auto_chunk(c, L)) {  // (a lane's batch is one chunk of ks_run)
+            lane1_off = ks_chunk_words(c, L, widest, false);
             if (int rc = ensure_scratch(c, (size_t)LANES * lane1_off)) return rc;
             nlanes = LANES;
             // whatever a lane's batches would build on first use is built HERE, on the caller's stream, before the lanes
@@ -2709,11 +2682,8 @@ static int run_forest(hefx_context *c, int L, const std::vector<ForestNode> &nod
             std::fill(lane_of.begin(), lane_of.end(), 0);
     }
     hipStream_t lane_stream[LANES] = {(hipStream_t)stream, c->streams[0]};
-    if (nlanes > 1) {
-        HIPCHK(hipEventRecord(c->ev_fork, lane_stream[0]));
-        for (int q = 1; q < nlanes; ++q) HIPCHK(hipStreamWaitEvent(lane_stream[q], c->ev_fork, 0));
-    }
     int lane_rc = HEFX_OK;
+    if (const hipError_t ef = ks_fork(c, lane_stream[0], nlanes - 1); ef != hipSuccess) lane_rc = hipfail(ef, "fork of the linear transform's lanes");
     for (int depth = 0; depth < max_depth && lane_rc == HEFX_OK; ++depth)
         for (int ln = 0; ln < nlanes && lane_rc == HEFX_OK; ++ln) {
             in.clear(), kk.clear(), pp.clear(), oo.clear(), ee.clear();
@@ -2732,18 +2702,50 @@ static int run_forest(hefx_context *c, int L, const std::vector<ForestNode> &nod
             // (node buffers are this context's workspace, disjoint by construction; the diagonals are the caller's and
             // cannot reach into it: the batch is trusted)
             // (an error leaves the loop, not the function: lane 1's stream must be joined to the caller's whatever happened)
-            lane_rc = ks_run(c, L, (int)in.size(), false, in.data(), ee.data(), kk.data(), nullptr, any_pt ? pp.data() : nullptr,
-                             oo.data(), lane_stream[ln], hoisted, nullptr, nullptr, true, (size_t)ln * lane1_off);
+            lane_rc = ks_run(c, L, {.n = (int)in.size(), .ct_in = in.data(), .elts = ee.data(), .keys = kk.data(), .pts = any_pt ? pp.data() : nullptr,
+                                    .ct_out = oo.data(), .hoist = hoisted, .trusted = true, .scratch_off = (size_t)ln * lane1_off},
+                             lane_stream[ln]);
         }
-    for (int q = 1; q < nlanes; ++q) {
-        hipError_t ej = hipEventRecord(c->ev_join[q - 1], lane_stream[q]);
-        if (ej == hipSuccess) ej = hipStreamWaitEvent(lane_stream[0], c->ev_join[q - 1], 0);
-        if (ej != hipSuccess && lane_rc == HEFX_OK) lane_rc = hipfail(ej, "join of the linear transform's lanes");
-    }
+    if (const hipError_t ej = ks_join(c, lane_stream[0], nlanes - 1); ej != hipSuccess && lane_rc == HEFX_OK)
+        lane_rc = hipfail(ej, "join of the linear transform's lanes");
     return lane_rc;
 }
 
-// Parts shared by lt_impl and hefx_linear_transform_cipher.
+// Parts shared by the linear transforms.
+// The shared argument check (`own`: the entry's own conditions), the null-key check with the key map, and the rotation plans
+// -- rotate(-d) into `first`, then term i = 1 .. nterms-1 (step steps[i], or i when steps is null; term 0 is the unrotated one)
+// handed to sink(i, plan); the plan vector is the sink's to keep (swap) or read.  direct_only: the text a step without a
+// direct Galois key (a plan of more than one element) is refused with, by the forms that need one.  A missing key or a step
+// too large is reported here, before anything runs, with SEAL's text, like the op-by-op sequence would.
+static int lt_args(bool own, int d, const void *diags, int nkeys, const uint32_t *key_elts, const uint64_t *const *keys)
+{
+    if (!own || d < 1 || !diags || nkeys < 0 || (nkeys && (!key_elts || !keys))) return fail(HEFX_ERR_INVALID, "bad linear-transform arguments");
+    return HEFX_OK;
+}
+static int lt_keys(LtKeys &K, int nkeys, const uint32_t *key_elts, const uint64_t *const *keys)
+{
+    for (int i = 0; i < nkeys; ++i)
+        if (!keys[i]) return fail(HEFX_ERR_INVALID, "null Galois key");
+    K.set(nkeys, key_elts, keys);
+    return HEFX_OK;
+}
+template <class Sink>
+static int lt_plans(const hefx_context *c, const LtKeys &K, int d, int nterms, const int *steps, const char *direct_only,
+                    std::vector<uint32_t> &first, Sink sink)
+{
+    if (const char *err = lt_plan(-d, c->n, K, first)) return fail(HEFX_ERR_INVALID, err);
+    std::vector<uint32_t> plan;
+    for (int i = 1; i < nterms; ++i) {
+        plan.clear();
+        const int step = steps ? steps[i] : i;
+        if (step == 0) return fail(HEFX_ERR_INVALID, "only term 0 may be unrotated");
+        if (const char *err = lt_plan(step, c->n, K, plan)) return fail(HEFX_ERR_INVALID, err);
+        if (direct_only && plan.size() != 1) return fail(HEFX_ERR_INVALID, direct_only);
+        sink(i, plan);
+    }
+    return HEFX_OK;
+}
+static const char LT_DIRECT_KEYS[] = "hoisted linear transform needs a direct Galois key for every step 1..d-1";
 // ct_new(t) = cts[t] + rotate(cts[t], -d) for `count` inputs in lockstep (helper.h:216-219 / :244-247): `first` is the plan of
 // the -d rotation; input t owns head + t * stride: ping at +0, pong at +ctw, ct_new at +2 ctw.  The sum rides in the epilogue
 // of the chain's last key switch (acc_out = acc_in + rotation, the kernels of hefx_apply_galois_add_batch): one launch
@@ -2762,8 +2764,8 @@ static int lt_ct_new(hefx_context *c, int L, int count, const uint64_t *const *c
             kk[(size_t)t] = K.at(first[s]);
             ee[(size_t)t] = first[s];
         }
-        if (int rc = ks_run(c, L, count, false, src.data(), ee.data(), kk.data(), nullptr, nullptr, dst.data(), stream, false,
-                            last ? ain.data() : nullptr, last ? aout.data() : nullptr))
+        if (int rc = ks_run(c, L, {.n = count, .ct_in = src.data(), .elts = ee.data(), .keys = kk.data(), .ct_out = dst.data(),
+                                   .acc_in = last ? ain.data() : nullptr, .acc_out = last ? aout.data() : nullptr}, stream))
             return rc;
         for (int t = 0; t < count; ++t) src[(size_t)t] = dst[(size_t)t];
     }
@@ -2822,8 +2824,7 @@ static int lt_impl(hefx_context *c, int L, int count, const uint64_t *const *cts
 {
     CTXCHK(c);
     if (int rc = check_ks_level(c, L)) return rc;
-    if (count < 1 || count > 64 || !cts || !outs || d < 1 || !diag_pts || nkeys < 0 || (nkeys && (!key_elts || !keys)))
-        return fail(HEFX_ERR_INVALID, "bad linear-transform arguments");
+    if (int rc = lt_args(count >= 1 && count <= 64 && cts && outs, d, diag_pts, nkeys, key_elts, keys)) return rc;
     for (int t = 0; t < count; ++t)
         if (!cts[t] || !outs[t]) return fail(HEFX_ERR_INVALID, "bad linear-transform arguments");
     for (int i = 0; i < count * d; ++i)
@@ -2835,29 +2836,16 @@ static int lt_impl(hefx_context *c, int L, int count, const uint64_t *const *cts
                                   {{cts, (size_t)count, 2 * pt_b}, {diag_pts, (size_t)count * d, pt_b}}, {"d_ct", "d_diag_pts"}))
             return rc;
     }
-    static const bool dbg = getenv("HEFX_DEBUG") != nullptr;  // host time of the call's phases on stderr
-    auto t_last = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!dbg) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[hefx] linear_transform(d=%d x %d): %-36s %7.1f us\n", d, count, what, std::chrono::duration<double, std::micro>(now - t_last).count());
-        t_last = now;
-    };
+    Lap lap{"linear_transform(d=" + std::to_string(d) + " x " + std::to_string(count) + ")"};  // host time of the call's phases
     LtKeys K;
-    for (int i = 0; i < nkeys; ++i)
-        if (!keys[i]) return fail(HEFX_ERR_INVALID, "null Galois key");
-    K.set(nkeys, key_elts, keys);
+    if (int rc = lt_keys(K, nkeys, key_elts, keys)) return rc;
     const size_t N = c->n, ctw = 2 * (size_t)L * N;
+    // plans of every step first (cheap), the node forest later -- while the GPU is already at work on ct_new
     std::vector<uint32_t> first;
-    if (const char *err = lt_plan(-d, N, K, first)) return fail(HEFX_ERR_INVALID, err);
-    // a missing key or a step too large must be reported before anything runs, like the op-by-op sequence would: plans of
-    // every step first (cheap), the node forest later -- while the GPU is already at work on ct_new
     std::vector<std::vector<uint32_t>> plans((size_t)d);
-    for (int l = 1; l < d; ++l) {
-        if (const char *err = lt_plan(l, N, K, plans[(size_t)l])) return fail(HEFX_ERR_INVALID, err);
-        if (hoisted && plans[(size_t)l].size() != 1)
-            return fail(HEFX_ERR_INVALID, "hoisted linear transform needs a direct Galois key for every step 1..d-1");
-    }
+    if (int rc = lt_plans(c, K, d, d, nullptr, hoisted ? LT_DIRECT_KEYS : nullptr, first,
+                          [&](int l, std::vector<uint32_t> &plan) { plans[(size_t)l].swap(plan); }))
+        return rc;
     lap("key map + rotation plans");
     // ---- workspace, part 1, per input: ping/pong for the first rotation chain, ct_new, product 0
     if (int rc = grow_retiring(c, &c->lt_head, &c->lt_head_cap, (size_t)count * 4 * ctw, 0, "linear-transform head")) return rc;
@@ -2933,23 +2921,12 @@ extern "C" int hefx_apply_galois_forest(hefx_context *c, int L, int n, const int
     // outputs pairwise disjoint; no external input or plaintext reaches into an output (byte ranges, like ks_run's check --
     // the per-depth batches below then run trusted)
     {
-        const size_t row = (size_t)c->n * sizeof(u64), out_b = 2 * (size_t)L * row, pt_b = (size_t)L * row;
-        std::vector<uintptr_t> o((size_t)n);
-        for (int i = 0; i < n; ++i) o[(size_t)i] = (uintptr_t)outs[i];
-        std::sort(o.begin(), o.end());
-        for (int i = 1; i < n; ++i)
-            if (o[(size_t)i - 1] + out_b > o[(size_t)i]) return fail(HEFX_ERR_INVALID, "rotation forest: two nodes write overlapping outputs");
-        auto hits = [&](const void *p, size_t bytes) {
-            const uintptr_t a = (uintptr_t)p;
-            auto it = std::upper_bound(o.begin(), o.end(), a);
-            if (it != o.begin() && *(it - 1) + out_b > a) return true;
-            return it != o.end() && *it < a + bytes;
-        };
-        for (int i = 0; i < n; ++i) {
-            if (parent[i] < 0 && hits(ext_in[i], out_b))
-                return fail(HEFX_ERR_INVALID, "rotation forest: an external input overlaps a node's output");
-            if (pts && pts[i] && hits(pts[i], pt_b)) return fail(HEFX_ERR_INVALID, "rotation forest: a plaintext overlaps a node's output");
-        }
+        const size_t pt_b = (size_t)L * c->n * sizeof(u64);
+        std::vector<const uint64_t *> ext((size_t)n);  // the inputs that are read: those of the roots
+        for (int i = 0; i < n; ++i) ext[(size_t)i] = nodes[(size_t)i].in_ext;
+        if (int rc = check_ranges("rotation forest", (size_t)n, outs, 2 * pt_b, {{ext.data(), (size_t)n, 2 * pt_b}, {pts, pts ? (size_t)n : 0, pt_b}},
+                                  {"d_ext_in", "d_pts"}, "two nodes write overlapping outputs"))
+            return rc;
     }
     return run_forest(c, L, nodes, max_depth, stream, false);
 }
@@ -2986,28 +2963,20 @@ extern "C" int hefx_linear_transform_cipher(hefx_context *c, int L, const uint64
 {
     CTXCHK(c);
     if (int rc = check_ks_level(c, L)) return rc;
-    if (!ct || !out3 || d < 1 || !diag_cts || nkeys < 0 || (nkeys && (!key_elts || !keys)))
-        return fail(HEFX_ERR_INVALID, "bad linear-transform arguments");
+    if (int rc = lt_args(ct && out3, d, diag_cts, nkeys, key_elts, keys)) return rc;
     for (int i = 0; i < d; ++i)
         if (!diag_cts[i]) return fail(HEFX_ERR_INVALID, "null diagonal ciphertext");
     LtKeys K;
-    for (int i = 0; i < nkeys; ++i)
-        if (!keys[i]) return fail(HEFX_ERR_INVALID, "null Galois key");
-    K.set(nkeys, key_elts, keys);
+    if (int rc = lt_keys(K, nkeys, key_elts, keys)) return rc;
     const size_t N = c->n, ctw = 2 * (size_t)L * N;
-    {  // the result may reach into no operand (byte ranges; refused before anything is submitted)
-        const uintptr_t o = (uintptr_t)out3, out_b = 3 * (size_t)L * N * sizeof(u64), in_b = ctw * sizeof(u64);
-        auto hits = [&](const void *p) { return (uintptr_t)p < o + out_b && o < (uintptr_t)p + in_b; };
-        if (hits(ct)) return fail(HEFX_ERR_INVALID, "linear transform: the output overlaps the input");
-        for (int i = 0; i < d; ++i)
-            if (hits(diag_cts[i])) return fail(HEFX_ERR_INVALID, "linear transform: the output overlaps a diagonal");
-    }
-    // plans of every step first: a missing key or a step too large is reported before anything runs, with SEAL's text
+    // the result may reach into no operand (byte ranges; refused before anything is submitted)
+    if (int rc = check_ranges("linear transform", 1, &out3, 3 * (size_t)L * N * sizeof(u64),
+                              {{&ct, 1, ctw * sizeof(u64)}, {diag_cts, (size_t)d, ctw * sizeof(u64)}}, {"d_ct", "d_diag_cts"}))
+        return rc;
+    // plans of every step first
     std::vector<uint32_t> first;
-    if (const char *err = lt_plan(-d, N, K, first)) return fail(HEFX_ERR_INVALID, err);
     std::vector<std::vector<uint32_t>> plans((size_t)d);
-    for (int l = 1; l < d; ++l)
-        if (const char *err = lt_plan(l, N, K, plans[(size_t)l])) return fail(HEFX_ERR_INVALID, err);
+    if (int rc = lt_plans(c, K, d, d, nullptr, nullptr, first, [&](int l, std::vector<uint32_t> &plan) { plans[(size_t)l].swap(plan); })) return rc;
     // ---- ct_new = ct + rotate(ct, -d)      (helper.h:216-219), the sum in the epilogue of the chain's last key switch
     if (int rc = grow_retiring(c, &c->lt_head, &c->lt_head_cap, 3 * ctw, 0, "linear-transform head")) return rc;
     uint64_t *ct_new = reinterpret_cast<uint64_t *>(c->lt_head) + 2 * ctw;
@@ -3045,8 +3014,7 @@ extern "C" int hefx_linear_transform_plain_bsgs(hefx_context *c, int L, const ui
 {
     CTXCHK(c);
     if (int rc = check_ks_level(c, L)) return rc;
-    if (!ct || !out || d < 1 || n1 < 1 || n1 > d || !shifted_diag_pts || nkeys < 0 || (nkeys && (!key_elts || !keys)))
-        return fail(HEFX_ERR_INVALID, "bad linear-transform arguments");
+    if (int rc = lt_args(ct && out && n1 >= 1 && n1 <= d, d, shifted_diag_pts, nkeys, key_elts, keys)) return rc;
     const int n2 = (d + n1 - 1) / n1;
     if ((size_t)d + (size_t)n1 * n2 > c->n / 2)
         return fail(HEFX_ERR_INVALID, "baby-step/giant-step transform: dimension too large for the slot count");
@@ -3058,44 +3026,22 @@ extern "C" int hefx_linear_transform_plain_bsgs(hefx_context *c, int L, const ui
                                   {"d_ct", "d_shifted_diag_pts"}))
             return rc;
     }
-    static const bool dbg = getenv("HEFX_DEBUG") != nullptr;  // host time of the call's phases on stderr
-    auto t_last = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!dbg) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[hefx] linear_transform(d=%d): %-36s %7.1f us\n", d, what, std::chrono::duration<double, std::micro>(now - t_last).count());
-        t_last = now;
-    };
     LtKeys K;
-    for (int i = 0; i < nkeys; ++i)
-        if (!keys[i]) return fail(HEFX_ERR_INVALID, "null Galois key");
-    K.set(nkeys, key_elts, keys);
+    if (int rc = lt_keys(K, nkeys, key_elts, keys)) return rc;
     const size_t N = c->n, ctw = 2 * (size_t)L * N;
-    std::vector<uint32_t> first, plan, belt, gelt;
-    if (const char *err = lt_plan(-d, N, K, first)) return fail(HEFX_ERR_INVALID, err);
-    for (int t = 1; t < n1 + n2 - 1; ++t) {  // baby steps 1..n1-1, then giant steps n1, 2*n1, ...
-        const int step = t < n1 ? t : (t - n1 + 1) * n1;
-        plan.clear();
-        if (const char *err = lt_plan(step, N, K, plan)) return fail(HEFX_ERR_INVALID, err);
-        if (plan.size() != 1)
-            return fail(HEFX_ERR_INVALID,
-                        "baby-step/giant-step transform needs a direct Galois key for every baby and giant step");
-        (t < n1 ? belt : gelt).push_back(plan[0]);
-    }
+    std::vector<uint32_t> first, belt, gelt;
+    std::vector<int> steps((size_t)(n1 + n2 - 1), 0);  // term 0, baby steps 1..n1-1, then giant steps n1, 2*n1, ...
+    for (int t = 1; t < n1 + n2 - 1; ++t) steps[(size_t)t] = t < n1 ? t : (t - n1 + 1) * n1;
+    if (int rc = lt_plans(c, K, d, n1 + n2 - 1, steps.data(), "baby-step/giant-step transform needs a direct Galois key for every baby and giant step",
+                          first, [&](int t, std::vector<uint32_t> &plan) { (t < n1 ? belt : gelt).push_back(plan[0]); }))
+        return rc;
     // ---- workspace: ping / pong / ct_new, n1-1 baby rotations, n2 inner sums, n2-1 rotated inner sums
     const size_t need = ctw * (size_t)(3 + (n1 - 1) + n2 + (n2 - 1));
     if (int rc = grow_retiring(c, &c->lt_ws, &c->lt_cap, need, 0, "linear-transform workspace")) return rc;
-    uint64_t *ping = reinterpret_cast<uint64_t *>(c->lt_ws), *pong = ping + ctw, *ct_new = pong + ctw,
+    uint64_t *ws = reinterpret_cast<uint64_t *>(c->lt_ws), *ct_new = ws + 2 * ctw,  // (ping at +0, pong at +ctw: lt_ct_new)
              *rots = ct_new + ctw, *inner = rots + (size_t)(n1 - 1) * ctw, *grot = inner + (size_t)n2 * ctw;
     // ---- ct_new = ct + rotate(ct, -d)      (helper.h:244-247)
-    const uint64_t *src = ct;
-    for (size_t t = 0; t < first.size(); ++t) {
-        uint64_t *dst = (t & 1) ? pong : ping;
-        const uint64_t *key = K.at(first[t]);
-        if (int rc = ks_run(c, L, 1, false, &src, &first[t], &key, nullptr, nullptr, &dst, stream)) return rc;
-        src = dst;
-    }
-    if (int rc = ew_common(c, EW_ADD, L, 2, 1, ct, src, ct_new, stream, true)) return rc;
+    if (int rc = lt_ct_new(c, L, 1, &ct, first, K, ws, 3 * ctw, ctw, stream)) return rc;
     std::vector<const uint64_t *> in, kk;
     std::vector<uint64_t *> oo;
     // ---- baby steps: rots[i-1] = rotate(ct_new, i)
@@ -3105,8 +3051,8 @@ extern "C" int hefx_linear_transform_plain_bsgs(hefx_context *c, int L, const ui
             kk.push_back(K.at(belt[i - 1]));
             oo.push_back(rots + (size_t)(i - 1) * ctw);
         }
-        if (int rc = ks_run(c, L, n1 - 1, false, in.data(), belt.data(), kk.data(), nullptr, nullptr, oo.data(), stream,
-                            hoisted_baby != 0))
+        if (int rc = ks_run(c, L, {.n = n1 - 1, .ct_in = in.data(), .elts = belt.data(), .keys = kk.data(), .ct_out = oo.data(), .hoist = hoisted_baby != 0},
+                            stream))
             return rc;
     }
     // ---- inner[j] = sum_i rotate(ct_new, i) (.) diag'[j*n1 + i]
@@ -3126,8 +3072,7 @@ extern "C" int hefx_linear_transform_plain_bsgs(hefx_context *c, int L, const ui
             oo.push_back(grot + (size_t)(j - 1) * ctw);
             res[j] = oo.back();
         }
-        if (int rc = ks_run(c, L, n2 - 1, false, in.data(), gelt.data(), kk.data(), nullptr, nullptr, oo.data(), stream))
-            return rc;
+        if (int rc = ks_run(c, L, {.n = n2 - 1, .ct_in = in.data(), .elts = gelt.data(), .keys = kk.data(), .ct_out = oo.data()}, stream)) return rc;
     }
     return add_many_impl(c, L, 2, n2, res.data(), nullptr, out, stream, true);
 }
@@ -3143,9 +3088,7 @@ static int lt2_impl(hefx_context *c, int L, const uint64_t *ct, int d, int nterm
     CTXCHK(c);
     if (int rc = check_ks_level(c, L)) return rc;
     if (L != c->k - 1) return fail(HEFX_ERR_UNSUPPORTED, "double hoisting is built for the top data level");
-    if (!ct || !out || d < 1 || nterms < 1 || !steps || steps[0] != 0 || !diag_pts_keylevel || nkeys < 0 ||
-        (nkeys && (!key_elts || !keys)))
-        return fail(HEFX_ERR_INVALID, "bad linear-transform arguments");
+    if (int rc = lt_args(ct && out && nterms >= 1 && steps && steps[0] == 0, d, diag_pts_keylevel, nkeys, key_elts, keys)) return rc;
     for (int i = 0; i < nterms; ++i)
         if (!diag_pts_keylevel[i]) return fail(HEFX_ERR_INVALID, "null diagonal plaintext");
     {
@@ -3154,68 +3097,39 @@ static int lt2_impl(hefx_context *c, int L, const uint64_t *ct, int d, int nterm
                                   {"d_ct", "d_diag_pts_keylevel"}))
             return rc;
     }
-    static const bool dbg = getenv("HEFX_DEBUG") != nullptr;  // host time of the call's phases on stderr
-    auto t_last = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!dbg) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[hefx] linear_transform(d=%d): %-36s %7.1f us\n", d, what, std::chrono::duration<double, std::micro>(now - t_last).count());
-        t_last = now;
-    };
     LtKeys K;
-    for (int i = 0; i < nkeys; ++i)
-        if (!keys[i]) return fail(HEFX_ERR_INVALID, "null Galois key");
-    K.set(nkeys, key_elts, keys);
+    if (int rc = lt_keys(K, nkeys, key_elts, keys)) return rc;
     const size_t N = c->n, ctw = 2 * (size_t)L * N;
     const int k = c->k, nrot = nterms - 1, chunks = nrot > 0 ? (nrot + lt2_chunk() - 1) / lt2_chunk() : 0;
-    std::vector<uint32_t> first, plan;
-    if (const char *err = lt_plan(-d, N, K, first)) return fail(HEFX_ERR_INVALID, err);
+    std::vector<uint32_t> first;
     std::vector<KsItem> items((size_t)nterms + 1);  // [0]: source (ct_new); [1..nterms-1]: rotations; last: the mod-down
+    if (int rc = lt_plans(c, K, d, nterms, steps, LT_DIRECT_KEYS, first, [&](int l, std::vector<uint32_t> &plan) {
+            KsItem &it = items[(size_t)l];
+            it.key = (const u64 *)K.at(plan[0]);
+            it.pt = (const u64 *)diag_pts_keylevel[l];
+            it.elt = plan[0];
+        }))
+        return rc;
     // ---- workspace
     const size_t ws_words = 4 * ctw + (size_t)chunks * (2 * (size_t)k + L) * N + (items.size() * sizeof(KsItem) + 7) / 8;
     if (int rc = grow_retiring(c, &c->lt_ws, &c->lt_cap, ws_words, 0, "linear-transform workspace")) return rc;
-    uint64_t *ping = reinterpret_cast<uint64_t *>(c->lt_ws), *pong = ping + ctw, *ct_new = pong + ctw, *cbuf = ct_new + ctw;
+    uint64_t *ws = reinterpret_cast<uint64_t *>(c->lt_ws), *ct_new = ws + 2 * ctw, *cbuf = ct_new + ctw;  // (ping, pong: lt_ct_new)
     u64 *partial_s = reinterpret_cast<u64 *>(cbuf + ctw), *partial_c0 = partial_s + (size_t)chunks * 2 * k * N;
     KsItem *d_items = reinterpret_cast<KsItem *>(partial_c0 + (size_t)chunks * L * N);
-    for (int l = 1; l < nterms; ++l) {
-        plan.clear();
-        if (steps[l] == 0) return fail(HEFX_ERR_INVALID, "only term 0 may be unrotated");
-        if (const char *err = lt_plan(steps[l], N, K, plan)) return fail(HEFX_ERR_INVALID, err);
-        if (plan.size() != 1)
-            return fail(HEFX_ERR_INVALID, "hoisted linear transform needs a direct Galois key for every step 1..d-1");
-        KsItem &it = items[l];
-        it.c_in = nullptr;
-        it.c_out = nullptr;
-        it.key = (const u64 *)K.at(plan[0]);
-        it.pt = (const u64 *)diag_pts_keylevel[l];
-        it.elt = plan[0];
-        it.flags = 0;
-        if (int rc = get_perm(c, plan[0], &it.perm)) return rc;
-    }
+    for (int l = 1; l < nterms; ++l)
+        if (int rc = get_perm(c, items[(size_t)l].elt, &items[(size_t)l].perm)) return rc;
     items[0] = KsItem{(const u64 *)ct_new, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1u, 0u};
     items[nterms] = KsItem{(const u64 *)cbuf, nullptr, nullptr, nullptr, (u64 *)out, nullptr, nullptr, 1u, 0u};
     // ---- ct_new = ct + rotate(ct, -d); cbuf = ct_new * diag_0
-    const uint64_t *src = ct;
-    for (size_t t = 0; t < first.size(); ++t) {
-        uint64_t *dst = (t & 1) ? pong : ping;
-        const uint64_t *key = K.at(first[t]);
-        if (int rc = ks_run(c, L, 1, false, &src, &first[t], &key, nullptr, nullptr, &dst, stream)) return rc;
-        src = dst;
-    }
-    if (int rc = ew_common(c, EW_ADD, L, 2, 1, ct, src, ct_new, stream, true)) return rc;
+    if (int rc = lt_ct_new(c, L, 1, &ct, first, K, ws, 3 * ctw, ctw, stream)) return rc;
     if (int rc = multiply_plain_impl(c, L, 2, 1, ct_new, diag_pts_keylevel[0], cbuf, stream, true)) return rc;
     if (nrot == 0) {
         HIPCHK(hipMemcpyAsync(out, cbuf, ctw * sizeof(u64), hipMemcpyDeviceToDevice, (hipStream_t)stream));
         return HEFX_OK;
     }
     // ---- decomposition of ct_new (once), gathered MACs of all rotations, one mod-down
-    const size_t per = ks_words_per_item(c, L) + ks_x_words(c, L, 1);
-    if (int rc = ensure_scratch(c, per)) return rc;
-    KsScratch S{};
-    S.d = c->scratch;
-    S.acc = S.d + (size_t)L * N;
-    S.u = S.acc + (size_t)2 * (L + 1) * N;
-    S.x = S.u + (size_t)2 * N;
+    if (int rc = ensure_scratch(c, ks_chunk_words(c, L, 1, false))) return rc;
+    KsScratch S = ks_scratch_at(c, L, 1, c->scratch);
     S.alias = nullptr;
     hipStream_t s = (hipStream_t)stream;
     // `items` is a local: the descriptors travel through the pinned mirror of a descriptor-ring slot (a slot's worth at a
@@ -3267,14 +3181,9 @@ extern "C" int hefx_rotate_hoisted_batch(hefx_context *c, int L, const uint64_t 
         if (!ct_out[i]) return fail(HEFX_ERR_INVALID, "null ciphertext pointer in batch");
         if (pts && !pts[i]) return fail(HEFX_ERR_INVALID, "null plaintext pointer in batch");
     }
-    // the one source, the plaintexts and the outputs, for every n (ks_run's own check starts at two items or a plaintext and
-    // compares the source with the outputs for equality)
-    const size_t pt_b = (size_t)L * c->n * sizeof(u64);
-    if (int rc = check_ranges("rotate_hoisted_batch", (size_t)n, ct_out, 2 * pt_b, {{&ct_in, 1, 2 * pt_b}, {pts, (size_t)(pts ? n : 0), pt_b}},
-                              {"d_ct_in", "d_pts"}))
-        return rc;
+    // (the one source, the plaintexts and the outputs in bytes: ks_run's check, for every n; an output ON the source: its hoist test)
     std::vector<const uint64_t *> in((size_t)n, ct_in);
-    return ks_run(c, L, n, false, in.data(), elts, keys, nullptr, pts, ct_out, stream, true);
+    return ks_run(c, L, {.n = n, .ct_in = in.data(), .elts = elts, .keys = keys, .pts = pts, .ct_out = ct_out, .hoist = true}, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -6,8 +6,9 @@
 // fine when
 //   - no two outputs share a byte, and
 //   - no input shares a byte with an output -- except, for a list that says so (In::in_place), the EXACT in-place form:
-//     input i starts where ITS OWN output starts and has the output's size.  Input i's own output is output i / per_out
-//     (per_out = 1: item i's output; per_out = the list's length: the one output of a sum).
+//     input i starts where ITS OWN output starts and has the output's size.  Input i's own output is output
+//     out0 + i / per_out (per_out = 1: item i's output; per_out = the list's length: the one output of a sum; out0 = n for
+//     the inputs of the second of two output lists handed over back to back -- a key-switch batch's rotations, then its sums).
 // Adjacent blocks share no byte.  Null entries of an input list are skipped (optional operands); outputs are non-null.
 // O((n + inputs) log n) on the host, nothing is submitted.
 #pragma once
@@ -24,8 +25,9 @@ struct In {
     const uint64_t *const *ptrs;  // host array of `count` pointers
     size_t count;
     size_t bytes;           // size of every block of the list
-    bool in_place = false;  // input i may be output i / per_out, exactly
+    bool in_place = false;  // input i may be output out0 + i / per_out, exactly
     size_t per_out = 1;
+    size_t out0 = 0;        // index of input 0's own output
 };
 
 enum Verdict { FINE = 0, OUTPUTS_OVERLAP = 1, OUTPUT_OVERLAPS_INPUT = 2 };
@@ -57,7 +59,7 @@ inline Verdict check(size_t n, uint64_t *const *outs, size_t out_b, std::initial
             bool hit = it != o.end() && it->first < x + in.bytes;
             if (!hit && it != o.begin()) {
                 const auto &p = *(it - 1);
-                const bool own = in.in_place && p.first == x && in.bytes == out_b && p.second == i / (in.per_out ? in.per_out : 1);
+                const bool own = in.in_place && p.first == x && in.bytes == out_b && p.second == in.out0 + i / (in.per_out ? in.per_out : 1);
                 hit = p.first + out_b > x && !own;
             }
             if (hit) {

@@ -75,8 +75,6 @@ RULES = {
     "hefx_rotate_hoisted_batch": _row(NO_OVERLAP, (), ("an output == d_ct_in", "an output one row into a plaintext",
                                                        "n = 1: the output one row into d_ct_in"), f"{G}::test_linear_transform_refusals"),
     # ---- entries whose rule was stated and tested before
-    "hefx_multiply_sum": _row(UNCHANGED, (), ("any output on any input or output, in bytes",),
-                              "tests/test_gpu_multiply_sum.py::test_refusals_come_before_anything_is_written"),
     "hefx_multiply_sizes": _row(UNCHANGED, (), ("the output on an input, in bytes",),
                                 "tests/test_gpu_ct_sizes.py::test_refusals_come_before_anything_is_written"),
     "hefx_multiply_sizes_batch": _row(UNCHANGED, (), ("any output on any input or output, in bytes",),
@@ -85,24 +83,30 @@ RULES = {
                                    "tests/test_gpu_ct_sizes.py::test_refusals_come_before_anything_is_written"),
     "hefx_relinearize_sizes_batch": _row(UNCHANGED, (), ("any output on any input or output, in bytes",),
                                          "tests/test_gpu_ct_sizes.py::test_refusals_come_before_anything_is_written"),
-    # (the check is ks_run's, which this table leaves as it is; it had no test of its own for the relinearisations)
     "hefx_relinearize": _row(NO_OVERLAP, (), ("d_ct2 == d_ct3", "d_ct2 one row into d_ct3", "d_ct3 one row into d_ct2"), f"{G}::test_refusals"),
     "hefx_relinearize_batch": _row(NO_OVERLAP, (), ("d_ct2[i] == d_ct3[j]", "two outputs one row apart"), f"{G}::test_refusals"),
-    "hefx_apply_galois": _row(UNCHANGED, ("d_ct_out == d_ct_in",), (), "tests/test_gpu_parity.py::test_apply_galois_bit_exact"),
-    "hefx_apply_galois_batch": _row(UNCHANGED, ("d_ct_out[i] == d_ct_in[i]",), ("an item's input or output on another item's output",),
-                                    "tests/test_gpu_parity.py::test_invalid_arguments_raise"),
-    "hefx_rotate_multiply_plain_batch": _row(UNCHANGED, ("d_ct_out[i] == d_ct_in[i]",),
-                                             ("an input, plaintext or output on another item's output",),
-                                             "tests/test_gpu_parity.py::test_invalid_arguments_raise"),
-    "hefx_apply_galois_add_batch": _row(UNCHANGED, ("d_acc_out[i] == d_acc_in[i]", "d_ct_out[i] == d_ct_in[i]"),
-                                        ("a sum on another item's sum, rotation or input",),
-                                        "tests/test_gpu_round4.py::test_apply_galois_add_batch_refuses_overlapping_sums"),
-    "hefx_rotate_add_chain": _row(UNCHANGED, ("d_ct_out[i] == d_ct_in[i]",), ("any two of the 2n outputs overlapping",),
-                                  "tests/test_gpu_round5.py::test_chain_refuses_null_and_overlapping_outputs_before_anything_runs"),
-    "hefx_apply_galois_forest": _row(UNCHANGED, (), ("outputs on one another, on an external input or a plaintext",),
-                                     "tests/test_gpu_round5.py::test_apply_galois_forest_bit_exact_vs_node_by_node"),
-    "hefx_linear_transform_cipher": _row(UNCHANGED, (), ("d_out3 on d_ct or a diagonal",),
-                                         "tests/test_gpu_multiply_sum.py::test_linear_transform_cipher_missing_key_and_aliasing_errors"),
+    # ---- the key-switch host path: one check (ks_run's, through csrc/hefx_ranges.h) for every n, the rotations and the sums
+    # as one list of 2n outputs
+    "hefx_apply_galois": _row(IN_PLACE, ("d_ct_out == d_ct_in",), ("d_ct_out one row into d_ct_in", "d_ct_in one row into d_ct_out"),
+                              f"{G}::test_apply_galois_one_item"),
+    "hefx_apply_galois_batch": _row(IN_PLACE, ("d_ct_out[i] == d_ct_in[i]",),
+                                    ("d_ct_out[1] == d_ct_in[0]", "an input one row into an output", "two outputs one row apart"),
+                                    f"{G}::test_key_switch_batch_aliasing"),
+    "hefx_rotate_multiply_plain_batch": _row(IN_PLACE, ("d_ct_out[i] == d_ct_in[i]",),
+                                             ("d_ct_out[1] == d_ct_in[0]", "an output on a plaintext", "two outputs one row apart"),
+                                             f"{G}::test_key_switch_batch_aliasing"),
+    "hefx_apply_galois_add_batch": _row(IN_PLACE, ("d_acc_out[i] == d_acc_in[i]", "d_ct_out[i] == d_ct_in[i]"),
+                                        ("a sum on the other item's sum, on a rotation output or on an input",
+                                         "d_acc_in[i] one row into d_acc_out[i]", "d_acc_in[0] == d_acc_out[1]"),
+                                        f"{G}::test_apply_galois_add_batch_aliasing"),
+    "hefx_rotate_add_chain": _row(IN_PLACE, ("d_ct_out[i] == d_ct_in[i]",), ("any two of the 2n outputs overlapping",),
+                                  f"{G}::test_rotate_add_chain_aliasing"),
+    "hefx_apply_galois_forest": _row(NO_OVERLAP, (), ("outputs on one another", "an output on an external input", "an output on a plaintext"),
+                                     f"{G}::test_apply_galois_forest_refusals"),
+    "hefx_linear_transform_cipher": _row(NO_OVERLAP, (), ("d_out3 on d_ct", "d_out3 on a diagonal", "a diagonal one row into d_out3"),
+                                         f"{G}::test_linear_transform_cipher_refusals"),
+    "hefx_multiply_sum": _row(NO_OVERLAP, (), ("an output on an input of the other group", "two outputs one row apart"),
+                              f"{G}::test_multiply_sum_refusals"),
 }
 
 # hefx_add_many with d_out == d_in[i]: (n, i) on both sides of every path of add_many_impl -- one launch (n <= 48), two

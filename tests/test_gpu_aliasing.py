@@ -512,8 +512,171 @@ def test_linear_transform_refusals(name):
     case = Case(e, o, bufs)
     for moves in _standard_moves(ins, outs, exact, cross):
         _refused(case, call, moves, ks=True)
-    if name == "hefx_rotate_hoisted_batch":  # one item, no plaintext: the form ks_run's own check does not look at
+    if name == "hefx_rotate_hoisted_batch":  # one item, no plaintext: ks_run's check runs for one item too
         lone = lambda p: lib.hefx_rotate_hoisted_batch(h, L, p["ct"], 1, ke, kk, None, arr([p["o0"]]), None)  # noqa: E731
         for moves in ({"o0": ("row_into", "ct")}, {"ct": ("row_into", "o0")}, {"o0": ("on", "ct")}):
             _refused(case, lone, moves, ks=True)
     _accepted(case, call, want())
+
+
+# ---- the key-switch host path: one rule for every n, the rotations and the sums as one list of outputs -------------------
+def _ks_refused_then_accepted(case, call, moves, want):
+    for m in moves:
+        _refused(case, call, m, ks=True)
+    _accepted(case, call, want)
+
+
+def test_apply_galois_one_item():
+    """hefx_apply_galois: d_ct_out == d_ct_in is served from a scratch copy; an output one row into the input (or the input
+    one row into the output) computed wrong words silently before the check ran for one item -- now refused"""
+    o, e, L, d, elts, key, dkey, rot = _lt_env()
+    lib, _, capi = _lib()
+    assert A.RULES["hefx_apply_galois"]["kind"] == A.IN_PLACE
+    c2 = 2 * L * N
+    ct = _top(o, L, 2)
+    call = lambda p, out="out": lib.hefx_apply_galois(e._h, L, p["in"], elts[0], dkey.ptr, p[out], None)  # noqa: E731
+    case = Case(e, o, [("in", c2, ct), ("out", c2, None)])
+    _ks_refused_then_accepted(case, call, [{"out": ("row_into", "in")}, {"in": ("row_into", "out")}], {"out": rot(ct, 1)})
+    case = Case(e, o, [("in", c2, ct), ("out", c2, None)])
+    _accepted(case, lambda p: call(p, "in"), {"in": rot(ct, 1)})
+
+
+@pytest.mark.parametrize("name", ["hefx_apply_galois_batch", "hefx_rotate_multiply_plain_batch"])
+def test_key_switch_batch_aliasing(name):
+    """n = 2: an item's own in-place rotation is served; the standard overlaps, the cross pair d_ct_out[1] == d_ct_in[0] and
+    an output on a plaintext are refused"""
+    o, e, L, d, elts, key, dkey, rot = _lt_env()
+    lib, arr, capi = _lib()
+    assert A.RULES[name]["kind"] == A.IN_PLACE
+    LN, c2 = L * N, 2 * L * N
+    cts = [o.uniform(L, 2, 90), _top(o, L, 2)]
+    pts = [o.uniform(L, 1, 92 + i)[0] for i in range(2)]
+    ke, kk = capi.u32_array(elts[:2]), arr([dkey.ptr] * 2)
+    fused = name == "hefx_rotate_multiply_plain_batch"
+    bufs = [("i0", c2, cts[0]), ("i1", c2, cts[1])] + ([("p0", LN, pts[0]), ("p1", LN, pts[1])] if fused else []) + [("o0", c2, None), ("o1", c2, None)]
+
+    def call(p, outs="o"):
+        ins, oo = arr([p["i0"], p["i1"]]), arr([p[f"{outs}0"], p[f"{outs}1"]])
+        if fused:
+            return lib.hefx_rotate_multiply_plain_batch(e._h, L, 2, ins, ke, kk, arr([p["p0"], p["p1"]]), oo, None)
+        return lib.hefx_apply_galois_batch(e._h, L, 2, ins, ke, kk, oo, None)
+
+    want = [o.rotate_mulplain(cts[i], elts[i], key, pts[i]) if fused else rot(cts[i], i + 1) for i in range(2)]
+    moves = _standard_moves(["i0", "i1"] + (["p1"] if fused else []), ["o0", "o1"], exact=[("o0", "p0")] if fused else [],
+                            cross=[("o1", "i0")] + ([("o1", "p0")] if fused else []))
+    _ks_refused_then_accepted(Case(e, o, bufs), call, moves, {"o0": want[0], "o1": want[1]})
+    _accepted(Case(e, o, bufs), lambda p: call(p, "i"), {"i0": want[0], "i1": want[1]})
+    e.check_transparent()
+
+
+def _rotate_add_bufs(o, L):
+    c2 = 2 * L * N
+    cts = [o.uniform(L, 2, 110), _top(o, L, 2)]
+    accs = [_top(o, L, 2), o.uniform(L, 2, 111)]
+    bufs = [("i0", c2, cts[0]), ("i1", c2, cts[1]), ("a0", c2, accs[0]), ("a1", c2, accs[1])] + [(x, c2, None) for x in ("s0", "s1", "o0", "o1")]
+    return cts, accs, bufs
+
+
+def test_apply_galois_add_batch_aliasing():
+    """hefx_apply_galois_add_batch, n = 2: d_acc_out[i] == d_acc_in[i] and d_ct_out[i] == d_ct_in[i] are served (together); a
+    sum on the other item's sum, on a rotation output or on an input, d_acc_in[i] one row into d_acc_out[i] and
+    d_acc_in[0] == d_acc_out[1] are refused"""
+    o, e, L, d, elts, key, dkey, rot = _lt_env()
+    lib, arr, capi = _lib()
+    assert A.RULES["hefx_apply_galois_add_batch"]["kind"] == A.IN_PLACE
+    cts, accs, bufs = _rotate_add_bufs(o, L)
+    ke, kk = capi.u32_array(elts[:2]), arr([dkey.ptr] * 2)
+
+    def call(p, sums="s", outs="o"):
+        return lib.hefx_apply_galois_add_batch(e._h, L, 2, arr([p["i0"], p["i1"]]), ke, kk, arr([p["a0"], p["a1"]]),
+                                               arr([p[f"{sums}0"], p[f"{sums}1"]]), arr([p[f"{outs}0"], p[f"{outs}1"]]), None)
+
+    r = [rot(cts[i], i + 1) for i in range(2)]
+    s = [o.add(accs[i], r[i]) for i in range(2)]
+    moves = _standard_moves(["i0", "a1"], ["o0", "o1", "s0", "s1"], cross=[("s1", "s0"), ("s0", "o1"), ("s1", "o1"), ("s0", "i1"), ("s1", "i1"), ("a0", "s1")])
+    moves += [{"a0": ("row_into", "s0")}, {"a1": ("row_into", "s1")}]
+    _ks_refused_then_accepted(Case(e, o, bufs), call, moves, {"o0": r[0], "o1": r[1], "s0": s[0], "s1": s[1]})
+    _accepted(Case(e, o, bufs), lambda p: call(p, "a", "i"), {"i0": r[0], "i1": r[1], "a0": s[0], "a1": s[1]})
+
+
+def test_rotate_add_chain_aliasing():
+    """hefx_rotate_add_chain, n = 2, steps = 3 (level 1 through the front door, one level in each ping-pong direction): any two
+    of the 2n outputs overlapping are refused; d_ct_out[i] == d_ct_in[i] is served; the words are the oracle's rotate and add,
+    step by step"""
+    import itertools
+    o, e, L, d, elts, key, dkey, rot = _lt_env()
+    lib, arr, capi = _lib()
+    assert A.RULES["hefx_rotate_add_chain"]["kind"] == A.IN_PLACE
+    cts, accs, bufs = _rotate_add_bufs(o, L)
+    ke, kk = capi.u32_array(elts[:2]), arr([dkey.ptr] * 2)
+
+    def call(p, outs="o"):
+        return lib.hefx_rotate_add_chain(e._h, L, 2, arr([p["i0"], p["i1"]]), ke, kk, arr([p["a0"], p["a1"]]), arr([p["s0"], p["s1"]]),
+                                         arr([p[f"{outs}0"], p[f"{outs}1"]]), 3, None)
+
+    t, a = list(cts), list(accs)
+    for _ in range(3):
+        t = [rot(t[i], i + 1) for i in range(2)]
+        a = [o.add(a[i], t[i]) for i in range(2)]
+    moves = [{x: (how, y)} for x, y in itertools.combinations(["o0", "o1", "s0", "s1"], 2) for how in ("row_into", "on")]
+    _ks_refused_then_accepted(Case(e, o, bufs), call, moves, {"o0": t[0], "o1": t[1], "s0": a[0], "s1": a[1]})
+    _accepted(Case(e, o, bufs), lambda p: call(p, "i"), {"i0": t[0], "i1": t[1], "s0": a[0], "s1": a[1]})
+
+
+def test_apply_galois_forest_refusals():
+    """hefx_apply_galois_forest, three nodes -- a root, its child, a second root with a fused plaintext: outputs on one another,
+    on an external input or on the plaintext are refused; adjacent, the words of the node-by-node rotations"""
+    o, e, L, d, elts, key, dkey, rot = _lt_env()
+    lib, arr, capi = _lib()
+    assert A.RULES["hefx_apply_galois_forest"]["kind"] == A.NO_OVERLAP
+    LN, c2 = L * N, 2 * L * N
+    ext = [o.uniform(L, 2, 120), _top(o, L, 2)]
+    pt = o.uniform(L, 1, 121)[0]
+    bufs = [("e0", c2, ext[0]), ("e2", c2, ext[1]), ("p2", LN, pt)] + [(f"o{i}", c2, None) for i in range(3)]
+    parent = (C.c_int32 * 3)(-1, 0, -1)
+    ke, kk = capi.u32_array([elts[0], elts[1], elts[1]]), arr([dkey.ptr] * 3)
+    call = lambda p: lib.hefx_apply_galois_forest(e._h, L, 3, parent, arr([p["e0"], None, p["e2"]]), ke, kk, arr([None, None, p["p2"]]),  # noqa: E731
+                                                  arr([p["o0"], p["o1"], p["o2"]]), None)
+    moves = _standard_moves(["e0", "e2", "p2"], ["o0", "o1", "o2"], exact=[("o0", "e0"), ("o2", "e2"), ("o2", "p2")],
+                            cross=[("o1", "o0"), ("o2", "o0"), ("o1", "e2"), ("o0", "p2")])
+    n0 = rot(ext[0], 1)
+    _ks_refused_then_accepted(Case(e, o, bufs), call, moves, {"o0": n0, "o1": rot(n0, 2), "o2": o.rotate_mulplain(ext[1], elts[1], key, pt)})
+    e.check_transparent()
+
+
+def test_linear_transform_cipher_refusals():
+    """hefx_linear_transform_cipher, d = 3: d_out3 on d_ct or on a diagonal and a diagonal one row into d_out3 are refused;
+    adjacent, the words of rotate, multiply and the sum of the products over the oracle"""
+    o, e, L, d, elts, key, dkey, rot = _lt_env()
+    lib, arr, capi = _lib()
+    assert A.RULES["hefx_linear_transform_cipher"]["kind"] == A.NO_OVERLAP
+    c2, c3 = 2 * L * N, 3 * L * N
+    ct = o.uniform(L, 2, 130)
+    diags = [_top(o, L, 2)] + [o.uniform(L, 2, 131 + i) for i in range(1, d)]
+    bufs = [("ct", c2, ct)] + [(f"g{i}", c2, diags[i]) for i in range(d)] + [("out", c3, None)]
+    ke, kk = capi.u32_array(elts), arr([dkey.ptr] * 3)
+    call = lambda p: lib.hefx_linear_transform_cipher(e._h, L, p["ct"], d, arr([p[f"g{i}"] for i in range(d)]), 3, ke, kk, p["out"], None)  # noqa: E731
+    ct_new = o.add(ct, rot(ct, -d))
+    want = o.multiply(ct_new, diags[0])
+    for l in range(1, d):
+        want = o.add(want, o.multiply(rot(ct_new, l), diags[l]))
+    moves = _standard_moves(["ct"] + [f"g{i}" for i in range(d)], ["out"], exact=[("out", "ct"), ("out", "g0"), ("out", "g2")])
+    _ks_refused_then_accepted(Case(e, o, bufs), call, moves, {"out": want})
+
+
+def test_multiply_sum_refusals():
+    """hefx_multiply_sum, n = 4, group = 2: an output on an input of the other group and two outputs one row apart (and the
+    other standard overlaps) are refused; adjacent, the sums of the oracle's products"""
+    o, e = _env()
+    lib, arr, _ = _lib()
+    assert A.RULES["hefx_multiply_sum"]["kind"] == A.NO_OVERLAP
+    L = 3
+    c2, c3 = 2 * L * N, 3 * L * N
+    a = [_top(o, L, 2)] + [o.uniform(L, 2, 140 + i) for i in range(1, 4)]
+    b = [_top(o, L, 2)] + [o.uniform(L, 2, 150 + i) for i in range(1, 4)]
+    bufs = [(f"a{i}", c2, a[i]) for i in range(4)] + [(f"b{i}", c2, b[i]) for i in range(4)] + [("o0", c3, None), ("o1", c3, None)]
+    call = lambda p: lib.hefx_multiply_sum(e._h, L, 4, 2, arr([p[f"a{i}"] for i in range(4)]), arr([p[f"b{i}"] for i in range(4)]),  # noqa: E731
+                                           arr([p["o0"], p["o1"]]), None)
+    moves = _standard_moves(["a0", "a3", "b2"], ["o0", "o1"], exact=[("o0", "a1")], cross=[("o0", "a2"), ("o1", "b0"), ("o1", "o0")])
+    want = {f"o{g}": o.add(o.multiply(a[2 * g], b[2 * g]), o.multiply(a[2 * g + 1], b[2 * g + 1])) for g in range(2)}
+    _ks_refused_then_accepted(Case(e, o, bufs), call, moves, want)
