@@ -197,7 +197,10 @@ int hefx_multiply_plain_batch(hefx_context *ctx, int L, int size, int n, const u
  * allocation included), an input of the call -- ciphertext or plaintext, of ANY group -- or another output:
  * HEFX_ERR_INVALID before anything is submitted (the groups are parallel workgroups of one launch).
  * The canonical residues of the sums, i.e. the bits of n multiply_plain calls followed by add_many.  The pointer
- * arrays are host arrays of device pointers.  Transparency is the caller's check (the plaintexts' zero flags). */
+ * arrays are host arrays of device pointers.  Transparency is the caller's check (the plaintexts' zero flags).
+ * A group longer than a descriptor-ring slot (2 * group + 1 > 10240 pointers) is summed in slot-sized parts and the parts
+ * are added with hefx_add_many, as for hefx_multiply_sum below and with its limit: more than 96 parts (more than 491 424
+ * terms in one group) is HEFX_ERR_UNSUPPORTED "group too long" before anything is submitted. */
 int hefx_multiply_plain_sum(hefx_context *ctx, int L, int size, int n, int group, const uint64_t *const *d_cts,
                             const uint64_t *const *d_pts, uint64_t *const *d_outs, void *stream);
 

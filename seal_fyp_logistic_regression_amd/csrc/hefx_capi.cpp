@@ -311,6 +311,61 @@ static int ensure_scratch(hefx_context *c, size_t words)
     return grow_retiring(c, &c->scratch, &c->scratch_words, words, (size_t)8 << 20, "scratch");
 }
 
+// One slot of the descriptor ring: h its pinned host mirror, d its device copy -- KS_MAX_CHUNK key-switch descriptors or,
+// through htab() / dtab(), a table of RING_SLOT_PTRS pointers.  ring_take hands out the next slot once its previous user has
+// drained; the caller fills h, copies it to d (or wherever the descriptors live) and launches on `s`; ring_commit then
+// owns the slot until that work has run.  Both return the HIP status and leave the slot usable, so a caller that must not
+// return early (ks_run, between fork and join) can carry on.
+struct RingSlot {
+    KsItem *h, *d;
+    unsigned idx;
+    const uint64_t **htab() const { return reinterpret_cast<const uint64_t **>(h); }
+    const u64 *const *dtab() const { return reinterpret_cast<const u64 *const *>(d); }
+};
+constexpr int RING_SLOT_PTRS = (int)(sizeof(KsItem) * KS_MAX_CHUNK / sizeof(void *));
+static hipError_t ring_take(hefx_context *c, RingSlot &r)
+{
+    r.idx = c->ring_next++ % KS_RING;
+    r.h = c->h_items + (size_t)r.idx * KS_MAX_CHUNK;
+    r.d = c->d_items + (size_t)r.idx * KS_MAX_CHUNK;
+    if (!c->ring_busy[r.idx]) return hipSuccess;
+    c->ring_busy[r.idx] = false;
+    return hipEventSynchronize(c->ring_ev[r.idx]);
+}
+static hipError_t ring_commit(hefx_context *c, const RingSlot &r, hipStream_t s)
+{
+    const hipError_t e = hipEventRecord(c->ring_ev[r.idx], s);
+    c->ring_busy[r.idx] = e == hipSuccess;
+    return e;
+}
+
+// The one loop that cuts a batch into slot-sized slices of a pointer table.  An item takes ptrs_per_item pointers and, in
+// the grouped layout (group > 0:  n operands | n operands | one output per group), every group one more; a slice holds
+// whole groups.  table_slice_items is how many items one slice takes at most (callers size scratch by it).
+static int table_slice_items(int ptrs_per_item, int max_slice = 0, int group = 0)
+{
+    const int items = group ? RING_SLOT_PTRS / (ptrs_per_item * group + 1) * group : RING_SLOT_PTRS / ptrs_per_item;
+    return max_slice > 0 && items > max_slice ? max_slice : items;
+}
+// fill(hp, i0, cnt) writes the table of items [i0, i0 + cnt) into the pinned mirror; run(dp, i0, cnt) launches on its
+// device copy and returns a HEFX_* code.
+template <class Fill, class Run>
+static int table_slices(hefx_context *c, int n, int ptrs_per_item, hipStream_t s, Fill fill, Run run, int max_slice = 0, int group = 0)
+{
+    const int slice = table_slice_items(ptrs_per_item, max_slice, group);
+    for (int i0 = 0; i0 < n; i0 += slice) {
+        const int cnt = n - i0 < slice ? n - i0 : slice;
+        const size_t ptrs = (size_t)ptrs_per_item * cnt + (group ? (cnt + group - 1) / group : 0);
+        RingSlot r;
+        HIPCHK(ring_take(c, r));
+        fill(r.htab(), i0, cnt);
+        HIPCHK(hipMemcpyAsync((void *)r.dtab(), r.htab(), sizeof(void *) * ptrs, hipMemcpyHostToDevice, s));
+        if (int rc = run(r.dtab(), i0, cnt)) return rc;
+        HIPCHK(ring_commit(c, r, s));
+    }
+    return HEFX_OK;
+}
+
 extern "C" const char *hefx_last_error(void) { return g_err.c_str(); }
 extern "C" const char *hefx_version(void) { return "hefx 0.1 (gfx950, HIP)"; }
 
@@ -946,21 +1001,17 @@ static int add_many_impl(hefx_context *c, int L, int size, int n, const uint64_t
     // wide sums: one launch reduces groups of 16 through a device pointer table (a ring slot of the key-switch
     // descriptors doubles as the table), then the partials are summed below
     constexpr int TABLE_GROUP = 16;
-    constexpr int TABLE_MAX = (int)(sizeof(KsItem) * KS_MAX_CHUNK / sizeof(void *));
+    constexpr int TABLE_MAX = RING_SLOT_PTRS;
     hipStream_t s = (hipStream_t)stream;
     std::vector<const uint64_t *> partial_ptrs;
-    // inputs [i0, i0 + cnt) -> ceil(cnt / TABLE_GROUP) partial sums at dst (scratch), cnt <= TABLE_MAX
+    // inputs [i0, i0 + cnt) -> ceil(cnt / TABLE_GROUP) partial sums at dst (scratch), cnt <= TABLE_MAX: one slice
     auto table_level = [&](int i0, int cnt, u64 *dst) -> int {
-        const unsigned slot = c->ring_next++ % KS_RING;
-        if (c->ring_busy[slot]) HIPCHK(hipEventSynchronize(c->ring_ev[slot]));
-        const uint64_t **hp = reinterpret_cast<const uint64_t **>(c->h_items + (size_t)slot * KS_MAX_CHUNK);
-        const u64 *const *dp = reinterpret_cast<const u64 *const *>(c->d_items + (size_t)slot * KS_MAX_CHUNK);
-        for (int i = 0; i < cnt; ++i) hp[i] = in[i0 + i];
-        HIPCHK(hipMemcpyAsync((void *)dp, hp, sizeof(void *) * cnt, hipMemcpyHostToDevice, s));
-        HIPCHK(launch_add_many_table(c->T, L, size, dp, cnt, TABLE_GROUP, dst, s));
-        HIPCHK(hipEventRecord(c->ring_ev[slot], s));
-        c->ring_busy[slot] = true;
-        return HEFX_OK;
+        return table_slices(
+            c, cnt, 1, s, [&](const uint64_t **hp, int, int m) { std::copy(in + i0, in + i0 + m, hp); },
+            [&](const u64 *const *dp, int, int m) -> int {
+                HIPCHK(launch_add_many_table(c->T, L, size, dp, m, TABLE_GROUP, dst, s));
+                return HEFX_OK;
+            });
     };
     // out (accumulate: += ) the sum of m blocks of `words` words each, by launches of up to ADD_MANY_GROUP pointers
     auto direct = [&](const uint64_t *const *p, int m, u64 *dst, const uint64_t *first_pt) -> int {
@@ -1007,8 +1058,47 @@ extern "C" int hefx_add_many(hefx_context *c, int L, int size, int n, const uint
     return add_many_impl(c, L, size, n, in, nullptr, out, stream, false);
 }
 
+// The launches of the grouped sums (hefx_multiply_plain_sum / _batch, hefx_multiply_sum) for validated arguments: outs[g] =
+// the sum over group g of a[i] (*) b[i], `size` polynomials each.  launch(d_tab, cnt, group) runs on the device table
+// cnt operands | cnt operands | ceil(cnt / group) outputs.  A group that needs more pointers than a slot (2 * group + 1):
+// slot-sized parts of it are summed into scratch and hefx_add_many adds the parts -- canonical residues of the same
+// integer sums.  At most 2 * ADD_MANY_GROUP parts, the sums hefx_add_many forms without a scratch level of its own (which
+// would land on the parts); a longer group is refused before anything is submitted.
+template <class Launch>
+static int grouped_sums(hefx_context *c, int L, int size, int n, int group, const uint64_t *const *a, const uint64_t *const *b,
+                        uint64_t *const *outs, hipStream_t s, const char *entry, Launch launch)
+{
+    auto submit = [&](int m, int grp, const uint64_t *const *pa, const uint64_t *const *pb, uint64_t *const *po) {
+        return table_slices(
+            c, m, 2, s,
+            [&](const uint64_t **hp, int i0, int cnt) {
+                std::copy(pa + i0, pa + i0 + cnt, hp);
+                std::copy(pb + i0, pb + i0 + cnt, hp + cnt);
+                std::copy(po + i0 / grp, po + i0 / grp + (cnt + grp - 1) / grp, hp + 2 * cnt);
+            },
+            [&](const u64 *const *dp, int, int cnt) -> int {
+                HIPCHK(launch(dp, cnt, grp));
+                return HEFX_OK;
+            },
+            0, grp);
+    };
+    const int part = (RING_SLOT_PTRS - 1) / 2;
+    if (group <= part) return submit(n, group, a, b, outs);
+    if ((group + part - 1) / part > 2 * ADD_MANY_GROUP) return fail(HEFX_ERR_UNSUPPORTED, std::string(entry) + ": group too long");
+    const size_t words = (size_t)size * L * c->n;
+    for (int i0 = 0, g = 0; i0 < n; i0 += group, ++g) {
+        const int len = (n - i0 < group) ? n - i0 : group, nparts = (len + part - 1) / part;
+        if (int rc = ensure_scratch(c, words * nparts)) return rc;
+        std::vector<uint64_t *> pp((size_t)nparts);
+        for (int t = 0; t < nparts; ++t) pp[(size_t)t] = reinterpret_cast<uint64_t *>(c->scratch + (size_t)t * words);
+        if (int rc = submit(len, part, a + i0, b + i0, pp.data())) return rc;
+        if (int rc = add_many_impl(c, L, size, nparts, pp.data(), nullptr, outs[g], s, true)) return rc;
+    }
+    return HEFX_OK;
+}
+
 // entry: the C-ABI entry the call came through (for the message), or nullptr for an engine-internal call on disjoint
-// workspace, which skips the aliasing check (the inner sums of the baby-step/giant-step transform, the parts of a long group)
+// workspace, which skips the aliasing check (the inner sums of the baby-step/giant-step transform)
 static int mulplain_sum_impl(hefx_context *c, int L, int size, int n, int group, const uint64_t *const *cts,
                              const uint64_t *const *pts, uint64_t *const *outs, void *stream, const char *entry)
 {
@@ -1029,41 +1119,9 @@ static int mulplain_sum_impl(hefx_context *c, int L, int size, int n, int group,
                                   {"d_cts", "d_pts"}))
             return rc;
     }
-    // the pointer table travels through a ring slot of the key-switch descriptors; whole groups per slice
-    constexpr int TABLE_MAX = (int)(sizeof(KsItem) * KS_MAX_CHUNK / sizeof(void *));
-    if (2 * group + 1 > TABLE_MAX) {  // a group longer than one table slice: partial sums in scratch, then add_many
-        const int part = (TABLE_MAX - 1) / 2;
-        const size_t words = (size_t)size * L * c->n;
-        for (int g = 0; g < groups; ++g) {
-            const int i0 = g * group, len = (n - i0 < group) ? n - i0 : group, nparts = (len + part - 1) / part;
-            if (int rc = ensure_scratch(c, words * nparts)) return rc;
-            std::vector<uint64_t *> pp(nparts);
-            for (int t = 0; t < nparts; ++t) pp[t] = reinterpret_cast<uint64_t *>(c->scratch + (size_t)t * words);
-            if (int rc = mulplain_sum_impl(c, L, size, len, part, cts + i0, pts + i0, pp.data(), stream, nullptr)) return rc;
-            if (int rc = add_many_impl(c, L, size, nparts, pp.data(), nullptr, outs[g], stream, true)) return rc;
-        }
-        return HEFX_OK;
-    }
-    const int gps = TABLE_MAX / (2 * group + 1);  // groups per slice
     hipStream_t s = (hipStream_t)stream;
-    for (int g0 = 0; g0 < groups; g0 += gps) {
-        const int ng = groups - g0 < gps ? groups - g0 : gps;
-        const int i0 = g0 * group, cnt = (n - i0 < ng * group) ? n - i0 : ng * group;
-        const unsigned slot = c->ring_next++ % KS_RING;
-        if (c->ring_busy[slot]) HIPCHK(hipEventSynchronize(c->ring_ev[slot]));
-        const uint64_t **hp = reinterpret_cast<const uint64_t **>(c->h_items + (size_t)slot * KS_MAX_CHUNK);
-        const u64 *const *dp = reinterpret_cast<const u64 *const *>(c->d_items + (size_t)slot * KS_MAX_CHUNK);
-        for (int i = 0; i < cnt; ++i) {
-            hp[i] = cts[i0 + i];
-            hp[cnt + i] = pts[i0 + i];
-        }
-        for (int g = 0; g < ng; ++g) hp[2 * cnt + g] = outs[g0 + g];
-        HIPCHK(hipMemcpyAsync((void *)dp, hp, sizeof(void *) * (2 * (size_t)cnt + ng), hipMemcpyHostToDevice, s));
-        HIPCHK(launch_mulplain_sum(c->T, L, size, dp, cnt, group, s));
-        HIPCHK(hipEventRecord(c->ring_ev[slot], s));
-        c->ring_busy[slot] = true;
-    }
-    return HEFX_OK;
+    return grouped_sums(c, L, size, n, group, cts, pts, outs, s, entry ? entry : "multiply_plain_sum",
+                        [=](const u64 *const *dp, int cnt, int grp) { return launch_mulplain_sum(c->T, L, size, dp, cnt, grp, s); });
 }
 
 extern "C" int hefx_multiply_plain_sum(hefx_context *c, int L, int size, int n, int group,
@@ -1073,151 +1131,69 @@ extern "C" int hefx_multiply_plain_sum(hefx_context *c, int L, int size, int n, 
     return mulplain_sum_impl(c, L, size, n, group, cts, pts, outs, stream, "multiply_plain_sum");
 }
 
-// (the product kernels read every operand word a lane needs before the lane writes, but a lane's three output words lie in
-// three polynomials and its reads in two: an output that shares bytes with an operand is read by other lanes after it is
+// The one tensor product behind hefx_multiply, hefx_square, hefx_multiply_batch, hefx_multiply_sizes[_batch] and
+// hefx_bfv_multiply: n products a[i] (sa polynomials) x b[i] (sb) -> out[i] (sa + sb - 1).  batch: through a device pointer
+// table, else n == 1 and one direct launch.  entry names the caller in a refusal; nullptr: operands in engine workspace,
+// disjoint by construction, no aliasing check.
+// (The kernel reads every operand word a lane needs before the lane writes, but a lane's output words lie in sa + sb - 1
+// polynomials and its reads in sa and sb: an output that shares bytes with an operand is read by other lanes after it is
 // written.  Refused, the exact alias included.)
-static int multiply_impl(hefx_context *c, int L, const uint64_t *a, const uint64_t *b, uint64_t *out3, void *stream,
-                         const char *entry)
+static int multiply_common(hefx_context *c, int L, int n, int sa, const uint64_t *const *a, int sb, const uint64_t *const *b,
+                           uint64_t *const *out, void *stream, const char *entry, bool batch)
 {
     CTXCHK(c);
     if (int rc = check_level(c, L)) return rc;
-    if (!a || !b || !out3) return fail(HEFX_ERR_INVALID, "null operand");
-    if (entry) {
-        const size_t poly_b = (size_t)L * c->n * sizeof(u64);
-        if (int rc = check_ranges(entry, 1, &out3, 3 * poly_b, {{&a, 1, 2 * poly_b}, {&b, 1, 2 * poly_b}}, {"d_a", "d_b"})) return rc;
-    }
-    HIPCHK(launch_multiply(c->T, L, (const u64 *)a, (const u64 *)b, (u64 *)out3, (hipStream_t)stream));
-    return HEFX_OK;
-}
-extern "C" int hefx_multiply(hefx_context *c, int L, const uint64_t *a, const uint64_t *b, uint64_t *out3,
-                             void *stream)
-{
-    return multiply_impl(c, L, a, b, out3, stream, "multiply");
-}
-// check: false when hefx_multiply_sizes_batch has already held the same buffers to the same rule
-static int multiply_batch_impl(hefx_context *c, int L, int n, const uint64_t *const *a, const uint64_t *const *b,
-                               uint64_t *const *out3, void *stream, bool check)
-{
-    CTXCHK(c);
-    if (int rc = check_level(c, L)) return rc;
-    if (n < 1 || !a || !b || !out3) return fail(HEFX_ERR_INVALID, "bad multiply batch arguments");
-    for (int i = 0; i < n; ++i)
-        if (!a[i] || !b[i] || !out3[i]) return fail(HEFX_ERR_INVALID, "null operand in multiply batch");
-    if (check) {
-        const size_t poly_b = (size_t)L * c->n * sizeof(u64);
-        if (int rc = check_ranges("multiply_batch", (size_t)n, out3, 3 * poly_b, {{a, (size_t)n, 2 * poly_b}, {b, (size_t)n, 2 * poly_b}},
-                                  {"d_a", "d_b"}))
-            return rc;
-    }
-    constexpr int SLICE = (int)(sizeof(KsItem) * KS_MAX_CHUNK / sizeof(void *)) / 3;  // pointer-table ring slot
-    hipStream_t s = (hipStream_t)stream;
-    for (int i0 = 0; i0 < n; i0 += SLICE) {
-        const int cnt = n - i0 < SLICE ? n - i0 : SLICE;
-        const unsigned slot = c->ring_next++ % KS_RING;
-        if (c->ring_busy[slot]) HIPCHK(hipEventSynchronize(c->ring_ev[slot]));
-        const uint64_t **hp = reinterpret_cast<const uint64_t **>(c->h_items + (size_t)slot * KS_MAX_CHUNK);
-        const u64 *const *dp = reinterpret_cast<const u64 *const *>(c->d_items + (size_t)slot * KS_MAX_CHUNK);
-        for (int i = 0; i < cnt; ++i) {
-            hp[i] = a[i0 + i];
-            hp[cnt + i] = b[i0 + i];
-            hp[2 * cnt + i] = out3[i0 + i];
-        }
-        HIPCHK(hipMemcpyAsync((void *)dp, hp, sizeof(void *) * 3 * (size_t)cnt, hipMemcpyHostToDevice, s));
-        HIPCHK(launch_multiply_table(c->T, L, dp, cnt, s));
-        HIPCHK(hipEventRecord(c->ring_ev[slot], s));
-        c->ring_busy[slot] = true;
-    }
-    return HEFX_OK;
-}
-extern "C" int hefx_multiply_batch(hefx_context *c, int L, int n, const uint64_t *const *a, const uint64_t *const *b,
-                                   uint64_t *const *out3, void *stream)
-{
-    return multiply_batch_impl(c, L, n, a, b, out3, stream, true);
-}
-extern "C" int hefx_square(hefx_context *c, int L, const uint64_t *a, uint64_t *out3, void *stream)
-{
-    return multiply_impl(c, L, a, a, out3, stream, "square");
-}
-
-template <class Fill, class Run>
-static int table_slices(hefx_context *c, int n, int ptrs_per_item, hipStream_t s, Fill fill, Run run, int max_slice = 0);
-
-static int check_ct_sizes(int sa, int sb)
-{
-    if (sa < 2 || sb < 2)
-        return fail(HEFX_ERR_INVALID, "multiply: every operand needs at least 2 polynomials");
+    if (sa < 2 || sb < 2) return fail(HEFX_ERR_INVALID, "multiply: every operand needs at least 2 polynomials");
     if (sa + sb - 1 > HEFX_CT_SIZE_MAX)
         return fail(HEFX_ERR_INVALID, "multiply: the result would have more than HEFX_CT_SIZE_MAX = " +
                                           std::to_string(HEFX_CT_SIZE_MAX) + " polynomials");
-    return HEFX_OK;
-}
-
-extern "C" int hefx_multiply_sizes_batch(hefx_context *c, int L, int n, int sa, const uint64_t *const *a, int sb,
-                                         const uint64_t *const *b, uint64_t *const *out, void *stream)
-{
-    CTXCHK(c);
-    if (int rc = check_level(c, L)) return rc;
-    if (int rc = check_ct_sizes(sa, sb)) return rc;
-    if (n < 1 || !a || !b || !out) return fail(HEFX_ERR_INVALID, "bad multiply batch arguments");
+    if (n < 1 || !a || !b || !out) return fail(HEFX_ERR_INVALID, batch ? "bad multiply batch arguments" : "null operand");
     for (int i = 0; i < n; ++i)
-        if (!a[i] || !b[i] || !out[i]) return fail(HEFX_ERR_INVALID, "null operand in multiply batch");
-    const size_t poly_b = (size_t)L * c->n * sizeof(u64);
-    if (int rc = check_ranges("multiply", (size_t)n, out, (size_t)(sa + sb - 1) * poly_b, {{a, (size_t)n, sa * poly_b}, {b, (size_t)n, sb * poly_b}},
-                              {"d_a", "d_b"}))
-        return rc;
-    if (sa == 2 && sb == 2) return multiply_batch_impl(c, L, n, a, b, out, stream, false);
+        if (!a[i] || !b[i] || !out[i]) return fail(HEFX_ERR_INVALID, batch ? "null operand in multiply batch" : "null operand");
+    if (entry) {
+        const size_t poly_b = (size_t)L * c->n * sizeof(u64);
+        if (int rc = check_ranges(entry, (size_t)n, out, (size_t)(sa + sb - 1) * poly_b, {{a, (size_t)n, sa * poly_b}, {b, (size_t)n, sb * poly_b}},
+                                  {"d_a", "d_b"}))
+            return rc;
+    }
     hipStream_t s = (hipStream_t)stream;
+    if (!batch) {
+        HIPCHK(launch_multiply_sizes(c->T, L, sa, sb, (const u64 *)a[0], (const u64 *)b[0], (u64 *)out[0], nullptr, 1, s));
+        return HEFX_OK;
+    }
     return table_slices(
         c, n, 3, s,
         [&](const uint64_t **hp, int i0, int cnt) {
             for (int i = 0; i < cnt; ++i) hp[i] = a[i0 + i], hp[cnt + i] = b[i0 + i], hp[2 * cnt + i] = out[i0 + i];
         },
-        [&](const u64 *const *dp, int, int cnt) {
-            return launch_multiply_sizes(c->T, L, sa, sb, nullptr, nullptr, nullptr, dp, cnt, s);
+        [&](const u64 *const *dp, int, int cnt) -> int {
+            HIPCHK(launch_multiply_sizes(c->T, L, sa, sb, nullptr, nullptr, nullptr, dp, cnt, s));
+            return HEFX_OK;
         });
 }
-
+extern "C" int hefx_multiply(hefx_context *c, int L, const uint64_t *a, const uint64_t *b, uint64_t *out3,
+                             void *stream)
+{
+    return multiply_common(c, L, 1, 2, &a, 2, &b, &out3, stream, "multiply", false);
+}
+extern "C" int hefx_square(hefx_context *c, int L, const uint64_t *a, uint64_t *out3, void *stream)
+{
+    return multiply_common(c, L, 1, 2, &a, 2, &a, &out3, stream, "square", false);
+}
+extern "C" int hefx_multiply_batch(hefx_context *c, int L, int n, const uint64_t *const *a, const uint64_t *const *b,
+                                   uint64_t *const *out3, void *stream)
+{
+    return multiply_common(c, L, n, 2, a, 2, b, out3, stream, "multiply_batch", true);
+}
+extern "C" int hefx_multiply_sizes_batch(hefx_context *c, int L, int n, int sa, const uint64_t *const *a, int sb,
+                                         const uint64_t *const *b, uint64_t *const *out, void *stream)
+{
+    return multiply_common(c, L, n, sa, a, sb, b, out, stream, "multiply", true);
+}
 extern "C" int hefx_multiply_sizes(hefx_context *c, int L, int sa, const uint64_t *a, int sb, const uint64_t *b,
                                    uint64_t *out, void *stream)
 {
-    CTXCHK(c);
-    if (int rc = check_level(c, L)) return rc;
-    if (int rc = check_ct_sizes(sa, sb)) return rc;
-    if (!a || !b || !out) return fail(HEFX_ERR_INVALID, "null operand");
-    const size_t poly_b = (size_t)L * c->n * sizeof(u64);
-    if (int rc = check_ranges("multiply", 1, &out, (size_t)(sa + sb - 1) * poly_b, {{&a, 1, sa * poly_b}, {&b, 1, sb * poly_b}}, {"d_a", "d_b"}))
-        return rc;
-    if (sa == 2 && sb == 2) return multiply_impl(c, L, a, b, out, stream, nullptr);
-    HIPCHK(launch_multiply_sizes(c->T, L, sa, sb, (const u64 *)a, (const u64 *)b, (u64 *)out, nullptr, 1, (hipStream_t)stream));
-    return HEFX_OK;
-}
-
-// the launches of hefx_multiply_sum for validated arguments whose groups fit a table slice (2 * group + 1 pointers): the
-// pointer table travels through a ring slot of the key-switch descriptors, whole groups per slice
-static int mul_sum_submit(hefx_context *c, int L, int n, int group, const uint64_t *const *a, const uint64_t *const *b,
-                          uint64_t *const *outs, hipStream_t s)
-{
-    constexpr int TABLE_MAX = (int)(sizeof(KsItem) * KS_MAX_CHUNK / sizeof(void *));
-    const int groups = (n + group - 1) / group;
-    const int gps = TABLE_MAX / (2 * group + 1);  // groups per slice
-    for (int g0 = 0; g0 < groups; g0 += gps) {
-        const int ng = groups - g0 < gps ? groups - g0 : gps;
-        const int i0 = g0 * group, cnt = (n - i0 < ng * group) ? n - i0 : ng * group;
-        const unsigned slot = c->ring_next++ % KS_RING;
-        if (c->ring_busy[slot]) HIPCHK(hipEventSynchronize(c->ring_ev[slot]));
-        const uint64_t **hp = reinterpret_cast<const uint64_t **>(c->h_items + (size_t)slot * KS_MAX_CHUNK);
-        const u64 *const *dp = reinterpret_cast<const u64 *const *>(c->d_items + (size_t)slot * KS_MAX_CHUNK);
-        for (int i = 0; i < cnt; ++i) {
-            hp[i] = a[i0 + i];
-            hp[cnt + i] = b[i0 + i];
-        }
-        for (int g = 0; g < ng; ++g) hp[2 * cnt + g] = outs[g0 + g];
-        HIPCHK(hipMemcpyAsync((void *)dp, hp, sizeof(void *) * (2 * (size_t)cnt + ng), hipMemcpyHostToDevice, s));
-        HIPCHK(launch_mul_sum(c->T, L, dp, cnt, group, s));
-        HIPCHK(hipEventRecord(c->ring_ev[slot], s));
-        c->ring_busy[slot] = true;
-    }
-    return HEFX_OK;
+    return multiply_common(c, L, 1, sa, &a, sb, &b, &out, stream, "multiply", false);
 }
 
 extern "C" int hefx_multiply_sum(hefx_context *c, int L, int n, int group, const uint64_t *const *a,
@@ -1240,23 +1216,8 @@ extern "C" int hefx_multiply_sum(hefx_context *c, int L, int n, int group, const
                               {"d_a", "d_b"}))
         return rc;
     hipStream_t s = (hipStream_t)stream;
-    constexpr int TABLE_MAX = (int)(sizeof(KsItem) * KS_MAX_CHUNK / sizeof(void *));
-    // A group longer than one table slice (2 * group + 1 pointers): slice-sized parts' sums land in scratch and
-    // hefx_add_many (size 3) adds them, as hefx_multiply_plain_sum does -- canonical residues of the same integer sums.
-    // At most 2 * ADD_MANY_GROUP parts per group: the sums hefx_add_many forms without a scratch level of its own.
-    const int part = 2 * group + 1 > TABLE_MAX ? (TABLE_MAX - 1) / 2 : group;
-    if (part >= group) return mul_sum_submit(c, L, n, group, a, b, outs, s);
-    if ((group + part - 1) / part > 2 * ADD_MANY_GROUP) return fail(HEFX_ERR_UNSUPPORTED, "multiply_sum: group too long");
-    const size_t words = 3 * (size_t)L * c->n;
-    for (int g = 0; g < groups; ++g) {
-        const int i0 = g * group, len = (n - i0 < group) ? n - i0 : group, nparts = (len + part - 1) / part;
-        if (int rc = ensure_scratch(c, words * nparts)) return rc;
-        std::vector<uint64_t *> pp((size_t)nparts);
-        for (int t = 0; t < nparts; ++t) pp[(size_t)t] = reinterpret_cast<uint64_t *>(c->scratch + (size_t)t * words);
-        if (int rc = mul_sum_submit(c, L, len, part, a + i0, b + i0, pp.data(), s)) return rc;
-        if (int rc = add_many_impl(c, L, 3, nparts, pp.data(), nullptr, outs[g], stream, true)) return rc;
-    }
-    return HEFX_OK;
+    return grouped_sums(c, L, 3, n, group, a, b, outs, s, "multiply_sum",
+                        [=](const u64 *const *dp, int cnt, int grp) { return launch_mul_sum(c->T, L, dp, cnt, grp, s); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1612,15 +1573,12 @@ static int ks_run(hefx_context *c, int L, const KsRequest &rq, void *stream)
     ++c->stat_ks_calls;
     for (int base = 0; base < n && herr == hipSuccess; base += chunk, ++ci) {
         const int cnt = (n - base < chunk) ? n - base : chunk;
-        const unsigned slot = c->ring_next++ % KS_RING;
-        if (c->ring_busy[slot]) {  // its previous chunk has drained
-            KS_TRY(hipEventSynchronize(c->ring_ev[slot]));
-            c->ring_busy[slot] = false;
-        }
-        KsItem *hb = c->h_items + (size_t)slot * KS_MAX_CHUNK, *db = c->d_items + (size_t)slot * KS_MAX_CHUNK;
+        RingSlot ring;
+        KS_TRY(ring_take(c, ring));  // (its previous chunk has drained)
+        KsItem *hb = ring.h, *db = ring.d;
         KsScratch S = ks_scratch_at(c, L, cnt, c->scratch + scratch_off + (two ? (size_t)(ci % ns) * half_words : 0));
         S.qmod = c->d_qmod;
-        S.gate = c->d_gate + slot;
+        S.gate = c->d_gate + ring.idx;
         S.gate_hits = c->d_gate + KS_RING;
         if (++c->gate_seq == 0) c->gate_seq = 1;
         S.gate_tag = c->gate_seq;
@@ -1689,7 +1647,7 @@ static int ks_run(hefx_context *c, int L, const KsRequest &rq, void *stream)
         c->stat_ks_items += (uint64_t)cnt, c->stat_ks_hoisted += nsrc ? (uint64_t)cnt : 0, ++c->stat_ks_chunks;
         if (!small) KS_TRY(hipMemcpyAsync(db, hb, sizeof(KsItem) * (cnt + nsrc), hipMemcpyHostToDevice, cs));
         KS_TRY(launch_keyswitch_chunk(c->T, L, cnt, db, relin, S, chunk_alias, small ? hb : nullptr, quarter, cs, prof, nsrc));
-        if (herr == hipSuccess && hipEventRecord(c->ring_ev[slot], cs) == hipSuccess) c->ring_busy[slot] = true;
+        if (herr == hipSuccess) (void)ring_commit(c, ring, cs);
     }
 #undef KS_TRY
     if (const hipError_t ej = ks_join(c, user, two ? ns : 0); ej != hipSuccess && herr == hipSuccess)
@@ -1961,28 +1919,6 @@ static int rescale_common(hefx_context *c, int L, int size, int count, const uin
     return HEFX_OK;
 }
 
-// Pointer tables of the *_batch entries travel through a ring slot of the key-switch descriptors (pinned host mirror
-// -> device copy, one async copy per slice).  fill(hp, i0, cnt) writes the slice's table; run(dp, cnt) launches on it.
-template <class Fill, class Run>
-static int table_slices(hefx_context *c, int n, int ptrs_per_item, hipStream_t s, Fill fill, Run run, int max_slice)
-{
-    int SLICE = (int)(sizeof(KsItem) * KS_MAX_CHUNK / sizeof(void *)) / ptrs_per_item;
-    if (max_slice > 0 && SLICE > max_slice) SLICE = max_slice;
-    for (int i0 = 0; i0 < n; i0 += SLICE) {
-        const int cnt = n - i0 < SLICE ? n - i0 : SLICE;
-        const unsigned slot = c->ring_next++ % KS_RING;
-        if (c->ring_busy[slot]) HIPCHK(hipEventSynchronize(c->ring_ev[slot]));
-        const uint64_t **hp = reinterpret_cast<const uint64_t **>(c->h_items + (size_t)slot * KS_MAX_CHUNK);
-        const u64 *const *dp = reinterpret_cast<const u64 *const *>(c->d_items + (size_t)slot * KS_MAX_CHUNK);
-        fill(hp, i0, cnt);
-        HIPCHK(hipMemcpyAsync((void *)dp, hp, sizeof(void *) * (size_t)ptrs_per_item * cnt, hipMemcpyHostToDevice, s));
-        HIPCHK(run(dp, i0, cnt));
-        HIPCHK(hipEventRecord(c->ring_ev[slot], s));
-        c->ring_busy[slot] = true;
-    }
-    return HEFX_OK;
-}
-
 extern "C" int hefx_rescale_to_next_batch(hefx_context *c, int L, int size, int n, const uint64_t *const *in,
                                           uint64_t *const *out, void *stream)
 {
@@ -1997,16 +1933,16 @@ extern "C" int hefx_rescale_to_next_batch(hefx_context *c, int L, int size, int 
         const size_t rows_b = (size_t)size * c->n * sizeof(u64);
         if (int rc = check_ranges("rescale_to_next_batch", (size_t)n, out, rows_b * (L - 1), {{in, (size_t)n, rows_b * L}}, {"d_in"})) return rc;
     }
-    const int SLICE = (int)(sizeof(KsItem) * KS_MAX_CHUNK / sizeof(void *)) / 2;
-    if (int rc = ensure_scratch(c, (size_t)c->n * size * (n < SLICE ? n : SLICE))) return rc;
+    if (int rc = ensure_scratch(c, (size_t)c->n * size * std::min(n, table_slice_items(2)))) return rc;
     const bool rounded = c->rescale_mode == HEFX_RESCALE_ROUND;
     return table_slices(
         c, n, 2, (hipStream_t)stream,
         [&](const uint64_t **hp, int i0, int cnt) {
             for (int i = 0; i < cnt; ++i) hp[i] = in[i0 + i], hp[cnt + i] = out[i0 + i];
         },
-        [&](const u64 *const *dp, int, int cnt) {
-            return launch_rescale(c->T, L, size, cnt, nullptr, nullptr, dp, c->scratch, rounded, (hipStream_t)stream);
+        [&](const u64 *const *dp, int, int cnt) -> int {
+            HIPCHK(launch_rescale(c->T, L, size, cnt, nullptr, nullptr, dp, c->scratch, rounded, (hipStream_t)stream));
+            return HEFX_OK;
         });
 }
 
@@ -2029,8 +1965,9 @@ static int addsub_batch(hefx_context *c, bool sub, int L, int size, int n, const
         [&](const uint64_t **hp, int i0, int cnt) {
             for (int i = 0; i < cnt; ++i) hp[i] = a[i0 + i], hp[cnt + i] = b[i0 + i], hp[2 * cnt + i] = out[i0 + i];
         },
-        [&](const u64 *const *dp, int, int cnt) {
-            return launch_addsub_table(c->T, sub, L, size, dp, cnt, (hipStream_t)stream);
+        [&](const u64 *const *dp, int, int cnt) -> int {
+            HIPCHK(launch_addsub_table(c->T, sub, L, size, dp, cnt, (hipStream_t)stream));
+            return HEFX_OK;
         });
 }
 extern "C" int hefx_add_batch(hefx_context *c, int L, int size, int n, const uint64_t *const *a,
@@ -2477,13 +2414,14 @@ static int encode_batch_impl(hefx_context *c, int L, const double *h_re, const d
     hipStream_t s = (hipStream_t)stream;
     return table_slices(
         c, count, 1, s, [&](const uint64_t **hp, int i0, int cnt) { for (int i = 0; i < cnt; ++i) hp[i] = d_outs[i0 + i]; },
-        [&](const u64 *const *dp, int i0, int cnt) -> hipError_t {
+        [&](const u64 *const *dp, int i0, int cnt) -> int {
             // (the encode sizes its own staging; the scratch region is only this call's output area)
-            if (ensure_scratch(c, words * (size_t)cnt) != HEFX_OK) return hipErrorOutOfMemory;
-            if (encode_impl(c, L, h_re + (size_t)i0 * nvalues, h_im ? h_im + (size_t)i0 * nvalues : nullptr, nvalues, cnt, scale,
-                            (uint64_t *)c->scratch, s, wide) != HEFX_OK)
-                return hipErrorUnknown;
-            return launch_scatter_rows(c->scratch, dp, cnt, words, s);
+            if (int rc = ensure_scratch(c, words * (size_t)cnt)) return rc;
+            if (int rc = encode_impl(c, L, h_re + (size_t)i0 * nvalues, h_im ? h_im + (size_t)i0 * nvalues : nullptr, nvalues, cnt,
+                                     scale, (uint64_t *)c->scratch, s, wide))
+                return rc;
+            HIPCHK(launch_scatter_rows(c->scratch, dp, cnt, words, s));
+            return HEFX_OK;
         },
         cap);
 }
@@ -3136,13 +3074,11 @@ static int lt2_impl(hefx_context *c, int L, const uint64_t *ct, int d, int nterm
     // time) into the workspace, the slot owned until its copy has run -- no wait for the stream
     for (size_t i0 = 0; i0 < items.size(); i0 += KS_MAX_CHUNK) {
         const size_t cnt = std::min<size_t>(KS_MAX_CHUNK, items.size() - i0);
-        const unsigned slot = c->ring_next++ % KS_RING;
-        if (c->ring_busy[slot]) HIPCHK(hipEventSynchronize(c->ring_ev[slot]));
-        KsItem *hb = c->h_items + (size_t)slot * KS_MAX_CHUNK;
-        memcpy(hb, items.data() + i0, sizeof(KsItem) * cnt);
-        HIPCHK(hipMemcpyAsync(d_items + i0, hb, sizeof(KsItem) * cnt, hipMemcpyHostToDevice, s));
-        HIPCHK(hipEventRecord(c->ring_ev[slot], s));
-        c->ring_busy[slot] = true;
+        RingSlot ring;
+        HIPCHK(ring_take(c, ring));
+        memcpy(ring.h, items.data() + i0, sizeof(KsItem) * cnt);
+        HIPCHK(hipMemcpyAsync(d_items + i0, ring.h, sizeof(KsItem) * cnt, hipMemcpyHostToDevice, s));
+        HIPCHK(ring_commit(c, ring, s));
     }
     HIPCHK(launch_lt2_decompose(c->T, L, d_items, d_items + 1, nrot, S, (const u64 *)ct_new, partial_s, partial_c0,
                                 (u64 *)cbuf, s));
@@ -3297,16 +3233,15 @@ extern "C" int hefx_encrypt_batch(hefx_context *c, int L, int n, const uint64_t 
                 hp[cnt + i] = outs[i0 + i];
             }
         },
-        [&](const u64 *const *dp, int i0, int cnt) -> hipError_t {  // cnt <= cap: one slice, one set of launches
+        [&](const u64 *const *dp, int i0, int cnt) -> int {  // cnt <= cap: one slice, one set of launches
             u64 *u = c->scratch, *ee = u + (size_t)cnt * rowsz;
             const uint64_t sid = 4 * (first_stream_id + (uint64_t)i0);
-            hipError_t e = launch_sample(c->T, SAMPLE_TERNARY, k, c->noise, sid + 0, cnt, L, 0, u, s, 4);
-            if (e == hipSuccess) e = launch_sample(c->T, SAMPLE_NOISE, k, c->noise, sid + 1, cnt, L, 0, ee, s, 4);
-            if (e == hipSuccess)
-                e = launch_sample(c->T, SAMPLE_NOISE, k, c->noise, sid + 2, cnt, L, 0, ee + (size_t)cnt * rowsz, s, 4);
-            if (e == hipSuccess) e = launch_ntt(c->T, false, u, 3 * cnt, L, 0, s);
-            if (e == hipSuccess) e = launch_encrypt_combine_table(c->T, L, cnt, (const u64 *)pk, u, ee, dp, s);
-            return e;
+            HIPCHK(launch_sample(c->T, SAMPLE_TERNARY, k, c->noise, sid + 0, cnt, L, 0, u, s, 4));
+            HIPCHK(launch_sample(c->T, SAMPLE_NOISE, k, c->noise, sid + 1, cnt, L, 0, ee, s, 4));
+            HIPCHK(launch_sample(c->T, SAMPLE_NOISE, k, c->noise, sid + 2, cnt, L, 0, ee + (size_t)cnt * rowsz, s, 4));
+            HIPCHK(launch_ntt(c->T, false, u, 3 * cnt, L, 0, s));
+            HIPCHK(launch_encrypt_combine_table(c->T, L, cnt, (const u64 *)pk, u, ee, dp, s));
+            return HEFX_OK;
         },
         cap);
 }
@@ -3591,9 +3526,10 @@ extern "C" int hefx_refresh_batch(hefx_context *c, int L_in, int size, int L_out
                 hp[2 * cnt + i] = cts[i0 + i];
             }
         },
-        [&](const u64 *const *dp, int i0, int cnt) -> hipError_t {
-            return refresh_group(c, L_in, size, L_out, cnt, nullptr, nullptr, dp, (const u64 *)sk, (const u64 *)pk, k,
-                                 first_stream_id + (uint64_t)i0, s);
+        [&](const u64 *const *dp, int i0, int cnt) -> int {
+            HIPCHK(refresh_group(c, L_in, size, L_out, cnt, nullptr, nullptr, dp, (const u64 *)sk, (const u64 *)pk, k,
+                                 first_stream_id + (uint64_t)i0, s));
+            return HEFX_OK;
         },
         cap);
 }
@@ -3782,10 +3718,9 @@ extern "C" int hefx_bfv_multiply(hefx_bfv *b, int sa, const uint64_t *a, int sb,
         HIPCHK(bfv_extend(b, b->lift_mul, A, sb, (const u64 *)bb, wb, s));
         HIPCHK(launch_ntt(T, false, wb, sb, A, 0, s));
     }
-    if (sa == 2 && sb == 2)
-        HIPCHK(launch_multiply(T, A, wa, wb, prod, s));
-    else
-        HIPCHK(launch_multiply_sizes(T, A, sa, sb, wa, wb, prod, nullptr, 1, s));
+    const uint64_t *pa = (const uint64_t *)wa, *pb = (const uint64_t *)wb;
+    uint64_t *po = (uint64_t *)prod;
+    if (int rc = multiply_common(b->wk, A, 1, sa, &pa, sb, &pb, &po, stream, nullptr, false)) return rc;
     HIPCHK(launch_ntt(T, true, prod, sr, A, 0, s));
     BfvRoundTables R{b->d_tab, b->d_tab + A, b->wk->d_qmod, b->tmod};
     HIPCHK(launch_bfv_round(T, R, A, L, false, sr, prod, wpoly, (u64 *)out, s));

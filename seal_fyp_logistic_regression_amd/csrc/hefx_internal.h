@@ -130,9 +130,6 @@ hipError_t launch_mulplain_sum(const DevTables &T, int L, int size, const u64 *c
                                hipStream_t s);
 // table: n a-pointers | n b-pointers | ceil(n/group) size-3 output pointers (device memory)
 hipError_t launch_mul_sum(const DevTables &T, int L, const u64 *const *d_tab, int n, int group, hipStream_t s);
-// table: n a-pointers | n b-pointers | n output pointers (device memory)
-hipError_t launch_multiply_table(const DevTables &T, int L, const u64 *const *d_tab, int n, hipStream_t s);
-hipError_t launch_multiply(const DevTables &T, int L, const u64 *a, const u64 *b, u64 *out3, hipStream_t s);
 // sa x sb -> sa+sb-1 polynomials (2 <= sa, sb; sa+sb-1 <= HEFX_CT_SIZE_MAX); d_tab == nullptr: a x b -> out, otherwise n
 // products through the device table  n a-pointers | n b-pointers | n output pointers  (a, b, out unused)
 hipError_t launch_multiply_sizes(const DevTables &T, int L, int sa, int sb, const u64 *a, const u64 *b, u64 *out,

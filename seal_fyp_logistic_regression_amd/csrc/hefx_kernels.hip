@@ -437,83 +437,6 @@ hipError_t launch_add_many(const DevTables &T, int L, int size, const PtrGroup &
     return hipGetLastError();
 }
 
-// K3/K11: size-2 x size-2 tensor product: c0=a0b0, c1=a0b1+a1b0, c2=a1b1 (b==a gives square)
-__global__ __launch_bounds__(256) void multiply_kernel(DevTables T, int L, size_t pairs_per_poly,
-                                                       const ulonglong2 *__restrict__ a,
-                                                       const ulonglong2 *__restrict__ b, ulonglong2 *__restrict__ out)
-{
-    const int logn = T.logn;
-    for (size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x; w < pairs_per_poly;
-         w += (size_t)gridDim.x * blockDim.x) {
-        const int j = (int)(w >> (logn - 1));
-        const ModConst mc = T.mods[j];
-        ulonglong2 a0 = a[w], a1 = a[w + pairs_per_poly], b0 = b[w], b1 = b[w + pairs_per_poly];
-        ulonglong2 c0, c1, c2;
-        c0.x = mulmod(a0.x, b0.x, mc);
-        c0.y = mulmod(a0.y, b0.y, mc);
-        c2.x = mulmod(a1.x, b1.x, mc);
-        c2.y = mulmod(a1.y, b1.y, mc);
-        {
-            u64 lo = 0, hi = 0;
-            mac128(lo, hi, a0.x, b1.x);
-            mac128(lo, hi, a1.x, b0.x);
-            c1.x = barrett128(lo, hi, mc);
-            lo = hi = 0;
-            mac128(lo, hi, a0.y, b1.y);
-            mac128(lo, hi, a1.y, b0.y);
-            c1.y = barrett128(lo, hi, mc);
-        }
-        gst16(out + w, c0);
-        gst16(out + w + pairs_per_poly, c1);
-        gst16(out + w + 2 * pairs_per_poly, c2);
-    }
-}
-
-hipError_t launch_multiply(const DevTables &T, int L, const u64 *a, const u64 *b, u64 *out3, hipStream_t s)
-{
-    const size_t pairs = (size_t)L * ((size_t)1 << T.logn) / 2;
-    int blocks = (int)((pairs + 255) / 256);
-    if (blocks > 256 * 8) blocks = 256 * 8;
-    hipLaunchKernelGGL(multiply_kernel, dim3(blocks), dim3(256), 0, s, T, L, pairs,
-                       reinterpret_cast<const ulonglong2 *>(a), reinterpret_cast<const ulonglong2 *>(b),
-                       reinterpret_cast<ulonglong2 *>(out3));
-    return hipGetLastError();
-}
-
-// n independent size-2 x size-2 products through a DEVICE pointer table  a[0..n) | b[0..n) | out[0..n)  (the rows of
-// an encrypted data set times one weight ciphertext, logistic_regression_ckks.cpp:217-220 -> helper.h:432): one
-// launch instead of n.  Same arithmetic as multiply_kernel.
-__global__ __launch_bounds__(256) void multiply_table_kernel(DevTables T, int L, size_t pairs_per_poly,
-                                                             const u64 *const *__restrict__ tab, int n)
-{
-    const int logn = T.logn;
-    const int item = blockIdx.y;
-    const ulonglong2 *__restrict__ a = reinterpret_cast<const ulonglong2 *>((tab[item]));
-    const ulonglong2 *__restrict__ b = reinterpret_cast<const ulonglong2 *>((tab[n + item]));
-    ulonglong2 *__restrict__ out = reinterpret_cast<ulonglong2 *>((const_cast<u64 *>(tab[2 * n + item])));
-    for (size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x; w < pairs_per_poly;
-         w += (size_t)gridDim.x * blockDim.x) {
-        const ModConst mc = T.mods[(int)(w >> (logn - 1))];
-        const ulonglong2 a0 = gld16(a + w), a1 = gld16(a + w + pairs_per_poly), b0 = gld16(b + w), b1 = gld16(b + w + pairs_per_poly);
-        ulonglong2 c0, c1, c2;
-        c0.x = mulmod(a0.x, b0.x, mc);
-        c0.y = mulmod(a0.y, b0.y, mc);
-        c2.x = mulmod(a1.x, b1.x, mc);
-        c2.y = mulmod(a1.y, b1.y, mc);
-        u64 lo = 0, hi = 0;
-        mac128(lo, hi, a0.x, b1.x);
-        mac128(lo, hi, a1.x, b0.x);
-        c1.x = barrett128(lo, hi, mc);
-        lo = hi = 0;
-        mac128(lo, hi, a0.y, b1.y);
-        mac128(lo, hi, a1.y, b0.y);
-        c1.y = barrett128(lo, hi, mc);
-        gst16(out + w, c0);
-        gst16(out + w + pairs_per_poly, c1);
-        gst16(out + w + 2 * pairs_per_poly, c2);
-    }
-}
-
 // tab[i][0..words) = src[i*words ..]: the contiguous results of a batched producer (hefx_ckks_encode over many vectors)
 // handed to their separately allocated owners in one launch
 __global__ __launch_bounds__(256) void scatter_rows_kernel(const u64 *__restrict__ src, const u64 *const *__restrict__ tab,
@@ -533,16 +456,6 @@ hipError_t launch_scatter_rows(const u64 *src, const u64 *const *d_tab, int n, s
     hipLaunchKernelGGL(scatter_rows_kernel, dim3(blocks, n), dim3(256), 0, s, src, d_tab, pairs);
     return hipGetLastError();
 }
-
-hipError_t launch_multiply_table(const DevTables &T, int L, const u64 *const *d_tab, int n, hipStream_t s)
-{
-    const size_t pairs = (size_t)L * ((size_t)1 << T.logn) / 2;
-    int blocks = (int)((pairs + 255) / 256);
-    if (blocks > 64) blocks = 64;  // n items in grid.y fill the chip
-    hipLaunchKernelGGL(multiply_table_kernel, dim3(blocks, n), dim3(256), 0, s, T, L, pairs, d_tab, n);
-    return hipGetLastError();
-}
-
 
 // n independent element-wise sums / differences through a DEVICE pointer table  a[0..n) | b[0..n) | out[0..n): the adds
 // of n dot-product chains advancing in lockstep (helper.h:464,475 over the rows of logistic_regression_ckks.cpp:217)
@@ -595,14 +508,16 @@ hipError_t launch_addsub_table(const DevTables &T, bool sub, int L, int size, co
 //               OWN records (the same addresses from the same lane within a few hundred instructions), so the repeats are
 //               cache hits and HBM still sees each operand word once; holding up to 17 records under a run-time index
 //               would put them in scratch memory.
+// The block size is a constant of the launcher, not blockDim.x: read from the dispatch packet it cost these kernels a
+// dependent vector load in front of the first operand load, which the one-product form (a microsecond of work) shows.
+constexpr unsigned MUL_BLOCK = 256;
 template <int SA, int SB>
 __device__ __forceinline__ void multiply_sizes_body(const DevTables &T, size_t pairs_per_poly, int sa, int sb,
                                                     const ulonglong2 *__restrict__ a, const ulonglong2 *__restrict__ b,
                                                     ulonglong2 *__restrict__ out)
 {
     const int logn = T.logn;
-    for (size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x; w < pairs_per_poly;
-         w += (size_t)gridDim.x * blockDim.x) {
+    for (size_t w = (size_t)blockIdx.x * MUL_BLOCK + threadIdx.x; w < pairs_per_poly; w += (size_t)gridDim.x * MUL_BLOCK) {
         const ModConst mc = T.mods[(int)(w >> (logn - 1))];
         if constexpr (SA > 0) {
             ulonglong2 ra[SA], rb[SB];
@@ -646,7 +561,7 @@ __device__ __forceinline__ void multiply_sizes_body(const DevTables &T, size_t p
 }
 
 template <int SA, int SB>
-__global__ __launch_bounds__(256) void multiply_sizes_kernel(DevTables T, size_t pairs_per_poly, int sa, int sb,
+__global__ __launch_bounds__(MUL_BLOCK) void multiply_sizes_kernel(DevTables T, size_t pairs_per_poly, int sa, int sb,
                                                              const ulonglong2 *__restrict__ a,
                                                              const ulonglong2 *__restrict__ b, ulonglong2 *__restrict__ out)
 {
@@ -655,7 +570,7 @@ __global__ __launch_bounds__(256) void multiply_sizes_kernel(DevTables T, size_t
 
 // the pointer-table twin (a[0..n) | b[0..n) | out[0..n), one (sa, sb) for all items), item = blockIdx.y
 template <int SA, int SB>
-__global__ __launch_bounds__(256) void multiply_sizes_table_kernel(DevTables T, size_t pairs_per_poly, int sa, int sb,
+__global__ __launch_bounds__(MUL_BLOCK) void multiply_sizes_table_kernel(DevTables T, size_t pairs_per_poly, int sa, int sb,
                                                                    const u64 *const *__restrict__ tab, int n)
 {
     const int item = blockIdx.y;
@@ -669,7 +584,7 @@ hipError_t launch_multiply_sizes(const DevTables &T, int L, int sa, int sb, cons
                                  const u64 *const *d_tab, int n, hipStream_t s)
 {
     const size_t pairs = (size_t)L * ((size_t)1 << T.logn) / 2;
-    int blocks = (int)((pairs + 255) / 256);
+    int blocks = (int)((pairs + MUL_BLOCK - 1) / MUL_BLOCK);
     const int cap = d_tab ? 64 : 256 * 8;  // n items in grid.y fill the chip
     if (blocks > cap) blocks = cap;
     const ulonglong2 *pa = reinterpret_cast<const ulonglong2 *>(a), *pb = reinterpret_cast<const ulonglong2 *>(b);
@@ -677,13 +592,14 @@ hipError_t launch_multiply_sizes(const DevTables &T, int L, int sa, int sb, cons
 #define LAUNCH(SA, SB)                                                                                                    \
     do {                                                                                                                  \
         if (d_tab)                                                                                                        \
-            hipLaunchKernelGGL((multiply_sizes_table_kernel<SA, SB>), dim3(blocks, n), dim3(256), 0, s, T, pairs, sa, sb, \
+            hipLaunchKernelGGL((multiply_sizes_table_kernel<SA, SB>), dim3(blocks, n), dim3(MUL_BLOCK), 0, s, T, pairs, sa, sb, \
                                d_tab, n);                                                                                 \
         else                                                                                                              \
-            hipLaunchKernelGGL((multiply_sizes_kernel<SA, SB>), dim3(blocks), dim3(256), 0, s, T, pairs, sa, sb, pa, pb,  \
+            hipLaunchKernelGGL((multiply_sizes_kernel<SA, SB>), dim3(blocks), dim3(MUL_BLOCK), 0, s, T, pairs, sa, sb, pa, pb,  \
                                po);                                                                                       \
     } while (0)
     switch (sa >= 2 && sa <= 4 && sb >= 2 && sb <= 4 ? sa * 8 + sb : 0) {
+        case 2 * 8 + 2: LAUNCH(2, 2); break;
         case 2 * 8 + 3: LAUNCH(2, 3); break;
         case 2 * 8 + 4: LAUNCH(2, 4); break;
         case 3 * 8 + 2: LAUNCH(3, 2); break;

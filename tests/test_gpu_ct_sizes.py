@@ -82,10 +82,12 @@ def test_product_word_for_word(name):
 # ------------------------------------------------------------------------------------------------------------------
 # 2. the largest residues
 # ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("shape", [(8, 9), (2, 15)])
+@pytest.mark.parametrize("shape", [(8, 9), (2, 15), (2, 2)])
 def test_accumulator_holds_at_the_largest_residues(shape):
     """every input word q_j - 1 with primes just below 2^61: (q-1)^2 = 1 mod q, so output k is the number of pairs
-    i + j = k, mod q -- Python integers, no backend.  The twin of test_fold_intervals_hold_at_the_largest_residues."""
+    i + j = k, mod q -- Python integers, no backend.  The twin of test_fold_intervals_hold_at_the_largest_residues.
+    (2, 2) -- outputs 1, 2, 1 -- also through hefx_multiply, hefx_square and a hefx_multiply_batch of three: one kernel
+    family behind all of them."""
     o, e, L = _mk("p_min61")
     assert sum(p > 1 << 60 for p in o.primes[:L]) >= 8
     sa, sb = shape
@@ -96,11 +98,16 @@ def test_accumulator_holds_at_the_largest_residues(shape):
             x[:, j, :] = o.primes[j] - 1
         return e.to_device(x)
 
-    got = e.multiply_sizes(L, sa, top(sa), sb, top(sb)).download()
-    for k in range(sa + sb - 1):
-        terms = sum(1 for i in range(sa) if 0 <= k - i < sb)
-        for j in range(L):
-            assert (got[k, j] == terms % o.primes[j]).all(), (shape, k, j)
+    da, db = top(sa), top(sb)
+    results = [e.multiply_sizes(L, sa, da, sb, db)]
+    if shape == (2, 2):
+        results += [e.multiply(L, da, db), e.square(L, da)] + e.multiply_batch(L, [da, db, da], [db, db, da])
+    for which, out in enumerate(results):
+        got = out.download()
+        for k in range(sa + sb - 1):
+            terms = sum(1 for i in range(sa) if 0 <= k - i < sb)
+            for j in range(L):
+                assert (got[k, j] == terms % o.primes[j]).all(), (shape, which, k, j)
 
 
 # ------------------------------------------------------------------------------------------------------------------

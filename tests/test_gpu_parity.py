@@ -134,8 +134,9 @@ def test_add_many(c2):
 
 def test_multiply_plain_sum_bit_exact(c2):
     """hefx_multiply_plain_sum (helper.h:265-278 in one pass): uniform residues, against multiply_plain + add per term;
-    one group, ragged groups, a sum longer than one accumulator fold (128), more groups than one pointer-table slice,
-    size-3 ciphertexts, and the argument checks."""
+    one group, ragged groups, a sum longer than one accumulator fold (128), a long group beside a short one, size-3
+    ciphertexts, and the argument checks.  (All within one pointer-table slice of 10240 pointers; groups across a slice:
+    tests/test_gpu_table_slices.py.)"""
     o, e, _ = c2
     L = 3
     cts = [o.uniform(L, 2, 7000 + i) for i in range(9)]
@@ -149,7 +150,7 @@ def test_multiply_plain_sum_bit_exact(c2):
             acc = t if acc is None else o.add(acc, t)
         return acc
 
-    for n, group in ((5, None), (23, 4), (300, 300), (700, 3), (1500, 1400)):  # last: groups beyond one table slice
+    for n, group in ((5, None), (23, 4), (300, 300), (700, 3), (1500, 1400)):  # last: a group of 1400 and a ragged one of 100
         idx = [(i % 9, (3 * i + 1) % 7) for i in range(n)]
         g = n if group is None else group
         outs = e.multiply_plain_sum(L, 2, [dct[a] for a, _ in idx], [dpt[b] for _, b in idx], group)
@@ -167,8 +168,9 @@ def test_multiply_plain_sum_bit_exact(c2):
 def test_row_batched_ops_bit_exact(c2):
     """hefx_multiply_batch and the count-batched add / rescale behind Evaluator.multiply_many / add_pairs /
     rescale_to_next_many_inplace: n independent ciphertexts per launch, same bits as one call each -- with one shared
-    right operand (the weight ciphertext of logistic_regression_ckks.cpp:217-220), across pointer-table slices, and
-    for inputs that are NOT views of one slab (per-item fallback)."""
+    right operand (the weight ciphertext of logistic_regression_ckks.cpp:217-220), 450 items (one pointer-table slice
+    today; 425 / 426 is where a slice ended while a slot held fewer pointers -- across a slice:
+    tests/test_gpu_table_slices.py), and for inputs that are NOT views of one slab (per-item fallback)."""
     o, e, _ = c2
     L, n = 3, 450
     cts = [o.uniform(L, 2, 9000 + i) for i in range(7)]

@@ -437,7 +437,8 @@ def test_pointer_table_batch_entries_bit_exact():
         for i in range(4):
             assert (r3[i].download() == o.rescale(M[3 - i], rounded=rounded)).all()
     e.set_rescale_rounded(False)
-    # more items than one table slice (the ring slot holds 1536 pointers: 512 triples / 768 pairs)
+    # a long batch of repeated operands, probed at 511 / 512 and 767 / 768: where a table slice ended while a ring slot held
+    # 1536 pointers.  A slot holds 10240 today, so this stays within one slice; tests/test_gpu_table_slices.py crosses one
     big = 800
     idx = [i % n for i in range(big)]
     outs = e.add_batch(L, 2, [dB[i] for i in idx], [dB[(i + 1) % n] for i in idx])

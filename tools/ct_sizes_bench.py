@@ -1,5 +1,6 @@
 """The general-size ciphertext product and relinearisation on the MI355X (hefx_multiply_sizes[_batch],
-hefx_relinearize_sizes) at C3 (N=16384, L=5) and C2 (N=8192, L=3), against the size-2 x size-2 entries they leave alone.
+hefx_relinearize_sizes) at C3 (N=16384, L=5) and C2 (N=8192, L=3), against the size-2 x size-2 entries (hefx_multiply,
+hefx_multiply_batch: the <2, 2> instances of the same kernel family, reached through their own entries).
 
   product     device-event time per call and achieved bytes/s on the algorithmic bytes 8 N L (2 (sa + sb) - 1) at the shapes
               (2,2), (3,2), (3,3), (4,4), (8,9): one product (latency; operands cache-resident) and a batch of BATCH distinct
@@ -22,7 +23,7 @@ quick = "--quick" in args
 SHAPES = [(2, 2), (3, 2), (3, 3), (4, 4), (8, 9)]
 BATCH, CALLS, REPEATS, HBM_PEAK = (8, 3, 2, 8e12) if quick else (256, 20, 5, 8e12)
 # registers / waves per SIMD of the kernels behind each shape (hipcc -Rpass-analysis=kernel-resource-usage, gfx950)
-RESOURCES = {(2, 2): ("multiply_kernel", 52, 8), (3, 2): ("multiply_sizes_kernel<3, 2>", 57, 8),
+RESOURCES = {(2, 2): ("multiply_sizes_kernel<2, 2>", 53, 8), (3, 2): ("multiply_sizes_kernel<3, 2>", 57, 8),
              (3, 3): ("multiply_sizes_kernel<3, 3>", 70, 7), (4, 4): ("multiply_sizes_kernel<4, 4>", 90, 5),
              (8, 9): ("multiply_sizes_kernel<0, 0>", 54, 8)}
 
