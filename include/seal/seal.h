@@ -10,7 +10,8 @@
 // semantic handles, so SEAL's copy-heavy call style -- helper.h:237 passes GaloisKeys BY VALUE -- costs
 // nothing).  Host-side: parameter bookkeeping (parms_id chain, scale), SEAL's validity checks and exception
 // types/messages, NAF decomposition of rotation steps (App. A.7), random sampling and the complex FFT of
-// CKKSEncoder.  BFV-only classes exist so that the drivers compile; they throw std::logic_error when used.
+// CKKSEncoder.  The BFV classes (BatchEncoder, IntegerEncoder, the BFV branches of Encryptor / Evaluator / Decryptor) run
+// on the same engine through include/hefx_bfv.h; shim_bfv.h holds their host fall-backs.
 #pragma once
 
 #include <algorithm>
@@ -1051,12 +1052,13 @@ inline void Engine::flush_multi(std::vector<Node> &K, const Fusion &fz, int max_
     if (copied_back) check(hefx_stream_sync(ctx_raw, nullptr));
 }
 
-inline BufPtr upload(const std::shared_ptr<Engine> &e, const std::vector<std::uint64_t> &h)
+inline BufPtr upload(const std::shared_ptr<Engine> &e, const std::uint64_t *h, std::size_t words)
 {
-    BufPtr b = new_buf(e, h.size());
-    check(hefx_upload(e->ready({}), b->p, h.data(), h.size() * 8, nullptr));
+    BufPtr b = new_buf(e, words);
+    check(hefx_upload(e->ready({}), b->p, h, words * 8, nullptr));
     return b;
 }
+inline BufPtr upload(const std::shared_ptr<Engine> &e, const std::vector<std::uint64_t> &h) { return upload(e, h.data(), h.size()); }
 inline std::vector<std::uint64_t> download(const BufPtr &b, std::size_t words = 0)
 {
     std::vector<std::uint64_t> h(words ? words : b->words);
@@ -2194,8 +2196,13 @@ private:
         auto c = shim::new_buf(e, (std::size_t)2 * L * n);
         shim::check(hefx_encrypt(e->ready({}), L, pk_.buf->p, nullptr, rnd_.key.data(), rnd_.stream(), c->p, nullptr));
         shim::check(hefx_ntt_inverse(e->ready({}), c->p, 2, L, 0, nullptr));
-        auto dm = shim::upload(e, shim::bfv_scaled_plain(*ctx_, plain.bfv));
-        shim::check(hefx_add_plain(e->ready({}), L, 2, c->p, dm->p, c->p, nullptr));
+        if (hefx_bfv *dev = ctx_->bfv_device(B)) {  // only the message travels; Delta * m is formed where c0 lies
+            auto dm = shim::upload(e, plain.bfv);
+            shim::check(hefx_bfv_scale_plain_add(dev, dm->p, (int)plain.bfv.size(), c->p, c->p, nullptr));
+        } else {
+            auto dm = shim::upload(e, shim::bfv_scaled_plain(*ctx_, plain.bfv));  // host fall-back: a level the engine does not serve
+            shim::check(hefx_add_plain(e->ready({}), L, 2, c->p, dm->p, c->p, nullptr));
+        }
         dest.set(c, 2, L, ctx_->id_of_rows(L), 1.0);
         dest.ntt_form_ = false;
     }
@@ -2250,9 +2257,9 @@ public:
 
 private:
     // BFV: x = [c0 + c1 s (+ c2 s^2)]_Q on the GPU (NTT domain), then m = round(t*x/Q) mod t per coefficient, on the GPU
-    // as well (hefx_bfv_decrypt_round): only m comes back.  The noise budget, when asked for, is host work on x as it
-    // always was: t*x = quo*Q + rem, |rem centred| is the invariant noise.  `host`, or a level the engine does not serve:
-    // the rounding on the host too.
+    // as well (hefx_bfv_decrypt_round): only m comes back.  The noise budget, when asked for, comes from the same x
+    // (hefx_bfv_noise_budget): t*x = quo*Q + rem, |rem centred| is the invariant noise, and one word comes back.  `host`,
+    // or a level the engine does not serve: rounding and budget on the host (shim_bfv.h decrypt_round_host).
     void decrypt_bfv(const Ciphertext &ct, Plaintext &dest, int *budget, bool host = false) const
     {
         namespace bf = shim::bfv;
@@ -2273,12 +2280,15 @@ private:
             (void)e->ready({});
             shim::check(hefx_bfv_decrypt_round(dev, acc->p, m->p, nullptr));
             dest.bfv = shim::download(m);
-        }
-        if (!dev || budget) {
+            if (budget) {  // one 32-bit word comes back
+                auto w = shim::new_buf(e, 1);
+                shim::check(hefx_bfv_noise_budget(dev, acc->p, reinterpret_cast<std::uint32_t *>(w->get()), nullptr));
+                *budget = (int)(std::uint32_t)shim::download(w)[0];
+            }
+        } else {
             const std::vector<std::uint64_t> x = shim::download(acc);
             bf::Big worst;
-            std::vector<std::uint64_t> m = bf::decrypt_round_host(B.data, B.t, x, n, &worst);
-            if (!dev) dest.bfv.swap(m);
+            dest.bfv = bf::decrypt_round_host(B.data, B.t, x, n, &worst);  // host fall-back: `host`, or a level the engine does not serve
             if (budget) *budget = std::max(0, B.data.M.bits() - worst.bits() - 1);
         }
         while (dest.bfv.size() > 1 && dest.bfv.back() == 0) dest.bfv.pop_back();  // SEAL keeps the significant coefficients
@@ -2598,7 +2608,8 @@ private:
 
 // BatchEncoder (BFV; vector_ops.cpp:127-193, 5_rotation.cpp:108-164): N slots as a 2 x N/2 matrix, slot i <-> the
 // evaluation point psi^(3^i) (row 0) / psi^(-3^i) (row 1), so that X -> X^(3^k) rotates the rows by k and X -> X^(2N-1)
-// swaps them.  Host arithmetic modulo the plain modulus (shim_bfv.h PlainNtt).
+// swaps them.  Permutation and transform modulo the plain modulus run on the GPU (hefx_bfv_batch_encode / _decode); the
+// host arithmetic of shim_bfv.h PlainNtt is the fall-back.
 class BatchEncoder {
 public:
     template <class Ctx>
@@ -2624,12 +2635,20 @@ public:
         const std::uint64_t t = ctx_->plain_modulus_value();
         if (values.size() > n) throw std::invalid_argument("values has invalid size");
         dest = Plaintext();
-        dest.bfv.assign(n, 0);
-        for (std::size_t i = 0; i < values.size(); ++i) {
+        for (std::size_t i = 0; i < values.size(); ++i)
             if (values[i] >= t) throw std::invalid_argument("input value is larger than plain_modulus");
-            dest.bfv[index_[i]] = values[i];
+        hefx_bfv *dev = values.empty() ? nullptr : device();
+        if (dev) {  // the values go up, the polynomial comes back: permutation and transform modulo t on the device
+            auto &e = ctx_->engine();
+            auto dv = shim::upload(e, values);
+            auto m = shim::new_buf(e, n);
+            shim::check(hefx_bfv_batch_encode(dev, dv->p, (int)values.size(), m->p, nullptr));
+            dest.bfv = shim::download(m);
+            return;
         }
-        ctx_->bfv().pntt.inverse(dest.bfv);
+        dest.bfv.assign(n, 0);
+        for (std::size_t i = 0; i < values.size(); ++i) dest.bfv[index_[i]] = values[i];
+        ctx_->bfv().pntt.inverse(dest.bfv);  // host fall-back: no device object for this shape
     }
     void encode(const std::vector<std::int64_t> &values, Plaintext &dest) const
     {
@@ -2647,7 +2666,15 @@ public:
         if (plain.bfv.empty() || plain.bfv.size() > n) throw std::invalid_argument("plain is not valid for encryption parameters");
         std::vector<std::uint64_t> tmp(plain.bfv);
         tmp.resize(n, 0);
-        ctx_->bfv().pntt.forward(tmp);
+        if (hefx_bfv *dev = device()) {
+            auto &e = ctx_->engine();
+            auto dm = shim::upload(e, tmp);
+            auto v = shim::new_buf(e, n);
+            shim::check(hefx_bfv_batch_decode(dev, dm->p, v->p, nullptr));
+            dest = shim::download(v);
+            return;
+        }
+        ctx_->bfv().pntt.forward(tmp);  // host fall-back: no device object for this shape
         dest.resize(n);
         for (std::size_t i = 0; i < n; ++i) dest[i] = tmp[index_[i]];
     }
@@ -2661,6 +2688,14 @@ public:
     }
 
 private:
+    // the top level's device object when it serves the slot transform (t is a batching prime by the constructor's check;
+    // null: a shape hefx_bfv_create answers HEFX_ERR_UNSUPPORTED to)
+    hefx_bfv *device() const
+    {
+        hefx_bfv *dev = ctx_->bfv_device(ctx_->bfv());
+        return dev && hefx_bfv_batching(dev) ? dev : nullptr;
+    }
+
     std::shared_ptr<SEALContext> ctx_;
     std::vector<std::size_t> index_;
 };
@@ -2779,9 +2814,15 @@ public:
         check_ct(a);
         if (!ctx_->is_ckks()) {  // BFV: c0 += Delta * m (vector_ops.cpp:178)
             if (p.bfv.empty()) throw std::invalid_argument("plain is not valid for encryption parameters");
-            auto dm = shim::upload(eng(), shim::bfv_scaled_plain(*ctx_, p.bfv, a.rows));
             auto out = shim::new_buf(eng(), a.buf->words);
-            shim::check(hefx_add_plain(eng()->ready({a.buf.get()}), a.rows, (int)a.size(), a.buf->p, dm->p, out->p, nullptr));
+            if (hefx_bfv *dev = ctx_->bfv_device(ctx_->bfv(a.rows))) {  // the ciphertext copied, Delta * m added into its c0 in place
+                auto dm = shim::upload(eng(), p.bfv.data(), std::min(p.bfv.size(), ctx_->n()));
+                shim::check(hefx_copy(eng()->ready({a.buf.get()}), out->p, a.buf->p, a.buf->words * 8, nullptr));
+                shim::check(hefx_bfv_scale_plain_add(dev, dm->p, (int)dm->words, out->p, out->p, nullptr));
+            } else {
+                auto dm = shim::upload(eng(), shim::bfv_scaled_plain(*ctx_, p.bfv, a.rows));  // host fall-back: a level the engine does not serve
+                shim::check(hefx_add_plain(eng()->ready({a.buf.get()}), a.rows, (int)a.size(), a.buf->p, dm->p, out->p, nullptr));
+            }
             dest.set(out, a.size(), a.rows, a.parms_id(), a.scale());
             dest.ntt_form_ = false;
             return;
@@ -2805,9 +2846,16 @@ public:
             if (zero) throw std::logic_error("result ciphertext is transparent");
             auto &e = eng();
             const int L = a.rows;
-            auto pt = shim::upload(e, shim::bfv_lifted_plain(*ctx_, p.bfv, L));
+            shim::BufPtr pt;
+            if (hefx_bfv *dev = ctx_->bfv_device(ctx_->bfv(L))) {  // only the message travels; lifted and transformed on the device
+                auto dm = shim::upload(e, p.bfv.data(), std::min(p.bfv.size(), ctx_->n()));
+                pt = shim::new_buf(e, (std::size_t)L * ctx_->n());
+                shim::check(hefx_bfv_lift_plain(dev, dm->p, (int)dm->words, 1, pt->p, nullptr));
+            } else {
+                pt = shim::upload(e, shim::bfv_lifted_plain(*ctx_, p.bfv, L));  // host fall-back: a level the engine does not serve
+                shim::check(hefx_ntt_forward(e->ready({}), pt->p, 1, L, 0, nullptr));
+            }
             auto tmp = shim::new_buf(e, a.buf->words), out = shim::new_buf(e, a.buf->words);
-            shim::check(hefx_ntt_forward(e->ready({}), pt->p, 1, L, 0, nullptr));
             shim::check(hefx_copy(e->ready({a.buf.get()}), tmp->p, a.buf->p, a.buf->words * 8, nullptr));
             shim::check(hefx_ntt_forward(e->ready({}), tmp->p, (int)a.size(), L, 0, nullptr));
             shim::check(hefx_multiply_plain(e->ready({}), L, (int)a.size(), 1, tmp->p, pt->p, out->p, nullptr));

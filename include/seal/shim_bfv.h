@@ -8,10 +8,14 @@
 //     same hefx_* entry points as CKKS -- a BFV ciphertext is kept in coefficient form, so those calls are bracketed
 //     by hefx_ntt_forward / hefx_ntt_inverse; NTTs are exact and linear, so the residues are the ones a
 //     coefficient-domain implementation produces;
-//   * what is specific to BFV is plain multi-precision integer work on the host: Delta*m scaling,
-//     the noise budget and BatchEncoder's NTT modulo the plain modulus.  The round(t*x/Q) of decryption and the tensor
-//     product scaled by t/Q run on the GPU (include/hefx_bfv.h); their host forms below (multiply_host,
-//     decrypt_round_host) are the fall-back for unsupported shapes and the self-test's comparison.
+//   * what is specific to BFV runs on the GPU as well (include/hefx_bfv.h): the tensor product scaled by t/Q, the
+//     round(t*x/Q) of decryption, Delta*m added to c0 (encryption, add_plain), the centred lift of a message
+//     (multiply_plain), the noise budget, and BatchEncoder's permutation and NTT modulo the plain modulus.  Only the N
+//     words of a message travel between host and device;
+//   * this header is left with the host forms of all of that -- multiply_host, decrypt_round_host (with the noise in
+//     `worst`), PlainNtt, and in seal.h bfv_scaled_plain / bfv_lifted_plain: plain multi-precision integer work, the
+//     fall-back for the shapes hefx_bfv_create answers HEFX_ERR_UNSUPPORTED to and what the self-tests
+//     (drivers/bfv_selftest.cpp, drivers/bfv_front_selftest.cpp) compare the device words with.
 // It follows the textbook BFV definition (Fan-Vercauteren with Delta = floor(Q/t)); SEAL's BEHZ RNS variant computes the
 // same rounded quantities up to its documented approximation error in the noise, so decrypted results agree while
 // ciphertext bits need not -- BFV is outside the bit-exact contract.

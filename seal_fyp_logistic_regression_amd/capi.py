@@ -146,6 +146,12 @@ _BFV_SIGS = {
     "hefx_bfv_aux_count": (_i, [_vp]),
     "hefx_bfv_multiply": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp]),
     "hefx_bfv_decrypt_round": (_i, [_vp, _vp, _vp, _vp]),
+    "hefx_bfv_scale_plain_add": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "hefx_bfv_lift_plain": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "hefx_bfv_noise_budget": (_i, [_vp, _vp, _vp, _vp]),
+    "hefx_bfv_batching": (_i, [_vp]),
+    "hefx_bfv_batch_encode": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "hefx_bfv_batch_decode": (_i, [_vp, _vp, _vp, _vp]),
 }
 BFV_SYMBOLS = sorted(_BFV_SIGS)
 BFV_MAX_BASIS = 16  # HEFX_BFV_MAX_BASIS

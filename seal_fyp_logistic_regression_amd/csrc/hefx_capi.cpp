@@ -3549,6 +3549,13 @@ struct hefx_bfv {
     u64 *d_work = nullptr;  // a [5][A][N] | b [5][A][N] | product [6][A][N]
     ModConst tmod{};
     LiftTables lift_mul{}, lift_dec{};
+    // scale-add, lift, noise budget: Delta mod q_j [L] | t mod q_j [L]; the word the budget's reduction meets in; bits(Q)
+    u64 *d_front = nullptr;
+    uint32_t *d_wmax = nullptr;
+    uint32_t qbits = 0;
+    // batching (t prime, t = 1 mod 2N): a one-prime context over {t} for the slot transform, and BatchEncoder's slot order
+    hefx_context *pt = nullptr;
+    uint32_t *d_index = nullptr;
 };
 
 // little-endian big integers on the host, for the sizing rule only
@@ -3663,6 +3670,52 @@ extern "C" int hefx_bfv_create(hefx_context *c, int L, uint64_t t, hefx_bfv **ou
     }
     b->lift_mul = lift_tables(b->wk, L, A);
     b->lift_dec = lift_tables(b->wk, L, b->Ad);
+    // Delta = (Q - r) / t exactly, r = Q mod t, and t is a unit modulo every q_j: Delta mod q_j = -r t^-1 mod q_j
+    {
+        u64 r = 1 % t;
+        std::vector<u64> Qw{1};
+        for (int j = 0; j < L; ++j) {
+            r = h_mulmod(r, basis[(size_t)j] % t, t);
+            big_mul_small(Qw, basis[(size_t)j]);
+        }
+        while (Qw.size() > 1 && !Qw.back()) Qw.pop_back();
+        b->qbits = (uint32_t)(64 * (Qw.size() - 1) + 64 - (size_t)__builtin_clzll(Qw.back()));
+        std::vector<u64> front((size_t)2 * L);
+        for (int j = 0; j < L; ++j) {
+            const u64 q = basis[(size_t)j];
+            front[(size_t)j] = h_mulmod((q - r % q) % q, h_invmod(t % q, q), q);
+            front[(size_t)L + j] = t % q;
+        }
+        e = hipMalloc((void **)&b->d_front, front.size() * sizeof(u64));
+        if (e == hipSuccess) e = hipMemcpy(b->d_front, front.data(), front.size() * sizeof(u64), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMalloc((void **)&b->d_wmax, sizeof(uint32_t));
+    }
+    // batching: the slot transform is the engine's negacyclic NTT modulo t (its psi is the minimal root), slot i at the
+    // bit-reversed position of its evaluation point 3^i (row 0) / -3^i (row 1)
+    if (e == hipSuccess && t % two_n == 1 && h_is_prime(t)) {
+        if (int rc = hefx_context_create(c->n, reinterpret_cast<const uint64_t *>(&t), 1, c->device, &b->pt)) {
+            hefx_bfv_destroy(b);
+            return rc;
+        }
+        std::vector<uint32_t> index(N);
+        const auto bitrev = [&](uint32_t x) {
+            uint32_t v = 0;
+            for (int i = 0; i < c->logn; ++i) v = (v << 1) | ((x >> i) & 1);
+            return v;
+        };
+        u64 pos = 1;
+        for (size_t i = 0; i < N / 2; ++i) {
+            index[i] = bitrev((uint32_t)((pos - 1) >> 1));
+            index[N / 2 + i] = bitrev((uint32_t)((two_n - pos - 1) >> 1));
+            pos = (pos * 3) & (two_n - 1);
+        }
+        e = hipMalloc((void **)&b->d_index, N * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemcpy(b->d_index, index.data(), N * sizeof(uint32_t), hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) {
+        hefx_bfv_destroy(b);
+        return hipfail(e, "bfv_create");
+    }
     *out = b;
     return HEFX_OK;
 }
@@ -3675,6 +3728,10 @@ extern "C" void hefx_bfv_destroy(hefx_bfv *b)
         (void)hipDeviceSynchronize();
         if (b->d_tab) (void)hipFree(b->d_tab);
         if (b->d_work) (void)hipFree(b->d_work);
+        if (b->d_front) (void)hipFree(b->d_front);
+        if (b->d_wmax) (void)hipFree(b->d_wmax);
+        if (b->d_index) (void)hipFree(b->d_index);
+        if (b->pt) hefx_context_destroy(b->pt);
         hefx_context_destroy(b->wk);
     }
     delete b;
@@ -3740,5 +3797,99 @@ extern "C" int hefx_bfv_decrypt_round(hefx_bfv *b, const uint64_t *x, uint64_t *
     HIPCHK(bfv_extend(b, b->lift_dec, b->Ad, 1, (const u64 *)x, w, s));
     BfvRoundTables R{b->d_tab, b->d_tab + 2 * (size_t)A, b->d_tab + 3 * (size_t)A, b->tmod};
     HIPCHK(launch_bfv_round(b->wk->T, R, b->Ad, L, true, 1, w, (size_t)A * N, (u64 *)m, s));
+    return HEFX_OK;
+}
+
+// ---- the rest of BFV's arithmetic: Delta m into c_0, the lifted message, the noise budget, the slot transform
+static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+extern "C" int hefx_bfv_scale_plain_add(hefx_bfv *b, const uint64_t *m, int ncoeff, const uint64_t *c0, uint64_t *out,
+                                        void *stream)
+{
+    if (!b) return fail(HEFX_ERR_INVALID, "null bfv object");
+    CTXCHK(b->ctx);
+    if (!m || !out) return fail(HEFX_ERR_INVALID, "null operand");
+    const int L = b->L;
+    const size_t N = b->ctx->n, row = N * sizeof(u64);
+    if (ncoeff < 1 || (size_t)ncoeff > N) return fail(HEFX_ERR_INVALID, "bfv_scale_plain_add: ncoeff must be in [1, N]");
+    const size_t m_b = (size_t)ncoeff * sizeof(u64);
+    if (c0) {  // d_out == d_c0_in exactly is the in-place form
+        if (int rc = check_ranges("bfv_scale_plain_add", 1, &out, row * L, {{&m, 1, m_b}, {&c0, 1, row * L, true}}, {"d_m", "d_c0_in"}))
+            return rc;
+    } else if (int rc = check_ranges("bfv_scale_plain_add", 1, &out, row * L, {{&m, 1, m_b}}, {"d_m"})) {
+        return rc;
+    }
+    const BfvFrontTables F{b->d_front, b->d_front + L, b->t};
+    const bool vec = aligned16(m) && aligned16(out) && (!c0 || aligned16(c0));
+    HIPCHK(launch_bfv_scale_add(b->wk->T, F, L, (const u64 *)m, ncoeff, (const u64 *)c0, (u64 *)out, vec, (hipStream_t)stream));
+    return HEFX_OK;
+}
+
+extern "C" int hefx_bfv_lift_plain(hefx_bfv *b, const uint64_t *m, int ncoeff, int ntt_form, uint64_t *out, void *stream)
+{
+    if (!b) return fail(HEFX_ERR_INVALID, "null bfv object");
+    CTXCHK(b->ctx);
+    if (!m || !out) return fail(HEFX_ERR_INVALID, "null operand");
+    const int L = b->L;
+    const size_t N = b->ctx->n, row = N * sizeof(u64);
+    if (ncoeff < 1 || (size_t)ncoeff > N) return fail(HEFX_ERR_INVALID, "bfv_lift_plain: ncoeff must be in [1, N]");
+    if (int rc = check_ranges("bfv_lift_plain", 1, &out, row * L, {{&m, 1, (size_t)ncoeff * sizeof(u64)}}, {"d_m"})) return rc;
+    const BfvFrontTables F{b->d_front, b->d_front + L, b->t};
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(launch_bfv_lift_plain(b->wk->T, F, L, (const u64 *)m, ncoeff, (u64 *)out, aligned16(m) && aligned16(out), s));
+    if (ntt_form) HIPCHK(launch_ntt(b->wk->T, false, (u64 *)out, 1, L, 0, s));  // rows 0 .. L-1 of the working basis: the data primes
+    return HEFX_OK;
+}
+
+extern "C" int hefx_bfv_noise_budget(hefx_bfv *b, const uint64_t *x, uint32_t *budget, void *stream)
+{
+    if (!b) return fail(HEFX_ERR_INVALID, "null bfv object");
+    CTXCHK(b->ctx);
+    if (!x || !budget) return fail(HEFX_ERR_INVALID, "null operand");
+    const int L = b->L;
+    const size_t row = (size_t)b->ctx->n * sizeof(u64);
+    {  // the output is four bytes, not a list of 64-bit words (check_ranges): compared here
+        const uintptr_t o = (uintptr_t)budget, i0 = (uintptr_t)x, i1 = i0 + row * L;
+        if (o + sizeof(uint32_t) > i0 && o < i1) return fail(HEFX_ERR_INVALID, "bfv_noise_budget: d_budget overlaps d_x");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const BfvFrontTables F{b->d_front, b->d_front + L, b->t};
+    HIPCHK(hipMemsetAsync(b->d_wmax, 0, sizeof(uint32_t), s));
+    HIPCHK(launch_bfv_noise_bits(b->wk->T, F, b->lift_mul, L, (const u64 *)x, b->d_wmax, s));
+    HIPCHK(launch_bfv_budget_finish(b->d_wmax, b->qbits, budget, s));
+    return HEFX_OK;
+}
+
+extern "C" int hefx_bfv_batching(const hefx_bfv *b) { return b && b->pt ? 1 : 0; }
+
+extern "C" int hefx_bfv_batch_encode(hefx_bfv *b, const uint64_t *values, int nvalues, uint64_t *m, void *stream)
+{
+    if (!b) return fail(HEFX_ERR_INVALID, "null bfv object");
+    CTXCHK(b->ctx);
+    if (!b->pt) return fail(HEFX_ERR_UNSUPPORTED, "bfv_batch_encode: the plain modulus is not a prime that is 1 mod 2N");
+    if (!values || !m) return fail(HEFX_ERR_INVALID, "null operand");
+    const size_t N = b->ctx->n;
+    if (nvalues < 1 || (size_t)nvalues > N) return fail(HEFX_ERR_INVALID, "bfv_batch_encode: nvalues must be in [1, N]");
+    if (int rc = check_ranges("bfv_batch_encode", 1, &m, N * sizeof(u64), {{&values, 1, (size_t)nvalues * sizeof(u64)}}, {"d_values"}))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(launch_bfv_slot_scatter(b->pt->T, b->d_index, (const u64 *)values, nvalues, (u64 *)m, s));
+    HIPCHK(launch_ntt(b->pt->T, true, (u64 *)m, 1, 1, 0, s));
+    return HEFX_OK;
+}
+
+extern "C" int hefx_bfv_batch_decode(hefx_bfv *b, const uint64_t *m, uint64_t *values, void *stream)
+{
+    if (!b) return fail(HEFX_ERR_INVALID, "null bfv object");
+    CTXCHK(b->ctx);
+    if (!b->pt) return fail(HEFX_ERR_UNSUPPORTED, "bfv_batch_decode: the plain modulus is not a prime that is 1 mod 2N");
+    if (!m || !values) return fail(HEFX_ERR_INVALID, "null operand");
+    const size_t N = b->ctx->n;
+    if (int rc = check_ranges("bfv_batch_decode", 1, &values, N * sizeof(u64), {{&m, 1, N * sizeof(u64)}}, {"d_m"})) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    u64 *w = b->d_work;
+    HIPCHK(launch_bfv_slot_reduce(b->pt->T, (const u64 *)m, w, s));
+    HIPCHK(launch_ntt(b->pt->T, false, w, 1, 1, 0, s));
+    HIPCHK(launch_bfv_slot_gather(b->pt->T, b->d_index, w, (u64 *)values, s));
     return HEFX_OK;
 }

@@ -204,6 +204,31 @@ struct BfvRoundTables {
 // in: npoly polynomials of >= A rows, in_stride words apart, coefficient form; out [npoly][L][N], or `plain` [npoly][N]
 hipError_t launch_bfv_round(const DevTables &T, const BfvRoundTables &R, int A, int L, bool plain, int npoly, const u64 *in,
                             size_t in_stride, u64 *out, hipStream_t s);
+// The rest of BFV's arithmetic (hefx_bfv.hip): per-row constants of the object, device memory, indexed like the first L
+// rows of T (the data primes).
+struct BfvFrontTables {
+    const u64 *delta;  // [L]  floor(Q / t) mod q_j
+    const u64 *tmod;   // [L]  t mod q_j
+    u64 t;
+};
+// out[j][n] = c0[j][n] + delta[j] * m[n] mod q_j for n < ncoeff, c0[j][n] behind; c0 == nullptr: zeros; c0 == out allowed.
+// vec: every pointer is 16-byte aligned -- one thread per 16-byte record, otherwise one per word
+hipError_t launch_bfv_scale_add(const DevTables &T, const BfvFrontTables &F, int L, const u64 *m, int ncoeff, const u64 *c0,
+                                u64 *out, bool vec, hipStream_t s);
+// out[j][n] = m[n] mod q_j (m[n] <= t/2) or q_j - ((t - m[n]) mod q_j), zeros behind ncoeff
+hipError_t launch_bfv_lift_plain(const DevTables &T, const BfvFrontTables &F, int L, const u64 *m, int ncoeff, u64 *out,
+                                 bool vec, hipStream_t s);
+// *wmax (zeroed by the caller on s) = max over n of the bit length of |t x^[n] mod Q centred|, x [L][N]; half: the digits
+// of (Q-1)/2 (LiftTables::half); then *budget = max(0, qbits - *wmax - 1)
+hipError_t launch_bfv_noise_bits(const DevTables &T, const BfvFrontTables &F, const LiftTables &D, int L, const u64 *x,
+                                 uint32_t *wmax, hipStream_t s);
+hipError_t launch_bfv_budget_finish(const uint32_t *wmax, uint32_t qbits, uint32_t *budget, hipStream_t s);
+// slot permutation of BatchEncoder over the one-prime context Tt = {t}: encode: out[index[i]] = values[i] mod t (i <
+// nvalues), 0 for the other i < N; reduce: out[i] = in[i] mod t; gather: out[i] = in[index[i]]
+hipError_t launch_bfv_slot_scatter(const DevTables &Tt, const uint32_t *index, const u64 *values, int nvalues, u64 *out,
+                                   hipStream_t s);
+hipError_t launch_bfv_slot_reduce(const DevTables &Tt, const u64 *in, u64 *out, hipStream_t s);
+hipError_t launch_bfv_slot_gather(const DevTables &Tt, const uint32_t *index, const u64 *in, u64 *out, hipStream_t s);
 // plaintext i = round(vals[i] * scale) in every word of its rows ([count][L][N])
 hipError_t launch_encode_scalar(const DevTables &T, const double *vals, int count, double scale, int L, u64 *out,
                                 hipStream_t s);

@@ -698,7 +698,8 @@ class Engine:
 
 class BfvPlan:
     """The BFV entries of include/hefx_bfv.h for one (engine, L, t): the tensor product scaled by t/Q and the rounding of
-    decryption, exact, on device buffers in COEFFICIENT form.  Owns the working basis and scratch (hefx_bfv); calls of one
+    decryption, and the rest of the scheme's arithmetic (Delta m into c0, the lifted message, the noise budget, the slot
+    transform of batching), exact, on device buffers in COEFFICIENT form.  Owns the working basis and scratch (hefx_bfv); calls of one
     plan must be ordered on the device, two plans may run on two streams at once."""
 
     def __init__(self, engine: Engine, L: int, t: int):
@@ -731,4 +732,47 @@ class BfvPlan:
         """x [L][N] -> m [N], m = round(t x^ / Q) mod t"""
         out = out if out is not None else DeviceArray(self.engine, (self.engine.N,))
         capi.check(capi.lib().hefx_bfv_decrypt_round(self._h, x.ptr, out.ptr, stream))
+        return out
+
+    def scale_plain_add(self, m: DeviceArray, c0: Optional[DeviceArray] = None, out: Optional[DeviceArray] = None,
+                        ncoeff: Optional[int] = None, stream=None) -> DeviceArray:
+        """m [ncoeff] (default: all of m), c0 [L][N] or None for zeros -> out = c0 + (Delta mod q_j) m in the first ncoeff
+        coefficients of every row, c0 behind them; out may be c0 itself"""
+        ncoeff = m.nwords if ncoeff is None else int(ncoeff)
+        out = out if out is not None else DeviceArray(self.engine, (self.L, self.engine.N))
+        capi.check(capi.lib().hefx_bfv_scale_plain_add(self._h, m.ptr, ncoeff, c0.ptr if c0 is not None else None, out.ptr, stream))
+        return out
+
+    def lift_plain(self, m: DeviceArray, ntt_form: bool = False, out: Optional[DeviceArray] = None,
+                   ncoeff: Optional[int] = None, stream=None) -> DeviceArray:
+        """m [ncoeff] -> [L][N], coefficients above t/2 as negative numbers modulo every prime, zeros behind ncoeff;
+        ntt_form: transformed forward, the operand of Engine.multiply_plain"""
+        ncoeff = m.nwords if ncoeff is None else int(ncoeff)
+        out = out if out is not None else DeviceArray(self.engine, (self.L, self.engine.N))
+        capi.check(capi.lib().hefx_bfv_lift_plain(self._h, m.ptr, ncoeff, 1 if ntt_form else 0, out.ptr, stream))
+        return out
+
+    def noise_budget(self, x: DeviceArray, out: Optional[DeviceArray] = None, stream=None) -> DeviceArray:
+        """x [L][N] -> one word whose low 32 bits are max(0, bits(Q) - bits(max |t x^ mod Q centred|) - 1); a buffer made
+        here is zeroed first, so its word IS the budget: int(out.download()[0])"""
+        out = out if out is not None else self.engine.zeros(1, stream=stream)
+        capi.check(capi.lib().hefx_bfv_noise_budget(self._h, x.ptr, out.ptr, stream))
+        return out
+
+    def batching(self) -> bool:
+        """t is a prime that is 1 mod 2N: batch_encode / batch_decode are served"""
+        return bool(capi.lib().hefx_bfv_batching(self._h))
+
+    def batch_encode(self, values: DeviceArray, out: Optional[DeviceArray] = None, nvalues: Optional[int] = None,
+                     stream=None) -> DeviceArray:
+        """values [nvalues] -> m [N] with values[i] in slot i (BatchEncoder's order) and 0 in the other slots"""
+        nvalues = values.nwords if nvalues is None else int(nvalues)
+        out = out if out is not None else DeviceArray(self.engine, (self.engine.N,))
+        capi.check(capi.lib().hefx_bfv_batch_encode(self._h, values.ptr, nvalues, out.ptr, stream))
+        return out
+
+    def batch_decode(self, m: DeviceArray, out: Optional[DeviceArray] = None, stream=None) -> DeviceArray:
+        """m [N] -> the N slot values"""
+        out = out if out is not None else DeviceArray(self.engine, (self.engine.N,))
+        capi.check(capi.lib().hefx_bfv_batch_decode(self._h, m.ptr, out.ptr, stream))
         return out
