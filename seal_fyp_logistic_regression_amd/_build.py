@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libhefx.so")
 SOURCES = ["hefx_keyswitch.hip", "hefx_kernels.hip", "hefx_encode.hip", "hefx_sample.hip", "hefx_bfv.hip", "hefx_capi.cpp"]  # slowest first
-HEADERS = ["hefx_internal.h", "hefx_modarith.cuh", "hefx_ntt.cuh", "hefx_ntt8.cuh", "hefx_mac.cuh", "hefx_ranges.h", "hefx_crt.cuh",
+HEADERS = ["hefx_internal.h", "hefx_modarith.cuh", "hefx_ntt.cuh", "hefx_ntt8.cuh", "hefx_mac.cuh", "hefx_ranges.h", "hefx_lt_plan.h", "hefx_crt.cuh",
            "../../include/hefx.h", "../../include/hefx_refresh.h", "../../include/hefx_bfv.h"]
 DEPS = SOURCES + HEADERS  # a change in any of them rebuilds the library (a header: every object; a source: its object)
 # The arithmetic probe (tests/test_gpu_arith_primitives.py): ONE device primitive per thread on the caller's operands.  A test
@@ -84,9 +84,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
     for src in SOURCES:
         obj = os.path.join(CSRC, os.path.splitext(src)[0] + ".o")
         objs.append(obj)
-        # the public headers and the host-only range check are only seen by the C-ABI translation unit (a doc edit there
+        # the public headers and the host-only range check and planner are only seen by the C-ABI translation unit (a doc edit there
         # must not cost four minutes of kernels)
-        hdrs = [h for h in HEADERS if src == "hefx_capi.cpp" or not h.endswith(("hefx.h", "hefx_refresh.h", "hefx_bfv.h", "hefx_ranges.h"))]
+        hdrs = [h for h in HEADERS if src == "hefx_capi.cpp" or not h.endswith(("hefx.h", "hefx_refresh.h", "hefx_bfv.h", "hefx_ranges.h", "hefx_lt_plan.h"))]
         hdr_t = max(os.path.getmtime(os.path.join(CSRC, h)) for h in hdrs)
         if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(hdr_t, os.path.getmtime(os.path.join(CSRC, src))):
             continue  # this object is newer than its source and every header it includes

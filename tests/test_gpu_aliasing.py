@@ -662,6 +662,17 @@ def test_linear_transform_cipher_refusals():
         want = o.add(want, o.multiply(rot(ct_new, l), diags[l]))
     moves = _standard_moves(["ct"] + [f"g{i}" for i in range(d)], ["out"], exact=[("out", "ct"), ("out", "g0"), ("out", "g2")])
     _ks_refused_then_accepted(Case(e, o, bufs), call, moves, {"out": want})
+    # wrong in two ways at once -- a null Galois key AND the result on an operand: every linear transform checks the aliasing
+    # rule before the keys ("The linear transforms' host path"), so the overlap is what is reported; nothing is written
+    case = Case(e, o, bufs)
+    no_key = lambda p: lib.hefx_linear_transform_cipher(e._h, L, p["ct"], d, arr([p[f"g{i}"] for i in range(d)]), 3, ke,  # noqa: E731
+                                                        arr([dkey.ptr, None, dkey.ptr]), p["out"], None)
+    before = e.ks_stats()
+    for m, text in [({"out": ("on", "ct")}, "overlap"), ({"out": ("row_into", "g1")}, "overlap"), (None, "null Galois key")]:
+        with pytest.raises(ValueError, match=text):
+            capi.check(no_key(case.place(m)))
+        e.sync()
+        assert case.unchanged() and e.ks_stats() == before, m
 
 
 def test_multiply_sum_refusals():

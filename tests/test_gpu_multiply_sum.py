@@ -240,6 +240,38 @@ def test_linear_transform_cipher_d40_c2_direct_keys_bit_exact():
     assert stats[1] >= d - 1, list(stats)  # the forest's depth ran on the hoisted path
 
 
+def _lt_cipher_d160():
+    """(sha256 of the result's words, launch sequences) of Linear_Transform_Cipher at d = 160, N = 4096, default keys"""
+    import hashlib
+    from seal_fyp_logistic_regression_amd import algorithms as alg
+    from tests.test_gpu_composites import make, bits
+    d = 160
+    rng = np.random.default_rng(161)
+    M, v = rng.standard_normal((d, d)), rng.standard_normal(d)
+    e = make(4096, [50, 30, 30, 50], "gpu")
+    diags = [e["enc"].encrypt(e["encoder"].encode(x, 2.0 ** 30)) for x in alg.get_all_diagonals(M)]
+    ct = e["enc"].encrypt(e["encoder"].encode(v, 2.0 ** 30))
+    eng = e["ctx"].backend.engine
+    s0 = eng.ks_stats()["chunks"]
+    out = alg.linear_transform_cipher(e["ev"], ct, diags, e["gk"])
+    return hashlib.sha256(np.ascontiguousarray(bits(e, out)).tobytes()).hexdigest(), eng.ks_stats()["chunks"] - s0
+
+
+def test_linear_transform_cipher_d160_unfused_forest_on_two_lanes_bit_exact_vs_one_lane():
+    """the reference's default keys at d = 160, N = 4096: an UNFUSED forest (no diagonal rides in a key switch, nodes shared per
+    (parent, element)) of about 200 nodes, above the 96-node bound, so its subtrees run on two lanes.  The words must be those
+    of the same call in a fresh process with HEFX_LT_LANES=0 (the one-lane words are the oracle's at d = 16 above)."""
+    import sys
+    digest, seqs = _lt_cipher_d160()
+    code = f"import sys; sys.path.insert(0, {ROOT!r}); from tests.test_gpu_multiply_sum import _lt_cipher_d160; print(*_lt_cipher_d160())"
+    p = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, HEFX_LT_LANES="0"), capture_output=True, text=True,
+                       timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    one_lane_digest, one_lane_seqs = p.stdout.split()[-2:]
+    assert one_lane_digest == digest
+    assert seqs > int(one_lane_seqs), (seqs, one_lane_seqs)  # the laned call really submitted more (smaller) launch sequences
+
+
 def test_linear_transform_cipher_missing_key_and_aliasing_errors():
     from seal_fyp_logistic_regression_amd import algorithms as alg
     from seal_fyp_logistic_regression_amd import seal as S
