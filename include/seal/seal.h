@@ -2771,6 +2771,7 @@ public:
     explicit Evaluator(const Ctx &context) : ctx_(shim::as_ptr(context))
     {
     }
+    const std::shared_ptr<SEALContext> &shim_context() const { return ctx_; }  // (for the extension headers: shim_poly.h)
 
     // ---- add / sub / negate (helper.h:219,247,259,464,475; logistic_regression_ckks.cpp:288,341-342)
     void add(const Ciphertext &a, const Ciphertext &b, Ciphertext &dest) const { addsub(a, b, dest, false); }

@@ -7,7 +7,7 @@ Citations are /root/reference/helper.h unless noted.
 """
 from __future__ import annotations
 
-from typing import List, Sequence
+from typing import List, Optional, Sequence
 
 import operator
 
@@ -806,6 +806,39 @@ def horner_cipher(ev: Evaluator, encoder: CKKSEncoder, encryptor, ctx: Ciphertex
     return temp
 
 
+def evaluate_polynomial(ev: Evaluator, ct: Ciphertext, coeffs: Sequence[float], relin_keys: KSwitchKeys,
+                        basis: str = "power", target_scale: Optional[float] = None) -> Ciphertext:
+    """sum_i coeffs[i] ct^i (basis "power") or sum_i coeffs[i] T_i(ct) ("chebyshev", slots in [-1, 1]) in
+    ceil(log2(degree + 1)) levels: the Paterson-Stockmeyer plan of hefx_poly_plan (include/hefx_poly.h) executed step by
+    step.  The result has that many rows fewer than ct and carries target_scale (default: ct's scale) as the plan states
+    it -- scales are tracked through every product and rescale, never overwritten.  MUL: mod_switch_to the lower level,
+    multiply, relinearize; COMBINE: Evaluator.scalar_combine (one fused pass on the HIP engine) and rescale_to_next;
+    ADD: add.  Not the reference's Horner_cipher / Tree_cipher and not their bits: those stay as they are."""
+    from . import capi, poly
+    if ct.size() != 2:
+        raise ValueError("encrypted size must be 2")
+    plan = poly.plan(coeffs, basis, ev.ctx.primes[:ct.parms_id()], ct.scale, target_scale)
+    slots: List[Optional[Ciphertext]] = [None] * plan.nslots
+    slots[0] = ct
+    for st in plan.steps:
+        if st.op == capi.POLY_MUL:
+            a, b = slots[st.a].copy(), slots[st.b].copy()
+            ev.mod_switch_to_inplace(a, st.level)
+            if st.a == st.b:
+                b = a  # a square: Evaluator.multiply sees the one payload
+            else:
+                ev.mod_switch_to_inplace(b, st.level)
+            slots[st.dst] = ev.relinearize_inplace(ev.multiply(a, b), relin_keys)
+        elif st.op == capi.POLY_COMBINE:
+            out = ev.scalar_combine([slots[t.src] for t in st.terms], [[t.coef for t in st.terms]],
+                                    [t.wscale for t in st.terms], None if st.constant is None else [st.constant],
+                                    scale=st.cscale, parms_id=st.level)[0]
+            slots[st.dst] = ev.rescale_to_next_inplace(out)
+        else:
+            slots[st.dst] = ev.add(slots[st.a], slots[st.b])
+    return slots[plan.steps[-1].dst]
+
+
 def cipher_dot_product_many(ev: Evaluator, As: Sequence[Ciphertext], Bs: Sequence[Ciphertext], size: int,
                             relin_keys: KSwitchKeys, gal_keys: KSwitchKeys, log_sum: bool = False) -> List[Ciphertext]:
     """len(As) independent cipher_dot_product calls (helper.h:416-502) advanced in lockstep: the rotate-by-1 chain
@@ -865,9 +898,14 @@ SIGMOID_COEFFS = {3: [0.5, 1.20069, 0.00001, -0.81562],
 
 def predict_cipher_weights(ev: Evaluator, encoder: CKKSEncoder, encryptor, features: Sequence[Ciphertext],
                            weights: Ciphertext, num_weights: int, scale: float, gal_keys: KSwitchKeys,
-                           relin_keys: KSwitchKeys, degree: int = 3, log_sum: bool = False) -> Ciphertext:
+                           relin_keys: KSwitchKeys, degree: int = 3, log_sum: bool = False,
+                           poly: str = "horner") -> Ciphertext:
     """predict_cipher_weights, /root/reference/logistic_regression_ckks.cpp:208-266.  log_sum=True: the fast window
-    sum of cipher_dot_product_many (same prediction values, not the reference's noise bits)."""
+    sum of cipher_dot_product_many (same prediction values, not the reference's noise bits).  poly="horner" (default): the
+    reference's Horner_cipher, its bits; "ps": the same sigmoid polynomial through evaluate_polynomial --
+    ceil(log2(degree + 1)) levels instead of `degree`, the prediction at `scale` with nothing overwritten."""
+    if poly not in ("horner", "ps"):
+        raise ValueError("poly must be 'horner' or 'ps'")
     num_rows = len(features)
     results = cipher_dot_product_many(ev, features, [weights] * num_rows, num_weights, relin_keys, gal_keys,
                                       log_sum)                                                             # :220
@@ -882,12 +920,14 @@ def predict_cipher_weights(ev: Evaluator, encoder: CKKSEncoder, encryptor, featu
     ev.rescale_to_next_inplace(lin)                                                                        # :239
     lin.scale = 2.0 ** int(np.log2(lin.scale))                                                             # :242
     coeffs = SIGMOID_COEFFS[degree]                                                                        # :245-262
+    if poly == "ps":
+        return evaluate_polynomial(ev, lin, coeffs, relin_keys, "power", target_scale=scale)
     return horner_cipher(ev, encoder, encryptor, lin, len(coeffs) - 1, coeffs, scale, relin_keys)         # :264
 
 
 def lr_gradient(ev: Evaluator, encoder: CKKSEncoder, encryptor, features: Sequence[Ciphertext],
                 features_T: Sequence[Ciphertext], labels: Ciphertext, weights: Ciphertext, gal_keys: KSwitchKeys,
-                relin_keys: KSwitchKeys, scale: float, degree: int = 3):
+                relin_keys: KSwitchKeys, scale: float, degree: int = 3, poly: str = "horner"):
     """update_weights up to its manual rescale, /root/reference/logistic_regression_ckks.cpp:269-323: everything the
     training step computes before SEAL refuses it at :336.  Returns (gradient, pred_labels): the gradient after :323
     (size 2, one prime left, scale snapped to a power of two) and the operand of the sub at :288.
@@ -895,10 +935,11 @@ def lr_gradient(ev: Evaluator, encoder: CKKSEncoder, encryptor, features: Sequen
     Slot j < num_weights of the gradient is sum_i X[i, j] * (sigmoid(z_i) - y_i).  z_i is the dot product the
     reference's window sum leaves in slot i of row i (helper.h:455-476, masked at :222-229): all of X[i] . w for
     i <= num_weights, the terms k >= i - num_weights for the rows after that, nothing from row 2 * num_weights on --
-    reproduced, not fixed."""
+    reproduced, not fixed.  poly: as predict_cipher_weights ("ps" leaves the prediction, and so everything after it,
+    degree - ceil(log2(degree + 1)) levels higher)."""
     num_obs, num_weights = len(features), len(features_T)
     pred = predict_cipher_weights(ev, encoder, encryptor, features, weights, num_weights, scale, gal_keys,
-                                  relin_keys, degree)                                                       # :282
+                                  relin_keys, degree, poly=poly)                                            # :282
     labels = labels.copy()
     ev.mod_switch_to_inplace(labels, pred.parms_id())                                                      # :286
     pred_labels = ev.sub(pred, labels)                                                                     # :288

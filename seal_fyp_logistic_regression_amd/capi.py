@@ -158,6 +158,29 @@ BFV_MAX_BASIS = 16  # HEFX_BFV_MAX_BASIS
 BFV_SIZE_MAX = 6    # HEFX_BFV_SIZE_MAX
 
 
+# include/hefx_poly.h: the scalar combination of ciphertexts and the polynomial planner
+class PolyStep(C.Structure):  # hefx_poly_step
+    _fields_ = [("op", C.c_int32), ("dst", C.c_int32), ("a", C.c_int32), ("b", C.c_int32), ("level", C.c_int32),
+                ("has_const", C.c_int32), ("constant", C.c_double), ("cscale", C.c_double), ("scale", C.c_double)]
+
+
+class PolyTerm(C.Structure):  # hefx_poly_term
+    _fields_ = [("src", C.c_int32), ("pad_", C.c_int32), ("coef", C.c_double), ("wscale", C.c_double)]
+
+
+_POLY_SIGS = {
+    "hefx_scalar_combine": (_i, [_vp, _i, _i, _i, _pp, C.POINTER(_i), _i, _vp, _vp, _pp, _vp]),
+    "hefx_poly_weight_residue": (_u64, [C.c_double, C.c_double, _u64]),
+    "hefx_poly_plan": (_i, [_i, C.POINTER(C.c_double), _i, _i, C.POINTER(_u64), C.c_double, C.c_double, C.POINTER(PolyStep), _i,
+                            C.POINTER(_i), C.POINTER(PolyTerm), _i, C.POINTER(_i), C.POINTER(_i)]),
+}
+POLY_SYMBOLS = sorted(_POLY_SIGS)
+COMBINE_MAX_IN = 256  # HEFX_COMBINE_MAX_IN
+COMBINE_MAX_OUT = 16  # HEFX_COMBINE_MAX_OUT
+POLY_MUL, POLY_COMBINE, POLY_ADD = 0, 1, 2       # HEFX_POLY_*
+POLY_BASIS = {"power": 0, "chebyshev": 1}        # HEFX_POLY_BASIS_*
+
+
 def library_path() -> str:
     # HEFX_LIB: development override to A/B alternative builds of the same ABI
     return os.environ.get("HEFX_LIB") or _build.SO
@@ -172,7 +195,8 @@ def lib():
     if not os.path.exists(path):
         raise HefxError(f"{path} is missing: build the HIP extension first (__graft_entry__.build())")
     L = C.CDLL(path, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in list(_SIGS.items()) + list(_REFRESH_SIGS.items()) + list(_BFV_SIGS.items()):
+    for name, (res, args) in (list(_SIGS.items()) + list(_REFRESH_SIGS.items()) + list(_BFV_SIGS.items())
+                              + list(_POLY_SIGS.items())):
         f = getattr(L, name)
         f.restype = res
         f.argtypes = args

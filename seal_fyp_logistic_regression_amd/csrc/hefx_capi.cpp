@@ -5,6 +5,7 @@
 #include "../../include/hefx.h"
 #include "../../include/hefx_refresh.h"
 #include "../../include/hefx_bfv.h"
+#include "../../include/hefx_poly.h"
 
 #include <chrono>
 #include <cmath>
@@ -26,6 +27,7 @@
 #include "hefx_internal.h"
 #include "hefx_ranges.h"
 #include "hefx_lt_plan.h"
+#include "hefx_poly_plan.h"
 
 using namespace hefx;
 typedef unsigned __int128 u128;
@@ -3703,5 +3705,92 @@ extern "C" int hefx_bfv_batch_decode(hefx_bfv *b, const uint64_t *m, uint64_t *v
     HIPCHK(launch_bfv_slot_reduce(b->pt->T, (const u64 *)m, w, s));
     HIPCHK(launch_ntt(b->pt->T, false, w, 1, 1, 0, s));
     HIPCHK(launch_bfv_slot_gather(b->pt->T, b->d_index, w, (u64 *)values, s));
+    return HEFX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Polynomial evaluation (include/hefx_poly.h): the scalar combination behind every step of a plan, and the planner
+// (hefx_poly_plan.h, host only) handed out as a flat step list.
+// ---------------------------------------------------------------------------------------------
+// The weights and constants travel with the pointers: one descriptor-ring slot per launch holds the table hefx_poly.hip lays
+// out, filled from the caller's host arrays before the call returns.  The widest output tile that fits the slot (at most 8:
+// the register report at the kernel) is taken; G outputs run as ceil(G / tile) launches, each with a slot of its own.
+extern "C" int hefx_scalar_combine(hefx_context *c, int L, int size, int m, const uint64_t *const *d_in, const int *in_rows, int G,
+                                   const uint64_t *h_weights, const uint64_t *h_consts, uint64_t *const *d_out, void *stream)
+{
+    CTXCHK(c);
+    if (int rc = check_level(c, L)) return rc;
+    if (m < 1 || m > HEFX_COMBINE_MAX_IN) return fail(HEFX_ERR_INVALID, "scalar_combine: m out of range");
+    if (G < 1 || G > HEFX_COMBINE_MAX_OUT) return fail(HEFX_ERR_INVALID, "scalar_combine: G out of range");
+    if (size < 1 || !d_in || !in_rows || !h_weights || !d_out) return fail(HEFX_ERR_INVALID, "bad scalar_combine arguments");
+    for (int k = 0; k < m; ++k) {
+        if (!d_in[k]) return fail(HEFX_ERR_INVALID, "null input in scalar_combine");
+        if (in_rows[k] < L || in_rows[k] > c->k) return fail(HEFX_ERR_INVALID, "scalar_combine: every input needs at least L rows");
+    }
+    for (int g = 0; g < G; ++g)
+        if (!d_out[g]) return fail(HEFX_ERR_INVALID, "null output in scalar_combine");
+    for (size_t i = 0, n = (size_t)G * m * L; i < n; ++i)
+        if (h_weights[i] >= c->primes[i % (size_t)L]) return fail(HEFX_ERR_INVALID, "scalar_combine: a weight is not below its modulus");
+    for (size_t i = 0, n = h_consts ? (size_t)G * L : 0; i < n; ++i)
+        if (h_consts[i] >= c->primes[i % (size_t)L]) return fail(HEFX_ERR_INVALID, "scalar_combine: a constant is not below its modulus");
+    // every lane of every tile reads all inputs: no output may share a byte with any input (all its rows) or another output
+    const size_t row_b = (size_t)c->n * sizeof(u64), out_b = (size_t)size * L * row_b;
+    for (int k = 0; k < m; ++k) {
+        const hefx_ranges::Verdict v = hefx_ranges::check((size_t)G, d_out, out_b, {{d_in + k, 1, (size_t)size * in_rows[k] * row_b}});
+        if (v != hefx_ranges::FINE)
+            return fail(HEFX_ERR_INVALID, std::string("scalar_combine: ") + hefx_ranges::text(v) +
+                                              (v == hefx_ranges::OUTPUT_OVERLAPS_INPUT ? " (d_in, entry " + std::to_string(k) + ")" : std::string()));
+    }
+    int gt = 1;
+    while (gt < G && gt < 8) gt *= 2;
+    while (gt > 1 && scalar_combine_table_words(L, m, gt, h_consts != nullptr) > (size_t)RING_SLOT_PTRS) gt /= 2;
+    if (scalar_combine_table_words(L, m, gt, h_consts != nullptr) > (size_t)RING_SLOT_PTRS)
+        return fail(HEFX_ERR_UNSUPPORTED, "scalar_combine: m * L weights do not fit a descriptor slot");
+    hipStream_t s = (hipStream_t)stream;
+    for (int g0 = 0; g0 < G; g0 += gt) {
+        const int cnt = G - g0 < gt ? G - g0 : gt;
+        RingSlot r;
+        HIPCHK(ring_take(c, r));
+        u64 *t = reinterpret_cast<u64 *>(r.h);
+        const size_t words = scalar_combine_table_words(L, m, gt, h_consts != nullptr);
+        for (int k = 0; k < m; ++k) {
+            t[k] = (u64)(uintptr_t)d_in[k];
+            t[m + k] = (u64)in_rows[k] * c->n;
+        }
+        for (int g = 0; g < gt; ++g) t[2 * m + g] = g < cnt ? (u64)(uintptr_t)d_out[g0 + g] : 0;
+        u64 *wt = t + 2 * m + gt, *ct = wt + (size_t)L * m * gt;
+        for (int j = 0; j < L; ++j)
+            for (int k = 0; k < m; ++k)
+                for (int g = 0; g < gt; ++g)
+                    wt[((size_t)j * m + k) * gt + g] = g < cnt ? h_weights[((size_t)(g0 + g) * m + k) * L + j] : 0;
+        if (h_consts)
+            for (int j = 0; j < L; ++j)
+                for (int g = 0; g < gt; ++g) ct[(size_t)j * gt + g] = g < cnt ? h_consts[(size_t)(g0 + g) * L + j] : 0;
+        HIPCHK(hipMemcpyAsync((void *)r.d, t, words * sizeof(u64), hipMemcpyHostToDevice, s));
+        HIPCHK(launch_scalar_combine(c->T, L, size, m, cnt, gt, reinterpret_cast<const u64 *>(r.d), h_consts != nullptr, s));
+        HIPCHK(ring_commit(c, r, s));
+    }
+    return HEFX_OK;
+}
+
+extern "C" uint64_t hefx_poly_weight_residue(double value, double scale, uint64_t q) { return hefx_poly::weight_residue(value, scale, q); }
+
+static_assert(sizeof(hefx_poly_step) == 6 * 4 + 3 * 8 && sizeof(hefx_poly_term) == 2 * 4 + 2 * 8, "hefx_poly.h: the layouts the bindings read");
+extern "C" int hefx_poly_plan(int degree, const double *coeffs, int basis, int nprimes, const uint64_t *primes, double in_scale,
+                              double target_scale, hefx_poly_step *steps, int max_steps, int *nsteps, hefx_poly_term *terms,
+                              int max_terms, int *nterms, int *nslots)
+{
+    if (!nsteps || !nterms || !nslots) return fail(HEFX_ERR_INVALID, "bad polynomial plan arguments");
+    hefx_poly::Plan P;
+    if (const char *err = hefx_poly::plan(degree, coeffs, basis, nprimes, primes, in_scale, target_scale, P))
+        return fail(HEFX_ERR_INVALID, std::string("poly_plan: ") + err);
+    *nsteps = (int)P.steps.size(), *nterms = (int)P.terms.size(), *nslots = P.nslots;
+    if ((int)P.steps.size() > max_steps || (int)P.terms.size() > max_terms || !steps || !terms)
+        return fail(HEFX_ERR_INVALID, "poly_plan: the step or term array is too small");
+    for (size_t i = 0; i < P.steps.size(); ++i) {
+        const hefx_poly::Step &st = P.steps[i];
+        steps[i] = hefx_poly_step{st.op, st.dst, st.a, st.b, st.level, st.has_const, st.constant, st.cscale, st.scale};
+    }
+    for (size_t i = 0; i < P.terms.size(); ++i) terms[i] = hefx_poly_term{P.terms[i].src, 0, P.terms[i].coef, P.terms[i].wscale};
     return HEFX_OK;
 }

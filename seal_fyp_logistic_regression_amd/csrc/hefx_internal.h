@@ -258,6 +258,11 @@ hipError_t launch_keygen_combine(const DevTables &T, const u64 *sk, const u64 *n
                                  u64 *out, hipStream_t s);
 hipError_t launch_galois_permute(const DevTables &T, const uint32_t *perm, const u64 *in, int rows, u64 *out,
                                  hipStream_t s);
+// hefx_scalar_combine (hefx_poly.hip): G <= gt outputs of one tile, gt in {1, 2, 4, 8}, through the device table laid out
+// there (scalar_combine_table_words words)
+size_t scalar_combine_table_words(int L, int m, int gt, bool has_const);
+hipError_t launch_scalar_combine(const DevTables &T, int L, int size, int m, int G, int gt, const u64 *d_tab, bool has_const,
+                                 hipStream_t s);
 hipError_t warm_kernels(hipStream_t s);
 hipError_t warm_keyswitch(hipStream_t s);
 hipError_t warm_encode(hipStream_t s);

@@ -609,6 +609,28 @@ class Engine:
             int(first_stream_id), capi.ptr_array([o.ptr for o in outs]), stream))
         return outs
 
+    # ---- scalar combinations of ciphertexts (include/hefx_poly.h)
+    def scalar_combine(self, L, size, ins, in_rows, weights, consts=None, outs=None, stream=None):
+        """outs[g] = sum_k weights[g][k] * ins[k] + consts[g] over the first L rows of every input, one pass over the inputs
+        (hefx_scalar_combine).  ins[k]: [size][in_rows[k]][N], in_rows[k] >= L; weights: [G][m][L] residues (uint64);
+        consts: [G][L] residues or None.  Returns the G outputs, [size][L][N] each."""
+        w = np.ascontiguousarray(weights, dtype=np.uint64)
+        m = len(ins)
+        if w.ndim != 3 or w.shape[1] != m or w.shape[2] != L or len(in_rows) != m:
+            raise ValueError("scalar_combine: weights must be [G][m][L], one row count per input")
+        G = w.shape[0]
+        cst = None
+        if consts is not None:
+            cst = np.ascontiguousarray(consts, dtype=np.uint64)
+            if cst.shape != (G, L):
+                raise ValueError("scalar_combine: consts must be [G][L]")
+        outs = outs if outs is not None else self.empty_many(G, (size, L, self.N))
+        rows = (C.c_int * m)(*[int(r) for r in in_rows])
+        capi.check(capi.lib().hefx_scalar_combine(
+            self._h, L, size, m, capi.ptr_array([x.ptr for x in ins]), rows, G, w.ctypes.data,
+            cst.ctypes.data if cst is not None else None, capi.ptr_array([o.ptr for o in outs]), stream))
+        return outs
+
     # ---- CKKS encode on the GPU
     @staticmethod
     def _encode_args(values):

@@ -155,6 +155,12 @@ class GpuBackend:
     def multiply_plain_sum(self, L, size, cts, pts, group=None):
         return self.engine.multiply_plain_sum(L, size, cts, pts, group)
 
+    def scalar_combine(self, L, size, ins, in_rows, weights, consts=None):
+        """outs[g] = sum_k weights[g][k] * ins[k] + consts[g] in one pass (hefx_scalar_combine; weights [G][m][L] and consts
+        [G][L] are residues); the oracle-backed twin of the tests has no such method and Evaluator.scalar_combine composes
+        the same words from mod_drop, multiply_plain, add_many and add_plain"""
+        return self.engine.scalar_combine(L, size, ins, in_rows, weights, consts)
+
     def multiply_batch(self, L, As, Bs):
         return self.engine.multiply_batch(L, As, Bs)
 
@@ -1047,6 +1053,62 @@ class Evaluator:
                 raise RuntimeError("result ciphertext is transparent")
         outs = self.be.multiply_plain_sum(L, size, [a.data for a in cts], [p.data for p in pts], group)
         return [Ciphertext()._set(o, size, L, scale) for o in outs]
+
+    def scalar_combine(self, cts: Sequence[Ciphertext], weights, wscales: Sequence[float], consts=None,
+                       scale: Optional[float] = None, parms_id: Optional[int] = None) -> List[Ciphertext]:
+        """G scalar combinations of the same ciphertexts: out[g] = sum_k weights[g][k] * cts[k] + consts[g], at level
+        parms_id (default: the lowest level among cts; higher inputs are read through their row prefix) and scale S.
+        weights: [G][m] floats (or [m] for one output); weight (g, k) is the scalar plaintext encode(weights[g][k],
+        wscales[k]), so cts[k].scale * wscales[k] must be S for every k -- S is `scale` when given, else
+        cts[0].scale * wscales[0]; consts: [G] floats encoded at S, or None.
+        The words and the checks of the op-by-op sequence -- mod_switch_to, encode, multiply_plain per term, add_many,
+        add_plain -- from ONE pass over the inputs where the backend has hefx_scalar_combine, else from that sequence."""
+        from .poly import weight_residue
+        cts = list(cts)
+        W = np.atleast_2d(np.asarray(weights, dtype=np.float64))
+        m, G = len(cts), W.shape[0]
+        if m < 1 or W.shape[1] != m or len(wscales) != m:
+            raise ValueError("scalar_combine: need one weight per output and ciphertext, one weight scale per ciphertext")
+        cvals = None if consts is None else np.atleast_1d(np.asarray(consts, dtype=np.float64))
+        if cvals is not None and cvals.shape != (G,):
+            raise ValueError("scalar_combine: need one constant per output")
+        L = int(parms_id) if parms_id is not None else min(c.parms_id() for c in cts)
+        size = cts[0].size()
+        S = float(scale) if scale is not None else cts[0].scale * float(wscales[0])
+        for c, ws in zip(cts, wscales):
+            if c.parms_id() < L:
+                raise ValueError("cannot switch to higher level modulus")
+            if c.size() != size:
+                raise ValueError("add_many: mixed sizes are not supported by the fused reduction")
+            self._check_scale(float(ws), L)
+            self._check_scale(c.scale * float(ws), L)
+            if not self._close(S, c.scale * float(ws)):
+                raise ValueError("scale mismatch")
+        self._check_scale(S, L)
+        q = self.ctx.primes[:L]
+        wres = np.empty((G, m, L), dtype=np.uint64)
+        for g in range(G):
+            for k in range(m):
+                wres[g, k] = [weight_residue(W[g, k], wscales[k], p) for p in q]
+                if _c_round(float(W[g, k]) * float(wscales[k])) == 0:
+                    raise RuntimeError("result ciphertext is transparent")  # multiply_plain by the zero plaintext
+        cres = None if cvals is None else np.array([[weight_residue(v, S, p) for p in q] for v in cvals], dtype=np.uint64)
+        rows = [c.parms_id() for c in cts]
+        native = getattr(self.be, "scalar_combine", None)
+        if native is not None and m <= 256 and G <= 16:
+            datas = native(L, size, [c.data for c in cts], rows, wres, cres)
+        else:
+            N, be = self.ctx.N, self.be
+            low = [c.data if r == L else be.mod_drop(r, L, size, c.data) for c, r in zip(cts, rows)]
+            datas = []
+            for g in range(G):
+                prods = [be.multiply_plain(L, size, x, be.from_host(np.repeat(wres[g, k][:, None], N, axis=1)))
+                         for k, x in enumerate(low)]
+                acc = be.add_many(L, size, prods)
+                if cres is not None:
+                    acc = be.add_plain(L, size, acc, be.from_host(np.repeat(cres[g][:, None], N, axis=1)))
+                datas.append(acc)
+        return [Ciphertext()._set(d, size, L, S) for d in datas]
 
     def multiply_sum(self, As: Sequence[Ciphertext], Bs: Sequence[Ciphertext], group: Optional[int] = None):
         """add_many(multiply(As[i], Bs[i])) per group of `group` consecutive terms (None: one group) in one pass over
