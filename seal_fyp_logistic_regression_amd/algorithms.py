@@ -839,6 +839,81 @@ def evaluate_polynomial(ev: Evaluator, ct: Ciphertext, coeffs: Sequence[float], 
     return slots[plan.steps[-1].dst]
 
 
+# ---- the homomorphic DFT: coefficients to slots and back (dft.py plans, these run) ------------------------------------------
+def _dft_rotations(ev: Evaluator, cts: Sequence[Ciphertext], steps: Sequence[int], gal_keys: KSwitchKeys) -> List[Ciphertext]:
+    """rotate_vector(cts[i], steps[i]) for every i as one batch of independent key switches; a step of zero is the input.
+    Every step needs its direct Galois key (plan.galois_steps())."""
+    from .seal import galois_elt_from_step
+    jobs = [i for i, s in enumerate(steps) if s]
+    elts = [galois_elt_from_step(steps[i], ev.ctx.N) for i in jobs]
+    if any(not gal_keys.has_key(e) for e in elts):
+        raise ValueError("Galois key not present")
+    out = [c.copy() for c in cts]
+    if jobs:
+        L = cts[0].parms_id()
+        datas = ev.be.apply_galois_batch(L, [cts[i].data for i in jobs], elts, [gal_keys.key(e) for e in elts])
+        for i, d in zip(jobs, datas):
+            out[i] = Ciphertext()._set(d, 2, L, cts[i].scale)
+    return out
+
+
+def _dft_stage(ev: Evaluator, xs: Sequence[Ciphertext], stage, table, gal_keys: KSwitchKeys) -> List[Ciphertext]:
+    """One stage of a dft.Plan on its one or two input ciphertexts (dft.Stage states the three modes): the baby rotations of
+    every input as one batch, ALL inner sums -- both chains, every giant step -- as one Evaluator.plain_combine, the giant
+    rotations as one batch and their sums, one batched rescale.  table[matrix][giant][baby]: plan.encode(...)[stage]."""
+    if len(xs) != stage.inputs or any(x.size() != 2 for x in xs) or len({x.parms_id() for x in xs}) != 1:
+        raise ValueError("dft stage: needs %d size-2 ciphertexts of one level" % stage.inputs)
+    nb, ng = len(stage.babies), len(stage.giants)
+    rots = _dft_rotations(ev, [x for x in xs for _ in stage.babies], list(stage.babies) * len(xs), gal_keys)
+    rows = []
+    for c in range(stage.outputs):
+        for gi in range(ng):
+            row = [None] * (len(xs) * nb)
+            # (input, matrix) pairs that feed output c
+            feeds = [(0, c)] if stage.mode == "split" else [(c, 0)] if stage.mode == "lockstep" else [(0, 0), (1, 1)]
+            for src, mat in feeds:
+                row[src * nb:(src + 1) * nb] = table[mat][gi]
+            rows.append(row)
+    inner = ev.plain_combine(rots, rows)
+    moved = _dft_rotations(ev, inner, list(stage.giants) * stage.outputs, gal_keys)
+    outs = [moved[c * ng] if ng == 1 else ev.add_many(moved[c * ng:(c + 1) * ng]) for c in range(stage.outputs)]
+    return ev.rescale_to_next_many_inplace(outs)
+
+
+def coeffs_to_slots(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitchKeys, encoded=None):
+    """CoeffToSlot: (ct_a, ct_b) whose slots hold the coefficients of ct's plaintext, ct_a[i] = m_R(i) / scale and
+    ct_b[i] = m_(N/2 + R(i)) / scale (R: bit reversal of the N/2 slot indices, dft.bit_reversal), both plan.levels levels
+    below ct and at ct's scale (tracked through every stage, not overwritten).  plan: dft.plan(N, levels, dft.C2S, ...) for
+    the primes below ct's level; gal_keys: galois_keys(plan.galois_steps(), conjugate=True); encoded:
+    plan.encode(encoder, ct.parms_id()), the plan's plaintexts (made here with a host encoder when not given -- a caller
+    that transforms more than once passes them)."""
+    from . import dft
+    if plan.direction != dft.C2S or plan.N != ev.ctx.N:
+        raise ValueError("coeffs_to_slots: the plan is not a CoeffToSlot plan of this ring")
+    if encoded is None:
+        encoded = plan.encode(CKKSEncoder(ev.ctx, device_encode=False), ct.parms_id())
+    xs = [ct]
+    for stage, table in zip(plan.stages, encoded):
+        xs = _dft_stage(ev, xs, stage, table, gal_keys)
+    return tuple(ev.add(x, ev.complex_conjugate(x, gal_keys)) for x in xs)    # 2 Re(.)
+
+
+def slots_to_coeffs(ev: Evaluator, ct_a: Ciphertext, ct_b: Ciphertext, plan, gal_keys: KSwitchKeys, encoded=None) -> Ciphertext:
+    """SlotToCoeff, the inverse map: from ct_a, ct_b with REAL slots x_a, x_b (in the bit-reversed order coeffs_to_slots
+    leaves) the ciphertext whose plaintext has the coefficients scale * x_a[R^-1], scale * x_b[R^-1] -- slots
+    F_s..F_1 x_a + D F_s..F_1 x_b -- plan.levels levels lower, at the inputs' scale.  plan: dft.plan(N, levels, dft.S2C, ...);
+    gal_keys: galois_keys(plan.galois_steps())."""
+    from . import dft
+    if plan.direction != dft.S2C or plan.N != ev.ctx.N:
+        raise ValueError("slots_to_coeffs: the plan is not a SlotToCoeff plan of this ring")
+    if encoded is None:
+        encoded = plan.encode(CKKSEncoder(ev.ctx, device_encode=False), ct_a.parms_id())
+    xs = [ct_a, ct_b]
+    for stage, table in zip(plan.stages, encoded):
+        xs = _dft_stage(ev, xs, stage, table, gal_keys)
+    return xs[0]
+
+
 def cipher_dot_product_many(ev: Evaluator, As: Sequence[Ciphertext], Bs: Sequence[Ciphertext], size: int,
                             relin_keys: KSwitchKeys, gal_keys: KSwitchKeys, log_sum: bool = False) -> List[Ciphertext]:
     """len(As) independent cipher_dot_product calls (helper.h:416-502) advanced in lockstep: the rotate-by-1 chain

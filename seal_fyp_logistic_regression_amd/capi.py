@@ -180,6 +180,15 @@ COMBINE_MAX_OUT = 16  # HEFX_COMBINE_MAX_OUT
 POLY_MUL, POLY_COMBINE, POLY_ADD = 0, 1, 2       # HEFX_POLY_*
 POLY_BASIS = {"power": 0, "chebyshev": 1}        # HEFX_POLY_BASIS_*
 
+# include/hefx_dft.h: the inner sums of a baby-step/giant-step stage of the homomorphic DFT
+_DFT_SIGS = {
+    "hefx_plain_combine": (_i, [_vp, _i, _i, _pp, _i, _pp, _pp, _vp]),
+}
+DFT_SYMBOLS = sorted(_DFT_SIGS)
+PLAIN_COMBINE_MAX_IN = 256   # HEFX_PLAIN_COMBINE_MAX_IN
+PLAIN_COMBINE_MAX_OUT = 64   # HEFX_PLAIN_COMBINE_MAX_OUT
+PLAIN_COMBINE_MAX_PTRS = 10240  # one descriptor-ring slot: m + G * m + G pointers
+
 
 def library_path() -> str:
     # HEFX_LIB: development override to A/B alternative builds of the same ABI
@@ -196,7 +205,7 @@ def lib():
         raise HefxError(f"{path} is missing: build the HIP extension first (__graft_entry__.build())")
     L = C.CDLL(path, mode=C.RTLD_GLOBAL)
     for name, (res, args) in (list(_SIGS.items()) + list(_REFRESH_SIGS.items()) + list(_BFV_SIGS.items())
-                              + list(_POLY_SIGS.items())):
+                              + list(_POLY_SIGS.items()) + list(_DFT_SIGS.items())):
         f = getattr(L, name)
         f.restype = res
         f.argtypes = args

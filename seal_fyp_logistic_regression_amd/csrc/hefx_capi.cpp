@@ -6,6 +6,7 @@
 #include "../../include/hefx_refresh.h"
 #include "../../include/hefx_bfv.h"
 #include "../../include/hefx_poly.h"
+#include "../../include/hefx_dft.h"
 
 #include <chrono>
 #include <cmath>
@@ -3792,5 +3793,71 @@ extern "C" int hefx_poly_plan(int degree, const double *coeffs, int basis, int n
         steps[i] = hefx_poly_step{st.op, st.dst, st.a, st.b, st.level, st.has_const, st.constant, st.cscale, st.scale};
     }
     for (size_t i = 0; i < P.terms.size(); ++i) terms[i] = hefx_poly_term{P.terms[i].src, 0, P.terms[i].coef, P.terms[i].wscale};
+    return HEFX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The homomorphic DFT (include/hefx_dft.h): the inner sums of a baby-step/giant-step stage in one pass.
+// ---------------------------------------------------------------------------------------------
+// One descriptor-ring slot holds the table hefx_dft.hip lays out, and one launch runs all tiles side by side.  Everything is
+// checked before the slot is taken.
+//
+// The tile width.  A wider tile reads the inputs fewer times (d + 2 m ceil(G / tile) volumes of L N words for d terms) but
+// the call then has fewer waves: row_waves = L * N / 128 per tile, each a long chain of loads and 128-bit products.  The
+// widest tile (8: the register report at the kernel) is halved until the call has PLAIN_COMBINE_TARGET_WAVES waves or the
+// tile is one output; a tile is never wider than G needs, and a table that the padding of the last tile pushes past the slot
+// takes the next narrower tile (a tile of one has no padding: m + G * m + G words, the bound the header states).
+// 4096 waves -- four per SIMD of the MI355X, what the register report allows tiles of up to four -- is the measured optimum
+// of 0 (always the widest), 2048, 4096, 8192 and 16384 at N = 16384, L = 5 and N = 32768, L = 8 (device time per call,
+// m = G = 8 dense: 33.6 / 23.9 / 21.8 / 21.8 / 21.9 us and 49.0 / 49.5 / 47.0 / 51.4 / 61.6 us; DESIGN.md has the table).
+constexpr size_t PLAIN_COMBINE_TARGET_WAVES = 4096;
+static int plain_combine_tile(int G, int m, size_t row_waves)
+{
+    int gt = 8;
+    while (gt > 1 && gt / 2 >= G) gt /= 2;
+    while (gt > 1 && row_waves * (size_t)((G + gt - 1) / gt) < PLAIN_COMBINE_TARGET_WAVES) gt /= 2;
+    while (gt > 1 && plain_combine_table_words(m, G, gt) > (size_t)RING_SLOT_PTRS) gt /= 2;
+    return gt;
+}
+
+extern "C" int hefx_plain_combine(hefx_context *c, int L, int m, const uint64_t *const *d_in, int G, const uint64_t *const *d_pts,
+                                  uint64_t *const *d_out, void *stream)
+{
+    CTXCHK(c);
+    if (int rc = check_level(c, L)) return rc;
+    if (m < 1 || m > HEFX_PLAIN_COMBINE_MAX_IN) return fail(HEFX_ERR_INVALID, "plain_combine: m out of range");
+    if (G < 1 || G > HEFX_PLAIN_COMBINE_MAX_OUT) return fail(HEFX_ERR_INVALID, "plain_combine: G out of range");
+    if (!d_in || !d_pts || !d_out) return fail(HEFX_ERR_INVALID, "bad plain_combine arguments");
+    if ((size_t)m + (size_t)G * m + G > (size_t)RING_SLOT_PTRS)
+        return fail(HEFX_ERR_UNSUPPORTED, "plain_combine: m + G * m + G pointers do not fit a descriptor slot");
+    for (int k = 0; k < m; ++k)
+        if (!d_in[k]) return fail(HEFX_ERR_INVALID, "null input in plain_combine");
+    for (int g = 0; g < G; ++g) {
+        if (!d_out[g]) return fail(HEFX_ERR_INVALID, "null output in plain_combine");
+        bool any = false;
+        for (int k = 0; k < m && !any; ++k) any = d_pts[(size_t)g * m + k] != nullptr;
+        if (!any) return fail(HEFX_ERR_INVALID, "plain_combine: an output has no term");
+    }
+    // every lane of every tile reads all inputs of its terms: no output may share a byte with any input, any plaintext (null
+    // entries are skipped) or another output
+    const size_t pt_b = (size_t)L * c->n * sizeof(u64);
+    if (int rc = check_ranges("plain_combine", (size_t)G, d_out, 2 * pt_b, {{d_in, (size_t)m, 2 * pt_b}, {d_pts, (size_t)G * m, pt_b}},
+                              {"d_in", "d_pts"}))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int gt = plain_combine_tile(G, m, (size_t)L * (c->n / 128));
+    RingSlot r;
+    HIPCHK(ring_take(c, r));
+    u64 *t = reinterpret_cast<u64 *>(r.h);
+    for (int k = 0; k < m; ++k) t[k] = (u64)(uintptr_t)d_in[k];
+    for (int g0 = 0; g0 < G; g0 += gt) {
+        u64 *ot = t + m + (size_t)(g0 / gt) * ((size_t)gt + (size_t)m * gt), *pt = ot + gt;
+        for (int g = 0; g < gt; ++g) ot[g] = g0 + g < G ? (u64)(uintptr_t)d_out[g0 + g] : 0;
+        for (int k = 0; k < m; ++k)
+            for (int g = 0; g < gt; ++g) pt[(size_t)k * gt + g] = g0 + g < G ? (u64)(uintptr_t)d_pts[(size_t)(g0 + g) * m + k] : 0;
+    }
+    HIPCHK(hipMemcpyAsync((void *)r.d, t, plain_combine_table_words(m, G, gt) * sizeof(u64), hipMemcpyHostToDevice, s));
+    HIPCHK(launch_plain_combine(c->T, L, m, G, gt, reinterpret_cast<const u64 *>(r.d), s));
+    HIPCHK(ring_commit(c, r, s));
     return HEFX_OK;
 }

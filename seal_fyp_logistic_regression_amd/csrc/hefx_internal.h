@@ -263,6 +263,10 @@ hipError_t launch_galois_permute(const DevTables &T, const uint32_t *perm, const
 size_t scalar_combine_table_words(int L, int m, int gt, bool has_const);
 hipError_t launch_scalar_combine(const DevTables &T, int L, int size, int m, int G, int gt, const u64 *d_tab, bool has_const,
                                  hipStream_t s);
+// hefx_plain_combine (hefx_dft.hip): G outputs in ceil(G / gt) tiles of one launch, gt in {1, 2, 4, 8}, through the device
+// table laid out there (plain_combine_table_words words)
+size_t plain_combine_table_words(int m, int G, int gt);
+hipError_t launch_plain_combine(const DevTables &T, int L, int m, int G, int gt, const u64 *d_tab, hipStream_t s);
 hipError_t warm_kernels(hipStream_t s);
 hipError_t warm_keyswitch(hipStream_t s);
 hipError_t warm_encode(hipStream_t s);

@@ -631,6 +631,20 @@ class Engine:
             cst.ctypes.data if cst is not None else None, capi.ptr_array([o.ptr for o in outs]), stream))
         return outs
 
+    # ---- plaintext combinations of ciphertexts (include/hefx_dft.h)
+    def plain_combine(self, L, ins, pts, outs=None, stream=None):
+        """outs[g] = sum_k pts[g][k] (.) ins[k] over the non-None plaintexts of row g, one pass over the inputs
+        (hefx_plain_combine).  ins[k]: [2][L][N]; pts: [G][m] of [L][N] plaintexts or None (a structural zero).  Returns the
+        G outputs, [2][L][N] each."""
+        m, G = len(ins), len(pts)
+        if any(len(row) != m for row in pts):
+            raise ValueError("plain_combine: every output needs one plaintext (or None) per input")
+        outs = outs if outs is not None else self.empty_many(G, (2, L, self.N))
+        flat = [None if p is None else p.ptr for row in pts for p in row]
+        capi.check(capi.lib().hefx_plain_combine(self._h, L, m, capi.ptr_array([x.ptr for x in ins]), G, capi.ptr_array(flat),
+                                                 capi.ptr_array([o.ptr for o in outs]), stream))
+        return outs
+
     # ---- CKKS encode on the GPU
     @staticmethod
     def _encode_args(values):

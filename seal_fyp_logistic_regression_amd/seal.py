@@ -161,6 +161,11 @@ class GpuBackend:
         the same words from mod_drop, multiply_plain, add_many and add_plain"""
         return self.engine.scalar_combine(L, size, ins, in_rows, weights, consts)
 
+    def plain_combine(self, L, ins, pts):
+        """outs[g] = sum_k pts[g][k] (.) ins[k] over the non-None plaintexts of row g in one pass (hefx_plain_combine); the
+        oracle-backed twin of the tests has no such method and Evaluator.plain_combine takes multiply_plain_sum per output"""
+        return self.engine.plain_combine(L, ins, pts)
+
     def multiply_batch(self, L, As, Bs):
         return self.engine.multiply_batch(L, As, Bs)
 
@@ -589,11 +594,15 @@ class KeyGenerator:
             elts += [pow(3, 1 << i, 2 * N), pow(3, N // 2 - (1 << i), 2 * N)]
         return sorted(set(elts))
 
-    def galois_keys(self, steps: Optional[Sequence[int]] = None) -> KSwitchKeys:
-        """keygen.galois_keys(): default = 3^(+-2^i) and 2N-1 (power-of-two steps only, App. A.7)."""
+    def galois_keys(self, steps: Optional[Sequence[int]] = None, conjugate: bool = False) -> KSwitchKeys:
+        """keygen.galois_keys(): default = 3^(+-2^i) and 2N-1 (power-of-two steps only, App. A.7).  conjugate=True adds the
+        key of the Galois element 2N - 1 (Evaluator.complex_conjugate) behind the keys of `steps`, whose sampler streams
+        stay what they are without it; the default set already holds it."""
         from . import galois_tables
         N = self.ctx.N
         elts = self.default_galois_elts() if steps is None else [galois_elt_from_step(s, N) for s in steps]
+        if conjugate and 2 * N - 1 not in elts:
+            elts = elts + [2 * N - 1]
         gk = KSwitchKeys()
         permute = getattr(self.ctx.backend, "galois_permute", None)
         for g in elts:
@@ -1110,6 +1119,59 @@ class Evaluator:
                 datas.append(acc)
         return [Ciphertext()._set(d, size, L, S) for d in datas]
 
+    def plain_combine(self, cts: Sequence[Ciphertext], pts_matrix: Sequence[Sequence[Optional[Plaintext]]]) -> List[Ciphertext]:
+        """G plaintext combinations of the same ciphertexts: out[g] = sum_k pts_matrix[g][k] (.) cts[k] over the entries that
+        are not None (None: a structural zero, no term) -- the inner sums of a baby-step/giant-step matrix product, all giant
+        steps at once.  The ciphertexts share one level and scale and so do the plaintexts; the result's scale is their
+        product.  The words and the checks of multiply_plain per term and add_many, from ONE pass over the inputs where the
+        backend has hefx_plain_combine (small uniform shapes: from one grouped multiply_plain_sum, see below), else from
+        multiply_plain_sum per output."""
+        cts = list(cts)
+        rows = [list(r) for r in pts_matrix]
+        m = len(cts)
+        if m < 1 or not rows or any(len(r) != m for r in rows):
+            raise ValueError("plain_combine: need one plaintext (or None) per output and ciphertext")
+        L, size, ct_scale = cts[0].parms_id(), cts[0].size(), cts[0].scale
+        for c in cts:
+            if c.parms_id() != L:
+                raise ValueError("encrypted1 and encrypted2 parameter mismatch")
+            if c.size() != 2 or size != 2:
+                raise ValueError("encrypted size must be 2")
+            if not self._close(ct_scale, c.scale):
+                raise ValueError("scale mismatch")
+        scale = None
+        for r in rows:
+            if all(p is None for p in r):
+                raise ValueError("plain_combine: an output has no term")
+            for p in r:
+                if p is None:
+                    continue
+                if p.parms_id() != L:
+                    raise ValueError("encrypted_ntt and plain_ntt parameter mismatch")
+                s = ct_scale * p.scale
+                self._check_scale(s, L)
+                if scale is not None and not self._close(scale, s):
+                    raise ValueError("scale mismatch")
+                scale = s if scale is None else scale
+                if p.is_zero:
+                    raise RuntimeError("result ciphertext is transparent")
+        native = getattr(self.be, "plain_combine", None)
+        G = len(rows)
+        counts = [sum(p is not None for p in r) for r in rows]
+        grouped = getattr(self.be, "multiply_plain_sum", None) if native is not None and len(set(counts)) == 1 else None
+        if grouped is not None and not (m >= 8 and G >= 4 and sum(counts) * L * self.ctx.N >= 1 << 23):
+            # MEASURED (profiles/dft.json, DESIGN.md): where every output has the same number of terms the sums are ONE
+            # grouped hefx_multiply_plain_sum, and on the MI355X the fused call beats that one only from 8 inputs, 4 outputs
+            # and 2^23 words of terms up; below, the same words come from the grouped call
+            datas = grouped(L, 2, [c.data for r in rows for c, p in zip(cts, r) if p is not None],
+                            [p.data for r in rows for p in r if p is not None], counts[0])
+        elif native is not None and m <= 256 and G <= 64 and m + G * m + G <= 10240:
+            datas = native(L, [c.data for c in cts], [[None if p is None else p.data for p in r] for r in rows])
+        else:
+            datas = [self.be.multiply_plain_sum(L, 2, [c.data for c, p in zip(cts, r) if p is not None],
+                                                [p.data for p in r if p is not None])[0] for r in rows]
+        return [Ciphertext()._set(d, 2, L, scale) for d in datas]
+
     def multiply_sum(self, As: Sequence[Ciphertext], Bs: Sequence[Ciphertext], group: Optional[int] = None):
         """add_many(multiply(As[i], Bs[i])) per group of `group` consecutive terms (None: one group) in one pass over
         the operands (hefx_multiply_sum): the products and the sum of Linear_Transform_Cipher (helper.h:222-231) and
@@ -1247,3 +1309,17 @@ class Evaluator:
 
     def rotate_vector_inplace(self, a, steps, galois_keys):
         return self.rotate_vector(a, steps, galois_keys, a)
+
+    def complex_conjugate(self, a: Ciphertext, galois_keys: KSwitchKeys, destination=None):
+        """Evaluator::complex_conjugate: the Galois element 2N - 1, every slot conjugated"""
+        if a.size() != 2:
+            raise ValueError("encrypted size must be 2")
+        elt = 2 * self.ctx.N - 1
+        if not galois_keys.has_key(elt):
+            raise ValueError("Galois key not present")
+        data = self.be.apply_galois(a.parms_id(), a.data, elt, galois_keys.key(elt))
+        out = destination if destination is not None else Ciphertext()
+        return out._set(data, 2, a.parms_id(), a.scale)
+
+    def complex_conjugate_inplace(self, a, galois_keys):
+        return self.complex_conjugate(a, galois_keys, a)
