@@ -839,6 +839,96 @@ def evaluate_polynomial(ev: Evaluator, ct: Ciphertext, coeffs: Sequence[float], 
     return slots[plan.steps[-1].dst]
 
 
+def evaluate_polynomial_many(ev: Evaluator, cts: Sequence[Ciphertext], coeffs: Sequence[float], relin_keys: KSwitchKeys,
+                             basis: str = "power", target_scale: Optional[float] = None, lazy: bool = True) -> List[Ciphertext]:
+    """evaluate_polynomial on n ciphertexts of one level and scale in lockstep: the same unchanged plan (poly.plan), every
+    step one batched call over the n items.  lazy=True defers every MUL whose only reader is a COMBINE (and whose result is
+    not the plan's) into that COMBINE: relinearisation is linear, so the node  sum_p u_p (a_p * b_p) + sum_k w_k ct_k + c  is
+    formed at size 3 by ONE Evaluator.product_combine (hefx_product_combine on the HIP engine) and followed by one
+    relinearize_many and one rescale_to_next_many -- plan.relinearizations(True) key switches per item instead of plan.muls
+    (12 against 19 at degree 31).  Any other MUL runs as in evaluate_polynomial.  lazy=False gives the words of
+    evaluate_polynomial per item; lazy=True gives other words (a sum relinearised once is not the sum of the parts
+    relinearised one by one, only the same plaintext) at the same level and scale."""
+    from . import capi, poly
+    cts = list(cts)
+    if not cts:
+        return []
+    if any(c.size() != 2 for c in cts):
+        raise ValueError("encrypted size must be 2")
+    if any(c.parms_id() != cts[0].parms_id() or c.scale != cts[0].scale for c in cts):
+        raise ValueError("evaluate_polynomial_many: the ciphertexts must share one level and one scale")
+    n = len(cts)
+    plan = poly.plan(coeffs, basis, ev.ctx.primes[:cts[0].parms_id()], cts[0].scale, target_scale)
+    deferred = plan.deferred() if lazy else {}
+    producer = {plan.steps[i].dst: plan.steps[i] for i in deferred}   # slot -> the MUL that was not run
+    slots: List[Optional[List[Ciphertext]]] = [None] * plan.nslots
+    slots[0] = cts
+    for i, st in enumerate(plan.steps):
+        if st.op == capi.POLY_MUL:
+            if i in deferred:
+                continue
+            As = [ev.mod_switch_to_inplace(c.copy(), st.level) for c in slots[st.a]]
+            # (a square: Evaluator.multiply sees the one payload)
+            Bs = As if st.a == st.b else [ev.mod_switch_to_inplace(c.copy(), st.level) for c in slots[st.b]]
+            slots[st.dst] = ev.relinearize_many_inplace(ev.multiply_many(As, Bs), relin_keys)
+        elif st.op == capi.POLY_COMBINE:
+            products = [(slots[producer[t.src].a], slots[producer[t.src].b], t.coef, t.wscale) for t in st.terms if t.src in producer]
+            if products:
+                lin = [(slots[t.src], t.coef, t.wscale) for t in st.terms if t.src not in producer]
+                outs = ev.product_combine(products, lin, st.constant, scale=st.cscale, parms_id=st.level)
+                ev.relinearize_many_inplace(outs, relin_keys)
+            else:
+                outs = [ev.scalar_combine([slots[t.src][k] for t in st.terms], [[t.coef for t in st.terms]],
+                                          [t.wscale for t in st.terms], None if st.constant is None else [st.constant],
+                                          scale=st.cscale, parms_id=st.level)[0] for k in range(n)]
+            slots[st.dst] = ev.rescale_to_next_many_inplace(outs)
+        else:
+            slots[st.dst] = ev.add_pairs(slots[st.a], slots[st.b])
+    return slots[plan.steps[-1].dst]
+
+
+# ---- EvalMod and bootstrapping (bootstrap.py plans, these run) -----------------------------------------------------------------
+def eval_mod(ev: Evaluator, cts: Sequence[Ciphertext], plan, relin_keys: KSwitchKeys, lazy: bool = True) -> List[Ciphertext]:
+    """EvalMod on n ciphertexts in lockstep (the two outputs of CoeffToSlot): slots u = (I + eps) / K' in [-1, 1] become
+    sin(2 pi eps), about 2 pi eps.  The Chebyshev interpolant of cos((2 pi K' u - pi / 2) / 2^r) through
+    evaluate_polynomial_many, then r double angles cos 2t = 2 cos^2 t - 1, each ONE Evaluator.product_combine (P = 1, a = b,
+    weight 2, constant -1), one relinearisation and one rescale: one level each, where the planner would spend two on a
+    degree 2.  The weight is the integer 2 at scale 1, so a double angle takes scale s to s^2 / q; the polynomial's target
+    scale (plan.poly_target_scale) is the one from which r of them end at plan.scale.  Scales are tracked, never overwritten."""
+    cts = list(cts)
+    L = cts[0].parms_id()
+    if L != plan.evalmod_level:
+        raise ValueError("eval_mod: the ciphertexts are not at the level the plan was made for")
+    ys = evaluate_polynomial_many(ev, cts, plan.coeffs, relin_keys, basis="chebyshev",
+                                  target_scale=plan.poly_target_scale, lazy=lazy)
+    for _ in range(plan.r):
+        ys = ev.product_combine([(ys, ys, 2.0, 1.0)], (), -1.0)
+        ev.relinearize_many_inplace(ys, relin_keys)
+        ev.rescale_to_next_many_inplace(ys)
+    return ys
+
+
+def bootstrap(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitchKeys, relin_keys: KSwitchKeys, encoded=None) -> Ciphertext:
+    """CKKS bootstrapping with evaluation keys only: a size-2 ciphertext at the last prime q_0 and scale plan.scale comes back
+    at level plan.result_level encrypting the same message (to the precision of bootstrap.plan), at plan.scale as a computed
+    value.  Evaluator.mod_raise to the top (the plaintext becomes m + q_0 I), coeffs_to_slots with scale / (q_0 K') folded
+    into its factor, eval_mod on both outputs in lockstep, slots_to_coeffs with q_0 / (2 pi scale) folded into its factor.
+    plan: bootstrap.plan(...) for this context's chain; gal_keys: galois_keys(plan.galois_steps(), conjugate=True); the
+    secret key must be sparse enough for plan.K (KeyGenerator(hamming_weight=...)); encoded: plan.encode(encoder)."""
+    if ct.size() != 2 or ct.parms_id() != 1:
+        raise ValueError("bootstrap: needs a size-2 ciphertext at the last prime")
+    if plan.N != ev.ctx.N or list(plan.primes) != list(ev.ctx.primes):
+        raise ValueError("bootstrap: the plan was made for another ring or chain")
+    if not ev._close(ct.scale, plan.scale):
+        raise ValueError("scale mismatch")
+    if encoded is None:
+        encoded = plan.encode(CKKSEncoder(ev.ctx, device_encode=False))
+    raised = ev.mod_raise(ct, plan.top_level)
+    ca, cb = coeffs_to_slots(ev, raised, plan.c2s, gal_keys, encoded[0])
+    ya, yb = eval_mod(ev, [ca, cb], plan, relin_keys)
+    return slots_to_coeffs(ev, ya, yb, plan.s2c, gal_keys, encoded[1])
+
+
 # ---- the homomorphic DFT: coefficients to slots and back (dft.py plans, these run) ------------------------------------------
 def _dft_rotations(ev: Evaluator, cts: Sequence[Ciphertext], steps: Sequence[int], gal_keys: KSwitchKeys) -> List[Ciphertext]:
     """rotate_vector(cts[i], steps[i]) for every i as one batch of independent key switches; a step of zero is the input.

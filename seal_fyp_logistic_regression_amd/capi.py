@@ -189,6 +189,17 @@ PLAIN_COMBINE_MAX_IN = 256   # HEFX_PLAIN_COMBINE_MAX_IN
 PLAIN_COMBINE_MAX_OUT = 64   # HEFX_PLAIN_COMBINE_MAX_OUT
 PLAIN_COMBINE_MAX_PTRS = 10240  # one descriptor-ring slot: m + G * m + G pointers
 
+# include/hefx_bootstrap.h: the fused node of EvalMod (products, linear terms and a constant as one size-3 sum)
+_BOOTSTRAP_SIGS = {
+    "hefx_product_combine": (_i, [_vp, _i, _i, _i, _pp, C.POINTER(_i), _pp, C.POINTER(_i), _vp, _i, _pp, C.POINTER(_i), _vp, _vp,
+                                  _pp, _vp]),
+}
+BOOTSTRAP_SYMBOLS = sorted(_BOOTSTRAP_SIGS)
+PRODUCT_COMBINE_MAX_PRODUCTS = 32  # HEFX_PRODUCT_COMBINE_MAX_PRODUCTS
+PRODUCT_COMBINE_MAX_LIN = 64       # HEFX_PRODUCT_COMBINE_MAX_LIN
+PRODUCT_COMBINE_MAX_ITEMS = 64     # HEFX_PRODUCT_COMBINE_MAX_ITEMS
+PRODUCT_COMBINE_MAX_WORDS = 10240  # one descriptor-ring slot: 2P + m + L (P + m + 1) + n (2P + m + 1) words
+
 
 def library_path() -> str:
     # HEFX_LIB: development override to A/B alternative builds of the same ABI
@@ -205,7 +216,7 @@ def lib():
         raise HefxError(f"{path} is missing: build the HIP extension first (__graft_entry__.build())")
     L = C.CDLL(path, mode=C.RTLD_GLOBAL)
     for name, (res, args) in (list(_SIGS.items()) + list(_REFRESH_SIGS.items()) + list(_BFV_SIGS.items())
-                              + list(_POLY_SIGS.items()) + list(_DFT_SIGS.items())):
+                              + list(_POLY_SIGS.items()) + list(_DFT_SIGS.items()) + list(_BOOTSTRAP_SIGS.items())):
         f = getattr(L, name)
         f.restype = res
         f.argtypes = args

@@ -7,6 +7,7 @@
 #include "../../include/hefx_bfv.h"
 #include "../../include/hefx_poly.h"
 #include "../../include/hefx_dft.h"
+#include "../../include/hefx_bootstrap.h"
 
 #include <chrono>
 #include <cmath>
@@ -3858,6 +3859,91 @@ extern "C" int hefx_plain_combine(hefx_context *c, int L, int m, const uint64_t 
     }
     HIPCHK(hipMemcpyAsync((void *)r.d, t, plain_combine_table_words(m, G, gt) * sizeof(u64), hipMemcpyHostToDevice, s));
     HIPCHK(launch_plain_combine(c->T, L, m, G, gt, reinterpret_cast<const u64 *>(r.d), s));
+    HIPCHK(ring_commit(c, r, s));
+    return HEFX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The fused node of EvalMod (include/hefx_bootstrap.h): products, linear terms and the constant of a plan's node as one size-3
+// sum, for n items in lockstep.
+// ---------------------------------------------------------------------------------------------
+// One descriptor-ring slot holds the table hefx_bootstrap.hip lays out -- strides, weights, the constant and the n pointer
+// records -- and one launch runs all items and rows.  Everything is checked before the slot is taken.
+extern "C" int hefx_product_combine(hefx_context *c, int L, int n, int P, const uint64_t *const *d_a, const int *a_rows,
+                                    const uint64_t *const *d_b, const int *b_rows, const uint64_t *h_u, int m,
+                                    const uint64_t *const *d_lin, const int *lin_rows, const uint64_t *h_w, const uint64_t *h_c,
+                                    uint64_t *const *d_out, void *stream)
+{
+    CTXCHK(c);
+    if (int rc = check_level(c, L)) return rc;
+    if (P < 1 || P > HEFX_PRODUCT_COMBINE_MAX_PRODUCTS) return fail(HEFX_ERR_INVALID, "product_combine: P out of range");
+    if (m < 0 || m > HEFX_PRODUCT_COMBINE_MAX_LIN) return fail(HEFX_ERR_INVALID, "product_combine: m out of range");
+    if (n < 1 || n > HEFX_PRODUCT_COMBINE_MAX_ITEMS) return fail(HEFX_ERR_INVALID, "product_combine: n out of range");
+    if (!d_a || !a_rows || !d_b || !b_rows || !h_u || !d_out || (m > 0 && (!d_lin || !lin_rows || !h_w)))
+        return fail(HEFX_ERR_INVALID, "bad product_combine arguments");
+    const bool has_const = h_c != nullptr;
+    if (product_combine_table_words(L, n, P, m, has_const) > (size_t)RING_SLOT_PTRS)
+        return fail(HEFX_ERR_UNSUPPORTED, "product_combine: strides, weights and pointers do not fit a descriptor slot");
+    for (int p = 0; p < P; ++p)
+        if (a_rows[p] < L || a_rows[p] > c->k || b_rows[p] < L || b_rows[p] > c->k)
+            return fail(HEFX_ERR_INVALID, "product_combine: every operand needs at least L rows");
+    for (int k = 0; k < m; ++k)
+        if (lin_rows[k] < L || lin_rows[k] > c->k) return fail(HEFX_ERR_INVALID, "product_combine: every linear term needs at least L rows");
+    for (int i = 0; i < n; ++i) {
+        for (int p = 0; p < P; ++p)
+            if (!d_a[(size_t)i * P + p] || !d_b[(size_t)i * P + p]) return fail(HEFX_ERR_INVALID, "null operand in product_combine");
+        for (int k = 0; k < m; ++k)
+            if (!d_lin[(size_t)i * m + k]) return fail(HEFX_ERR_INVALID, "null linear term in product_combine");
+        if (!d_out[i]) return fail(HEFX_ERR_INVALID, "null output in product_combine");
+    }
+    for (size_t i = 0, e = (size_t)P * L; i < e; ++i)
+        if (h_u[i] >= c->primes[i % (size_t)L]) return fail(HEFX_ERR_INVALID, "product_combine: a weight is not below its modulus");
+    for (size_t i = 0, e = (size_t)m * L; i < e; ++i)
+        if (h_w[i] >= c->primes[i % (size_t)L]) return fail(HEFX_ERR_INVALID, "product_combine: a weight is not below its modulus");
+    for (int j = 0; has_const && j < L; ++j)
+        if (h_c[j] >= c->primes[j]) return fail(HEFX_ERR_INVALID, "product_combine: a constant is not below its modulus");
+    // every lane reads all operands of its item, and the items run side by side: no output may share a byte with an operand
+    // or a linear term of ANY item (all its rows) or with another output.  Operand p has its own size: one column at a time
+    const size_t row_b = (size_t)c->n * sizeof(u64), out_b = 3 * (size_t)L * row_b;
+    std::vector<const uint64_t *> col((size_t)n);
+    auto column = [&](const uint64_t *const *ptrs, int width, int at, int rows, const char *name) -> int {
+        for (int i = 0; i < n; ++i) col[(size_t)i] = ptrs[(size_t)i * width + at];
+        const hefx_ranges::Verdict v = hefx_ranges::check((size_t)n, d_out, out_b, {{col.data(), (size_t)n, 2 * (size_t)rows * row_b}});
+        if (v == hefx_ranges::FINE) return HEFX_OK;
+        return fail(HEFX_ERR_INVALID, std::string("product_combine: ") + hefx_ranges::text(v) +
+                                          (v == hefx_ranges::OUTPUT_OVERLAPS_INPUT ? std::string(" (") + name + ", entry " + std::to_string(at) + ")" : std::string()));
+    };
+    for (int p = 0; p < P; ++p) {
+        if (int rc = column(d_a, P, p, a_rows[p], "d_a")) return rc;
+        if (int rc = column(d_b, P, p, b_rows[p], "d_b")) return rc;
+    }
+    for (int k = 0; k < m; ++k)
+        if (int rc = column(d_lin, m, k, lin_rows[k], "d_lin")) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    RingSlot r;
+    HIPCHK(ring_take(c, r));
+    u64 *t = reinterpret_cast<u64 *>(r.h);
+    for (int p = 0; p < P; ++p) {
+        t[p] = (u64)a_rows[p] * c->n;
+        t[P + p] = (u64)b_rows[p] * c->n;
+    }
+    for (int k = 0; k < m; ++k) t[2 * P + k] = (u64)lin_rows[k] * c->n;
+    u64 *ut = t + 2 * P + m, *wt = ut + (size_t)L * P, *ct = wt + (size_t)L * m, *rec = ct + (has_const ? L : 0);
+    for (int j = 0; j < L; ++j) {
+        for (int p = 0; p < P; ++p) ut[(size_t)j * P + p] = h_u[(size_t)p * L + j];
+        for (int k = 0; k < m; ++k) wt[(size_t)j * m + k] = h_w[(size_t)k * L + j];
+        if (has_const) ct[j] = h_c[j];
+    }
+    for (int i = 0; i < n; ++i, rec += 2 * P + m + 1) {
+        for (int p = 0; p < P; ++p) {
+            rec[p] = (u64)(uintptr_t)d_a[(size_t)i * P + p];
+            rec[P + p] = (u64)(uintptr_t)d_b[(size_t)i * P + p];
+        }
+        for (int k = 0; k < m; ++k) rec[2 * P + k] = (u64)(uintptr_t)d_lin[(size_t)i * m + k];
+        rec[2 * P + m] = (u64)(uintptr_t)d_out[i];
+    }
+    HIPCHK(hipMemcpyAsync((void *)r.d, t, product_combine_table_words(L, n, P, m, has_const) * sizeof(u64), hipMemcpyHostToDevice, s));
+    HIPCHK(launch_product_combine(c->T, L, n, P, m, reinterpret_cast<const u64 *>(r.d), has_const, s));
     HIPCHK(ring_commit(c, r, s));
     return HEFX_OK;
 }

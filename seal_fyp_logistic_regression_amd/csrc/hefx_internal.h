@@ -267,6 +267,10 @@ hipError_t launch_scalar_combine(const DevTables &T, int L, int size, int m, int
 // table laid out there (plain_combine_table_words words)
 size_t plain_combine_table_words(int m, int G, int gt);
 hipError_t launch_plain_combine(const DevTables &T, int L, int m, int G, int gt, const u64 *d_tab, hipStream_t s);
+// hefx_product_combine (hefx_bootstrap.hip): n items of one node, P products and m linear terms, in one launch through the
+// device table laid out there (product_combine_table_words words)
+size_t product_combine_table_words(int L, int n, int P, int m, bool has_const);
+hipError_t launch_product_combine(const DevTables &T, int L, int n, int P, int m, const u64 *d_tab, bool has_const, hipStream_t s);
 hipError_t warm_kernels(hipStream_t s);
 hipError_t warm_keyswitch(hipStream_t s);
 hipError_t warm_encode(hipStream_t s);

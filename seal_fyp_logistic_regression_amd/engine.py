@@ -645,6 +645,40 @@ class Engine:
                                                  capi.ptr_array([o.ptr for o in outs]), stream))
         return outs
 
+    # ---- the fused node of EvalMod (include/hefx_bootstrap.h)
+    def product_combine(self, L, As, a_rows, Bs, b_rows, u, lins=None, lin_rows=(), w=None, c=None, outs=None, stream=None):
+        """outs[i] = sum_p u[p] * (As[i][p] (x) Bs[i][p]) + sum_k w[k] * lins[i][k] + c, size 3 and not relinearised, for the n
+        items in one launch (hefx_product_combine).  As, Bs: [n][P] of [2][a_rows[p] | b_rows[p]][N]; lins: [n][m] of
+        [2][lin_rows[k]][N] (m may be 0); u: [P][L], w: [m][L], c: [L] residues (uint64), c may be None.  Returns the n
+        outputs, [3][L][N] each."""
+        n, P = len(As), len(a_rows)
+        m = len(lin_rows)
+        lins = lins if lins is not None else [[] for _ in range(n)]
+        if len(Bs) != n or len(lins) != n or len(b_rows) != P or any(len(r) != P for r in As) or any(len(r) != P for r in Bs) \
+                or any(len(r) != m for r in lins):
+            raise ValueError("product_combine: every item needs P operand pairs and m linear terms")
+        uu = np.ascontiguousarray(u, dtype=np.uint64)
+        if uu.shape != (P, L):
+            raise ValueError("product_combine: u must be [P][L]")
+        ww = None
+        if m:
+            ww = np.ascontiguousarray(w, dtype=np.uint64)
+            if ww.shape != (m, L):
+                raise ValueError("product_combine: w must be [m][L]")
+        cc = None
+        if c is not None:
+            cc = np.ascontiguousarray(c, dtype=np.uint64)
+            if cc.shape != (L,):
+                raise ValueError("product_combine: c must be [L]")
+        outs = outs if outs is not None else self.empty_many(n, (3, L, self.N))
+        ints = lambda v: (C.c_int * max(len(v), 1))(*[int(x) for x in v])
+        capi.check(capi.lib().hefx_product_combine(
+            self._h, L, n, P, capi.ptr_array([x.ptr for r in As for x in r]), ints(a_rows),
+            capi.ptr_array([x.ptr for r in Bs for x in r]), ints(b_rows), uu.ctypes.data, m,
+            capi.ptr_array([x.ptr for r in lins for x in r]) if m else None, ints(lin_rows) if m else None,
+            ww.ctypes.data if m else None, cc.ctypes.data if cc is not None else None, capi.ptr_array([o.ptr for o in outs]), stream))
+        return outs
+
     # ---- CKKS encode on the GPU
     @staticmethod
     def _encode_args(values):

@@ -57,6 +57,31 @@ class Plan(NamedTuple):
     def muls(self) -> int:
         return sum(1 for s in self.steps if s.op == capi.POLY_MUL)
 
+    def deferred(self) -> dict:
+        """{index of a MUL step: index of the COMBINE it can be deferred into}: the MULs whose result is read exactly once,
+        by a COMBINE, and is not the plan's result.  Relinearisation is linear, so such a product can stay at size 3 inside
+        its consumer's sum (Evaluator.product_combine) and the sum be relinearised once."""
+        readers: dict = {}
+        for i, s in enumerate(self.steps):
+            for src in ([t.src for t in s.terms] if s.op == capi.POLY_COMBINE else [s.a, s.b]):
+                readers.setdefault(src, []).append(i)
+        final = self.steps[-1].dst
+        out = {}
+        for i, s in enumerate(self.steps):
+            r = readers.get(s.dst, [])
+            if s.op == capi.POLY_MUL and s.dst != final and len(r) == 1 and self.steps[r[0]].op == capi.POLY_COMBINE:
+                out[i] = r[0]
+        return out
+
+    def relinearizations(self, lazy: bool = True) -> int:
+        """key switches of one run of the plan: one per MUL when every product is relinearised on its own (lazy=False, what
+        evaluate_polynomial does); with lazy=True one per MUL that cannot be deferred and one per COMBINE that takes
+        deferred products (evaluate_polynomial_many)"""
+        if not lazy:
+            return self.muls
+        d = self.deferred()
+        return self.muls - len(d) + len(set(d.values()))
+
     @property
     def result_level(self) -> int:
         last = self.steps[-1]

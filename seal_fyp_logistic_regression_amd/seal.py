@@ -166,6 +166,13 @@ class GpuBackend:
         oracle-backed twin of the tests has no such method and Evaluator.plain_combine takes multiply_plain_sum per output"""
         return self.engine.plain_combine(L, ins, pts)
 
+    def product_combine(self, L, As, a_rows, Bs, b_rows, u, lins, lin_rows, w, c=None):
+        """outs[i] = sum_p u[p] * (As[i][p] (x) Bs[i][p]) + sum_k w[k] * lins[i][k] + c at size 3 in one pass
+        (hefx_product_combine; u [P][L], w [m][L] and c [L] are residues); the oracle-backed twin of the tests has no such
+        method and Evaluator.product_combine composes the same words from mod_drop, multiply, multiply_plain, add_many, add
+        and add_plain"""
+        return self.engine.product_combine(L, As, a_rows, Bs, b_rows, u, lins, lin_rows, w, c)
+
     def multiply_batch(self, L, As, Bs):
         return self.engine.multiply_batch(L, As, Bs)
 
@@ -504,17 +511,60 @@ def _key32(seed) -> bytes:
     return hashlib.sha256(b"hefx-seed:" + str(int(seed)).encode()).digest()
 
 
+def sparse_ternary_secret(key32: bytes, N: int, hamming_weight: int) -> np.ndarray:
+    """The coefficients (int64, in {-1, 0, 1}) of a secret with exactly hamming_weight nonzero entries, a function of key32
+    alone: positions by a partial Fisher-Yates shuffle, then one sign bit each, both from the SHA-256 counter stream of
+    key32 (64-bit words, a word outside the largest multiple of the range is drawn again: no modulo bias).  Host only."""
+    import hashlib
+    h = int(hamming_weight)
+    if not 1 <= h <= N:
+        raise ValueError("hamming_weight must lie in 1 .. poly_modulus_degree")
+    state = {"ctr": 0, "buf": []}
+
+    def word() -> int:
+        if not state["buf"]:
+            d = hashlib.sha256(b"hefx-sparse-secret:" + key32 + state["ctr"].to_bytes(8, "little")).digest()
+            state["ctr"] += 1
+            state["buf"] = [int.from_bytes(d[i:i + 8], "little") for i in range(0, 32, 8)]
+        return state["buf"].pop()
+
+    def below(r: int) -> int:
+        limit = (1 << 64) - (1 << 64) % r
+        while True:
+            w = word()
+            if w < limit:
+                return w % r
+
+    idx = list(range(N))
+    for i in range(h):
+        j = i + below(N - i)
+        idx[i], idx[j] = idx[j], idx[i]
+    out = np.zeros(N, dtype=np.int64)
+    for i in range(h):
+        out[idx[i]] = 1 if word() & 1 else -1
+    return out
+
+
 class KeyGenerator:
     """Randomness from the backend's counter-mode sampler (hefx_sample_*: ChaCha20 keystream, SEAL 3.4.5's
     distributions; SEAL seeds from random_device, so keys are inputs to parity, never outputs); all modular
     arithmetic on the backend (App. A.11).  The default seed=None draws the sampler key from the OS (os.urandom);
-    an integer seed is for tests and tools only -- it makes the secret key publicly derivable."""
+    an integer seed is for tests and tools only -- it makes the secret key publicly derivable.
+    hamming_weight=h: a sparse secret with exactly h entries of +-1 (sparse_ternary_secret, drawn on the host from the same
+    key32) in place of the uniform ternary one -- what bootstrapping needs: the integer part I of a mod-raised plaintext
+    m + q_0 I has about (h + 1) / 12 of variance per coefficient, and EvalMod's range K must cover it.  The sampler streams of
+    every other key are what they are without it.  None: the uniform ternary secret, word for word as before."""
 
-    def __init__(self, context: SEALContext, seed: Optional[int] = None):
+    def __init__(self, context: SEALContext, seed: Optional[int] = None, hamming_weight: Optional[int] = None):
         self.ctx = context
         self._key32, self._stream = _key32(seed), 0
         be, k = context.backend, context.k
-        h = be.sample("ternary", self._key32, 2 * self._next_stream(), 1, k)
+        if hamming_weight is None:
+            h = be.sample("ternary", self._key32, 2 * self._next_stream(), 1, k)
+        else:
+            self._next_stream()  # (the uniform secret's stream stays unused: the other keys keep their stream ids)
+            coef = sparse_ternary_secret(self._key32, context.N, hamming_weight)
+            h = be.from_host(np.stack([(coef % int(q)).astype(np.uint64) for q in context.primes[:k]])[None])
         be.ntt_forward(h, 1, k, 0)
         self._sk = SecretKey(be.to_host(h).reshape(k, context.N), h)
 
@@ -1118,6 +1168,126 @@ class Evaluator:
                     acc = be.add_plain(L, size, acc, be.from_host(np.repeat(cres[g][:, None], N, axis=1)))
                 datas.append(acc)
         return [Ciphertext()._set(d, size, L, S) for d in datas]
+
+    def product_combine(self, products, lin=(), const: Optional[float] = None, scale: Optional[float] = None,
+                        parms_id: Optional[int] = None) -> List[Ciphertext]:
+        """A node of a polynomial plan with its products still inside, for n items in lockstep:
+            out[i] = sum_p coef_p * (a_p[i] * b_p[i]) + sum_k coef_k * ct_k[i] + const,
+        size 3 and NOT relinearised -- relinearisation is linear, so the caller relinearises the sum once instead of every
+        product.  products: (a, b, coef, wscale) with a and b lists of n size-2 ciphertexts (a[i] is b[i] for a square); lin:
+        (cts, coef, wscale) with cts a list of n size-2 ciphertexts; the weight of a term is the scalar plaintext
+        encode(coef, wscale).  Level parms_id (default: the lowest level among the operands; higher operands are read through
+        their row prefix) and scale S: a.scale * b.scale * wscale and ct.scale * wscale must be S for every term -- S is `scale`
+        when given, else the first product's; const is encoded at S.
+        The words and the checks of the op-by-op sequence -- mod_switch_to, multiply per product, encode and multiply_plain per
+        term, add_many, add, add_plain -- from ONE pass over the operands where the backend has hefx_product_combine, else
+        from that sequence."""
+        from .poly import weight_residue
+        products = [(list(a), list(b), float(cf), float(ws)) for a, b, cf, ws in products]
+        lin = [(list(cts), float(cf), float(ws)) for cts, cf, ws in lin]
+        P, m = len(products), len(lin)
+        if P < 1:
+            raise ValueError("product_combine: need at least one product")
+        n = len(products[0][0])
+        if n < 1 or any(len(a) != n or len(b) != n for a, b, _, _ in products) or any(len(cts) != n for cts, _, _ in lin):
+            raise ValueError("product_combine: every term needs one operand per item")
+        everyone = [x for a, b, _, _ in products for x in a + b] + [x for cts, _, _ in lin for x in cts]
+        L = int(parms_id) if parms_id is not None else min(x.parms_id() for x in everyone)
+        a0, b0, _, ws0 = products[0]
+        S = float(scale) if scale is not None else a0[0].scale * b0[0].scale * ws0
+        for a, b, _, ws in products:
+            for x, y in zip(a, b):
+                if x.parms_id() < L or y.parms_id() < L:
+                    raise ValueError("cannot switch to higher level modulus")
+                if x.size() != 2 or y.size() != 2:
+                    raise ValueError("multiply: only size-2 operands are supported (all reference call sites)")
+                if x.parms_id() != a[0].parms_id() or y.parms_id() != b[0].parms_id():
+                    raise ValueError("encrypted1 and encrypted2 parameter mismatch")
+                self._check_scale(x.scale * y.scale, L)
+                self._check_scale(ws, L)
+                self._check_scale(x.scale * y.scale * ws, L)
+                if not self._close(S, x.scale * y.scale * ws):
+                    raise ValueError("scale mismatch")
+        for cts, _, ws in lin:
+            for x in cts:
+                if x.parms_id() < L:
+                    raise ValueError("cannot switch to higher level modulus")
+                if x.size() != 2:
+                    raise ValueError("add_many: mixed sizes are not supported by the fused reduction")
+                if x.parms_id() != cts[0].parms_id():
+                    raise ValueError("encrypted1 and encrypted2 parameter mismatch")
+                self._check_scale(ws, L)
+                self._check_scale(x.scale * ws, L)
+                if not self._close(S, x.scale * ws):
+                    raise ValueError("scale mismatch")
+        self._check_scale(S, L)
+        q = self.ctx.primes[:L]
+        for cf, ws in [(cf, ws) for _, _, cf, ws in products] + [(cf, ws) for _, cf, ws in lin]:
+            if _c_round(cf * ws) == 0:
+                raise RuntimeError("result ciphertext is transparent")  # multiply_plain by the zero plaintext
+        ures = np.array([[weight_residue(cf, ws, p) for p in q] for _, _, cf, ws in products], dtype=np.uint64).reshape(P, L)
+        wres = np.array([[weight_residue(cf, ws, p) for p in q] for _, cf, ws in lin], dtype=np.uint64).reshape(m, L)
+        cres = None if const is None else np.array([weight_residue(const, S, p) for p in q], dtype=np.uint64)
+        a_rows, b_rows = [a[0].parms_id() for a, _, _, _ in products], [b[0].parms_id() for _, b, _, _ in products]
+        lin_rows = [cts[0].parms_id() for cts, _, _ in lin]
+        native = getattr(self.be, "product_combine", None)
+        words = 2 * P + m + L * (P + m + 1) + n * (2 * P + m + 1)
+        if native is not None and P <= 32 and m <= 64 and n <= 64 and words <= 10240:
+            datas = native(L, [[a[i].data for a, _, _, _ in products] for i in range(n)], a_rows,
+                           [[b[i].data for _, b, _, _ in products] for i in range(n)], b_rows, ures,
+                           [[cts[i].data for cts, _, _ in lin] for i in range(n)], lin_rows, wres, cres)
+        else:
+            datas = [self._product_combine_composed(L, [(a[i], b[i]) for a, b, _, _ in products], [cts[i] for cts, _, _ in lin],
+                                                    ures, wres, cres) for i in range(n)]
+        return [Ciphertext()._set(d, 3, L, S) for d in datas]
+
+    def _product_combine_composed(self, L, pairs, lins, ures, wres, cres):
+        """one item of product_combine op by op: mod_drop, multiply, multiply_plain by the constant polynomial of each weight
+        at size 3 / size 2, add_many per size, the size-2 sum added into the first two polynomials, add_plain"""
+        N, be = self.ctx.N, self.be
+        const_poly = lambda res: be.from_host(np.repeat(np.asarray(res, dtype=np.uint64)[:, None], N, axis=1))
+        low = lambda x: x.data if x.parms_id() == L else be.mod_drop(x.parms_id(), L, 2, x.data)
+        terms3 = []
+        for p, (a, b) in enumerate(pairs):
+            da = low(a)
+            t = be.square(L, da) if a.data is b.data else be.multiply(L, da, low(b))
+            terms3.append(be.multiply_plain(L, 3, t, const_poly(ures[p])))
+        acc = terms3[0] if len(terms3) == 1 else be.add_many(L, 3, terms3)
+        if lins:
+            terms2 = [be.multiply_plain(L, 2, low(x), const_poly(wres[k])) for k, x in enumerate(lins)]
+            lin2 = terms2[0] if len(terms2) == 1 else be.add_many(L, 2, terms2)
+            acc = self._addsub(Ciphertext()._set(acc, 3, L, 1.0), Ciphertext()._set(lin2, 2, L, 1.0), False).data
+        if cres is not None:
+            acc = be.add_plain(L, 3, acc, const_poly(cres))
+        return acc
+
+    def mod_raise(self, ct: Ciphertext, parms_id: Optional[int] = None) -> Ciphertext:
+        """The first step of CKKS bootstrapping: both polynomials of ct, taken as integer polynomials with centred
+        coefficients below its level's modulus Q, written mod the primes of level parms_id (default: the first level).  The
+        result decrypts to m + Q * I for a small integer polynomial I (about sqrt((h + 1) / 12) per coefficient for a secret
+        key of Hamming weight h); the scale is unchanged.  hefx_mod_raise with count = 2 where the backend has it, else
+        ntt_inverse, lift_coefficients and ntt_forward of the new rows.  N <= 16384 (the range of hefx_mod_raise)."""
+        L_in = ct.parms_id()
+        L_out = int(parms_id) if parms_id is not None else self.ctx.first_parms_id()
+        if ct.size() != 2:
+            raise ValueError("encrypted size must be 2")
+        if L_out < L_in or L_out > self.ctx.first_parms_id():
+            raise ValueError("mod_raise: the target level must lie between the ciphertext's and the first level")
+        if self.ctx.N > 16384:
+            raise ValueError("mod_raise: poly_modulus_degree above 16384 is not supported (the range of hefx_mod_raise)")
+        if L_out == L_in:
+            return ct.copy()
+        be, N = self.be, self.ctx.N
+        native = getattr(be, "mod_raise", None)
+        if native is not None:
+            data = native(L_in, L_out, ct.data, 2)
+        else:
+            old = np.array(be.to_host(ct.data), dtype=np.uint64).reshape(2, L_in, N)
+            coef = np.asarray(be.to_host(be.ntt_inverse(be.from_host(old), 2, L_in, 0))).reshape(2, L_in, N)
+            new = np.stack([lift_coefficients(coef[p], self.ctx.primes, L_in, L_out) for p in range(2)])
+            new = np.asarray(be.to_host(be.ntt_forward(be.from_host(new), 2, L_out - L_in, L_in))).reshape(2, L_out - L_in, N)
+            data = be.from_host(np.concatenate([old, new], axis=1))
+        return Ciphertext()._set(data, 2, L_out, ct.scale)
 
     def plain_combine(self, cts: Sequence[Ciphertext], pts_matrix: Sequence[Sequence[Optional[Plaintext]]]) -> List[Ciphertext]:
         """G plaintext combinations of the same ciphertexts: out[g] = sum_k pts_matrix[g][k] (.) cts[k] over the entries that
