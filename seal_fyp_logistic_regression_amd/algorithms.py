@@ -914,7 +914,9 @@ def bootstrap(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitchKeys, relin_
     value.  Evaluator.mod_raise to the top (the plaintext becomes m + q_0 I), coeffs_to_slots with scale / (q_0 K') folded
     into its factor, eval_mod on both outputs in lockstep, slots_to_coeffs with q_0 / (2 pi scale) folded into its factor.
     plan: bootstrap.plan(...) for this context's chain; gal_keys: galois_keys(plan.galois_steps(), conjugate=True); the
-    secret key must be sparse enough for plan.K (KeyGenerator(hamming_weight=...)); encoded: plan.encode(encoder)."""
+    secret key must be sparse enough for plan.K (KeyGenerator(hamming_weight=...)); encoded: plan.encode(encoder).
+    A sparse plan (bootstrap.plan(..., slots=ns): the message is ns values tiled over the slots) goes mod_raise, subsum,
+    coeffs_to_slots_packed, eval_mod on the ONE ciphertext, slots_to_coeffs_packed; the result is ns-periodic again."""
     if ct.size() != 2 or ct.parms_id() != 1:
         raise ValueError("bootstrap: needs a size-2 ciphertext at the last prime")
     if plan.N != ev.ctx.N or list(plan.primes) != list(ev.ctx.primes):
@@ -924,6 +926,10 @@ def bootstrap(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitchKeys, relin_
     if encoded is None:
         encoded = plan.encode(CKKSEncoder(ev.ctx, device_encode=False))
     raised = ev.mod_raise(ct, plan.top_level)
+    if plan.sparse_slots is not None:
+        x = coeffs_to_slots_packed(ev, subsum(ev, raised, plan.sparse_slots, gal_keys), plan.c2s, gal_keys, encoded[0])
+        (y,) = eval_mod(ev, [x], plan, relin_keys)
+        return slots_to_coeffs_packed(ev, y, plan.s2c, gal_keys, encoded[1])
     ca, cb = coeffs_to_slots(ev, raised, plan.c2s, gal_keys, encoded[0])
     ya, yb = eval_mod(ev, [ca, cb], plan, relin_keys)
     return slots_to_coeffs(ev, ya, yb, plan.s2c, gal_keys, encoded[1])
@@ -948,9 +954,12 @@ def _dft_rotations(ev: Evaluator, cts: Sequence[Ciphertext], steps: Sequence[int
 
 
 def _dft_stage(ev: Evaluator, xs: Sequence[Ciphertext], stage, table, gal_keys: KSwitchKeys) -> List[Ciphertext]:
-    """One stage of a dft.Plan on its one or two input ciphertexts (dft.Stage states the three modes): the baby rotations of
+    """One stage of a dft.Plan on its one or two input ciphertexts (dft.Stage states the four modes): the baby rotations of
     every input as one batch, ALL inner sums -- both chains, every giant step -- as one Evaluator.plain_combine, the giant
-    rotations as one batch and their sums, one batched rescale.  table[matrix][giant][baby]: plan.encode(...)[stage]."""
+    rotations as one batch and their sums, one batched rescale.  table[matrix][giant][baby]: plan.encode(...)[stage].
+    A packed ("single") stage's few babies of ONE ciphertext take the same apply_galois_batch: rotate_hoisted_batch, which
+    shares the digit decomposition at any count, measured within 1.3 % of it at 1 and 7 rotations, L = 14 and L = 4
+    (profiles/sparse_bootstrap.json, "baby_rotations")."""
     if len(xs) != stage.inputs or any(x.size() != 2 for x in xs) or len({x.parms_id() for x in xs}) != 1:
         raise ValueError("dft stage: needs %d size-2 ciphertexts of one level" % stage.inputs)
     nb, ng = len(stage.babies), len(stage.giants)
@@ -960,7 +969,7 @@ def _dft_stage(ev: Evaluator, xs: Sequence[Ciphertext], stage, table, gal_keys: 
         for gi in range(ng):
             row = [None] * (len(xs) * nb)
             # (input, matrix) pairs that feed output c
-            feeds = [(0, c)] if stage.mode == "split" else [(c, 0)] if stage.mode == "lockstep" else [(0, 0), (1, 1)]
+            feeds = {"split": [(0, c)], "lockstep": [(c, 0)], "merge": [(0, 0), (1, 1)], "single": [(0, 0)]}[stage.mode]
             for src, mat in feeds:
                 row[src * nb:(src + 1) * nb] = table[mat][gi]
             rows.append(row)
@@ -978,7 +987,7 @@ def coeffs_to_slots(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitchKeys, 
     plan.encode(encoder, ct.parms_id()), the plan's plaintexts (made here with a host encoder when not given -- a caller
     that transforms more than once passes them)."""
     from . import dft
-    if plan.direction != dft.C2S or plan.N != ev.ctx.N:
+    if plan.direction != dft.C2S or plan.N != ev.ctx.N or plan.slots is not None:
         raise ValueError("coeffs_to_slots: the plan is not a CoeffToSlot plan of this ring")
     if encoded is None:
         encoded = plan.encode(CKKSEncoder(ev.ctx, device_encode=False), ct.parms_id())
@@ -994,11 +1003,71 @@ def slots_to_coeffs(ev: Evaluator, ct_a: Ciphertext, ct_b: Ciphertext, plan, gal
     F_s..F_1 x_a + D F_s..F_1 x_b -- plan.levels levels lower, at the inputs' scale.  plan: dft.plan(N, levels, dft.S2C, ...);
     gal_keys: galois_keys(plan.galois_steps())."""
     from . import dft
-    if plan.direction != dft.S2C or plan.N != ev.ctx.N:
+    if plan.direction != dft.S2C or plan.N != ev.ctx.N or plan.slots is not None:
         raise ValueError("slots_to_coeffs: the plan is not a SlotToCoeff plan of this ring")
     if encoded is None:
         encoded = plan.encode(CKKSEncoder(ev.ctx, device_encode=False), ct_a.parms_id())
     xs = [ct_a, ct_b]
+    for stage, table in zip(plan.stages, encoded):
+        xs = _dft_stage(ev, xs, stage, table, gal_keys)
+    return xs[0]
+
+
+# ---- sparse packing: a message of ns <= N/4 slots (dft.plan_packed plans, these run) ----------------------------------------
+def subsum(ev: Evaluator, ct: Ciphertext, ns: int, gal_keys: KSwitchKeys) -> Ciphertext:
+    """SubSum: x <- x + rotate_vector(x, ns 2^i) for i < log2 g, g = N / (2 ns).  The steps generate the Galois group that
+    fixes the polynomials in X^g, so a plaintext t becomes g times its coefficients at the multiples of g (the slots: the sum
+    of the g values at distance ns, ns-periodic); a plaintext already in that subring becomes g times itself.  log2 g
+    dependent key switches, each with its sum in the key switch's epilogue where the backend has that entry
+    (rotate_add_chain with one step: acc_in = ct_in); every step needs its direct Galois key."""
+    from .seal import galois_elt_from_step
+    N = ev.ctx.N
+    if ct.size() != 2:
+        raise ValueError("encrypted size must be 2")
+    if ns < 2 or ns & (ns - 1) or 4 * ns > N:
+        raise ValueError("subsum: slots must be a power of two in 2 .. N/4")
+    L, x = ct.parms_id(), ct
+    fused = getattr(ev.be, "rotate_add_chain", None)
+    for i in range((N // (2 * ns)).bit_length() - 1):
+        elt = galois_elt_from_step(ns << i, N)
+        if not gal_keys.has_key(elt):
+            raise ValueError("Galois key not present")
+        if fused is not None:
+            _, (data,) = fused(L, [x.data], [elt], [gal_keys.key(elt)], [x.data], 1)
+            x = Ciphertext()._set(data, 2, L, x.scale)
+        else:
+            x = ev.add(x, ev.rotate_vector(x, ns << i, gal_keys))
+    return x
+
+
+def _packed_plan(ev: Evaluator, plan, direction: str, name: str):
+    if plan.direction != direction or plan.N != ev.ctx.N or plan.slots is None:
+        raise ValueError(name + ": the plan is not a packed plan of this direction and ring")
+
+
+def coeffs_to_slots_packed(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitchKeys, encoded=None) -> Ciphertext:
+    """CoeffToSlot of a sparsely packed ciphertext: ct's slots are ns-periodic, z tiled (subsum's result); the ONE result has
+    2 ns-periodic real slots [R a | R b] tiled, a and b the halves of the 2 ns coefficients on the stride (times the plan's
+    factor), R the bit reversal of ns indices.  Every stage is one matrix on one ciphertext, and 2 Re(.) is ONE conjugation.
+    plan: dft.plan_packed(N, ns, levels, dft.C2S, ...); gal_keys: galois_keys(plan.galois_steps(), conjugate=True)."""
+    from . import dft
+    _packed_plan(ev, plan, dft.C2S, "coeffs_to_slots_packed")
+    if encoded is None:
+        encoded = plan.encode(CKKSEncoder(ev.ctx, device_encode=False), ct.parms_id())
+    xs = [ct]
+    for stage, table in zip(plan.stages, encoded):
+        xs = _dft_stage(ev, xs, stage, table, gal_keys)
+    return ev.add(xs[0], ev.complex_conjugate(xs[0], gal_keys))
+
+
+def slots_to_coeffs_packed(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitchKeys, encoded=None) -> Ciphertext:
+    """SlotToCoeff, the inverse map: from real slots [x_a | x_b] tiled to the ns-periodic slots [z | z] tiled of the plaintext
+    with x_a[R^-1], x_b[R^-1] on the stride.  plan: dft.plan_packed(N, ns, levels, dft.S2C, ...)."""
+    from . import dft
+    _packed_plan(ev, plan, dft.S2C, "slots_to_coeffs_packed")
+    if encoded is None:
+        encoded = plan.encode(CKKSEncoder(ev.ctx, device_encode=False), ct.parms_id())
+    xs = [ct]
     for stage, table in zip(plan.stages, encoded):
         xs = _dft_stage(ev, xs, stage, table, gal_keys)
     return xs[0]

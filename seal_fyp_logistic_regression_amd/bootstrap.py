@@ -28,9 +28,10 @@ def chebyshev_interpolant(f, degree: int) -> np.ndarray:
 
 
 class Plan:
-    def __init__(self, N, primes, scale, K, r, degree, c2s, s2c, coeffs, poly_target_scale, max_value, model_error):
+    def __init__(self, N, primes, scale, K, r, degree, c2s, s2c, coeffs, poly_target_scale, max_value, model_error, slots=None):
         self.N, self.primes, self.scale, self.K, self.r, self.degree = N, [int(p) for p in primes], float(scale), K, r, degree
         self.Kp = K + 0.25
+        self.sparse_slots = slots   # None: all N / 2 slots; ns: plan(..., slots=ns).  (slots() is the embedding below.)
         self.c2s, self.s2c, self.coeffs = c2s, s2c, coeffs
         self.poly_target_scale, self.max_value, self.model_error = poly_target_scale, max_value, model_error
         self.top_level = len(self.primes) - 1
@@ -46,13 +47,23 @@ class Plan:
     def galois_steps(self) -> List[int]:
         """every rotation step either transform needs a direct Galois key for; the conjugation key on top:
         KeyGenerator.galois_keys(plan.galois_steps(), conjugate=True)"""
-        return sorted(set(self.c2s.galois_steps()) | set(self.s2c.galois_steps()))
+        return sorted(set(self.c2s.galois_steps()) | set(self.s2c.galois_steps()) | set(self.subsum_steps()))
+
+    def subsum_steps(self) -> List[int]:
+        """the rotation steps of SubSum, ns 2^i for i < log2 g, g = N / (2 ns): none in a dense plan"""
+        if self.sparse_slots is None:
+            return []
+        g = self.N // (2 * self.sparse_slots)
+        return [self.sparse_slots << i for i in range(g.bit_length() - 1)]
 
     def key_switches(self, lazy: bool = True) -> int:
-        """key switches of one bootstrap: both transforms, the polynomial's relinearisations on both chains, the double angles"""
+        """key switches of one bootstrap: SubSum (sparse plans), both transforms, the polynomial's relinearisations on
+        both chains (on the one chain of a sparse plan), the double angles"""
         from . import poly
         p = poly.plan(self.coeffs, "chebyshev", self.primes[:self.evalmod_level], self.scale, self.poly_target_scale)
-        return self.c2s.key_switches() + self.s2c.key_switches() + 2 * (p.relinearizations(lazy) + self.r)
+        chains = 2 if self.sparse_slots is None else 1
+        return (len(self.subsum_steps()) + self.c2s.key_switches() + self.s2c.key_switches()
+                + chains * (p.relinearizations(lazy) + self.r))
 
     def encode(self, encoder):
         """(CoeffToSlot's plaintexts at the top level, SlotToCoeff's at plan.s2c_level): the `encoded` of algorithms.bootstrap"""
@@ -92,7 +103,16 @@ class Plan:
         """The whole pipeline in float64 on the N coefficients t = m + q_0 I of a mod-raised plaintext: the encoder's
         embedding (slot j <-> root zeta^(3^j)) divided by the scale, CoeffToSlot, EvalMod with its approximation error,
         SlotToCoeff, and the embedding back.  Returns the N coefficients the bootstrapped ciphertext's plaintext has (noise
-        aside), at plan.scale: about m = t centred mod q_0."""
+        aside), at plan.scale: about m = t centred mod q_0.  A sparse plan expects m in the subring (coefficients at
+        multiples of g = N / (2 ns) only) under a general I: SubSum first, the packed transforms on one vector, and the
+        result is about m on the stride and about 0 elsewhere."""
+        if self.sparse_slots is not None:
+            x = self.slots(coeffs)
+            for step in self.subsum_steps():
+                x = x + np.roll(x, -step)
+            (u,) = self.c2s.apply([x])
+            (zz,) = self.s2c.apply([self.eval_mod(np.real(u)).astype(np.complex128)])
+            return self.coefficients(zz)
         ua, ub = (np.real(x) for x in self.c2s.apply([self.slots(coeffs)]))
         (zz,) = self.s2c.apply([self.eval_mod(ua).astype(np.complex128), self.eval_mod(ub).astype(np.complex128)])
         return self.coefficients(zz)
@@ -111,19 +131,30 @@ def model_error(coeffs: np.ndarray, K: int, r: int, band: float) -> float:
 
 
 def plan(N: int, primes: Sequence[int], scale: float, K: int = 12, r: int = 3, degree: int = 31, c2s_levels: int = 2,
-         s2c_levels: int = 2, max_value: float = 1.0, precision: float = 1e-4) -> Plan:
+         s2c_levels: int = 2, max_value: float = 1.0, precision: float = 1e-4, slots: Optional[int] = None) -> Plan:
     """The bootstrap of a ciphertext at primes[0] and `scale` on the chain `primes` (the context's coeff_modulus, the special
     prime last).  K: the integer part |I| the secret key allows (12 for Hamming weight 32); r double angles; `degree` of the
     interpolant; levels of the two transforms.  max_value: the largest |coefficient| / scale of a message (1.0 covers slots of
     magnitude up to 1).  ValueError when the chain is too short (the result must keep at least one prime) or when the float
     model's own error on the band |frac| <= scale max_value / q_0 around every integer in [-K, K] exceeds `precision`
-    (relative to max_value)."""
+    (relative to max_value).
+    slots=ns (a power of two, 2 <= ns <= N/4; ValueError otherwise): the sparse plan of a message of ns slots, whose plaintext
+    is a polynomial in X^g, g = N / (2 ns).  SubSum (plan.subsum_steps(): log2 g rotate-and-adds) brings the raised plaintext
+    back into that subring, times g; the transforms are dft.plan_packed's, of dimension 2 ns on ONE ciphertext, 1 / g folded
+    into CoeffToSlot's diagonals, their levels clipped to log2(ns); EvalMod runs on one chain.  plan.sparse_slots is ns."""
     primes = [int(p) for p in primes]
     top = len(primes) - 1
     if top < 1:
         raise ValueError("bootstrap plan: the chain needs data primes and a special prime")
     if K < 1 or r < 0 or degree < 1:
         raise ValueError("bootstrap plan: K >= 1, r >= 0, degree >= 1")
+    g = 1
+    if slots is not None:
+        slots = int(slots)
+        if slots < 2 or slots & (slots - 1) or 4 * slots > N:
+            raise ValueError("bootstrap plan: slots must be a power of two in 2 .. N/4")
+        g = N // (2 * slots)
+        c2s_levels, s2c_levels = (min(int(v), slots.bit_length() - 1) for v in (c2s_levels, s2c_levels))
     q0, Kp = float(primes[0]), K + 0.25
     depth = int(math.ceil(math.log2(degree + 1)))
     evalmod_level = top - int(c2s_levels)
@@ -142,7 +173,10 @@ def plan(N: int, primes: Sequence[int], scale: float, K: int = 12, r: int = 3, d
     target = float(scale)
     for i in range(r):
         target = math.sqrt(target * float(primes[s2c_level + i]))
-    c2s = dft.plan(N, c2s_levels, dft.C2S, [primes[top - 1 - i] for i in range(c2s_levels)], factor=float(scale) / (q0 * Kp))
-    s2c = dft.plan(N, s2c_levels, dft.S2C, [primes[s2c_level - 1 - i] for i in range(s2c_levels)],
-                   factor=q0 / (2.0 * np.pi * float(scale)))
-    return Plan(N, primes, scale, K, r, degree, c2s, s2c, coeffs, target, max_value, err)
+    make = dft.plan if slots is None else (lambda N_, *a, **kw: dft.plan_packed(N_, slots, *a, **kw))
+    # (sparse: 1 / g next to the small plan's 1 / (2 ns) is the dense 1 / N; in the diagonals, not in a relabelled scale --
+    # a scale of g 2^50 entering the polynomial would outgrow the primes)
+    c2s = make(N, c2s_levels, dft.C2S, [primes[top - 1 - i] for i in range(c2s_levels)], factor=float(scale) / (q0 * Kp * g))
+    s2c = make(N, s2c_levels, dft.S2C, [primes[s2c_level - 1 - i] for i in range(s2c_levels)],
+               factor=q0 / (2.0 * np.pi * float(scale)))
+    return Plan(N, primes, scale, K, r, degree, c2s, s2c, coeffs, target, max_value, err, slots)

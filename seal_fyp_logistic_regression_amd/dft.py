@@ -124,14 +124,16 @@ class Stage:
     split, and the prime its rescale drops.
       mode "split"     one input, two outputs:  out_c = mats[c] x             (CoeffToSlot's first stage: F^H and F^H D^H)
       mode "lockstep"  two inputs, two outputs: out_c = mats[0] x_c
-      mode "merge"     two inputs, one output:  out = mats[0] x_0 + mats[1] x_1   (SlotToCoeff's last stage: F and D F)"""
+      mode "merge"     two inputs, one output:  out = mats[0] x_0 + mats[1] x_1   (SlotToCoeff's last stage: F and D F)
+      mode "single"    one input, one output:   out = mats[0] x               (every stage of a packed plan, plan_packed)
+    n is the period of the diagonals: the slot count, or 2 ns in a packed plan, whose vectors are n-periodic and longer."""
 
     def __init__(self, mode: str, mats: List[Diags], n: int, stride: int, prime: int):
         self.mode, self.mats, self.n, self.stride, self.prime = mode, mats, n, stride, int(prime)
         self.indices = sorted(set().union(*[set(m) for m in mats]))
         self.babies, self.giants, self.pairs = split(self.indices, n, stride)
-        self.inputs = 1 if mode == "split" else 2
-        self.outputs = 1 if mode == "merge" else 2
+        self.inputs = 1 if mode in ("split", "single") else 2
+        self.outputs = 1 if mode in ("merge", "single") else 2
 
     def rotated(self, mat: int, giant: int, baby: int) -> Optional[np.ndarray]:
         """diagonal giant + baby of mats[mat], rotated by minus its giant step; None: a structural zero"""
@@ -147,8 +149,10 @@ class Stage:
         return self.inputs * sum(1 for b in self.babies if b) + self.outputs * sum(1 for g in self.giants if g)
 
     def apply(self, xs: Sequence[np.ndarray]) -> List[np.ndarray]:
-        """the stage in its baby/giant form on plain vectors (numpy rolls for rotations): what the ciphertexts go through"""
+        """the stage in its baby/giant form on plain vectors (numpy rolls for rotations): what the ciphertexts go through.
+        Vectors longer than the period meet the diagonals tiled, as the encoded plaintexts are."""
         rots = [[np.roll(x, -b) for b in self.babies] for x in xs]
+        reps = len(xs[0]) // self.n
         outs = []
         for c in range(self.outputs):
             acc = 0
@@ -159,15 +163,16 @@ class Stage:
                     for bi, b in enumerate(self.babies):
                         v = self.rotated(mat, g, b)
                         if v is not None:
-                            inner = inner + v * rots[src][bi]
+                            inner = inner + (v if reps == 1 else np.tile(v, reps)) * rots[src][bi]
                 acc = acc + np.roll(inner, -g)
             outs.append(acc)
         return outs
 
 
 class Plan:
-    def __init__(self, N: int, levels: int, direction: str, stages: List[Stage], factor):
+    def __init__(self, N: int, levels: int, direction: str, stages: List[Stage], factor, slots: Optional[int] = None):
         self.N, self.n, self.levels, self.direction, self.stages, self.factor = N, N // 2, levels, direction, stages, factor
+        self.slots = slots   # None: the dense plan of plan(); ns: the packed plan of plan_packed(), all stages "single"
 
     def galois_steps(self) -> List[int]:
         """every rotation step the plan needs a direct Galois key for (CoeffToSlot needs the conjugation key on top:
@@ -175,14 +180,16 @@ class Plan:
         return sorted({s for st in self.stages for s in st.babies + st.giants if s})
 
     def key_switches(self) -> int:
-        """key switches of one run: the rotations of every stage, and CoeffToSlot's two conjugations"""
-        return sum(st.key_switches() for st in self.stages) + (2 if self.direction == C2S else 0)
+        """key switches of one run: the rotations of every stage, and CoeffToSlot's conjugation of every output (two; one
+        in a packed plan)"""
+        return sum(st.key_switches() for st in self.stages) + (self.stages[-1].outputs if self.direction == C2S else 0)
 
     def primes(self) -> List[int]:
         return [st.prime for st in self.stages]
 
     def apply(self, xs: Sequence[np.ndarray]) -> List[np.ndarray]:
-        """the whole plan on plain vectors, conjugation included: [R a, R b] from [z], or [z] from [R a, R b]"""
+        """the whole plan on plain vectors, conjugation included: [R a, R b] from [z], or [z] from [R a, R b]; a packed
+        plan takes and gives ONE vector of N / 2 values, [R a | R b] tiled from [z | z] tiled or the reverse"""
         for st in self.stages:
             xs = st.apply(xs)
         return [x + np.conj(x) for x in xs] if self.direction == C2S else list(xs)
@@ -199,7 +206,8 @@ class Plan:
             todo = [(c, gi, bi, st.rotated(c, g, b)) for c in range(len(st.mats)) for gi, g in enumerate(st.giants)
                     for bi, b in enumerate(st.babies)]
             todo = [t for t in todo if t[3] is not None]
-            pts = encoder.encode_many([t[3] for t in todo], st.scale(), L)
+            reps = self.n // st.n   # (a packed plan's diagonals have period 2 ns: tiled over the N / 2 slots)
+            pts = encoder.encode_many([t[3] if reps == 1 else np.tile(t[3], reps) for t in todo], st.scale(), L)
             table = [[[None] * len(st.babies) for _ in st.giants] for _ in st.mats]
             for (c, gi, bi, _), p in zip(todo, pts):
                 table[c][gi][bi] = p
@@ -247,3 +255,46 @@ def plan(N: int, levels: int, direction: str, primes_of_the_stages: Sequence[int
             mode, mats = "lockstep", [M]
         stages.append(Stage(mode, mats, n, stride, primes_of_the_stages[i]))
     return Plan(N, levels, direction, stages, factor)
+
+
+# ---- packed plans: a message of ns <= N/4 slots, both halves in one ciphertext ------------------------------------------------
+def block_matrix(blocks: Sequence[Sequence[Optional[Diags]]], ns: int) -> Diags:
+    """the 2 ns x 2 ns matrix [[b00, b01], [b10, b11]] of ns x ns blocks (None: a zero block), by its cyclic diagonals of
+    length 2 ns: entry (i, (i + d) mod ns) of block (r, c) lies on diagonal c ns + (i + d) mod ns - r ns - i"""
+    out: Diags = {}
+    i = np.arange(ns)
+    for r in range(2):
+        for c in range(2):
+            for d, v in (blocks[r][c] or {}).items():
+                e = (c * ns + (i + d) % ns - r * ns - i) % (2 * ns)
+                for index in np.unique(e[v != 0]):
+                    at = i[(e == index) & (v != 0)]
+                    out.setdefault(int(index), np.zeros(2 * ns, dtype=np.complex128))[r * ns + at] += v[at]
+    return out
+
+
+def plan_packed(N: int, ns: int, levels: int, direction: str, primes_of_the_stages: Sequence[int], factor=1.0) -> Plan:
+    """The transform of a sparsely packed ciphertext of the ring of degree N: a message of ns slots, 2 <= ns <= N/4, whose
+    plaintext is a polynomial in Y = X^g, g = N / (2 ns).  Its N/2 slots are ns-periodic and the first ns are the slots of
+    the ring of degree 2 ns (3^ns = 1 mod 4 ns), so the stage matrices are those of plan(2 ns, ...); read 2 ns-periodic,
+    [z | z], both coefficient halves travel in ONE ciphertext and every stage is one 2 ns x 2 ns matrix in mode "single":
+        "split" (A, B) -> [[A, 0], [B, 0]]     "lockstep" M -> [[M, 0], [0, M]]     "merge" (M0, M1) -> [[M0, M1], [M0, M1]]
+    CoeffToSlot takes [z | z] to [R a | R b] with one conjugation; SlotToCoeff takes [R a | R b] to [z | z], ns-periodic
+    again.  1 <= levels <= log2(ns); `factor` next to the small plan's own 1 / (2 ns): the caller folds 1 / g in where the
+    input is a SubSum (bootstrap.plan does)."""
+    if N < 8 or N & (N - 1):
+        raise ValueError("dft plan: N must be a power of two, at least 8")
+    ns = int(ns)
+    if ns < 2 or ns & (ns - 1) or 4 * ns > N:
+        raise ValueError("dft plan: slots must be a power of two in 2 .. N/4")
+    small = plan(2 * ns, levels, direction, primes_of_the_stages, factor)
+    stages = []
+    for st in small.stages:
+        if st.mode == "split":
+            blocks = [[st.mats[0], None], [st.mats[1], None]]
+        elif st.mode == "merge":
+            blocks = [[st.mats[0], st.mats[1]], [st.mats[0], st.mats[1]]]
+        else:
+            blocks = [[st.mats[0], None], [None, st.mats[0]]]
+        stages.append(Stage("single", [block_matrix(blocks, ns)], 2 * ns, st.stride, st.prime))
+    return Plan(N, small.levels, direction, stages, factor, slots=ns)
