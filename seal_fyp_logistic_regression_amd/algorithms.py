@@ -29,107 +29,127 @@ def get_all_diagonals(U: np.ndarray) -> np.ndarray:
 
 
 # ---- linear transforms ----------------------------------------------------------------------
+def _rotations_of_many(ev: Evaluator, cts: Sequence[Ciphertext], steps: Sequence[int], gal_keys: KSwitchKeys,
+                       pts_per_input: Sequence[Sequence[Plaintext]] = None) -> List[List[Ciphertext]]:
+    """[[rotate_vector(ct, l) for l in steps] for ct in cts] over SEAL's NAF plans, for one or more inputs of one level and
+    size 2.  Identical (source payload, Galois element) pairs are computed once -- the key switch is deterministic, so
+    sharing cannot change a bit.  pts_per_input[t][i] (optional): multiply_plain of input t's rotation by steps[i], fused
+    into the last key switch of its plan (hefx_rotate_multiply_plain_batch).
+
+    Where the backend has it, the NAF forests of all inputs go out in ONE engine call (hefx_apply_galois_forest takes any
+    number of roots: the depths of the forests run side by side, so k inputs cost the dependent launch sequences of one,
+    and the engine schedules depth batches, subtrees on lanes and hoisted depths itself).  Other backends, and a single key
+    switch, run depth by depth, each engine call one batch of an input's independent key switches.  Step 0 has an empty
+    plan: its result is the input's copy, times its plaintext.  Inputs of mixed level or size are served one by one.
+
+    The plaintext checks are Evaluator._plain_product_scale's, per input over all its plaintexts, made after the rotation
+    plans (a missing Galois key raises first) and BEFORE anything is submitted.  Every single fault raises what
+    multiply_plain + add_many raise op by op; of two simultaneous faults the one multiply_plain reports first is raised."""
+    be = ev.be
+    fused = pts_per_input is not None
+    if len(cts) > 1 and (len({c.parms_id() for c in cts}) != 1 or any(c.size() != 2 for c in cts)):
+        return [_rotations_batched(ev, c, steps, gal_keys, pts_per_input[t] if fused else None) for t, c in enumerate(cts)]
+    plans = [ev.rotation_plan(s, gal_keys) for s in steps]
+    if not cts or not plans:
+        return [[] for _ in cts]
+    L = cts[0].parms_id()
+    if fused:
+        for ct, pts in zip(cts, pts_per_input):
+            ev._plain_product_scale(L, ct.scale, pts, L)
+    leaves = []  # [input][step] -> payload of the plan's last node (None: step 0)
+    if hasattr(be, "apply_galois_forest") and len(cts) * sum(len(p) for p in plans) > 1:
+        parents, ext, elts, node_pts = [], [], [], []
+        for t, ct in enumerate(cts):
+            index, row = {}, []
+            for i, p in enumerate(plans):
+                c = -1
+                for depth, elt in enumerate(p):
+                    fuse = fused and depth == len(p) - 1
+                    key = (c, elt, i if fuse else -1)
+                    j = index.get(key)
+                    if j is None:
+                        j = index[key] = len(parents)
+                        parents.append(c), ext.append(ct.data if c < 0 else None), elts.append(elt)
+                        node_pts.append(pts_per_input[t][i].data if fuse else None)
+                    c = j
+                row.append(c)
+            leaves.append(row)
+        outs = be.apply_galois_forest(L, parents, ext, elts, [gal_keys.key(e) for e in elts], node_pts if fused else None)
+        leaves = [[outs[j] if j >= 0 else None for j in row] for row in leaves]
+    else:
+        for t, ct in enumerate(cts):
+            cur = [ct.data if p else None for p in plans]
+            for depth in range(max(len(p) for p in plans)):
+                jobs, owner = {}, {}   # (id(source), element, fused owner) -> (source, element, plaintext); step -> its job
+                for i, p in enumerate(plans):
+                    if depth < len(p):
+                        fuse = fused and depth == len(p) - 1
+                        owner[i] = key = (id(cur[i]), p[depth], i if fuse else -1)
+                        jobs.setdefault(key, (cur[i], p[depth], pts_per_input[t][i].data if fuse else None))
+                done = {}
+                for with_pt in (False, True):
+                    ks = [k for k, job in jobs.items() if (job[2] is not None) == with_pt]
+                    if ks:
+                        src, el, pt = zip(*[jobs[k] for k in ks])
+                        keys = [gal_keys.key(e) for e in el]
+                        o = be.rotate_multiply_plain_batch(L, list(src), list(el), keys, list(pt)) if with_pt else \
+                            be.apply_galois_batch(L, list(src), list(el), keys)
+                        done.update(zip(ks, o))
+                for i, key in owner.items():
+                    cur[i] = done[key]
+            leaves.append(cur)
+    res = []
+    for t, ct in enumerate(cts):
+        row = []
+        for i, data in enumerate(leaves[t]):
+            if data is None:  # step 0: rotate_vector returns its input unchanged
+                row.append(ev.multiply_plain(ct.copy(), pts_per_input[t][i]) if fused else ct.copy())
+            else:
+                row.append(Ciphertext()._set(data, 2, L, ct.scale * pts_per_input[t][i].scale if fused else ct.scale))
+        res.append(row)
+    return res
+
+
 def _rotations_batched(ev: Evaluator, ct: Ciphertext, steps: Sequence[int], gal_keys: KSwitchKeys,
                        pts: Sequence[Plaintext] = None) -> List[Ciphertext]:
-    """rotate_vector(ct, l) for every l in `steps`, executed depth by depth over SEAL's NAF plans so that each
-    engine call is one batch of independent key switches.  Identical (source payload, Galois element) pairs are
-    computed once -- the key switch is deterministic, so sharing cannot change a bit.  When `pts` is given, the
-    last term of each plan is fused with multiply_plain (hefx_rotate_multiply_plain_batch)."""
-    be, L = ev.be, ct.parms_id()
-    plans = [ev.rotation_plan(s, gal_keys) for s in steps]
-    cur = [ct.data for _ in steps]
-    if hasattr(be, "apply_galois_forest") and sum(len(p) for p in plans) > 1:
-        # the engine's own scheduler for the whole forest (depth batches, subtrees on lanes, hoisted depths): one call
-        index, parents, elts, node_pts = {}, [], [], []
-        leaf = [-1] * len(plans)
-        for i, p in enumerate(plans):
-            c = -1
-            for depth, elt in enumerate(p):
-                fuse = pts is not None and depth == len(p) - 1
-                key = (c, elt, i if fuse else -1)
-                j = index.get(key)
-                if j is None:
-                    j = index[key] = len(parents)
-                    parents.append(c), elts.append(elt), node_pts.append(pts[i].data if fuse else None)
-                c = j
-            leaf[i] = c
-        outs = be.apply_galois_forest(L, parents, [ct.data if q < 0 else None for q in parents], elts,
-                                      [gal_keys.key(e) for e in elts], node_pts if pts is not None else None)
-        cur = [outs[j] if j >= 0 else ct.data for j in leaf]
-        plans_done = True
-    else:
-        plans_done = False
-    for depth in range(0 if plans_done else max((len(p) for p in plans), default=0)):
-        jobs, job_list, owner = {}, [], {}
-        for i, p in enumerate(plans):
-            if depth >= len(p):
-                continue
-            fuse = pts is not None and depth == len(p) - 1
-            key = (id(cur[i]), p[depth], i if fuse else -1)
-            if key not in jobs:
-                jobs[key] = len(job_list)
-                job_list.append((cur[i], p[depth], pts[i].data if fuse else None))
-            owner[i] = jobs[key]
-        outs = [None] * len(job_list)
-        plain = [j for j, t in enumerate(job_list) if t[2] is None]
-        fused = [j for j, t in enumerate(job_list) if t[2] is not None]
-        if plain:
-            o = be.apply_galois_batch(L, [job_list[j][0] for j in plain], [job_list[j][1] for j in plain],
-                                      [gal_keys.key(job_list[j][1]) for j in plain])
-            for j, x in zip(plain, o):
-                outs[j] = x
-        if fused:
-            o = be.rotate_multiply_plain_batch(L, [job_list[j][0] for j in fused], [job_list[j][1] for j in fused],
-                                               [gal_keys.key(job_list[j][1]) for j in fused],
-                                               [job_list[j][2] for j in fused])
-            for j, x in zip(fused, o):
-                outs[j] = x
-        for i, j in owner.items():
-            cur[i] = outs[j]
-    out = []
-    for i in range(len(steps)):
-        if not plans[i]:  # step 0: rotate_vector returns its input unchanged
-            c = ct.copy()
-            out.append(ev.multiply_plain(c, pts[i]) if pts is not None else c)
-            continue
-        scale = ct.scale
-        if pts is not None:
-            scale *= pts[i].scale
-            ev._check_scale(scale, L)
-            if pts[i].parms_id() != L:
-                raise ValueError("encrypted_ntt and plain_ntt parameter mismatch")
-            if pts[i].is_zero:
-                raise RuntimeError("result ciphertext is transparent")
-        out.append(Ciphertext()._set(cur[i], 2, L, scale))
-    return out
+    """rotate_vector(ct, l) for every l in `steps`, times pts[i] when given: _rotations_of_many for one input"""
+    return _rotations_of_many(ev, [ct], steps, gal_keys, None if pts is None else [pts])[0]
 
 
-_PT_STATE = operator.attrgetter("_parms_id", "_scale", "is_zero")
 _PT_PTR = operator.attrgetter("data.ptr")
 
 
-def _plain_product_scale(ev: Evaluator, ct: Ciphertext, pts: Sequence[Plaintext]) -> float:
-    """The checks multiply_plain + add_many would make over ct (.) pts[i], and the common product scale.  One set
-    comprehension when everything is in order (a 1000-diagonal transform is otherwise host-bound in this loop); the
-    element-by-element walk only runs to raise the exception of the FIRST offending plaintext, like the op-by-op
-    sequence."""
-    L = ct.parms_id()
-    if set(map(_PT_STATE, pts)) == {(L, pts[0]._scale, False)}:  # (one C-level pass: 25 us for 512 plaintexts)
-        scale = ct.scale * pts[0]._scale
-        ev._check_scale(scale, L)
-        return scale
-    scale = None
-    for p in pts:
-        if p.parms_id() != L:
-            raise ValueError("encrypted_ntt and plain_ntt parameter mismatch")
-        s = ct.scale * p.scale
-        ev._check_scale(s, L)
-        if scale is not None and not ev._close(scale, s):
-            raise ValueError("scale mismatch")
-        scale = s if scale is None else scale
-        if p.is_zero:
-            raise RuntimeError("result ciphertext is transparent")
-    return scale
+def _native_args(gal_keys: KSwitchKeys, operands: Sequence):
+    """(elements, key payloads, operand payloads) in the form the native entry points take -- the one place that knows the
+    HIP engine from the other backends.  There the tables are C arrays: the operands' built in one C-level pass, the two
+    of the key set built once and kept on it (512 keys: 0.1 ms of Python per call otherwise, with the GPU idle) until keys
+    are added or replaced.  Other backends get plain lists.  Missing keys / too large steps come back from the engine
+    with SEAL's messages (ValueError)."""
+    elts = sorted(gal_keys.keys)
+    keys = [gal_keys.key(e) for e in elts]
+    if not keys or not hasattr(keys[0], "ptr"):
+        return elts, keys, [x.data for x in operands]
+    from . import capi
+    # fingerprint: elements AND payload addresses -- a key replaced under an existing element, or one removed and another
+    # added, must not leave the native transform on the old payloads (0.03 ms at 512 keys against 0.1 ms for the C arrays)
+    mark = (tuple(elts), tuple(k.ptr for k in keys))
+    cache = getattr(gal_keys, "_native_args", None)
+    if cache is None or cache[0] != mark:
+        cache = gal_keys._native_args = (mark, capi.u32_array(elts), capi.ptr_array(list(mark[1])), keys)  # keys: kept alive
+    return cache[1], cache[2], capi.ptr_array(list(map(_PT_PTR, operands)))
+
+
+def _direct_elts(ev: Evaluator, steps: Sequence[int], gal_keys: KSwitchKeys, what: str) -> List[int]:
+    """the Galois element of every step, for the forms that run one key switch per rotation (the native entries make this
+    check themselves)"""
+    plans = [ev.rotation_plan(s, gal_keys) for s in steps]
+    if any(len(p) != 1 for p in plans):
+        raise ValueError(f"{what} needs a direct Galois key for every step")
+    return [p[0] for p in plans]
+
+
+def _duplicate(ev: Evaluator, ct: Ciphertext, d: int, gal_keys: KSwitchKeys) -> Ciphertext:
+    return ev.add(ct, ev.rotate_vector(ct, -d, gal_keys))            # helper.h:244-247
 
 
 def linear_transform_plain(ev: Evaluator, ct: Ciphertext, U_diagonals: Sequence[Plaintext],
@@ -147,112 +167,66 @@ def linear_transform_plain(ev: Evaluator, ct: Ciphertext, U_diagonals: Sequence[
     call (hoisted=False) takes the same path by itself whenever more than 32 rotations share a source."""
     d = len(U_diagonals)
     if hoisted == 2:
-        return _linear_transform_plain_hoisted2(ev, ct, U_diagonals, gal_keys)
-    if hoisted:
-        return _linear_transform_plain_hoisted(ev, ct, U_diagonals, gal_keys)
+        return _linear_transform_plain_hoisted2(ev, ct, d, None, U_diagonals, gal_keys)
     native = getattr(ev.be, "linear_transform_plain", None)
     if native is not None:  # the HIP engine runs the whole transform behind one C-ABI call, same bits
-        return _linear_transform_plain_native(ev, native, ct, U_diagonals, gal_keys)
-    ct_rot = ev.rotate_vector(ct, -d, gal_keys)                      # :244  fill with duplicate
-    ct_new = ev.add(ct, ct_rot)                                      # :247
+        return _linear_transform_plain_native(ev, native, ct, U_diagonals, gal_keys, bool(hoisted))
+    if hoisted:
+        return _linear_transform_plain_hoisted(ev, ct, U_diagonals, gal_keys)
+    ct_new = _duplicate(ev, ct, d, gal_keys)                         # :244-247  fill with duplicate
     res = [ev.multiply_plain(ct_new, U_diagonals[0])]                # :250
     res += _rotations_batched(ev, ct_new, list(range(1, d)), gal_keys, U_diagonals[1:])   # :252-257
     return ev.add_many(res)                                          # :259
 
 
-def _linear_transform_plain_hoisted2(ev: Evaluator, ct: Ciphertext, U_diagonals: Sequence[Plaintext],
-                                     gal_keys: KSwitchKeys) -> Ciphertext:
-    ctx, be = ev.ctx, ev.be
-    d, L = len(U_diagonals), ct.parms_id()
+def _linear_transform_plain_hoisted2(ev: Evaluator, ct: Ciphertext, d: int, steps: Sequence[int],
+                                     pts: Sequence[Plaintext], gal_keys: KSwitchKeys) -> Ciphertext:
+    """double hoisting (one mod-down for the whole transform) over the diagonals `steps` of a d x d matrix (steps[0] == 0;
+    None: all d of them, the dense entry): KEY-LEVEL plaintexts, ct at the top data level, direct keys for the other steps"""
+    ctx, be, L = ev.ctx, ev.be, ct.parms_id()
     if ct.size() != 2:
         raise ValueError("encrypted size must be 2")
     if L != ctx.first_parms_id():
         raise ValueError("double hoisting is built for the top data level")
-    scale = None
-    for p in U_diagonals:
-        if p.parms_id() != ctx.k:
-            raise ValueError("double hoisting needs key-level plaintexts (encode with parms_id = key level)")
-        s = ct.scale * p.scale
-        ev._check_scale(s, L)
-        if scale is not None and not ev._close(scale, s):
-            raise ValueError("scale mismatch")
-        scale = s if scale is None else scale
-        if p.is_zero:
-            raise RuntimeError("result ciphertext is transparent")
-    native = getattr(be, "linear_transform_plain", None)
+    scale = ev._plain_product_scale(L, ct.scale, pts, ctx.k)
+    dense = steps is None
+    steps = list(range(d)) if dense else steps
+    native = getattr(be, "linear_transform_plain" if dense else "linear_transform_plain_hoisted2_sparse", None)
     if native is not None:  # plans, key checks and everything else behind one C-ABI call (errors come back as ValueError)
-        elts = sorted(gal_keys.keys)
-        data = native(L, ct.data, [p.data for p in U_diagonals], elts, [gal_keys.key(e) for e in elts], hoisted=2)
+        elts, keys, diag = _native_args(gal_keys, pts)
+        data = native(L, ct.data, diag, elts, keys, hoisted=2) if dense else native(L, ct.data, d, steps, diag, elts, keys)
     else:  # the oracle twin: regular -d rotation, then the oracle's statement of the double-hoisted core
-        plans = [ev.rotation_plan(l, gal_keys) for l in range(1, d)]
-        if any(len(p) != 1 for p in plans):
-            raise ValueError("hoisted linear transform needs a direct Galois key for every step 1..d-1")
-        ct_new = ev.add(ct, ev.rotate_vector(ct, -d, gal_keys))
-        elts = [p[0] for p in plans]
-        data = be.lt_double_hoisted_core(ct_new.data, [p.data for p in U_diagonals], elts,
-                                         [gal_keys.key(e) for e in elts])
+        elts = _direct_elts(ev, steps[1:], gal_keys, "hoisted linear transform")
+        ct_new = _duplicate(ev, ct, d, gal_keys)
+        data = be.lt_double_hoisted_core(ct_new.data, [p.data for p in pts], elts, [gal_keys.key(e) for e in elts])
     return Ciphertext()._set(data, 2, L, scale)
 
 
 def _linear_transform_plain_hoisted(ev: Evaluator, ct: Ciphertext, U_diagonals: Sequence[Plaintext],
                                     gal_keys: KSwitchKeys) -> Ciphertext:
+    """hoisted=True on a backend without the native transform: the d-1 rotations of ct_new as one hoisted batch"""
     d, L = len(U_diagonals), ct.parms_id()
-    native = getattr(ev.be, "linear_transform_plain", None)
-    if native is not None:  # one C-ABI call (hefx_linear_transform_plain_hoisted), which also checks the keys
-        return _linear_transform_plain_native(ev, native, ct, U_diagonals, gal_keys, hoisted=True)
-    plans = [ev.rotation_plan(l, gal_keys) for l in range(1, d)]
-    if any(len(p) != 1 for p in plans):
-        raise ValueError("hoisted linear transform needs a direct Galois key for every step 1..d-1")
-    ct_new = ev.add(ct, ev.rotate_vector(ct, -d, gal_keys))          # helper.h:244-247, regular rotation
+    elts = _direct_elts(ev, range(1, d), gal_keys, "hoisted linear transform")
+    scale = ev._plain_product_scale(L, ct.scale, U_diagonals, L)
+    ct_new = _duplicate(ev, ct, d, gal_keys)                         # helper.h:244-247, regular rotation
     res = [ev.multiply_plain(ct_new, U_diagonals[0])]                # :250
-    for p in U_diagonals[1:]:
-        if p.parms_id() != L:
-            raise ValueError("encrypted_ntt and plain_ntt parameter mismatch")
-        ev._check_scale(ct_new.scale * p.scale, L)
-        if p.is_zero:
-            raise RuntimeError("result ciphertext is transparent")
-    elts = [p[0] for p in plans]
     outs = ev.be.rotate_hoisted_batch(L, ct_new.data, elts, [gal_keys.key(e) for e in elts],
                                       [p.data for p in U_diagonals[1:]])
-    res += [Ciphertext()._set(o, 2, L, ct_new.scale * p.scale) for o, p in zip(outs, U_diagonals[1:])]
+    res += [Ciphertext()._set(o, 2, L, scale) for o in outs]
     return ev.add_many(res)                                          # :259
 
 
 def _linear_transform_plain_native(ev: Evaluator, native, ct: Ciphertext, U_diagonals: Sequence[Plaintext],
                                    gal_keys: KSwitchKeys, hoisted: bool = False) -> Ciphertext:
-    """Same checks and bookkeeping as the op-by-op path (SEAL's exceptions), arithmetic in hefx_linear_transform_plain."""
+    """Same checks and bookkeeping as the op-by-op path (SEAL's exceptions), arithmetic in hefx_linear_transform_plain
+    (hoisted: hefx_linear_transform_plain_hoisted, which also checks the keys)."""
     L = ct.parms_id()
     if ct.size() != 2:
         raise ValueError("encrypted size must be 2")
-    scale = _plain_product_scale(ev, ct, U_diagonals)
-    # missing keys / too large steps come back from the engine with SEAL's messages (ValueError)
-    elts, keys = _native_key_args(gal_keys)
-    diag = [p.data for p in U_diagonals]
-    if diag and hasattr(diag[0], "ptr"):  # HIP engine: the pointer table in one C-level pass
-        from . import capi
-        diag = capi.ptr_array(list(map(_PT_PTR, U_diagonals)))
+    scale = ev._plain_product_scale(L, ct.scale, U_diagonals, L)
+    elts, keys, diag = _native_args(gal_keys, U_diagonals)
     data = native(L, ct.data, diag, elts, keys, **({"hoisted": True} if hoisted else {}))
     return Ciphertext()._set(data, 2, L, scale)
-
-
-def _native_key_args(gal_keys: KSwitchKeys):
-    """(elements, key payloads) of a key set in the form the native entry points take.  On the HIP engine the two C arrays
-    are built once per key set and kept on it (512 keys: 0.1 ms of Python per call otherwise, with the GPU idle); the set
-    is rebuilt when keys were added.  Other backends get plain lists."""
-    elts = sorted(gal_keys.keys)
-    keys = [gal_keys.key(e) for e in elts]
-    if not keys or not hasattr(keys[0], "ptr"):
-        return elts, keys
-    # fingerprint: elements AND payload addresses -- a key replaced under an existing element, or one removed and another
-    # added, must not leave the native transform on the old payloads (0.03 ms at 512 keys against 0.1 ms for the C arrays)
-    mark = (tuple(elts), tuple(k.ptr for k in keys))
-    cache = getattr(gal_keys, "_native_args", None)
-    if cache is not None and cache[0] == mark:
-        return cache[1], cache[2]
-    from . import capi
-    cache = (mark, capi.u32_array(elts), capi.ptr_array(list(mark[1])), keys)  # keys: kept alive
-    gal_keys._native_args = cache
-    return cache[1], cache[2]
 
 
 def linear_transforms_plain_many(ev: Evaluator, cts: Sequence[Ciphertext], diag_sets: Sequence[Sequence[Plaintext]],
@@ -270,12 +244,8 @@ def linear_transforms_plain_many(ev: Evaluator, cts: Sequence[Ciphertext], diag_
     if native is None or not same or len(cts) > 64:
         return [linear_transform_plain(ev, c, ds, gal_keys) for c, ds in zip(cts, diag_sets)]
     L = cts[0].parms_id()
-    scales = [_plain_product_scale(ev, c, ds) for c, ds in zip(cts, diag_sets)]   # SEAL's checks, transform by transform
-    elts, keys = _native_key_args(gal_keys)
-    flat = [p.data for ds in diag_sets for p in ds]
-    if flat and hasattr(flat[0], "ptr"):
-        from . import capi
-        flat = capi.ptr_array([p.ptr for p in flat])
+    scales = [ev._plain_product_scale(L, c.scale, ds, L) for c, ds in zip(cts, diag_sets)]   # SEAL's checks, transform by transform
+    elts, keys, flat = _native_args(gal_keys, [p for ds in diag_sets for p in ds])
     outs = native(L, [c.data for c in cts], flat, elts, keys)
     return [Ciphertext()._set(o, 2, L, s) for o, s in zip(outs, scales)]
 
@@ -328,17 +298,12 @@ def linear_transform_plain_bsgs(ev: Evaluator, ct: Ciphertext, shifted_diagonals
     if native is not None:  # the HIP engine: the whole composition behind one C-ABI call, same bits as the lines below
         if ct.size() != 2:
             raise ValueError("encrypted size must be 2")
-        scale = _plain_product_scale(ev, ct, shifted_diagonals)
-        elts = sorted(gal_keys.keys)
-        data = native(L, ct.data, [p.data for p in shifted_diagonals], n1, elts, [gal_keys.key(e) for e in elts],
-                      hoisted)
-        return Ciphertext()._set(data, 2, L, scale)
+        scale = ev._plain_product_scale(L, ct.scale, shifted_diagonals, L)
+        elts, keys, diag = _native_args(gal_keys, shifted_diagonals)
+        return Ciphertext()._set(native(L, ct.data, diag, n1, elts, keys, hoisted), 2, L, scale)
     baby = list(range(1, n1))
-    plans = [ev.rotation_plan(s, gal_keys) for s in baby + [j * n1 for j in range(1, n2)]]
-    if any(len(p) != 1 for p in plans):
-        raise ValueError("baby-step/giant-step transform needs a direct Galois key for every step of bsgs_steps(d)")
-    ct_new = ev.add(ct, ev.rotate_vector(ct, -d, gal_keys))          # helper.h:244-247
-    elts = [p[0] for p in plans]
+    elts = _direct_elts(ev, baby + [j * n1 for j in range(1, n2)], gal_keys, "baby-step/giant-step transform")
+    ct_new = _duplicate(ev, ct, d, gal_keys)                         # helper.h:244-247
     if hoisted and baby:
         data = be.rotate_hoisted_batch(L, ct_new.data, elts[:n1 - 1], [gal_keys.key(e) for e in elts[:n1 - 1]])
         rots = [ct_new] + [Ciphertext()._set(x, 2, L, ct_new.scale) for x in data]
@@ -360,7 +325,7 @@ def linear_transform_cipher(ev: Evaluator, ct: Ciphertext, U_diagonals: Sequence
     native = getattr(ev.be, "linear_transform_cipher", None)
     if native is not None and d:  # the HIP engine: the whole composition behind one C-ABI call, same bits as below
         return _linear_transform_cipher_native(ev, native, ct, U_diagonals, gal_keys)
-    ct_new = ev.add(ct, ev.rotate_vector(ct, -d, gal_keys))          # :216-219
+    ct_new = _duplicate(ev, ct, d, gal_keys)                         # :216-219
     rots = _rotations_batched(ev, ct_new, list(range(1, d)), gal_keys)
     res = [ev.multiply(ct_new, U_diagonals[0])]                      # :222
     res += [ev.multiply(r, U_diagonals[l + 1]) for l, r in enumerate(rots)]   # :227-228
@@ -387,11 +352,7 @@ def _linear_transform_cipher_native(ev: Evaluator, native, ct: Ciphertext, U_dia
     for u in U_diagonals[1:]:                                        # Evaluator::add_many over the products
         if not ev._close(scale, ct.scale * u.scale):
             raise ValueError("scale mismatch")
-    elts, keys = _native_key_args(gal_keys)
-    diag = [u.data for u in U_diagonals]
-    if hasattr(diag[0], "ptr"):
-        from . import capi
-        diag = capi.ptr_array([x.ptr for x in diag])
+    elts, keys, diag = _native_args(gal_keys, U_diagonals)
     return Ciphertext()._set(native(L, ct.data, diag, elts, keys), 3, L, scale)
 
 
@@ -463,20 +424,34 @@ def compute_all_powers(ev: Evaluator, ct: Ciphertext, degree: int, relin_keys: K
     return powers
 
 
+def _zero_like(ev: Evaluator, ct: Ciphertext) -> Ciphertext:
+    """the zero ciphertext at ct's size / level / scale (a rank's contribution when it owns no unit)"""
+    return ev.sub(ct, ct)
+
+
 def _matmul_step3(ev: Evaluator, ctA0: Ciphertext, ctB0: Ciphertext, ctAk: List[Ciphertext],
-                  ctBk: List[Ciphertext]) -> Ciphertext:
-    """matrix_multiplication.cpp:69-129: rescale the 2(n-1) transforms, A0*B0 + sum_k A_k*B_k.  The rescales are
-    independent, so they are one launch over their list; the n-1 products and the chain of add_inplace (:127-128) are
-    one fused sum (Evaluator.multiply_sum: no product is written) to which ctAB is added -- canonical residues of the
-    same integers, hence the same bits."""
+                  ctBk: List[Ciphertext], include_ab: bool = True) -> Ciphertext:
+    """matrix_multiplication.cpp:69-129: rescale the transforms, A0*B0 + sum_k A_k*B_k -- or one rank's share of that sum
+    (parallel.py): ctAk / ctBk are the transforms this rank owns, and include_ab says whether A0*B0 is counted here (the
+    serial product: all n-1 and True).  The rescales are independent, so they are one launch over their list; the products
+    and the chain of add_inplace (:127-128) are one fused sum (Evaluator.multiply_sum: no product is written) to which
+    ctAB is added -- canonical residues of the same integers, hence the same bits.  Every product is held to ctAB's
+    level and scale HERE, whether or not ctAB is counted, so that a mismatch raises on every rank before any of them
+    enters the all-reduce; the share carries ctAB's scale, as the serial sum carries its first addend's."""
     ev.rescale_to_next_many_inplace(list(ctAk) + list(ctBk))         # :69-73 (one launch pair over both families)
     ctAB = ev.multiply(ctA0, ctB0)                                   # :104
     ev.mod_switch_to_next_inplace(ctAB)                              # :112
     for c in ctAk + ctBk:
         c.scale = 2.0 ** int(np.log2(c.scale))                       # :117-121 "manual rescale"
+    for a, b in zip(ctAk, ctBk):                                     # add_inplace(ctAB, A_k * B_k), :127-128
+        ev._check_same(ctAB, a)
+        if not ev._close(ctAB.scale, a.scale * b.scale):
+            raise ValueError("scale mismatch")
     if not ctAk:
-        return ctAB
-    return ev.add(ctAB, ev.multiply_sum(ctAk, ctBk)[0])              # :123-129 (products and their sum in one pass)
+        return ctAB if include_ab else _zero_like(ev, ctAB)
+    share = ev.multiply_sum(ctAk, ctBk)[0]                           # :123-129 (products and their sum in one pass)
+    share.scale = ctAB.scale
+    return ev.add(ctAB, share) if include_ab else share
 
 
 def _linear_transforms_of_one_input(ev: Evaluator, ct: Ciphertext, diag_sets: Sequence[Sequence[Plaintext]],
@@ -486,66 +461,7 @@ def _linear_transforms_of_one_input(ev: Evaluator, ct: Ciphertext, diag_sets: Se
     and the same rotations rotate(ct_new, l) -- deterministic functions of ct -- so they are formed ONCE and each
     transform keeps only its sum of plaintext products (helper.h:250-259) -- the bits of the transform-by-transform
     loop with (n-1)x fewer key switches."""
-    if not diag_sets:
-        return []
-    d = len(diag_sets[0])
-    if any(len(ds) != d for ds in diag_sets):
-        return [linear_transform_plain(ev, ct, ds, gal_keys) for ds in diag_sets]
-    ct_new = _duplicate(ev, ct, d, gal_keys)                          # helper.h:244-247
-    rots = [ct_new] + _rotations_batched(ev, ct_new, list(range(1, d)), gal_keys)   # :255
-    terms_ct = [rots[l] for _ in diag_sets for l in range(d)]
-    terms_pt = [ds[l] for ds in diag_sets for l in range(d)]
-    return ev.multiply_plain_sum(terms_ct, terms_pt, group=d)        # :250, :256, :259
-
-
-def _rotations_of_many(ev: Evaluator, cts: Sequence[Ciphertext], steps: Sequence[int], gal_keys: KSwitchKeys,
-                       pts_per_input: Sequence[Sequence[Plaintext]] = None) -> List[List[Ciphertext]]:
-    """[[rotate_vector(ct, l) for l in steps] for ct in cts] with the NAF forests of all inputs in ONE engine call
-    (hefx_apply_galois_forest takes any number of roots): the depths of the forests run side by side, so k inputs cost the
-    dependent launch sequences of one.  pts_per_input[t][i] (optional): multiply_plain of input t's rotation by steps[i],
-    fused into the last key switch of its plan, with the checks of the op-by-op product (as _rotations_batched does for one
-    input).  Backends without the forest entry, a single input or a zero step take the per-input path."""
-    be = ev.be
-    if len(cts) < 2 or not hasattr(be, "apply_galois_forest") or any(s == 0 for s in steps) or not steps or \
-            len({c.parms_id() for c in cts}) != 1 or any(c.size() != 2 for c in cts):
-        return [_rotations_batched(ev, c, steps, gal_keys, pts_per_input[t] if pts_per_input is not None else None)
-                for t, c in enumerate(cts)]
-    L = cts[0].parms_id()
-    plans = [ev.rotation_plan(s, gal_keys) for s in steps]
-    parents, ext, elts, node_pts = [], [], [], []
-    leaf = [[-1] * len(plans) for _ in cts]
-    for t, ct in enumerate(cts):
-        index = {}
-        for i, p in enumerate(plans):
-            c = -1
-            for depth, elt in enumerate(p):
-                fuse = pts_per_input is not None and depth == len(p) - 1
-                key = (c, elt, i if fuse else -1)
-                j = index.get(key)
-                if j is None:
-                    j = index[key] = len(parents)
-                    parents.append(c), ext.append(ct.data if c < 0 else None), elts.append(elt)
-                    node_pts.append(pts_per_input[t][i].data if fuse else None)
-                c = j
-            leaf[t][i] = c
-    outs = be.apply_galois_forest(L, parents, ext, elts, [gal_keys.key(e) for e in elts],
-                                  node_pts if pts_per_input is not None else None)
-    res = []
-    for t, ct in enumerate(cts):
-        row = []
-        for i, j in enumerate(leaf[t]):
-            scale = ct.scale
-            if pts_per_input is not None:
-                p = pts_per_input[t][i]
-                scale *= p.scale
-                ev._check_scale(scale, L)
-                if p.parms_id() != L:
-                    raise ValueError("encrypted_ntt and plain_ntt parameter mismatch")
-                if p.is_zero:
-                    raise RuntimeError("result ciphertext is transparent")
-            row.append(Ciphertext()._set(outs[j], 2, L, scale))
-        res.append(row)
-    return res
+    return _linear_transforms_of_inputs(ev, [ct], [diag_sets], gal_keys)[0]
 
 
 def _linear_transforms_of_inputs(ev: Evaluator, cts: Sequence[Ciphertext],
@@ -554,14 +470,21 @@ def _linear_transforms_of_inputs(ev: Evaluator, cts: Sequence[Ciphertext],
     """[_linear_transforms_of_one_input(ct, sets) for ct, sets] with the rotations of ALL inputs formed together
     (matrix_multiplication.cpp:40-43: the V_k of ctA0 and the W_k of ctB0 are independent of one another): the -d rotations
     as one batch, the rotation forests in one call, every plaintext product and sum in one pass.  Per input the same
-    operations in the same order: same bits."""
-    ds = [len(s[0]) for s in diag_sets_per_input if s]
-    if len(cts) < 2 or len(ds) != len(cts) or len(set(ds)) != 1 or \
-            any(len(x) != ds[0] for s in diag_sets_per_input for x in s) or not hasattr(ev.be, "apply_galois_forest"):
+    operations in the same order: same bits.  Several inputs run together where the backend has the forest entry and all
+    transforms have one dimension, else one by one; one input whose transforms differ in dimension runs them one by one."""
+    ds = {len(x) for s in diag_sets_per_input for x in s}
+    together = len(cts) > 1 and all(diag_sets_per_input) and len(diag_sets_per_input) == len(cts) and len(ds) == 1 and \
+        hasattr(ev.be, "apply_galois_forest")
+    if len(cts) > 1 and not together:
         return [_linear_transforms_of_one_input(ev, c, s, gal_keys) for c, s in zip(cts, diag_sets_per_input)]
-    d = ds[0]
-    dup = _rotations_of_many(ev, cts, [-d], gal_keys)                 # helper.h:244
-    ct_news = [ev.add(c, r[0]) for c, r in zip(cts, dup)]             # :247
+    if len(ds) != 1:
+        return [[linear_transform_plain(ev, c, x, gal_keys) for x in s] for c, s in zip(cts, diag_sets_per_input)]
+    d = ds.pop()
+    if together:
+        dup = _rotations_of_many(ev, cts, [-d], gal_keys)             # helper.h:244
+        ct_news = [ev.add(c, r[0]) for c, r in zip(cts, dup)]         # :247
+    else:
+        ct_news = [_duplicate(ev, cts[0], d, gal_keys)]               # :244-247
     rots = _rotations_of_many(ev, ct_news, list(range(1, d)), gal_keys)   # :255
     terms_ct, terms_pt, counts = [], [], []
     for ct_new, rr, sets in zip(ct_news, rots, diag_sets_per_input):
@@ -649,10 +572,6 @@ def matmul_permutation_diagonals(n: int):
     return sigma, tau, phi, psi
 
 
-def _duplicate(ev: Evaluator, ct: Ciphertext, d: int, gal_keys: KSwitchKeys) -> Ciphertext:
-    return ev.add(ct, ev.rotate_vector(ct, -d, gal_keys))            # helper.h:244-247
-
-
 def _sparse_products(ev: Evaluator, ct_new: Ciphertext, terms, gal_keys: KSwitchKeys,
                      hoisted: bool = False) -> List[Ciphertext]:
     """[diag (.) rot_l(ct_new) for (l, diag) in terms], the rotations as one batch (fused with their products);
@@ -664,11 +583,8 @@ def _sparse_products(ev: Evaluator, ct_new: Ciphertext, terms, gal_keys: KSwitch
             out[i] = ev.multiply_plain(ct_new, p)                    # :250
     if hoisted and rot:
         L = ct_new.parms_id()
-        plans = [ev.rotation_plan(l, gal_keys) for _, l, _ in rot]
-        if any(len(pl) != 1 for pl in plans):
-            raise ValueError("hoisted rotations need a direct Galois key for every step")
-        scale = _plain_product_scale(ev, ct_new, [p for _, _, p in rot])
-        elts = [pl[0] for pl in plans]
+        elts = _direct_elts(ev, [l for _, l, _ in rot], gal_keys, "hoisted rotation")
+        scale = ev._plain_product_scale(L, ct_new.scale, [p for _, _, p in rot], L)
         data = ev.be.rotate_hoisted_batch(L, ct_new.data, elts, [gal_keys.key(x) for x in elts],
                                           [p.data for _, _, p in rot])
         for (i, _, _), x in zip(rot, data):
@@ -685,48 +601,13 @@ def linear_transform_plain_sparse(ev: Evaluator, ct: Ciphertext, d: int, diagona
     """Linear_Transform_Plain (helper.h:237-262) of a d x d matrix given by its non-zero diagonals {l: Plaintext}"""
     if not diagonals:
         raise ValueError("encrypteds cannot be empty")
-    if hoisted == 2:
-        return _linear_transform_plain_sparse_hoisted2(ev, ct, d, diagonals, gal_keys)
+    if hoisted == 2:  # double hoisting, see _linear_transform_plain_hoisted2: diagonal 0 must be present
+        if 0 not in diagonals:
+            raise ValueError("double hoisting over a subset of diagonals needs diagonal 0")
+        steps = [0] + sorted(l for l in diagonals if l)
+        return _linear_transform_plain_hoisted2(ev, ct, d, steps, [diagonals[l] for l in steps], gal_keys)
     ct_new = _duplicate(ev, ct, d, gal_keys)
     return ev.add_many(_sparse_products(ev, ct_new, sorted(diagonals.items()), gal_keys, hoisted))   # :259
-
-
-def _linear_transform_plain_sparse_hoisted2(ev: Evaluator, ct: Ciphertext, d: int, diagonals: dict,
-                                            gal_keys: KSwitchKeys) -> Ciphertext:
-    """double hoisting (one mod-down for the whole transform, see _linear_transform_plain_hoisted2) over the non-zero
-    diagonals: KEY-LEVEL plaintexts, ct at the top data level, diagonal 0 present, direct keys for the other steps"""
-    ctx, be, L = ev.ctx, ev.be, ct.parms_id()
-    if ct.size() != 2:
-        raise ValueError("encrypted size must be 2")
-    if L != ctx.first_parms_id():
-        raise ValueError("double hoisting is built for the top data level")
-    if 0 not in diagonals:
-        raise ValueError("double hoisting over a subset of diagonals needs diagonal 0")
-    steps = [0] + sorted(l for l in diagonals if l)
-    pts = [diagonals[l] for l in steps]
-    if any(p.parms_id() != ctx.k for p in pts):
-        raise ValueError("double hoisting needs key-level plaintexts (encode with parms_id = key level)")
-    scale = None
-    for p in pts:
-        s = ct.scale * p.scale
-        ev._check_scale(s, L)
-        if scale is not None and not ev._close(scale, s):
-            raise ValueError("scale mismatch")
-        scale = s if scale is None else scale
-        if p.is_zero:
-            raise RuntimeError("result ciphertext is transparent")
-    native = getattr(be, "linear_transform_plain_hoisted2_sparse", None)
-    if native is not None:
-        elts = sorted(gal_keys.keys)
-        data = native(L, ct.data, d, steps, [p.data for p in pts], elts, [gal_keys.key(e) for e in elts])
-    else:  # the oracle twin: regular -d rotation, then the oracle's statement of the double-hoisted core
-        plans = [ev.rotation_plan(l, gal_keys) for l in steps[1:]]
-        if any(len(p) != 1 for p in plans):
-            raise ValueError("hoisted linear transform needs a direct Galois key for every step")
-        ct_new = _duplicate(ev, ct, d, gal_keys)
-        elts = [p[0] for p in plans]
-        data = be.lt_double_hoisted_core(ct_new.data, [p.data for p in pts], elts, [gal_keys.key(e) for e in elts])
-    return Ciphertext()._set(data, 2, L, scale)
 
 
 def cc_matrix_multiplication_sparse(ev: Evaluator, ctA: Ciphertext, ctB: Ciphertext, dimension: int, U_sigma: dict,
@@ -736,7 +617,7 @@ def cc_matrix_multiplication_sparse(ev: Evaluator, ctA: Ciphertext, ctB: Ciphert
     Step-2 transforms read the same two duplicated ciphertexts, so all their rotations go out as two batches.
     hoisted=True (direct Galois keys for every step) runs the 2n-1 / n rotations of the sigma / tau transforms on one
     shared digit decomposition each; hoisted=2 additionally mods them down once per transform (U_sigma / U_tau then
-    hold KEY-LEVEL plaintexts, see _linear_transform_plain_sparse_hoisted2; Step 2 stays single-hoisted)."""
+    hold KEY-LEVEL plaintexts, see _linear_transform_plain_hoisted2; Step 2 stays single-hoisted)."""
     d = dimension * dimension
     ctA0 = linear_transform_plain_sparse(ev, ctA, d, U_sigma, gal_keys, hoisted)   # :22
     ctB0 = linear_transform_plain_sparse(ev, ctB, d, U_tau, gal_keys, hoisted)     # :25
@@ -979,6 +860,16 @@ def _dft_stage(ev: Evaluator, xs: Sequence[Ciphertext], stage, table, gal_keys: 
     return ev.rescale_to_next_many_inplace(outs)
 
 
+def _dft_run(ev: Evaluator, xs: List[Ciphertext], plan, gal_keys: KSwitchKeys, encoded) -> List[Ciphertext]:
+    """the stages of a dft.Plan in turn on xs; encoded: the plan's plaintexts at the inputs' level (None: made here with a
+    host encoder)"""
+    if encoded is None:
+        encoded = plan.encode(CKKSEncoder(ev.ctx, device_encode=False), xs[0].parms_id())
+    for stage, table in zip(plan.stages, encoded):
+        xs = _dft_stage(ev, xs, stage, table, gal_keys)
+    return xs
+
+
 def coeffs_to_slots(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitchKeys, encoded=None):
     """CoeffToSlot: (ct_a, ct_b) whose slots hold the coefficients of ct's plaintext, ct_a[i] = m_R(i) / scale and
     ct_b[i] = m_(N/2 + R(i)) / scale (R: bit reversal of the N/2 slot indices, dft.bit_reversal), both plan.levels levels
@@ -989,11 +880,7 @@ def coeffs_to_slots(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitchKeys, 
     from . import dft
     if plan.direction != dft.C2S or plan.N != ev.ctx.N or plan.slots is not None:
         raise ValueError("coeffs_to_slots: the plan is not a CoeffToSlot plan of this ring")
-    if encoded is None:
-        encoded = plan.encode(CKKSEncoder(ev.ctx, device_encode=False), ct.parms_id())
-    xs = [ct]
-    for stage, table in zip(plan.stages, encoded):
-        xs = _dft_stage(ev, xs, stage, table, gal_keys)
+    xs = _dft_run(ev, [ct], plan, gal_keys, encoded)
     return tuple(ev.add(x, ev.complex_conjugate(x, gal_keys)) for x in xs)    # 2 Re(.)
 
 
@@ -1005,12 +892,7 @@ def slots_to_coeffs(ev: Evaluator, ct_a: Ciphertext, ct_b: Ciphertext, plan, gal
     from . import dft
     if plan.direction != dft.S2C or plan.N != ev.ctx.N or plan.slots is not None:
         raise ValueError("slots_to_coeffs: the plan is not a SlotToCoeff plan of this ring")
-    if encoded is None:
-        encoded = plan.encode(CKKSEncoder(ev.ctx, device_encode=False), ct_a.parms_id())
-    xs = [ct_a, ct_b]
-    for stage, table in zip(plan.stages, encoded):
-        xs = _dft_stage(ev, xs, stage, table, gal_keys)
-    return xs[0]
+    return _dft_run(ev, [ct_a, ct_b], plan, gal_keys, encoded)[0]
 
 
 # ---- sparse packing: a message of ns <= N/4 slots (dft.plan_packed plans, these run) ----------------------------------------
@@ -1052,12 +934,8 @@ def coeffs_to_slots_packed(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitc
     plan: dft.plan_packed(N, ns, levels, dft.C2S, ...); gal_keys: galois_keys(plan.galois_steps(), conjugate=True)."""
     from . import dft
     _packed_plan(ev, plan, dft.C2S, "coeffs_to_slots_packed")
-    if encoded is None:
-        encoded = plan.encode(CKKSEncoder(ev.ctx, device_encode=False), ct.parms_id())
-    xs = [ct]
-    for stage, table in zip(plan.stages, encoded):
-        xs = _dft_stage(ev, xs, stage, table, gal_keys)
-    return ev.add(xs[0], ev.complex_conjugate(xs[0], gal_keys))
+    x = _dft_run(ev, [ct], plan, gal_keys, encoded)[0]
+    return ev.add(x, ev.complex_conjugate(x, gal_keys))
 
 
 def slots_to_coeffs_packed(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitchKeys, encoded=None) -> Ciphertext:
@@ -1065,12 +943,7 @@ def slots_to_coeffs_packed(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitc
     with x_a[R^-1], x_b[R^-1] on the stride.  plan: dft.plan_packed(N, ns, levels, dft.S2C, ...)."""
     from . import dft
     _packed_plan(ev, plan, dft.S2C, "slots_to_coeffs_packed")
-    if encoded is None:
-        encoded = plan.encode(CKKSEncoder(ev.ctx, device_encode=False), ct.parms_id())
-    xs = [ct]
-    for stage, table in zip(plan.stages, encoded):
-        xs = _dft_stage(ev, xs, stage, table, gal_keys)
-    return xs[0]
+    return _dft_run(ev, [ct], plan, gal_keys, encoded)[0]
 
 
 def cipher_dot_product_many(ev: Evaluator, As: Sequence[Ciphertext], Bs: Sequence[Ciphertext], size: int,

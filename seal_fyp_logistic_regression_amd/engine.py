@@ -513,19 +513,21 @@ class Engine:
         """double-hoisted transform over a subset of the diagonals (steps[0] == 0)"""
         out = out if out is not None else DeviceArray(self, (2, L, self.N))
         arr = (C.c_int * len(steps))(*[int(x) for x in steps])
+        karr = keys if isinstance(keys, C.Array) else capi.ptr_array([k.ptr for k in keys])
+        darr = diag_pts_keylevel if isinstance(diag_pts_keylevel, C.Array) else capi.ptr_array([p.ptr for p in diag_pts_keylevel])
         capi.check(capi.lib().hefx_linear_transform_plain_hoisted2_sparse(
-            self._h, L, ct.ptr, int(d), len(steps), arr, capi.ptr_array([p.ptr for p in diag_pts_keylevel]), len(keys),
-            capi.u32_array(key_elts), capi.ptr_array([k.ptr for k in keys]), out.ptr, stream))
+            self._h, L, ct.ptr, int(d), len(steps), arr, darr, len(karr), capi.u32_array(key_elts), karr, out.ptr, stream))
         return out
 
     def linear_transform_plain_bsgs(self, L, ct, shifted_diag_pts, n1, key_elts, keys, hoisted=True, out=None,
                                     stream=None):
         """baby-step / giant-step Linear_Transform_Plain in one native call (hefx_linear_transform_plain_bsgs)"""
         out = out if out is not None else DeviceArray(self, (2, L, self.N))
+        karr = keys if isinstance(keys, C.Array) else capi.ptr_array([k.ptr for k in keys])
+        darr = shifted_diag_pts if isinstance(shifted_diag_pts, C.Array) else capi.ptr_array([p.ptr for p in shifted_diag_pts])
         capi.check(capi.lib().hefx_linear_transform_plain_bsgs(
-            self._h, L, ct.ptr, len(shifted_diag_pts), int(n1), capi.ptr_array([p.ptr for p in shifted_diag_pts]),
-            len(keys), capi.u32_array(key_elts), capi.ptr_array([k.ptr for k in keys]), 1 if hoisted else 0, out.ptr,
-            stream))
+            self._h, L, ct.ptr, len(darr), int(n1), darr, len(karr), capi.u32_array(key_elts), karr, 1 if hoisted else 0,
+            out.ptr, stream))
         return out
 
     # ---- randomness, encrypt, decrypt on the GPU

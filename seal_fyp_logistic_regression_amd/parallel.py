@@ -198,18 +198,15 @@ def linear_transform_plain_sharded(ev: Evaluator, ct: Ciphertext, U_diagonals: S
     import torch.distributed as dist
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     d = len(U_diagonals)
-    ct_new = ev.add(ct, ev.rotate_vector(ct, -d, gal_keys))            # replicated: every rank needs ct_new
+    ct_new = alg._duplicate(ev, ct, d, gal_keys)                       # replicated: every rank needs ct_new
     mine = list(shard(d, rank, world))
     res: List[Ciphertext] = []
     steps = [l for l in mine if l > 0]
     if 0 in mine:
         res.append(ev.multiply_plain(ct_new, U_diagonals[0]))
     res += alg._rotations_batched(ev, ct_new, steps, gal_keys, [U_diagonals[l] for l in steps])
-    if res:
-        partial = ev.add_many(res)
-    else:  # more ranks than diagonals: contribute the zero ciphertext at the right level/scale
-        z = ev.multiply_plain(ct_new, U_diagonals[0])
-        partial = ev.sub(z, z)
+    # more ranks than diagonals: the zero ciphertext at the right level / scale
+    partial = ev.add_many(res) if res else alg._zero_like(ev, ev.multiply_plain(ct_new, U_diagonals[0]))
     return allreduce_ciphertext(ev, partial, group)
 
 
@@ -234,18 +231,10 @@ def linear_transforms_plain_sharded_many(ev: Evaluator, cts: Sequence[Ciphertext
     outs = []
     for ct_new, ds, pr in zip(ct_news, diag_sets, prods):
         res = ([ev.multiply_plain(ct_new, ds[0])] if 0 in mine else []) + list(pr)
-        if res:
-            partial = ev.add_many(res)
-        else:  # more ranks than diagonals: the zero ciphertext at the right level / scale
-            z = ev.multiply_plain(ct_new, ds[0])
-            partial = ev.sub(z, z)
+        # more ranks than diagonals: the zero ciphertext at the right level / scale
+        partial = ev.add_many(res) if res else alg._zero_like(ev, ev.multiply_plain(ct_new, ds[0]))
         outs.append(allreduce_ciphertext(ev, partial, group))
     return outs
-
-
-def _zero_like(ev: Evaluator, ct: Ciphertext) -> Ciphertext:
-    """the zero ciphertext at ct's size / level / scale (a rank's contribution when it owns no unit)"""
-    return ev.sub(ct, ct)
 
 
 def cc_matrix_multiplication_sharded(ev: Evaluator, ctA: Ciphertext, ctB: Ciphertext, dimension: int,
@@ -268,17 +257,8 @@ def cc_matrix_multiplication_sharded(ev: Evaluator, ctA: Ciphertext, ctB: Cipher
                                                                           [W_diagonals[k] for k in mine]], gal_keys)   # :42, :43
     else:
         ctAk, ctBk = [], []
-    ev.rescale_to_next_many_inplace(ctAk)                                          # :69-73
-    ev.rescale_to_next_many_inplace(ctBk)
-    ctAB = ev.multiply(ctA0, ctB0)                                                 # :104
-    ev.mod_switch_to_next_inplace(ctAB)                                            # :112
-    for c in ctAk + ctBk:
-        c.scale = 2.0 ** int(np.log2(c.scale))                                     # :117-121
-    terms = ([ctAB] if rank == 0 else []) + (ev.multiply_many(ctAk, ctBk) if ctAk else [])   # A_0 (.) B_0 counted once
-    partial = ev.add_many(terms) if terms else _zero_like(ev, ctAB)                # :123-129 (this rank's share)
-    out = allreduce_ciphertext(ev, partial, group)
-    out.scale = ctAB.scale  # the serial sum carries its first addend's scale (A_0 (.) B_0) on every rank
-    return out
+    # :69-129, this rank's share: A_0 (.) B_0 counted once, and its scale (the serial sum's first addend) on every rank
+    return allreduce_ciphertext(ev, alg._matmul_step3(ev, ctA0, ctB0, ctAk, ctBk, include_ab=rank == 0), group)
 
 
 def linear_transform_plain_sparse_sharded(ev: Evaluator, ct: Ciphertext, d: int, diagonals: dict,
@@ -289,11 +269,8 @@ def linear_transform_plain_sparse_sharded(ev: Evaluator, ct: Ciphertext, d: int,
     ct_new = alg._duplicate(ev, ct, d, gal_keys)                                   # replicated
     items = sorted(diagonals.items())
     mine = [items[i] for i in shard(len(items), rank, world)]
-    if mine:
-        partial = ev.add_many(alg._sparse_products(ev, ct_new, mine, gal_keys))
-    else:
-        z = ev.multiply_plain(ct_new, items[0][1])
-        partial = ev.sub(z, z)
+    partial = ev.add_many(alg._sparse_products(ev, ct_new, mine, gal_keys)) if mine else \
+        alg._zero_like(ev, ev.multiply_plain(ct_new, items[0][1]))
     return allreduce_ciphertext(ev, partial, group)
 
 
@@ -319,17 +296,8 @@ def cc_matrix_multiplication_sparse_sharded(ev: Evaluator, ctA: Ciphertext, ctB:
     mine = list(shard(dimension - 1, rank, world))
     ctAk = alg._sparse_transforms_of_one_input(ev, ctA0, d, [V_diagonals[k] for k in mine], gal_keys)   # :42
     ctBk = alg._sparse_transforms_of_one_input(ev, ctB0, d, [W_diagonals[k] for k in mine], gal_keys)   # :43
-    ev.rescale_to_next_many_inplace(ctAk)                                          # :69-73
-    ev.rescale_to_next_many_inplace(ctBk)
-    ctAB = ev.multiply(ctA0, ctB0)                                                 # :104
-    ev.mod_switch_to_next_inplace(ctAB)                                            # :112
-    for c in ctAk + ctBk:
-        c.scale = 2.0 ** int(np.log2(c.scale))                                     # :117-121
-    terms = ([ctAB] if rank == 0 else []) + (ev.multiply_many(ctAk, ctBk) if ctAk else [])   # A_0 (.) B_0 counted once
-    partial = ev.add_many(terms) if terms else _zero_like(ev, ctAB)                # :123-129 (this rank's share)
-    out = allreduce_ciphertext(ev, partial, group)
-    out.scale = ctAB.scale  # the serial sum carries its first addend's scale (A_0 (.) B_0) on every rank
-    return out
+    # :69-129, this rank's share: A_0 (.) B_0 counted once, and its scale (the serial sum's first addend) on every rank
+    return allreduce_ciphertext(ev, alg._matmul_step3(ev, ctA0, ctB0, ctAk, ctBk, include_ab=rank == 0), group)
 
 
 def predict_cipher_weights_sharded(ev: Evaluator, encoder, encryptor, features: Sequence[Ciphertext],
@@ -355,7 +323,7 @@ def predict_cipher_weights_sharded(ev: Evaluator, encoder, encryptor, features: 
         mask_pt = encoder.encode(np.ones(1), scale)
         ev.mod_switch_to_next_inplace(mask_pt)
         ev.multiply_plain_inplace(one, mask_pt)
-        partial = _zero_like(ev, one)
+        partial = alg._zero_like(ev, one)
     lin = allreduce_ciphertext(ev, partial, group)
     ev.relinearize_inplace(lin, relin_keys)                                         # :237 (no-op)
     ev.rescale_to_next_inplace(lin)                                                 # :239

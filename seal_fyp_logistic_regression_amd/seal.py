@@ -10,6 +10,7 @@ complex FFT of CKKSEncoder run on the host in numpy; their NTTs run on the GPU.
 from __future__ import annotations
 
 import math
+import operator
 import os
 from typing import Dict, List, Optional, Sequence
 
@@ -231,7 +232,7 @@ class GpuBackend:
 
     def apply_galois_forest(self, L, parents, ext_ins, elts, keys, pts=None):
         """a forest of rotations in one engine call (hefx_apply_galois_forest); the oracle-backed twin of the tests has no
-        such method and runs the same nodes depth by depth (algorithms._rotations_batched)"""
+        such method and runs the same nodes depth by depth (algorithms._rotations_of_many)"""
         return self.engine.apply_galois_forest(L, parents, ext_ins, elts, keys, pts)
 
     def rotate_add_chain(self, L, cts, elts, keys, accs, steps):
@@ -421,6 +422,9 @@ class Plaintext:
     @scale.setter
     def scale(self, v):
         self._scale = float(v)
+
+
+_PT_STATE = operator.attrgetter("_parms_id", "_scale", "is_zero")
 
 
 class Ciphertext:
@@ -945,6 +949,32 @@ class Evaluator:
         if new_scale <= 0 or int(math.log2(new_scale)) >= bits:
             raise ValueError("scale out of bounds")
 
+    def _plain_product_scale(self, L: int, ct_scale: float, pts: Sequence["Plaintext"], pt_level: int) -> float:
+        """The checks multiply_plain + add_many make over ct (.) pts[i] for a ciphertext at level L and scale ct_scale, and
+        the common product scale.  pt_level is the level the plaintexts must sit at: L, or the key level for the
+        double-hoisted transforms.  Per plaintext the order is multiply_plain's -- level, scale bound, closeness to the
+        first product, transparency -- and the FIRST offending plaintext raises, like the op-by-op sequence; every
+        composite states its plaintext checks through this function, so an input with two faults reports the one
+        multiply_plain would.  One set comparison when everything is in order (a 1000-diagonal transform is otherwise
+        host-bound in this loop); the element-by-element walk only runs to raise."""
+        if set(map(_PT_STATE, pts)) == {(pt_level, pts[0]._scale, False)}:  # (one C-level pass: 25 us for 512 plaintexts)
+            scale = ct_scale * pts[0]._scale
+            self._check_scale(scale, L)
+            return scale
+        scale = None
+        for p in pts:
+            if p.parms_id() != pt_level:
+                raise ValueError("encrypted_ntt and plain_ntt parameter mismatch" if pt_level == L else
+                                 "double hoisting needs key-level plaintexts (encode with parms_id = key level)")
+            s = ct_scale * p.scale
+            self._check_scale(s, L)
+            if scale is not None and not self._close(scale, s):
+                raise ValueError("scale mismatch")
+            scale = s if scale is None else scale
+            if p.is_zero:
+                raise RuntimeError("result ciphertext is transparent")
+        return scale
+
     # ---- add / sub / negate
     def _addsub(self, a: Ciphertext, b: Ciphertext, sub: bool) -> Ciphertext:
         self._check_same(a, b)
@@ -1097,19 +1127,15 @@ class Evaluator:
         if not cts or len(cts) != len(pts):
             raise ValueError("multiply_plain_sum: need as many plaintexts as ciphertexts")
         L, size = cts[0].parms_id(), cts[0].size()
-        scale = None
-        for a, p in zip(cts, pts):
-            if a.parms_id() != L or a.size() != size:
-                raise ValueError("encrypted parameter mismatch")
-            if a.parms_id() != p.parms_id():
-                raise ValueError("encrypted_ntt and plain_ntt parameter mismatch")
-            s = a.scale * p.scale
-            self._check_scale(s, L)
-            if scale is not None and not self._close(scale, s):
-                raise ValueError("scale mismatch")
-            scale = s if scale is None else scale
-            if p.is_zero:
-                raise RuntimeError("result ciphertext is transparent")
+        if any(a._parms_id != L or a._size != size for a in cts):
+            raise ValueError("encrypted parameter mismatch")
+        if len({a._scale for a in cts}) == 1:
+            scale = self._plain_product_scale(L, cts[0].scale, pts, L)
+        else:  # ciphertexts at several scales: term by term, each product held to the first
+            scale = self._plain_product_scale(L, cts[0].scale, pts[:1], L)
+            for a, p in zip(cts[1:], pts[1:]):
+                if not self._close(scale, self._plain_product_scale(L, a.scale, [p], L)):
+                    raise ValueError("scale mismatch")
         outs = self.be.multiply_plain_sum(L, size, [a.data for a in cts], [p.data for p in pts], group)
         return [Ciphertext()._set(o, size, L, scale) for o in outs]
 
@@ -1309,22 +1335,9 @@ class Evaluator:
                 raise ValueError("encrypted size must be 2")
             if not self._close(ct_scale, c.scale):
                 raise ValueError("scale mismatch")
-        scale = None
-        for r in rows:
-            if all(p is None for p in r):
-                raise ValueError("plain_combine: an output has no term")
-            for p in r:
-                if p is None:
-                    continue
-                if p.parms_id() != L:
-                    raise ValueError("encrypted_ntt and plain_ntt parameter mismatch")
-                s = ct_scale * p.scale
-                self._check_scale(s, L)
-                if scale is not None and not self._close(scale, s):
-                    raise ValueError("scale mismatch")
-                scale = s if scale is None else scale
-                if p.is_zero:
-                    raise RuntimeError("result ciphertext is transparent")
+        if any(all(p is None for p in r) for r in rows):
+            raise ValueError("plain_combine: an output has no term")
+        scale = self._plain_product_scale(L, ct_scale, [p for r in rows for p in r if p is not None], L)
         native = getattr(self.be, "plain_combine", None)
         G = len(rows)
         counts = [sum(p is not None for p in r) for r in rows]

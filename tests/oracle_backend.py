@@ -134,3 +134,23 @@ class OracleBackend:
         for j in range(L):
             v[:, j, :] %= np.uint64(self.primes[j])
         return v
+
+
+class _ForestTwin(OracleBackend):
+    """The oracle twin with the two engine entry points the lockstep composites look for -- a multi-root rotation forest and
+    the many-input linear transform -- each stated node by node / input by input on the oracle, so that the HOST logic of
+    algorithms._rotations_of_many / _linear_transforms_of_inputs / linear_transforms_plain_many (forest construction, leaf
+    bookkeeping, grouping of the product sums) runs on the CPU."""
+    calls = 0
+
+    def apply_galois_forest(self, L, parents, ext_ins, elts, keys, pts=None):
+        type(self).calls += 1
+        outs = []
+        for i, p in enumerate(parents):
+            assert p < i
+            src = ext_ins[i] if p < 0 else outs[p]
+            r = self.apply_galois_batch(L, [src], [elts[i]], [keys[i]])[0]
+            if pts is not None and pts[i] is not None:
+                r = self.multiply_plain(L, 2, r, pts[i])
+            outs.append(r)
+        return outs

@@ -195,6 +195,34 @@ def test_linear_transform_plain_many_refuses_bad_arguments():
         be.linear_transform_plain_many(L, [cts[0].data] * 65, [diags[0].data] * 65, elts, keys)
 
 
+@pytest.mark.parametrize("fused", [True, False], ids=["fused_plaintexts", "rotations_only"])
+def test_rotations_of_many_with_a_zero_step_ride_in_one_forest_bit_exact(fused):
+    """algorithms._rotations_of_many on two inputs at the top level with a ZERO step among the steps: the rotations of both
+    inputs go out as one hefx_apply_galois_forest (step 0 has no node: it is the input's copy, times its plaintext), step 3
+    through its two-term NAF plan.  N = 2048 is the smallest degree at which the engine key-switches.  Every word and
+    scale is the oracle twin's, which rotates input by input."""
+    from seal_fyp_logistic_regression_amd import algorithms as alg
+    from tests.test_gpu_composites import both, bits
+    steps = (0, 1, 3, -2)
+    rng = np.random.default_rng(66)
+    vs, ws = rng.uniform(-1, 1, (2, 8)), rng.uniform(-1, 1, (2, len(steps), 8))
+
+    def run(e):
+        scale = 2.0 ** 30
+        cts = [e["enc"].encrypt(e["encoder"].encode(v, scale)) for v in vs]
+        pts = [[e["encoder"].encode(w, scale) for w in row] for row in ws] if fused else None
+        return alg._rotations_of_many(e["ev"], cts, steps, e["gk"], pts)
+
+    r = both(2048, [50, 30, 30, 50], run)
+    (eg, rg), (eo, ro) = r["gpu"], r["oracle"]
+    assert eg["ctx"].backend.name == "hip" and hasattr(eg["ctx"].backend, "apply_galois_forest")
+    assert [len(row) for row in rg] == [len(row) for row in ro] == [len(steps)] * 2
+    for row_g, row_o in zip(rg, ro):
+        for cg, co in zip(row_g, row_o):
+            assert (cg.size(), cg.parms_id(), cg.scale) == (co.size(), co.parms_id(), co.scale)
+            assert (bits(eg, cg) == bits(eo, co)).all()
+
+
 def test_bench_eight_ranks_share_one_gpu_sharded_legs_keep_the_serial_bits():
     """The driver's scaling run goes to eight ranks; this box has one MI355X, so the eight ranks share it (gloo rendezvous
     and exchange, as in tests/test_gpu_round4.py's two-rank run) with workloads cut to fit: what is exercised is every

@@ -9,7 +9,7 @@ import pytest
 
 from seal_fyp_logistic_regression_amd import algorithms as alg
 from seal_fyp_logistic_regression_amd import seal as S
-from tests.oracle_backend import OracleBackend
+from tests.oracle_backend import OracleBackend, _ForestTwin
 
 GOLD = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "appendix_b.json")))
 
@@ -315,6 +315,95 @@ def test_multiply_plain_sum_equals_the_op_by_op_sequence_and_checks_like_it(env)
         ev.multiply_plain_sum(cts, pts[:4] + [low])
 
 
+class _Counting:
+    """a backend proxy that counts the calls it passes on"""
+
+    def __init__(self, be):
+        self._be, self.calls = be, 0
+
+    def __getattr__(self, name):
+        f = getattr(self._be, name)
+        if not callable(f):
+            return f
+
+        def call(*a, **k):
+            self.calls += 1
+            return f(*a, **k)
+        return call
+
+
+_KEY_LEVEL_MSG = "double hoisting needs key-level plaintexts (encode with parms_id = key level)"
+PLAIN_PRODUCT_SITES = ["multiply_plain_sum", "plain_combine", "plain_product_scale", "rotations_batched", "rotations_of_many",
+                       "hoisted", "hoisted2", "sparse_hoisted2"]
+
+
+@pytest.fixture(scope="module")
+def product_faults(env):
+    """three good plaintexts of d = 3 at the data level and at the key level, the four single faults as a replacement for
+    the last one, and what multiply_plain + add_many raise op by op for each"""
+    import copy
+    e = env
+    ev, encoder, ctx = e["ev"], e["encoder"], e["ctx"]
+    rng = np.random.default_rng(6)
+    scale = 2.0 ** 30
+    ct, ct2 = (e["enc"].encrypt(encoder.encode(rng.standard_normal(3), scale)) for _ in range(2))
+    L, K = ct.parms_id(), ctx.key_parms_id()
+    vals = rng.standard_normal((3, 3))
+    good = {lvl: [encoder.encode(v, scale, parms_id=lvl) for v in vals] for lvl in (L, K)}
+
+    def rescaled(p, s):
+        q = copy.copy(p)
+        q.scale = s
+        return q
+    faults = {lvl: {"level": encoder.encode(vals[2], scale, parms_id=lvl - 1),
+                    "bound": rescaled(good[lvl][2], 2.0 ** 120),
+                    "scale": rescaled(good[lvl][2], 2.0 ** 20),
+                    "zero": encoder.encode(np.zeros(3), scale, parms_id=lvl)} for lvl in (L, K)}
+    want = {}
+    for name, bad in faults[L].items():
+        with pytest.raises((ValueError, RuntimeError)) as info:
+            ev.add_many([ev.multiply_plain(ct, p) for p in good[L][:2] + [bad]])
+        want[name] = (type(info.value), str(info.value))
+    assert want == {"level": (ValueError, "encrypted_ntt and plain_ntt parameter mismatch"),
+                    "bound": (ValueError, "scale out of bounds"), "scale": (ValueError, "scale mismatch"),
+                    "zero": (RuntimeError, "result ciphertext is transparent")}
+    return dict(ct=ct, ct2=ct2, L=L, K=K, good=good, faults=faults, want=want, gk3=e["kg"].galois_keys([-3, 1, 2]))
+
+
+@pytest.mark.parametrize("fault", ["level", "bound", "scale", "zero"])
+@pytest.mark.parametrize("site", PLAIN_PRODUCT_SITES)
+def test_every_plaintext_product_site_checks_like_multiply_plain_and_add_many(env, product_faults, site, fault):
+    """One check (Evaluator._plain_product_scale) behind the eight places that form sum_i ct (.) pt_i: a single fault in the
+    LAST plaintext raises the exception, type and message, of the op-by-op sequence -- for the double-hoisted forms, whose
+    plaintexts sit at the key level, a wrong level raises their own message -- and the two rotation helpers raise before the
+    backend has received a call."""
+    f, ev = product_faults, env["ev"]
+    ct, L = f["ct"], f["L"]
+    lvl = f["K"] if "hoisted2" in site else L
+    pts = f["good"][lvl][:2] + [f["faults"][lvl][fault]]
+    want = (ValueError, _KEY_LEVEL_MSG) if lvl != L and fault == "level" else f["want"][fault]
+    be = _Counting(ev.be)
+    run = {
+        "multiply_plain_sum": lambda: ev.multiply_plain_sum([ct] * 3, pts),
+        "plain_combine": lambda: ev.plain_combine([ct] * 3, [pts]),
+        "plain_product_scale": lambda: ev._plain_product_scale(L, ct.scale, pts, L),
+        "rotations_batched": lambda: alg._rotations_batched(ev, ct, [1, 3, 5], env["gk"], pts),
+        "rotations_of_many": lambda: alg._rotations_of_many(ev, [f["ct2"], ct], [1, 3, 5], env["gk"], [f["good"][L], pts]),
+        "hoisted": lambda: alg.linear_transform_plain(ev, ct, pts, f["gk3"], hoisted=True),
+        "hoisted2": lambda: alg.linear_transform_plain(ev, ct, pts, f["gk3"], hoisted=2),
+        "sparse_hoisted2": lambda: alg.linear_transform_plain_sparse(ev, ct, 3, dict(enumerate(pts)), f["gk3"], hoisted=2),
+    }[site]
+    ev.be = be
+    try:
+        with pytest.raises(want[0]) as info:
+            run()
+    finally:
+        ev.be = be._be
+    assert (type(info.value), str(info.value)) == want
+    if site.startswith("rotations"):
+        assert be.calls == 0
+
+
 @pytest.mark.parametrize("d,n1", [(6, None), (7, 2), (9, 4), (5, 5)])
 def test_bsgs_linear_transform_decrypts_to_the_matrix_product(env, d, n1):
     """baby-step / giant-step form of Linear_Transform_Plain: n1-1 + n2-1 key switches, M.v in the first d slots,
@@ -389,26 +478,6 @@ def test_shared_rotations_in_the_matrix_product_keep_the_bits_of_the_per_transfo
     literal = [alg.linear_transform_plain(e["ev"], ct0, vd, e["gk"]) for vd in Vd]
     for a, b in zip(shared, literal):
         assert a.parms_id() == b.parms_id() and a.scale == b.scale and (a.data == b.data).all()
-
-
-class _ForestTwin(OracleBackend):
-    """The oracle twin with the two engine entry points the lockstep composites look for -- a multi-root rotation forest and
-    the many-input linear transform -- each stated node by node / input by input on the oracle, so that the HOST logic of
-    algorithms._rotations_of_many / _linear_transforms_of_inputs / linear_transforms_plain_many (forest construction, leaf
-    bookkeeping, grouping of the product sums) runs on the CPU."""
-    calls = 0
-
-    def apply_galois_forest(self, L, parents, ext_ins, elts, keys, pts=None):
-        type(self).calls += 1
-        outs = []
-        for i, p in enumerate(parents):
-            assert p < i
-            src = ext_ins[i] if p < 0 else outs[p]
-            r = self.apply_galois_batch(L, [src], [elts[i]], [keys[i]])[0]
-            if pts is not None and pts[i] is not None:
-                r = self.multiply_plain(L, 2, r, pts[i])
-            outs.append(r)
-        return outs
 
 
 def test_lockstep_transforms_of_several_inputs_keep_the_bits_of_the_loops():

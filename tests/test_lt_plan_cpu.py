@@ -66,6 +66,7 @@ class _Recorder:
 def _evaluator(N, backend=None):
     ev = types.SimpleNamespace(ctx=types.SimpleNamespace(N=N), be=backend, _check_scale=lambda scale, L: None)
     ev.rotation_plan = lambda steps, gk: S.Evaluator.rotation_plan(ev, steps, gk)
+    ev._plain_product_scale = lambda *a: S.Evaluator._plain_product_scale(ev, *a)
     return ev
 
 
@@ -105,7 +106,7 @@ def test_fused_forest_is_the_one_the_python_planner_builds(printed, N, steps, d)
     rec = _Recorder()
     ct = types.SimpleNamespace(data="ct", parms_id=lambda: 2, scale=1.0)
     # plaintexts that are their own diagonal index
-    diag = [types.SimpleNamespace(data=l, scale=1.0, parms_id=lambda: 2, is_zero=False) for l in range(1, d)]
+    diag = [types.SimpleNamespace(data=l, scale=1.0, _scale=1.0, parms_id=lambda: 2, _parms_id=2, is_zero=False) for l in range(1, d)]
     outs = alg._rotations_batched(_evaluator(N, rec), ct, list(range(1, d)), _Keys(N, False), diag)
     want = [(p, e, -1 if pt is None else pt) for p, e, pt in rec.forest]
     assert len(got) == len(want) and got == want

@@ -227,3 +227,29 @@ def test_comm_decision_cache_is_tied_to_the_group_object():
     assert par._decision_get(b, 2) is False
     par._decision_drop(b, 2)
     assert par._decision_get(b, 2) is None
+
+
+def test_step3_holds_every_product_to_ctAB_on_a_rank_that_does_not_count_it():
+    """The shared step 3 of the matrix product (algorithms._matmul_step3) on a rank other than 0 (include_ab=False), without
+    a process group: an A_k whose scale is off by 2^-10 raises "scale mismatch" THERE, before the all-reduce its peers would
+    otherwise wait in -- and with sound operands the shares of two ranks add up to the serial product's bits."""
+    from seal_fyp_logistic_regression_amd import algorithms as alg
+    from tests.test_host_api_cpu import make
+    e = make(2048, [50, 30, 30, 50], seed=3)
+    ev, encoder = e["ev"], e["encoder"]
+    rng = np.random.default_rng(12)
+    scale = 2.0 ** 30
+    A0, B0 = (e["enc"].encrypt(encoder.encode(rng.standard_normal(4), scale)) for _ in range(2))
+    fresh = lambda c: [ev.multiply_plain(c, encoder.encode(rng.standard_normal(4), scale))]   # scale 2^60, like a V_k transform
+    Ak, Bk = fresh(A0), fresh(B0)
+    copies = lambda cts: [c.copy() for c in cts]   # step 3 rescales its operands in place
+    serial = alg._matmul_step3(ev, A0, B0, copies(Ak), copies(Bk))
+    rank0 = alg._matmul_step3(ev, A0, B0, [], [], include_ab=True)
+    rank1 = alg._matmul_step3(ev, A0, B0, copies(Ak), copies(Bk), include_ab=False)
+    total = ev.add(rank0, rank1)
+    assert (total.size(), total.parms_id(), total.scale) == (serial.size(), serial.parms_id(), serial.scale)
+    assert (np.asarray(total.data) == np.asarray(serial.data)).all()
+    off = copies(Ak)
+    off[0].scale *= 2.0 ** -10
+    with pytest.raises(ValueError, match="^scale mismatch$"):
+        alg._matmul_step3(ev, A0, B0, off, copies(Bk), include_ab=False)
