@@ -13,6 +13,7 @@ import operator
 
 import numpy as np
 
+from . import poly as _poly
 from .seal import Ciphertext, CKKSEncoder, Evaluator, KSwitchKeys, Plaintext
 
 
@@ -129,14 +130,14 @@ def _native_args(gal_keys: KSwitchKeys, operands: Sequence):
     keys = [gal_keys.key(e) for e in elts]
     if not keys or not hasattr(keys[0], "ptr"):
         return elts, keys, [x.data for x in operands]
-    from . import capi
+    from .engine import ptr_array, u32_array
     # fingerprint: elements AND payload addresses -- a key replaced under an existing element, or one removed and another
     # added, must not leave the native transform on the old payloads (0.03 ms at 512 keys against 0.1 ms for the C arrays)
     mark = (tuple(elts), tuple(k.ptr for k in keys))
     cache = getattr(gal_keys, "_native_args", None)
     if cache is None or cache[0] != mark:
-        cache = gal_keys._native_args = (mark, capi.u32_array(elts), capi.ptr_array(list(mark[1])), keys)  # keys: kept alive
-    return cache[1], cache[2], capi.ptr_array(list(map(_PT_PTR, operands)))
+        cache = gal_keys._native_args = (mark, u32_array(elts), ptr_array(list(mark[1])), keys)  # keys: kept alive
+    return cache[1], cache[2], ptr_array(list(map(_PT_PTR, operands)))
 
 
 def _direct_elts(ev: Evaluator, steps: Sequence[int], gal_keys: KSwitchKeys, what: str) -> List[int]:
@@ -695,29 +696,7 @@ def evaluate_polynomial(ev: Evaluator, ct: Ciphertext, coeffs: Sequence[float], 
     it -- scales are tracked through every product and rescale, never overwritten.  MUL: mod_switch_to the lower level,
     multiply, relinearize; COMBINE: Evaluator.scalar_combine (one fused pass on the HIP engine) and rescale_to_next;
     ADD: add.  Not the reference's Horner_cipher / Tree_cipher and not their bits: those stay as they are."""
-    from . import capi, poly
-    if ct.size() != 2:
-        raise ValueError("encrypted size must be 2")
-    plan = poly.plan(coeffs, basis, ev.ctx.primes[:ct.parms_id()], ct.scale, target_scale)
-    slots: List[Optional[Ciphertext]] = [None] * plan.nslots
-    slots[0] = ct
-    for st in plan.steps:
-        if st.op == capi.POLY_MUL:
-            a, b = slots[st.a].copy(), slots[st.b].copy()
-            ev.mod_switch_to_inplace(a, st.level)
-            if st.a == st.b:
-                b = a  # a square: Evaluator.multiply sees the one payload
-            else:
-                ev.mod_switch_to_inplace(b, st.level)
-            slots[st.dst] = ev.relinearize_inplace(ev.multiply(a, b), relin_keys)
-        elif st.op == capi.POLY_COMBINE:
-            out = ev.scalar_combine([slots[t.src] for t in st.terms], [[t.coef for t in st.terms]],
-                                    [t.wscale for t in st.terms], None if st.constant is None else [st.constant],
-                                    scale=st.cscale, parms_id=st.level)[0]
-            slots[st.dst] = ev.rescale_to_next_inplace(out)
-        else:
-            slots[st.dst] = ev.add(slots[st.a], slots[st.b])
-    return slots[plan.steps[-1].dst]
+    return _run_plan(ev, [ct], coeffs, relin_keys, basis, target_scale, lazy=False, batched=False)[0]
 
 
 def evaluate_polynomial_many(ev: Evaluator, cts: Sequence[Ciphertext], coeffs: Sequence[float], relin_keys: KSwitchKeys,
@@ -730,29 +709,33 @@ def evaluate_polynomial_many(ev: Evaluator, cts: Sequence[Ciphertext], coeffs: S
     (12 against 19 at degree 31).  Any other MUL runs as in evaluate_polynomial.  lazy=False gives the words of
     evaluate_polynomial per item; lazy=True gives other words (a sum relinearised once is not the sum of the parts
     relinearised one by one, only the same plaintext) at the same level and scale."""
-    from . import capi, poly
-    cts = list(cts)
+    return _run_plan(ev, list(cts), coeffs, relin_keys, basis, target_scale, lazy, batched=True)
+
+
+def _run_plan(ev: Evaluator, cts: List[Ciphertext], coeffs, relin_keys: KSwitchKeys, basis, target_scale, lazy: bool, batched: bool):
+    """THE executor of a polynomial plan, on n ciphertexts of one level and scale in lockstep.  batched: every step is one
+    batched Evaluator call over the items; else the single-item calls item by item, which one item is faster through."""
     if not cts:
         return []
     if any(c.size() != 2 for c in cts):
         raise ValueError("encrypted size must be 2")
     if any(c.parms_id() != cts[0].parms_id() or c.scale != cts[0].scale for c in cts):
         raise ValueError("evaluate_polynomial_many: the ciphertexts must share one level and one scale")
-    n = len(cts)
-    plan = poly.plan(coeffs, basis, ev.ctx.primes[:cts[0].parms_id()], cts[0].scale, target_scale)
-    deferred = plan.deferred() if lazy else {}
+    plan = _poly.plan(coeffs, basis, ev.ctx.primes[:cts[0].parms_id()], cts[0].scale, target_scale)
+    n, deferred = len(cts), plan.deferred() if lazy else {}
     producer = {plan.steps[i].dst: plan.steps[i] for i in deferred}   # slot -> the MUL that was not run
     slots: List[Optional[List[Ciphertext]]] = [None] * plan.nslots
     slots[0] = cts
     for i, st in enumerate(plan.steps):
-        if st.op == capi.POLY_MUL:
+        if st.op == _poly.MUL:
             if i in deferred:
                 continue
             As = [ev.mod_switch_to_inplace(c.copy(), st.level) for c in slots[st.a]]
             # (a square: Evaluator.multiply sees the one payload)
             Bs = As if st.a == st.b else [ev.mod_switch_to_inplace(c.copy(), st.level) for c in slots[st.b]]
-            slots[st.dst] = ev.relinearize_many_inplace(ev.multiply_many(As, Bs), relin_keys)
-        elif st.op == capi.POLY_COMBINE:
+            slots[st.dst] = ev.relinearize_many_inplace(ev.multiply_many(As, Bs), relin_keys) if batched else \
+                [ev.relinearize_inplace(ev.multiply(a, b), relin_keys) for a, b in zip(As, Bs)]
+        elif st.op == _poly.COMBINE:
             products = [(slots[producer[t.src].a], slots[producer[t.src].b], t.coef, t.wscale) for t in st.terms if t.src in producer]
             if products:
                 lin = [(slots[t.src], t.coef, t.wscale) for t in st.terms if t.src not in producer]
@@ -762,9 +745,9 @@ def evaluate_polynomial_many(ev: Evaluator, cts: Sequence[Ciphertext], coeffs: S
                 outs = [ev.scalar_combine([slots[t.src][k] for t in st.terms], [[t.coef for t in st.terms]],
                                           [t.wscale for t in st.terms], None if st.constant is None else [st.constant],
                                           scale=st.cscale, parms_id=st.level)[0] for k in range(n)]
-            slots[st.dst] = ev.rescale_to_next_many_inplace(outs)
+            slots[st.dst] = ev.rescale_to_next_many_inplace(outs) if batched else [ev.rescale_to_next_inplace(o) for o in outs]
         else:
-            slots[st.dst] = ev.add_pairs(slots[st.a], slots[st.b])
+            slots[st.dst] = ev.add_pairs(slots[st.a], slots[st.b]) if batched else [ev.add(a, b) for a, b in zip(slots[st.a], slots[st.b])]
     return slots[plan.steps[-1].dst]
 
 

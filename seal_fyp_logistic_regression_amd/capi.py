@@ -189,6 +189,19 @@ PLAIN_COMBINE_MAX_IN = 256   # HEFX_PLAIN_COMBINE_MAX_IN
 PLAIN_COMBINE_MAX_OUT = 64   # HEFX_PLAIN_COMBINE_MAX_OUT
 PLAIN_COMBINE_MAX_PTRS = 10240  # one descriptor-ring slot: m + G * m + G pointers
 
+
+def plain_combine_route(native: bool, m: int, counts, words_per_term: int) -> str:
+    """How Evaluator.plain_combine forms G sums over m inputs, counts[g] terms of words_per_term (L * N) words in output g,
+    on a backend that has hefx_plain_combine (native) or not: "grouped", "fused" or "per_output"."""
+    G = len(counts)
+    if native and len(set(counts)) == 1 and not (m >= 8 and G >= 4 and sum(counts) * words_per_term >= 1 << 23):
+        # MEASURED (profiles/dft.json, DESIGN.md): where every output has the same number of terms the sums are ONE
+        # grouped hefx_multiply_plain_sum, and on the MI355X the fused call beats that one only from 8 inputs, 4 outputs
+        # and 2^23 words of terms up; below, the same words come from the grouped call
+        return "grouped"
+    fits = m <= PLAIN_COMBINE_MAX_IN and G <= PLAIN_COMBINE_MAX_OUT and m + G * m + G <= PLAIN_COMBINE_MAX_PTRS
+    return "fused" if native and fits else "per_output"
+
 # include/hefx_bootstrap.h: the fused node of EvalMod (products, linear terms and a constant as one size-3 sum)
 _BOOTSTRAP_SIGS = {
     "hefx_product_combine": (_i, [_vp, _i, _i, _i, _pp, C.POINTER(_i), _pp, C.POINTER(_i), _vp, _i, _pp, C.POINTER(_i), _vp, _vp,
@@ -198,7 +211,12 @@ BOOTSTRAP_SYMBOLS = sorted(_BOOTSTRAP_SIGS)
 PRODUCT_COMBINE_MAX_PRODUCTS = 32  # HEFX_PRODUCT_COMBINE_MAX_PRODUCTS
 PRODUCT_COMBINE_MAX_LIN = 64       # HEFX_PRODUCT_COMBINE_MAX_LIN
 PRODUCT_COMBINE_MAX_ITEMS = 64     # HEFX_PRODUCT_COMBINE_MAX_ITEMS
-PRODUCT_COMBINE_MAX_WORDS = 10240  # one descriptor-ring slot: 2P + m + L (P + m + 1) + n (2P + m + 1) words
+PRODUCT_COMBINE_MAX_WORDS = 10240  # one descriptor-ring slot
+
+
+def product_combine_words(L: int, n: int, P: int, m: int) -> int:
+    """words of hefx_product_combine's table with a constant: strides, weights and the constant per row, n pointer records"""
+    return 2 * P + m + L * (P + m + 1) + n * (2 * P + m + 1)
 
 
 def library_path() -> str:

@@ -49,10 +49,11 @@ static int hipfail(hipError_t e, const char *what)
 // The aliasing rule of include/hefx.h (stated per entry there, as a table in INTEGRATION.md), applied before anything is
 // submitted: n outputs of out_b bytes against the call's input lists (hefx_ranges.h).  `names` are the arguments the lists
 // came from, for the message.  Engine-internal calls on disjoint workspace skip it (the `trusted` arguments below).
-// texts (optional): the entry's own words for "two outputs overlap" and "an output overlaps an input".
+// texts (optional): the entry's own words for "two outputs overlap" and "an output overlaps an input"; entry_index: the index
+// to report in place of the input's position in its list (the column form below).
 static int check_ranges(const char *entry, size_t n, uint64_t *const *outs, size_t out_b,
                         std::initializer_list<hefx_ranges::In> ins, std::initializer_list<const char *> names,
-                        const char *outputs_text = nullptr, const char *input_text = nullptr)
+                        const char *outputs_text = nullptr, const char *input_text = nullptr, long entry_index = -1)
 {
     std::pair<size_t, size_t> which{0, 0};
     const hefx_ranges::Verdict v = hefx_ranges::check(n, outs, out_b, ins, &which);
@@ -60,8 +61,18 @@ static int check_ranges(const char *entry, size_t n, uint64_t *const *outs, size
     const char *own = v == hefx_ranges::OUTPUTS_OVERLAP ? outputs_text : input_text;
     std::string msg = std::string(entry) + ": " + (own ? own : hefx_ranges::text(v));
     if (v == hefx_ranges::OUTPUT_OVERLAPS_INPUT && which.first < names.size())
-        msg += std::string(" (") + names.begin()[which.first] + ", entry " + std::to_string(which.second) + ")";
+        msg += std::string(" (") + names.begin()[which.first] + ", entry " + std::to_string(entry_index < 0 ? (long)which.second : entry_index) + ")";
     return fail(HEFX_ERR_INVALID, msg);
+}
+// The column form, for operands whose size differs from column to column: the n outputs against entry `at` of every row of
+// the [rows][width] table `name`, `bytes` each; the message names the column.  No allocation per call: one row is read in place.
+static int check_ranges_column(const char *entry, size_t n, uint64_t *const *outs, size_t out_b, const char *name,
+                               const uint64_t *const *table, size_t rows, size_t width, size_t at, size_t bytes)
+{
+    static thread_local std::vector<const uint64_t *> col;
+    if (rows > 1) col.resize(rows);
+    for (size_t i = 0; rows > 1 && i < rows; ++i) col[i] = table[i * width + at];
+    return check_ranges(entry, n, outs, out_b, {{rows > 1 ? col.data() : table + at, rows, bytes}}, {name}, nullptr, nullptr, (long)at);
 }
 // HEFX_DEBUG: the host time since the previous lap on stderr, one line per phase of a call
 struct Lap {
@@ -353,6 +364,21 @@ static int table_slice_items(int ptrs_per_item, int max_slice = 0, int group = 0
     const int items = group ? RING_SLOT_PTRS / (ptrs_per_item * group + 1) * group : RING_SLOT_PTRS / ptrs_per_item;
     return max_slice > 0 && items > max_slice ? max_slice : items;
 }
+// One table in one slot: take it, fill(h) the pinned mirror, copy `words` of it to the device, launch(d) on the device copy
+// (it answers with a HEFX_* code or with the HIP status of its launch), commit.
+static int launch_code(int rc) { return rc; }
+static int launch_code(hipError_t e) { return e == hipSuccess ? HEFX_OK : hipfail(e, "kernel launch"); }
+template <class Fill, class Launch>
+static int slot_call(hefx_context *c, hipStream_t s, size_t words, Fill fill, Launch launch)
+{
+    RingSlot r;
+    HIPCHK(ring_take(c, r));
+    fill(reinterpret_cast<u64 *>(r.h));
+    HIPCHK(hipMemcpyAsync((void *)r.d, r.h, sizeof(u64) * words, hipMemcpyHostToDevice, s));
+    if (int rc = launch_code(launch(reinterpret_cast<const u64 *>(r.d)))) return rc;
+    HIPCHK(ring_commit(c, r, s));
+    return HEFX_OK;
+}
 // fill(hp, i0, cnt) writes the table of items [i0, i0 + cnt) into the pinned mirror; run(dp, i0, cnt) launches on its
 // device copy and returns a HEFX_* code.
 template <class Fill, class Run>
@@ -362,12 +388,9 @@ static int table_slices(hefx_context *c, int n, int ptrs_per_item, hipStream_t s
     for (int i0 = 0; i0 < n; i0 += slice) {
         const int cnt = n - i0 < slice ? n - i0 : slice;
         const size_t ptrs = (size_t)ptrs_per_item * cnt + (group ? (cnt + group - 1) / group : 0);
-        RingSlot r;
-        HIPCHK(ring_take(c, r));
-        fill(r.htab(), i0, cnt);
-        HIPCHK(hipMemcpyAsync((void *)r.dtab(), r.htab(), sizeof(void *) * ptrs, hipMemcpyHostToDevice, s));
-        if (int rc = run(r.dtab(), i0, cnt)) return rc;
-        HIPCHK(ring_commit(c, r, s));
+        auto fill_slice = [&](u64 *h) { fill(reinterpret_cast<const uint64_t **>(h), i0, cnt); };
+        auto run_slice = [&](const u64 *d) { return run(reinterpret_cast<const u64 *const *>(d), i0, cnt); };
+        if (int rc = slot_call(c, s, ptrs, fill_slice, run_slice)) return rc;
     }
     return HEFX_OK;
 }
@@ -825,6 +848,20 @@ static int check_level(const hefx_context *c, int L)
 {
     // data levels use q_0..q_{L-1}; the special prime (index k-1) is never a data prime unless k == 1
     if (L < 1 || L > c->k) return fail(HEFX_ERR_INVALID, "level L out of range");
+    return HEFX_OK;
+}
+// `count` residue vectors of L words each, word j of a vector against prime j (a null array has none)
+static int check_residues(const hefx_context *c, const char *entry, const char *what, const uint64_t *values, size_t count, int L)
+{
+    for (size_t i = 0, e = values ? count * (size_t)L : 0; i < e; ++i)
+        if (values[i] >= c->primes[i % (size_t)L]) return fail(HEFX_ERR_INVALID, std::string(entry) + ": " + what + " is not below its modulus");
+    return HEFX_OK;
+}
+// operands that are read through their first L rows have at least L, and no more than the chain
+static int check_rows(const hefx_context *c, const char *entry, const char *what, const int *rows, int n, int L)
+{
+    for (int i = 0; i < n; ++i)
+        if (rows[i] < L || rows[i] > c->k) return fail(HEFX_ERR_INVALID, std::string(entry) + ": every " + what + " needs at least L rows");
     return HEFX_OK;
 }
 static int check_ks_level(const hefx_context *c, int L)
@@ -3727,22 +3764,17 @@ extern "C" int hefx_scalar_combine(hefx_context *c, int L, int size, int m, cons
     if (size < 1 || !d_in || !in_rows || !h_weights || !d_out) return fail(HEFX_ERR_INVALID, "bad scalar_combine arguments");
     for (int k = 0; k < m; ++k) {
         if (!d_in[k]) return fail(HEFX_ERR_INVALID, "null input in scalar_combine");
-        if (in_rows[k] < L || in_rows[k] > c->k) return fail(HEFX_ERR_INVALID, "scalar_combine: every input needs at least L rows");
+        if (int rc = check_rows(c, "scalar_combine", "input", in_rows + k, 1, L)) return rc;
     }
     for (int g = 0; g < G; ++g)
         if (!d_out[g]) return fail(HEFX_ERR_INVALID, "null output in scalar_combine");
-    for (size_t i = 0, n = (size_t)G * m * L; i < n; ++i)
-        if (h_weights[i] >= c->primes[i % (size_t)L]) return fail(HEFX_ERR_INVALID, "scalar_combine: a weight is not below its modulus");
-    for (size_t i = 0, n = h_consts ? (size_t)G * L : 0; i < n; ++i)
-        if (h_consts[i] >= c->primes[i % (size_t)L]) return fail(HEFX_ERR_INVALID, "scalar_combine: a constant is not below its modulus");
-    // every lane of every tile reads all inputs: no output may share a byte with any input (all its rows) or another output
+    if (int rc = check_residues(c, "scalar_combine", "a weight", h_weights, (size_t)G * m, L)) return rc;
+    if (int rc = check_residues(c, "scalar_combine", "a constant", h_consts, (size_t)G, L)) return rc;
+    // every lane of every tile reads all inputs: no output may share a byte with any input (all its rows: a table of one row,
+    // one column at a time) or another output
     const size_t row_b = (size_t)c->n * sizeof(u64), out_b = (size_t)size * L * row_b;
-    for (int k = 0; k < m; ++k) {
-        const hefx_ranges::Verdict v = hefx_ranges::check((size_t)G, d_out, out_b, {{d_in + k, 1, (size_t)size * in_rows[k] * row_b}});
-        if (v != hefx_ranges::FINE)
-            return fail(HEFX_ERR_INVALID, std::string("scalar_combine: ") + hefx_ranges::text(v) +
-                                              (v == hefx_ranges::OUTPUT_OVERLAPS_INPUT ? " (d_in, entry " + std::to_string(k) + ")" : std::string()));
-    }
+    for (int k = 0; k < m; ++k)
+        if (int rc = check_ranges_column("scalar_combine", (size_t)G, d_out, out_b, "d_in", d_in, 1, (size_t)m, (size_t)k, (size_t)size * in_rows[k] * row_b)) return rc;
     int gt = 1;
     while (gt < G && gt < 8) gt *= 2;
     while (gt > 1 && scalar_combine_table_words(L, m, gt, h_consts != nullptr) > (size_t)RING_SLOT_PTRS) gt /= 2;
@@ -3751,26 +3783,23 @@ extern "C" int hefx_scalar_combine(hefx_context *c, int L, int size, int m, cons
     hipStream_t s = (hipStream_t)stream;
     for (int g0 = 0; g0 < G; g0 += gt) {
         const int cnt = G - g0 < gt ? G - g0 : gt;
-        RingSlot r;
-        HIPCHK(ring_take(c, r));
-        u64 *t = reinterpret_cast<u64 *>(r.h);
-        const size_t words = scalar_combine_table_words(L, m, gt, h_consts != nullptr);
-        for (int k = 0; k < m; ++k) {
-            t[k] = (u64)(uintptr_t)d_in[k];
-            t[m + k] = (u64)in_rows[k] * c->n;
-        }
-        for (int g = 0; g < gt; ++g) t[2 * m + g] = g < cnt ? (u64)(uintptr_t)d_out[g0 + g] : 0;
-        u64 *wt = t + 2 * m + gt, *ct = wt + (size_t)L * m * gt;
-        for (int j = 0; j < L; ++j)
-            for (int k = 0; k < m; ++k)
-                for (int g = 0; g < gt; ++g)
-                    wt[((size_t)j * m + k) * gt + g] = g < cnt ? h_weights[((size_t)(g0 + g) * m + k) * L + j] : 0;
-        if (h_consts)
+        auto fill = [&](u64 *t) {
+            for (int k = 0; k < m; ++k) {
+                t[k] = (u64)(uintptr_t)d_in[k];
+                t[m + k] = (u64)in_rows[k] * c->n;
+            }
+            for (int g = 0; g < gt; ++g) t[2 * m + g] = g < cnt ? (u64)(uintptr_t)d_out[g0 + g] : 0;
+            u64 *wt = t + 2 * m + gt, *ct = wt + (size_t)L * m * gt;
             for (int j = 0; j < L; ++j)
-                for (int g = 0; g < gt; ++g) ct[(size_t)j * gt + g] = g < cnt ? h_consts[(size_t)(g0 + g) * L + j] : 0;
-        HIPCHK(hipMemcpyAsync((void *)r.d, t, words * sizeof(u64), hipMemcpyHostToDevice, s));
-        HIPCHK(launch_scalar_combine(c->T, L, size, m, cnt, gt, reinterpret_cast<const u64 *>(r.d), h_consts != nullptr, s));
-        HIPCHK(ring_commit(c, r, s));
+                for (int k = 0; k < m; ++k)
+                    for (int g = 0; g < gt; ++g)
+                        wt[((size_t)j * m + k) * gt + g] = g < cnt ? h_weights[((size_t)(g0 + g) * m + k) * L + j] : 0;
+            if (h_consts)
+                for (int j = 0; j < L; ++j)
+                    for (int g = 0; g < gt; ++g) ct[(size_t)j * gt + g] = g < cnt ? h_consts[(size_t)(g0 + g) * L + j] : 0;
+        };
+        auto launch = [&](const u64 *d) { return launch_scalar_combine(c->T, L, size, m, cnt, gt, d, h_consts != nullptr, s); };
+        if (int rc = slot_call(c, s, scalar_combine_table_words(L, m, gt, h_consts != nullptr), fill, launch)) return rc;
     }
     return HEFX_OK;
 }
@@ -3847,20 +3876,16 @@ extern "C" int hefx_plain_combine(hefx_context *c, int L, int m, const uint64_t 
         return rc;
     hipStream_t s = (hipStream_t)stream;
     const int gt = plain_combine_tile(G, m, (size_t)L * (c->n / 128));
-    RingSlot r;
-    HIPCHK(ring_take(c, r));
-    u64 *t = reinterpret_cast<u64 *>(r.h);
-    for (int k = 0; k < m; ++k) t[k] = (u64)(uintptr_t)d_in[k];
-    for (int g0 = 0; g0 < G; g0 += gt) {
-        u64 *ot = t + m + (size_t)(g0 / gt) * ((size_t)gt + (size_t)m * gt), *pt = ot + gt;
-        for (int g = 0; g < gt; ++g) ot[g] = g0 + g < G ? (u64)(uintptr_t)d_out[g0 + g] : 0;
-        for (int k = 0; k < m; ++k)
-            for (int g = 0; g < gt; ++g) pt[(size_t)k * gt + g] = g0 + g < G ? (u64)(uintptr_t)d_pts[(size_t)(g0 + g) * m + k] : 0;
-    }
-    HIPCHK(hipMemcpyAsync((void *)r.d, t, plain_combine_table_words(m, G, gt) * sizeof(u64), hipMemcpyHostToDevice, s));
-    HIPCHK(launch_plain_combine(c->T, L, m, G, gt, reinterpret_cast<const u64 *>(r.d), s));
-    HIPCHK(ring_commit(c, r, s));
-    return HEFX_OK;
+    auto fill = [&](u64 *t) {
+        for (int k = 0; k < m; ++k) t[k] = (u64)(uintptr_t)d_in[k];
+        for (int g0 = 0; g0 < G; g0 += gt) {
+            u64 *ot = t + m + (size_t)(g0 / gt) * ((size_t)gt + (size_t)m * gt), *pt = ot + gt;
+            for (int g = 0; g < gt; ++g) ot[g] = g0 + g < G ? (u64)(uintptr_t)d_out[g0 + g] : 0;
+            for (int k = 0; k < m; ++k)
+                for (int g = 0; g < gt; ++g) pt[(size_t)k * gt + g] = g0 + g < G ? (u64)(uintptr_t)d_pts[(size_t)(g0 + g) * m + k] : 0;
+        }
+    };
+    return slot_call(c, s, plain_combine_table_words(m, G, gt), fill, [&](const u64 *d) { return launch_plain_combine(c->T, L, m, G, gt, d, s); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3884,11 +3909,9 @@ extern "C" int hefx_product_combine(hefx_context *c, int L, int n, int P, const 
     const bool has_const = h_c != nullptr;
     if (product_combine_table_words(L, n, P, m, has_const) > (size_t)RING_SLOT_PTRS)
         return fail(HEFX_ERR_UNSUPPORTED, "product_combine: strides, weights and pointers do not fit a descriptor slot");
-    for (int p = 0; p < P; ++p)
-        if (a_rows[p] < L || a_rows[p] > c->k || b_rows[p] < L || b_rows[p] > c->k)
-            return fail(HEFX_ERR_INVALID, "product_combine: every operand needs at least L rows");
-    for (int k = 0; k < m; ++k)
-        if (lin_rows[k] < L || lin_rows[k] > c->k) return fail(HEFX_ERR_INVALID, "product_combine: every linear term needs at least L rows");
+    if (int rc = check_rows(c, "product_combine", "operand", a_rows, P, L)) return rc;
+    if (int rc = check_rows(c, "product_combine", "operand", b_rows, P, L)) return rc;
+    if (int rc = check_rows(c, "product_combine", "linear term", lin_rows, m, L)) return rc;
     for (int i = 0; i < n; ++i) {
         for (int p = 0; p < P; ++p)
             if (!d_a[(size_t)i * P + p] || !d_b[(size_t)i * P + p]) return fail(HEFX_ERR_INVALID, "null operand in product_combine");
@@ -3896,54 +3919,43 @@ extern "C" int hefx_product_combine(hefx_context *c, int L, int n, int P, const 
             if (!d_lin[(size_t)i * m + k]) return fail(HEFX_ERR_INVALID, "null linear term in product_combine");
         if (!d_out[i]) return fail(HEFX_ERR_INVALID, "null output in product_combine");
     }
-    for (size_t i = 0, e = (size_t)P * L; i < e; ++i)
-        if (h_u[i] >= c->primes[i % (size_t)L]) return fail(HEFX_ERR_INVALID, "product_combine: a weight is not below its modulus");
-    for (size_t i = 0, e = (size_t)m * L; i < e; ++i)
-        if (h_w[i] >= c->primes[i % (size_t)L]) return fail(HEFX_ERR_INVALID, "product_combine: a weight is not below its modulus");
-    for (int j = 0; has_const && j < L; ++j)
-        if (h_c[j] >= c->primes[j]) return fail(HEFX_ERR_INVALID, "product_combine: a constant is not below its modulus");
+    if (int rc = check_residues(c, "product_combine", "a weight", h_u, (size_t)P, L)) return rc;
+    if (int rc = check_residues(c, "product_combine", "a weight", h_w, (size_t)m, L)) return rc;
+    if (int rc = check_residues(c, "product_combine", "a constant", h_c, 1, L)) return rc;
     // every lane reads all operands of its item, and the items run side by side: no output may share a byte with an operand
     // or a linear term of ANY item (all its rows) or with another output.  Operand p has its own size: one column at a time
     const size_t row_b = (size_t)c->n * sizeof(u64), out_b = 3 * (size_t)L * row_b;
-    std::vector<const uint64_t *> col((size_t)n);
-    auto column = [&](const uint64_t *const *ptrs, int width, int at, int rows, const char *name) -> int {
-        for (int i = 0; i < n; ++i) col[(size_t)i] = ptrs[(size_t)i * width + at];
-        const hefx_ranges::Verdict v = hefx_ranges::check((size_t)n, d_out, out_b, {{col.data(), (size_t)n, 2 * (size_t)rows * row_b}});
-        if (v == hefx_ranges::FINE) return HEFX_OK;
-        return fail(HEFX_ERR_INVALID, std::string("product_combine: ") + hefx_ranges::text(v) +
-                                          (v == hefx_ranges::OUTPUT_OVERLAPS_INPUT ? std::string(" (") + name + ", entry " + std::to_string(at) + ")" : std::string()));
+    auto column = [&](const char *name, const uint64_t *const *ptrs, int width, int at, int rows) {
+        return check_ranges_column("product_combine", (size_t)n, d_out, out_b, name, ptrs, (size_t)n, (size_t)width, (size_t)at, 2 * (size_t)rows * row_b);
     };
     for (int p = 0; p < P; ++p) {
-        if (int rc = column(d_a, P, p, a_rows[p], "d_a")) return rc;
-        if (int rc = column(d_b, P, p, b_rows[p], "d_b")) return rc;
+        if (int rc = column("d_a", d_a, P, p, a_rows[p])) return rc;
+        if (int rc = column("d_b", d_b, P, p, b_rows[p])) return rc;
     }
     for (int k = 0; k < m; ++k)
-        if (int rc = column(d_lin, m, k, lin_rows[k], "d_lin")) return rc;
+        if (int rc = column("d_lin", d_lin, m, k, lin_rows[k])) return rc;
     hipStream_t s = (hipStream_t)stream;
-    RingSlot r;
-    HIPCHK(ring_take(c, r));
-    u64 *t = reinterpret_cast<u64 *>(r.h);
-    for (int p = 0; p < P; ++p) {
-        t[p] = (u64)a_rows[p] * c->n;
-        t[P + p] = (u64)b_rows[p] * c->n;
-    }
-    for (int k = 0; k < m; ++k) t[2 * P + k] = (u64)lin_rows[k] * c->n;
-    u64 *ut = t + 2 * P + m, *wt = ut + (size_t)L * P, *ct = wt + (size_t)L * m, *rec = ct + (has_const ? L : 0);
-    for (int j = 0; j < L; ++j) {
-        for (int p = 0; p < P; ++p) ut[(size_t)j * P + p] = h_u[(size_t)p * L + j];
-        for (int k = 0; k < m; ++k) wt[(size_t)j * m + k] = h_w[(size_t)k * L + j];
-        if (has_const) ct[j] = h_c[j];
-    }
-    for (int i = 0; i < n; ++i, rec += 2 * P + m + 1) {
+    auto fill = [&](u64 *t) {
         for (int p = 0; p < P; ++p) {
-            rec[p] = (u64)(uintptr_t)d_a[(size_t)i * P + p];
-            rec[P + p] = (u64)(uintptr_t)d_b[(size_t)i * P + p];
+            t[p] = (u64)a_rows[p] * c->n;
+            t[P + p] = (u64)b_rows[p] * c->n;
         }
-        for (int k = 0; k < m; ++k) rec[2 * P + k] = (u64)(uintptr_t)d_lin[(size_t)i * m + k];
-        rec[2 * P + m] = (u64)(uintptr_t)d_out[i];
-    }
-    HIPCHK(hipMemcpyAsync((void *)r.d, t, product_combine_table_words(L, n, P, m, has_const) * sizeof(u64), hipMemcpyHostToDevice, s));
-    HIPCHK(launch_product_combine(c->T, L, n, P, m, reinterpret_cast<const u64 *>(r.d), has_const, s));
-    HIPCHK(ring_commit(c, r, s));
-    return HEFX_OK;
+        for (int k = 0; k < m; ++k) t[2 * P + k] = (u64)lin_rows[k] * c->n;
+        u64 *ut = t + 2 * P + m, *wt = ut + (size_t)L * P, *ct = wt + (size_t)L * m, *rec = ct + (has_const ? L : 0);
+        for (int j = 0; j < L; ++j) {
+            for (int p = 0; p < P; ++p) ut[(size_t)j * P + p] = h_u[(size_t)p * L + j];
+            for (int k = 0; k < m; ++k) wt[(size_t)j * m + k] = h_w[(size_t)k * L + j];
+            if (has_const) ct[j] = h_c[j];
+        }
+        for (int i = 0; i < n; ++i, rec += 2 * P + m + 1) {
+            for (int p = 0; p < P; ++p) {
+                rec[p] = (u64)(uintptr_t)d_a[(size_t)i * P + p];
+                rec[P + p] = (u64)(uintptr_t)d_b[(size_t)i * P + p];
+            }
+            for (int k = 0; k < m; ++k) rec[2 * P + k] = (u64)(uintptr_t)d_lin[(size_t)i * m + k];
+            rec[2 * P + m] = (u64)(uintptr_t)d_out[i];
+        }
+    };
+    return slot_call(c, s, product_combine_table_words(L, n, P, m, has_const), fill,
+                     [&](const u64 *d) { return launch_product_combine(c->T, L, n, P, m, d, has_const, s); });
 }

@@ -10,6 +10,20 @@ from typing import List,  Optional, Sequence
 import numpy as np
 
 from . import capi
+from .capi import ptr_array, u32_array  # (the C tables algorithms._native_args builds: it reaches the C-ABI through this layer)
+
+
+def _residues(values, shape, refusal: str) -> np.ndarray:
+    """residues as a C entry reads them: contiguous uint64 of `shape` (a leading None: any extent), else ValueError(refusal)"""
+    a = np.ascontiguousarray(values, dtype=np.uint64)
+    if a.ndim != len(shape) or a.shape[1:] != shape[1:] or shape[0] not in (None, a.shape[0]):
+        raise ValueError(refusal)
+    return a
+
+
+def _c_ints(values):
+    """a C int array (of one element for an empty list: ctypes has no empty array to point at)"""
+    return (C.c_int * max(len(values), 1))(*[int(v) for v in values])
 
 
 class DeviceArray:
@@ -616,20 +630,16 @@ class Engine:
         """outs[g] = sum_k weights[g][k] * ins[k] + consts[g] over the first L rows of every input, one pass over the inputs
         (hefx_scalar_combine).  ins[k]: [size][in_rows[k]][N], in_rows[k] >= L; weights: [G][m][L] residues (uint64);
         consts: [G][L] residues or None.  Returns the G outputs, [size][L][N] each."""
-        w = np.ascontiguousarray(weights, dtype=np.uint64)
         m = len(ins)
-        if w.ndim != 3 or w.shape[1] != m or w.shape[2] != L or len(in_rows) != m:
-            raise ValueError("scalar_combine: weights must be [G][m][L], one row count per input")
+        refusal = "scalar_combine: weights must be [G][m][L], one row count per input"
+        w = _residues(weights, (None, m, L), refusal)
+        if len(in_rows) != m:
+            raise ValueError(refusal)
         G = w.shape[0]
-        cst = None
-        if consts is not None:
-            cst = np.ascontiguousarray(consts, dtype=np.uint64)
-            if cst.shape != (G, L):
-                raise ValueError("scalar_combine: consts must be [G][L]")
+        cst = None if consts is None else _residues(consts, (G, L), "scalar_combine: consts must be [G][L]")
         outs = outs if outs is not None else self.empty_many(G, (size, L, self.N))
-        rows = (C.c_int * m)(*[int(r) for r in in_rows])
         capi.check(capi.lib().hefx_scalar_combine(
-            self._h, L, size, m, capi.ptr_array([x.ptr for x in ins]), rows, G, w.ctypes.data,
+            self._h, L, size, m, capi.ptr_array([x.ptr for x in ins]), _c_ints(in_rows), G, w.ctypes.data,
             cst.ctypes.data if cst is not None else None, capi.ptr_array([o.ptr for o in outs]), stream))
         return outs
 
@@ -659,25 +669,14 @@ class Engine:
         if len(Bs) != n or len(lins) != n or len(b_rows) != P or any(len(r) != P for r in As) or any(len(r) != P for r in Bs) \
                 or any(len(r) != m for r in lins):
             raise ValueError("product_combine: every item needs P operand pairs and m linear terms")
-        uu = np.ascontiguousarray(u, dtype=np.uint64)
-        if uu.shape != (P, L):
-            raise ValueError("product_combine: u must be [P][L]")
-        ww = None
-        if m:
-            ww = np.ascontiguousarray(w, dtype=np.uint64)
-            if ww.shape != (m, L):
-                raise ValueError("product_combine: w must be [m][L]")
-        cc = None
-        if c is not None:
-            cc = np.ascontiguousarray(c, dtype=np.uint64)
-            if cc.shape != (L,):
-                raise ValueError("product_combine: c must be [L]")
+        uu = _residues(u, (P, L), "product_combine: u must be [P][L]")
+        ww = _residues(w, (m, L), "product_combine: w must be [m][L]") if m else None
+        cc = None if c is None else _residues(c, (L,), "product_combine: c must be [L]")
         outs = outs if outs is not None else self.empty_many(n, (3, L, self.N))
-        ints = lambda v: (C.c_int * max(len(v), 1))(*[int(x) for x in v])
         capi.check(capi.lib().hefx_product_combine(
-            self._h, L, n, P, capi.ptr_array([x.ptr for r in As for x in r]), ints(a_rows),
-            capi.ptr_array([x.ptr for r in Bs for x in r]), ints(b_rows), uu.ctypes.data, m,
-            capi.ptr_array([x.ptr for r in lins for x in r]) if m else None, ints(lin_rows) if m else None,
+            self._h, L, n, P, capi.ptr_array([x.ptr for r in As for x in r]), _c_ints(a_rows),
+            capi.ptr_array([x.ptr for r in Bs for x in r]), _c_ints(b_rows), uu.ctypes.data, m,
+            capi.ptr_array([x.ptr for r in lins for x in r]) if m else None, _c_ints(lin_rows) if m else None,
             ww.ctypes.data if m else None, cc.ctypes.data if cc is not None else None, capi.ptr_array([o.ptr for o in outs]), stream))
         return outs
 

@@ -9,6 +9,8 @@ import math
 import struct
 from typing import List, NamedTuple, Optional, Sequence
 
+import numpy as np
+
 from . import capi
 
 
@@ -31,6 +33,15 @@ def weight_residue(value: float, scale: float, q: int) -> int:
     return (q - r) % q if x < 0 else r
 
 
+def weight_residues(values, scales, primes: Sequence[int]):
+    """[len(values)][len(primes)] uint64: weight_residue of values[i] at scales[i]"""
+    rows = [[weight_residue(v, s, q) for q in primes] for v, s in zip(values, scales)]
+    return np.array(rows, dtype=np.uint64) if rows else np.zeros((0, len(primes)), dtype=np.uint64)
+
+
+MUL, COMBINE, ADD = capi.POLY_MUL, capi.POLY_COMBINE, capi.POLY_ADD   # Step.op
+
+
 class Term(NamedTuple):
     src: int
     coef: float
@@ -38,7 +49,7 @@ class Term(NamedTuple):
 
 
 class Step(NamedTuple):
-    op: int              # capi.POLY_MUL / POLY_COMBINE / POLY_ADD
+    op: int              # MUL / COMBINE / ADD
     dst: int
     a: int               # MUL / ADD: operand slots (COMBINE: see terms)
     b: int
@@ -55,7 +66,7 @@ class Plan(NamedTuple):
 
     @property
     def muls(self) -> int:
-        return sum(1 for s in self.steps if s.op == capi.POLY_MUL)
+        return sum(1 for s in self.steps if s.op == MUL)
 
     def deferred(self) -> dict:
         """{index of a MUL step: index of the COMBINE it can be deferred into}: the MULs whose result is read exactly once,
@@ -63,13 +74,13 @@ class Plan(NamedTuple):
         its consumer's sum (Evaluator.product_combine) and the sum be relinearised once."""
         readers: dict = {}
         for i, s in enumerate(self.steps):
-            for src in ([t.src for t in s.terms] if s.op == capi.POLY_COMBINE else [s.a, s.b]):
+            for src in ([t.src for t in s.terms] if s.op == COMBINE else [s.a, s.b]):
                 readers.setdefault(src, []).append(i)
         final = self.steps[-1].dst
         out = {}
         for i, s in enumerate(self.steps):
             r = readers.get(s.dst, [])
-            if s.op == capi.POLY_MUL and s.dst != final and len(r) == 1 and self.steps[r[0]].op == capi.POLY_COMBINE:
+            if s.op == MUL and s.dst != final and len(r) == 1 and self.steps[r[0]].op == COMBINE:
                 out[i] = r[0]
         return out
 
@@ -85,7 +96,7 @@ class Plan(NamedTuple):
     @property
     def result_level(self) -> int:
         last = self.steps[-1]
-        return last.level - 1 if last.op == capi.POLY_COMBINE else last.level
+        return last.level - 1 if last.op == COMBINE else last.level
 
 
 def plan(coeffs: Sequence[float], basis: str, primes: Sequence[int], in_scale: float,
@@ -110,7 +121,7 @@ def plan(coeffs: Sequence[float], basis: str, primes: Sequence[int], in_scale: f
     capi.check(f(*args, steps, ns.value, C.byref(ns), terms, nt.value, C.byref(nt), C.byref(nsl)))
     out = []
     for s in steps:
-        tms = tuple(Term(t.src, t.coef, t.wscale) for t in terms[s.a:s.a + s.b]) if s.op == capi.POLY_COMBINE else ()
+        tms = tuple(Term(t.src, t.coef, t.wscale) for t in terms[s.a:s.a + s.b]) if s.op == COMBINE else ()
         out.append(Step(s.op, s.dst, s.a, s.b, s.level, tms, s.constant if s.has_const else None, s.cscale, s.scale))
     return Plan(out, nsl.value)
 
@@ -119,9 +130,9 @@ def format_plan(p: Plan) -> str:
     """the text drivers/poly_plan_selftest.cpp prints for the same plan, line for line"""
     lines = ["slots %d steps %d" % (p.nslots, len(p.steps))]
     for s in p.steps:
-        if s.op == capi.POLY_MUL:
+        if s.op == MUL:
             lines.append("MUL %d = %d * %d level %d scale %.17g" % (s.dst, s.a, s.b, s.level, s.scale))
-        elif s.op == capi.POLY_ADD:
+        elif s.op == ADD:
             lines.append("ADD %d = %d + %d level %d scale %.17g" % (s.dst, s.a, s.b, s.level, s.scale))
         else:
             t = " ".join("(%d %.17g %.17g)" % (t.src, t.coef, t.wscale) for t in s.terms)

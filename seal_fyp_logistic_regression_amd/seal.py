@@ -16,7 +16,9 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
+from . import capi
 from .engine import Engine
+from .poly import weight_residues
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1148,7 +1150,6 @@ class Evaluator:
         cts[0].scale * wscales[0]; consts: [G] floats encoded at S, or None.
         The words and the checks of the op-by-op sequence -- mod_switch_to, encode, multiply_plain per term, add_many,
         add_plain -- from ONE pass over the inputs where the backend has hefx_scalar_combine, else from that sequence."""
-        from .poly import weight_residue
         cts = list(cts)
         W = np.atleast_2d(np.asarray(weights, dtype=np.float64))
         m, G = len(cts), W.shape[0]
@@ -1160,39 +1161,13 @@ class Evaluator:
         L = int(parms_id) if parms_id is not None else min(c.parms_id() for c in cts)
         size = cts[0].size()
         S = float(scale) if scale is not None else cts[0].scale * float(wscales[0])
-        for c, ws in zip(cts, wscales):
-            if c.parms_id() < L:
-                raise ValueError("cannot switch to higher level modulus")
-            if c.size() != size:
-                raise ValueError("add_many: mixed sizes are not supported by the fused reduction")
-            self._check_scale(float(ws), L)
-            self._check_scale(c.scale * float(ws), L)
-            if not self._close(S, c.scale * float(ws)):
-                raise ValueError("scale mismatch")
-        self._check_scale(S, L)
-        q = self.ctx.primes[:L]
-        wres = np.empty((G, m, L), dtype=np.uint64)
-        for g in range(G):
-            for k in range(m):
-                wres[g, k] = [weight_residue(W[g, k], wscales[k], p) for p in q]
-                if _c_round(float(W[g, k]) * float(wscales[k])) == 0:
-                    raise RuntimeError("result ciphertext is transparent")  # multiply_plain by the zero plaintext
-        cres = None if cvals is None else np.array([[weight_residue(v, S, p) for p in q] for v in cvals], dtype=np.uint64)
-        rows = [c.parms_id() for c in cts]
+        wres = self._weighted_terms(L, S, size, [(([c],), w, float(ws)) for c, w, ws in zip(cts, W.T.tolist(), wscales)])
+        cres = None if cvals is None else weight_residues(cvals, [S] * G, self.ctx.primes[:L])
         native = getattr(self.be, "scalar_combine", None)
-        if native is not None and m <= 256 and G <= 16:
-            datas = native(L, size, [c.data for c in cts], rows, wres, cres)
+        if native is not None and m <= capi.COMBINE_MAX_IN and G <= capi.COMBINE_MAX_OUT:
+            datas = native(L, size, [c.data for c in cts], [c.parms_id() for c in cts], wres, cres)
         else:
-            N, be = self.ctx.N, self.be
-            low = [c.data if r == L else be.mod_drop(r, L, size, c.data) for c, r in zip(cts, rows)]
-            datas = []
-            for g in range(G):
-                prods = [be.multiply_plain(L, size, x, be.from_host(np.repeat(wres[g, k][:, None], N, axis=1)))
-                         for k, x in enumerate(low)]
-                acc = be.add_many(L, size, prods)
-                if cres is not None:
-                    acc = be.add_plain(L, size, acc, be.from_host(np.repeat(cres[g][:, None], N, axis=1)))
-                datas.append(acc)
+            datas = [self._combine_composed(L, size, [], cts, None, wres[g], None if cres is None else cres[g]) for g in range(G)]
         return [Ciphertext()._set(d, size, L, S) for d in datas]
 
     def product_combine(self, products, lin=(), const: Optional[float] = None, scale: Optional[float] = None,
@@ -1208,7 +1183,6 @@ class Evaluator:
         The words and the checks of the op-by-op sequence -- mod_switch_to, multiply per product, encode and multiply_plain per
         term, add_many, add, add_plain -- from ONE pass over the operands where the backend has hefx_product_combine, else
         from that sequence."""
-        from .poly import weight_residue
         products = [(list(a), list(b), float(cf), float(ws)) for a, b, cf, ws in products]
         lin = [(list(cts), float(cf), float(ws)) for cts, cf, ws in lin]
         P, m = len(products), len(lin)
@@ -1221,70 +1195,75 @@ class Evaluator:
         L = int(parms_id) if parms_id is not None else min(x.parms_id() for x in everyone)
         a0, b0, _, ws0 = products[0]
         S = float(scale) if scale is not None else a0[0].scale * b0[0].scale * ws0
-        for a, b, _, ws in products:
-            for x, y in zip(a, b):
-                if x.parms_id() < L or y.parms_id() < L:
-                    raise ValueError("cannot switch to higher level modulus")
-                if x.size() != 2 or y.size() != 2:
-                    raise ValueError("multiply: only size-2 operands are supported (all reference call sites)")
-                if x.parms_id() != a[0].parms_id() or y.parms_id() != b[0].parms_id():
-                    raise ValueError("encrypted1 and encrypted2 parameter mismatch")
-                self._check_scale(x.scale * y.scale, L)
-                self._check_scale(ws, L)
-                self._check_scale(x.scale * y.scale * ws, L)
-                if not self._close(S, x.scale * y.scale * ws):
-                    raise ValueError("scale mismatch")
-        for cts, _, ws in lin:
-            for x in cts:
-                if x.parms_id() < L:
-                    raise ValueError("cannot switch to higher level modulus")
-                if x.size() != 2:
-                    raise ValueError("add_many: mixed sizes are not supported by the fused reduction")
-                if x.parms_id() != cts[0].parms_id():
-                    raise ValueError("encrypted1 and encrypted2 parameter mismatch")
-                self._check_scale(ws, L)
-                self._check_scale(x.scale * ws, L)
-                if not self._close(S, x.scale * ws):
-                    raise ValueError("scale mismatch")
-        self._check_scale(S, L)
-        q = self.ctx.primes[:L]
-        for cf, ws in [(cf, ws) for _, _, cf, ws in products] + [(cf, ws) for _, cf, ws in lin]:
-            if _c_round(cf * ws) == 0:
-                raise RuntimeError("result ciphertext is transparent")  # multiply_plain by the zero plaintext
-        ures = np.array([[weight_residue(cf, ws, p) for p in q] for _, _, cf, ws in products], dtype=np.uint64).reshape(P, L)
-        wres = np.array([[weight_residue(cf, ws, p) for p in q] for _, cf, ws in lin], dtype=np.uint64).reshape(m, L)
-        cres = None if const is None else np.array([weight_residue(const, S, p) for p in q], dtype=np.uint64)
-        a_rows, b_rows = [a[0].parms_id() for a, _, _, _ in products], [b[0].parms_id() for _, b, _, _ in products]
-        lin_rows = [cts[0].parms_id() for cts, _, _ in lin]
+        terms = [((a, b), [cf], ws) for a, b, cf, ws in products] + [((cts,), [cf], ws) for cts, cf, ws in lin]
+        res = self._weighted_terms(L, S, 2, terms)[0]
+        ures, wres = res[:P], res[P:]
+        cres = None if const is None else weight_residues([const], [S], self.ctx.primes[:L])[0]
         native = getattr(self.be, "product_combine", None)
-        words = 2 * P + m + L * (P + m + 1) + n * (2 * P + m + 1)
-        if native is not None and P <= 32 and m <= 64 and n <= 64 and words <= 10240:
-            datas = native(L, [[a[i].data for a, _, _, _ in products] for i in range(n)], a_rows,
-                           [[b[i].data for _, b, _, _ in products] for i in range(n)], b_rows, ures,
-                           [[cts[i].data for cts, _, _ in lin] for i in range(n)], lin_rows, wres, cres)
+        if native is not None and P <= capi.PRODUCT_COMBINE_MAX_PRODUCTS and m <= capi.PRODUCT_COMBINE_MAX_LIN \
+                and n <= capi.PRODUCT_COMBINE_MAX_ITEMS and capi.product_combine_words(L, n, P, m) <= capi.PRODUCT_COMBINE_MAX_WORDS:
+            datas = native(L, [[a[i].data for a, _, _, _ in products] for i in range(n)], [a[0].parms_id() for a, _, _, _ in products],
+                           [[b[i].data for _, b, _, _ in products] for i in range(n)], [b[0].parms_id() for _, b, _, _ in products], ures,
+                           [[cts[i].data for cts, _, _ in lin] for i in range(n)], [cts[0].parms_id() for cts, _, _ in lin], wres, cres)
         else:
-            datas = [self._product_combine_composed(L, [(a[i], b[i]) for a, b, _, _ in products], [cts[i] for cts, _, _ in lin],
-                                                    ures, wres, cres) for i in range(n)]
+            datas = [self._combine_composed(L, 2, [(a[i], b[i]) for a, b, _, _ in products], [cts[i] for cts, _, _ in lin],
+                                            ures, wres, cres) for i in range(n)]
         return [Ciphertext()._set(d, 3, L, S) for d in datas]
 
-    def _product_combine_composed(self, L, pairs, lins, ures, wres, cres):
-        """one item of product_combine op by op: mod_drop, multiply, multiply_plain by the constant polynomial of each weight
-        at size 3 / size 2, add_many per size, the size-2 sum added into the first two polynomials, add_plain"""
+    def _weighted_terms(self, L: int, S: float, size: int, terms) -> np.ndarray:
+        """THE check of scalar weights times ciphertexts, or times products of two, summed at level L and scale S.  terms[t] =
+        (factors, weights, wscale): factors is (cts,) for a linear term of `size` polynomials or (a, b) for a product of two
+        size-2 operands, each a list over the items that run in lockstep; weights are the G scalars of the G outputs, weight g
+        the scalar plaintext encode(weights[g], wscale).  Term by term and item by item, in the order of the op-by-op sequence
+        (mod_switch_to, multiply, encode, multiply_plain, add_many): level not below L; size; one level per factor; the bounds
+        of the product's scale, of wscale and of the term's scale; closeness to S.  Then S itself, then transparency output by
+        output.  Returns the residues of the weights, [G][len(terms)][L]."""
+        check_scale = self._check_scale
+        for factors, _, ws in terms:
+            a, b = factors[0], factors[-1]   # (a linear term: its one factor stands in both places)
+            product = len(factors) == 2
+            need, size_text = (2, "multiply: only size-2 operands are supported (all reference call sites)") if product \
+                else (size, "add_many: mixed sizes are not supported by the fused reduction")
+            la, lb = a[0]._parms_id, b[0]._parms_id
+            for x, y in zip(a, b):
+                if x._parms_id < L or y._parms_id < L:
+                    raise ValueError("cannot switch to higher level modulus")
+                if x._size != need or y._size != need:
+                    raise ValueError(size_text)
+                if x._parms_id != la or y._parms_id != lb:
+                    raise ValueError("encrypted1 and encrypted2 parameter mismatch")
+                s = x._scale
+                if product:
+                    s = s * y._scale
+                    check_scale(s, L)
+                check_scale(ws, L)
+                check_scale(s * ws, L)
+                if not self._close(S, s * ws):
+                    raise ValueError("scale mismatch")
+        self._check_scale(S, L)
+        G = len(terms[0][1])
+        for g in range(G):
+            for _, w, ws in terms:
+                if _c_round(w[g] * ws) == 0:
+                    raise RuntimeError("result ciphertext is transparent")  # multiply_plain by the zero plaintext
+        flat = weight_residues([w[g] for g in range(G) for _, w, _ in terms], [ws for _, _, ws in terms] * G, self.ctx.primes[:L])
+        return flat.reshape(G, len(terms), L)
+
+    def _combine_composed(self, L, size, pairs, lins, ures, wres, cres):
+        """one output of scalar_combine (no pairs) or one item of product_combine op by op: mod_drop, multiply, multiply_plain
+        by the constant polynomial of each weight at size 3 / `size`, add_many per size, the sum of the linear terms added
+        into the first polynomials of the products' sum, add_plain"""
         N, be = self.ctx.N, self.be
         const_poly = lambda res: be.from_host(np.repeat(np.asarray(res, dtype=np.uint64)[:, None], N, axis=1))
-        low = lambda x: x.data if x.parms_id() == L else be.mod_drop(x.parms_id(), L, 2, x.data)
-        terms3 = []
-        for p, (a, b) in enumerate(pairs):
-            da = low(a)
-            t = be.square(L, da) if a.data is b.data else be.multiply(L, da, low(b))
-            terms3.append(be.multiply_plain(L, 3, t, const_poly(ures[p])))
-        acc = terms3[0] if len(terms3) == 1 else be.add_many(L, 3, terms3)
+        low = lambda x: x.data if x.parms_id() == L else be.mod_drop(x.parms_id(), L, x.size(), x.data)
+        total = lambda sz, terms: terms[0] if len(terms) == 1 else be.add_many(L, sz, terms)
+        tensor = lambda a, b: be.square(L, low(a)) if a.data is b.data else be.multiply(L, low(a), low(b))
+        acc = total(3, [be.multiply_plain(L, 3, tensor(a, b), const_poly(ures[p])) for p, (a, b) in enumerate(pairs)]) if pairs else None
         if lins:
-            terms2 = [be.multiply_plain(L, 2, low(x), const_poly(wres[k])) for k, x in enumerate(lins)]
-            lin2 = terms2[0] if len(terms2) == 1 else be.add_many(L, 2, terms2)
-            acc = self._addsub(Ciphertext()._set(acc, 3, L, 1.0), Ciphertext()._set(lin2, 2, L, 1.0), False).data
+            lin = total(size, [be.multiply_plain(L, size, low(x), const_poly(wres[k])) for k, x in enumerate(lins)])
+            acc = lin if acc is None else self._addsub(Ciphertext()._set(acc, 3, L, 1.0), Ciphertext()._set(lin, size, L, 1.0), False).data
         if cres is not None:
-            acc = be.add_plain(L, 3, acc, const_poly(cres))
+            acc = be.add_plain(L, 3 if pairs else size, acc, const_poly(cres))
         return acc
 
     def mod_raise(self, ct: Ciphertext, parms_id: Optional[int] = None) -> Ciphertext:
@@ -1338,18 +1317,13 @@ class Evaluator:
         if any(all(p is None for p in r) for r in rows):
             raise ValueError("plain_combine: an output has no term")
         scale = self._plain_product_scale(L, ct_scale, [p for r in rows for p in r if p is not None], L)
-        native = getattr(self.be, "plain_combine", None)
-        G = len(rows)
         counts = [sum(p is not None for p in r) for r in rows]
-        grouped = getattr(self.be, "multiply_plain_sum", None) if native is not None and len(set(counts)) == 1 else None
-        if grouped is not None and not (m >= 8 and G >= 4 and sum(counts) * L * self.ctx.N >= 1 << 23):
-            # MEASURED (profiles/dft.json): where every output has the same number of terms the sums are ONE
-            # grouped hefx_multiply_plain_sum, and on the MI355X the fused call beats that one only from 8 inputs, 4 outputs
-            # and 2^23 words of terms up; below, the same words come from the grouped call
-            datas = grouped(L, 2, [c.data for r in rows for c, p in zip(cts, r) if p is not None],
-                            [p.data for r in rows for p in r if p is not None], counts[0])
-        elif native is not None and m <= 256 and G <= 64 and m + G * m + G <= 10240:
-            datas = native(L, [c.data for c in cts], [[None if p is None else p.data for p in r] for r in rows])
+        route = capi.plain_combine_route(getattr(self.be, "plain_combine", None) is not None, m, counts, L * self.ctx.N)
+        if route == "grouped":
+            datas = self.be.multiply_plain_sum(L, 2, [c.data for r in rows for c, p in zip(cts, r) if p is not None],
+                                               [p.data for r in rows for p in r if p is not None], counts[0])
+        elif route == "fused":
+            datas = self.be.plain_combine(L, [c.data for c in cts], [[None if p is None else p.data for p in r] for r in rows])
         else:
             datas = [self.be.multiply_plain_sum(L, 2, [c.data for c, p in zip(cts, r) if p is not None],
                                                 [p.data for p in r if p is not None])[0] for r in rows]

@@ -222,6 +222,47 @@ def test_refusals_leave_the_outputs_alone():
                           outs=[e.empty(3, L, N) for _ in range(65)])
 
 
+def test_of_two_faults_the_one_checked_first_is_reported():
+    """hefx_product_combine checks its arguments in one fixed order: of two faults in one call the message is that of the
+    check that stands first in the entry.  Every operand is a window of one buffer, which no refused call may touch."""
+    from types import SimpleNamespace
+    N, primes, L, P, m, n = 1024, base_primes(), 2, 2, 2, 2
+    e = engine(N, primes)
+    rows = L + 1
+    blk = 2 * rows * N                                               # words of an operand, and of an output: 3 L N
+    pool = e.to_device(np.random.default_rng(12).integers(0, 1 << 40, (14 * blk,), dtype=np.uint64))
+    before = pool.download()
+    table = lambda first: [[pool.view((first + 2 * i + p) * blk, (2, rows, N)) for p in range(2)] for i in range(n)]
+    dA, dB, dL = table(0), table(4), table(8)                        # operand (i, p) of A is block 2 i + p, of B 4 + 2 i + p, ...
+    outs = [pool.view((12 + i) * blk, (3, L, N)) for i in range(n)]
+    on = lambda block, off=0: pool.view(block * blk + off, (3, L, N))
+    null = SimpleNamespace(ptr=None)
+    ok, few = [rows] * 2, [rows, L - 1]
+    ones, c = np.ones((2, L), dtype=np.uint64), np.zeros(L, dtype=np.uint64)
+    bad, c_bad = ones.copy(), c.copy()
+    bad[1, 1], c_bad[1] = primes[1], primes[1]
+    cases = [
+        ("product_combine: every operand needs at least L rows", dict(ar=few, u=bad)),
+        ("product_combine: every operand needs at least L rows", dict(lr=[L - 1, rows], br=few)),
+        ("product_combine: every operand needs at least L rows", dict(ar=few, dB=[[dB[0][0], null], dB[1]])),
+        ("product_combine: every linear term needs at least L rows", dict(lr=[L - 1, rows], w=bad)),
+        ("null linear term in product_combine", dict(dL=[dL[0], [null, dL[1][1]]], w=bad)),
+        ("product_combine: a weight is not below its modulus", dict(u=bad, c=c_bad)),
+        ("product_combine: a weight is not below its modulus", dict(w=bad, c=c_bad)),
+        ("product_combine: a constant is not below its modulus", dict(c=c_bad, outs=[outs[0], on(1)])),
+        ("product_combine: an output overlaps an input (d_b, entry 0)", dict(outs=[on(4 + 2), on(1)])),
+        ("product_combine: an output overlaps an input (d_a, entry 1)", dict(outs=[on(8), on(3)])),
+        ("product_combine: two outputs overlap", dict(outs=[on(0), on(0, 2)])),
+    ]
+    for text, kw in cases:
+        with pytest.raises(ValueError) as err:
+            e.product_combine(L, kw.get("dA", dA), kw.get("ar", ok), kw.get("dB", dB), kw.get("br", ok), kw.get("u", ones),
+                              kw.get("dL", dL), kw.get("lr", ok), kw.get("w", ones), kw.get("c", c), outs=kw.get("outs", outs))
+        assert str(err.value) == text
+    e.sync()
+    assert np.array_equal(pool.download(), before)
+
+
 # ---- asynchrony ------------------------------------------------------------------------------------------------------------
 def test_returns_while_its_stream_is_shut_and_keeps_no_host_pointer():
     from tests.hip_stream_gate import Stream

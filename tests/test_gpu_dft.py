@@ -222,6 +222,37 @@ def test_refusals_leave_the_outputs_alone():
         assert np.array_equal(o.download(), j)
 
 
+def test_of_two_faults_the_one_checked_first_is_reported():
+    """hefx_plain_combine checks its arguments in one fixed order: of two faults in one call the message is that of the
+    check that stands first in the entry.  Every operand is a window of one buffer, which no refused call may touch."""
+    N, primes, L, m, G = 1024, base_primes(), 2, 2, 2
+    e = engine(N, primes)
+    blk = 2 * L * N                                                  # words of an input and of an output; a plaintext is half
+    pool = e.to_device(np.random.default_rng(12).integers(0, 1 << 40, (6 * blk,), dtype=np.uint64))
+    before = pool.download()
+    ins = [pool.view(k * blk, (2, L, N)) for k in range(m)]
+    pts = [pool.view(2 * blk + k * (blk // 2), (L, N)) for k in range(4)]
+    outs = [pool.view((4 + g) * blk, (2, L, N)) for g in range(G)]
+    on = lambda word: pool.view(word, (2, L, N))
+    null = SimpleNamespace(ptr=None)
+    full, holes = [pts[:2], pts[2:]], [[None, None], pts[2:]]
+    cases = [
+        ("plain_combine: an output has no term", ins, holes, [outs[0], null]),
+        ("null output in plain_combine", ins, [pts[:2], [None, None]], [null, outs[1]]),
+        ("null input in plain_combine", [ins[0], null], holes, outs),
+        ("plain_combine: G out of range", [ins[0], null], [pts[:2]] * 65, [outs[0]] * 65),
+        ("plain_combine: an output overlaps an input (d_in, entry 0)", ins, full, [on(blk), on(0)]),
+        ("plain_combine: an output overlaps an input (d_in, entry 1)", ins, full, [on(2 * blk + 3 * (blk // 2) - 2), on(blk + 2)]),
+        ("plain_combine: two outputs overlap", ins, full, [on(blk), on(blk + 2)]),
+    ]
+    for text, ins_, matrix, outs_ in cases:
+        with pytest.raises(ValueError) as err:
+            e.plain_combine(L, ins_, matrix, outs=outs_)
+        assert str(err.value) == text
+    e.sync()
+    assert np.array_equal(pool.download(), before)
+
+
 # ---- asynchrony ------------------------------------------------------------------------------------------------------------
 def test_returns_while_its_stream_is_shut_and_keeps_no_host_pointer():
     import ctypes as C

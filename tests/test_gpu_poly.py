@@ -16,6 +16,7 @@ words of the same host code on the oracle-backed twin, which has no scalar_combi
 Key switching needs N >= 2048 on the engine, so these run at N = 2048 (N = 4096 on the LR chain)."""
 import os
 import subprocess
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -255,6 +256,41 @@ def test_refusals_leave_the_outputs_alone():
         e.scalar_combine(L, size, [dins[0]] * 257, [L + 1] * 257, np.ones((1, 257, L), dtype=np.uint64), outs=outs[:1])
     e.sync()
     assert np.array_equal(outs[0].download(), junk[0])
+
+
+def test_of_two_faults_the_one_checked_first_is_reported():
+    """hefx_scalar_combine checks its arguments in one fixed order: of two faults in one call the message is that of the
+    check that stands first in the entry.  Every operand is a window of one buffer, which no refused call may touch."""
+    N, primes, L, size, m, G = 1024, base_primes(), 2, 2, 2, 2
+    e = engine(N, primes)
+    rows = L + 1
+    blk = size * rows * N                                            # words of an input; an output is shorter
+    pool = e.to_device(np.random.default_rng(12).integers(0, 1 << 40, (4 * blk,), dtype=np.uint64))
+    before = pool.download()
+    ins = [pool.view(k * blk, (size, rows, N)) for k in range(m)]
+    outs = [pool.view((m + g) * blk, (size, L, N)) for g in range(G)]
+    on = lambda k, off=0: pool.view(k * blk + off, (size, L, N))     # an output that shares bytes with input k
+    null = SimpleNamespace(ptr=None)
+    ok, few = [rows] * m, [rows, L - 1]
+    w, c = np.ones((G, m, L), dtype=np.uint64), np.zeros((G, L), dtype=np.uint64)
+    w_bad, c_bad = w.copy(), c.copy()
+    w_bad[1, 1, 1], c_bad[0, 0] = primes[1], primes[0]
+    cases = [
+        ("scalar_combine: every input needs at least L rows", ins, few, w_bad, c, outs),
+        ("scalar_combine: every input needs at least L rows", [ins[0], null], [L - 1, rows], w, c, outs),
+        ("null input in scalar_combine", [null, ins[1]], few, w, c, outs),
+        ("scalar_combine: a weight is not below its modulus", ins, ok, w_bad, c_bad, outs),
+        ("scalar_combine: a constant is not below its modulus", ins, ok, w, c_bad, [outs[0], on(1)]),
+        ("scalar_combine: an output overlaps an input (d_in, entry 0)", ins, ok, w, c, [on(1), on(0, N // 2)]),
+        ("scalar_combine: two outputs overlap", ins, ok, w, c, [on(1), on(1, 2)]),
+        ("scalar_combine: G out of range", ins, few, np.ones((17, m, L), dtype=np.uint64), None, [outs[0]] * 17),
+    ]
+    for text, ins_, rows_, w_, c_, outs_ in cases:
+        with pytest.raises(ValueError) as err:
+            e.scalar_combine(L, size, ins_, rows_, w_, c_, outs=outs_)
+        assert str(err.value) == text
+    e.sync()
+    assert np.array_equal(pool.download(), before)
 
 
 # ---- asynchrony ------------------------------------------------------------------------------------------------------------

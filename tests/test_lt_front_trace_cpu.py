@@ -7,7 +7,6 @@ Backends: (a) the oracle twin, (b) the twin with the rotation-forest entry, (c) 
 native linear-transform entries, which return zeros (this pins WHICH native entry is chosen and with what arguments; its
 result bits are not compared).  `python -m tests.test_lt_front_trace_cpu` rewrites the fixture."""
 import functools
-import hashlib
 import json
 import os
 
@@ -17,6 +16,7 @@ import pytest
 from seal_fyp_logistic_regression_amd import algorithms as alg
 from seal_fyp_logistic_regression_amd import seal as S
 from tests.oracle_backend import OracleBackend, _ForestTwin
+from tests.trace_recording import Recorder, digest
 
 FIXTURE = os.path.join(os.path.dirname(__file__), "golden", "lt_front_traces.json")
 N, BITS, SCALE = 4096, [60, 40, 40, 40, 40, 60], 2.0 ** 40
@@ -42,51 +42,6 @@ class _NativeTwin(_ForestTwin):
 
 
 BACKENDS = {"oracle": OracleBackend, "forest": _ForestTwin, "native": _NativeTwin}
-
-_big = {}   # id -> (array, digest): key payloads are 2 MB each and are handed over on every native call
-
-
-def _h(a):
-    if a.size >= 1 << 18:
-        hit = _big.get(id(a))
-        if hit is None or hit[0] is not a:
-            hit = _big[id(a)] = (a, hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()[:16])
-        return hit[1]
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()[:16]
-
-
-def _enc(x):
-    if x is None or isinstance(x, (bool, int)):
-        return x
-    if isinstance(x, np.integer):
-        return int(x)
-    if isinstance(x, np.ndarray):
-        return _h(x)
-    if isinstance(x, (list, tuple, range)):
-        if any(isinstance(v, np.ndarray) for v in x):   # a table of arrays: its length, its None slots, one digest over all
-            joined = "".join("-" if v is None else _h(v) for v in x)
-            return {"n": len(x), "none": [i for i, v in enumerate(x) if v is None],
-                    "h": hashlib.sha256(joined.encode()).hexdigest()[:16]}
-        return [_enc(v) for v in x]
-    raise TypeError(f"unexpected operand in a backend call: {type(x)}")
-
-
-class _Recorder:
-    """every method call on the wrapped backend appends [name, positional operands, keyword operands, result]"""
-
-    def __init__(self, be):
-        self._be, self.log = be, []
-
-    def __getattr__(self, name):
-        f = getattr(self._be, name)     # AttributeError for an entry the backend lacks: hasattr / getattr(.., None) see through
-        if not callable(f):
-            return f
-
-        def call(*a, **k):
-            r = f(*a, **k)
-            self.log.append([name, [_enc(v) for v in a], {key: _enc(v) for key, v in sorted(k.items())}, _enc(r)])
-            return r
-        return call
 
 
 @functools.lru_cache(maxsize=None)
@@ -149,7 +104,7 @@ SCENARIOS = ["plain_d5", "plain_many_d5", "plain_hoisted_d5", "plain_hoisted2_d5
 def _run(backend, scenario):
     e = _env(backend)
     ev = e["ev"]
-    rec = _Recorder(e["be"])
+    rec = Recorder(e["be"])
     ev.be = rec
     try:
         outs = _scenarios(e)[scenario]()
@@ -157,7 +112,7 @@ def _run(backend, scenario):
         ev.be = e["be"]
     got = {"trace": rec.log}
     if backend != "native":   # the stubs return zeros: only their calls count
-        got["results"] = [[c.size(), c.parms_id(), c.scale, _h(np.asarray(c.data))] for c in outs]
+        got["results"] = [[c.size(), c.parms_id(), c.scale, digest(np.asarray(c.data))] for c in outs]
     return json.loads(json.dumps(got))
 
 

@@ -22,7 +22,7 @@ comes from tests/test_dft_cpu.py with DFT_RECORD=1)."""
 import json, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-from seal_fyp_logistic_regression_amd import Engine, _build, dft
+from seal_fyp_logistic_regression_amd import Engine, _build, capi, dft
 from seal_fyp_logistic_regression_amd import algorithms as alg
 from seal_fyp_logistic_regression_amd import seal as S
 
@@ -162,10 +162,9 @@ for N, bits in ((16384, [60, 40, 40, 40, 40, 60]), (32768, [60] + [40] * 7 + [60
         gt = tile_width(G, m, L, N)
         unfused_r, fused_r, wr = word_counts(pat, gt)
         t_f, t_o = dev["plain_combine"]["median_us"] * 1e-6, dev["multiply_plain_sum"]["median_us"] * 1e-6
-        uniform = len(set(counts)) == 1
         row = {"N": N, "L": L, "pattern": name, "m": m, "G": G, "terms": sum(counts), "tile": gt,
                "multiply_plain_sum_calls": ncalls, "host": res, "device": dev,
-               "evaluator_takes": "multiply_plain_sum" if uniform and not (m >= 8 and G >= 4 and sum(counts) * L * N >= 1 << 23) else "plain_combine",
+               "evaluator_takes": "multiply_plain_sum" if capi.plain_combine_route(True, m, counts, L * N) == "grouped" else "plain_combine",
                "reads_LN_words": {"multiply_plain_sum": unfused_r, "plain_combine": fused_r}, "writes_LN_words": wr,
                "plain_combine_bytes_per_s": round((fused_r + wr) * row_words * 8 / t_f),
                "plain_combine_share_of_8TBps": round((fused_r + wr) * row_words * 8 / t_f / HBM_PEAK, 4),
@@ -176,7 +175,7 @@ for N, bits in ((16384, [60, 40, 40, 40, 40, 60]), (32768, [60] + [40] * 7 + [60
         del ins, pts, fused_out, old_out, terms_ct, terms_pt
     del e
 
-# a shape at which the fused call loses goes back to multiply_plain_sum in Evaluator.plain_combine (its rule is restated in
+# a shape at which the fused call loses goes back to multiply_plain_sum in Evaluator.plain_combine (its rule answers in
 # "evaluator_takes") and is listed here; a shape listed here that the evaluator still sends to the fused call is a misdispatch
 out["shapes_where_the_fused_call_is_slower"] = [(r["N"], r["L"], r["pattern"]) for r in out["primitive"] if r["fused_is_slower"]]
 out["misdispatched"] = [(r["N"], r["L"], r["pattern"], r["old_over_fused"]) for r in out["primitive"]
