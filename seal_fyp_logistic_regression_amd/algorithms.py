@@ -981,6 +981,14 @@ def cipher_dot_product_many(ev: Evaluator, As: Sequence[Ciphertext], Bs: Sequenc
     return mults
 
 
+def _check_step_level(name: str, ev: Evaluator, level: int, operands: Sequence[Ciphertext]):
+    """level=s of predict_cipher_weights / lr_gradient: s must leave the step its levels, and every operand is already there"""
+    if int(level) != level or not 2 <= level <= ev.ctx.first_parms_id():
+        raise ValueError(name + ": level must lie between 2 and the first level")
+    if any(c.parms_id() != level for c in operands):
+        raise ValueError(name + ": features, labels and weights must already be at level %d" % level)
+
+
 SIGMOID_COEFFS = {3: [0.5, 1.20069, 0.00001, -0.81562],
                   5: [0.5, 1.53048, 0.00001, -2.3533056, 0.00001, 1.3511295],
                   7: [0.5, 1.73496, 0.00001, -4.19407, 0.00001, 5.43402, 0.00001, -2.50739]}
@@ -989,13 +997,17 @@ SIGMOID_COEFFS = {3: [0.5, 1.20069, 0.00001, -0.81562],
 def predict_cipher_weights(ev: Evaluator, encoder: CKKSEncoder, encryptor, features: Sequence[Ciphertext],
                            weights: Ciphertext, num_weights: int, scale: float, gal_keys: KSwitchKeys,
                            relin_keys: KSwitchKeys, degree: int = 3, log_sum: bool = False,
-                           poly: str = "horner") -> Ciphertext:
+                           poly: str = "horner", level: Optional[int] = None) -> Ciphertext:
     """predict_cipher_weights, /root/reference/logistic_regression_ckks.cpp:208-266.  log_sum=True: the fast window
     sum of cipher_dot_product_many (same prediction values, not the reference's noise bits).  poly="horner" (default): the
     reference's Horner_cipher, its bits; "ps": the same sigmoid polynomial through evaluate_polynomial --
-    ceil(log2(degree + 1)) levels instead of `degree`, the prediction at `scale` with nothing overwritten."""
+    ceil(log2(degree + 1)) levels instead of `degree`, the prediction at `scale` with nothing overwritten.
+    level=None: the step starts at the first level, as the reference's does.  level=s: it starts at level s (bootstrapped
+    weights come back at plan.result_level, far below the top); features and weights must already be there (ValueError)."""
     if poly not in ("horner", "ps"):
         raise ValueError("poly must be 'horner' or 'ps'")
+    if level is not None:
+        _check_step_level("predict_cipher_weights", ev, level, list(features) + [weights])
     num_rows = len(features)
     results = cipher_dot_product_many(ev, features, [weights] * num_rows, num_weights, relin_keys, gal_keys,
                                       log_sum)                                                             # :220
@@ -1003,7 +1015,7 @@ def predict_cipher_weights(ev: Evaluator, encoder: CKKSEncoder, encryptor, featu
     # masks go through one batched encode (one GPU launch on the HIP engine) -- same plaintexts, same order of use
     # masks go through one batched encode (one GPU launch on the HIP engine) -- same plaintexts, same order of use.
     # Encoding at the level below the top IS encode + mod_switch_to_next (:227): CKKS drops RNS rows, no arithmetic.
-    top = ev.ctx.first_parms_id()
+    top = ev.ctx.first_parms_id() if level is None else int(level)
     masks = encoder.encode_many(list(np.eye(num_rows)), scale, parms_id=top - 1)                           # :222-227
     lin = ev.multiply_plain_sum(results, masks)[0]                                                         # :229, :233
     ev.relinearize_inplace(lin, relin_keys)                                                                # :237 (no-op)
@@ -1017,7 +1029,7 @@ def predict_cipher_weights(ev: Evaluator, encoder: CKKSEncoder, encryptor, featu
 
 def lr_gradient(ev: Evaluator, encoder: CKKSEncoder, encryptor, features: Sequence[Ciphertext],
                 features_T: Sequence[Ciphertext], labels: Ciphertext, weights: Ciphertext, gal_keys: KSwitchKeys,
-                relin_keys: KSwitchKeys, scale: float, degree: int = 3, poly: str = "horner"):
+                relin_keys: KSwitchKeys, scale: float, degree: int = 3, poly: str = "horner", level: Optional[int] = None):
     """update_weights up to its manual rescale, /root/reference/logistic_regression_ckks.cpp:269-323: everything the
     training step computes before SEAL refuses it at :336.  Returns (gradient, pred_labels): the gradient after :323
     (size 2, one prime left, scale snapped to a power of two) and the operand of the sub at :288.
@@ -1026,10 +1038,13 @@ def lr_gradient(ev: Evaluator, encoder: CKKSEncoder, encryptor, features: Sequen
     reference's window sum leaves in slot i of row i (helper.h:455-476, masked at :222-229): all of X[i] . w for
     i <= num_weights, the terms k >= i - num_weights for the rows after that, nothing from row 2 * num_weights on --
     reproduced, not fixed.  poly: as predict_cipher_weights ("ps" leaves the prediction, and so everything after it,
-    degree - ceil(log2(degree + 1)) levels higher)."""
+    degree - ceil(log2(degree + 1)) levels higher).  level: as predict_cipher_weights; features, features_T, labels and
+    weights must already be at that level, and the gradient comes out lr_step_levels(degree, poly) - 1 levels below it."""
     num_obs, num_weights = len(features), len(features_T)
+    if level is not None:
+        _check_step_level("lr_gradient", ev, level, list(features) + list(features_T) + [labels, weights])
     pred = predict_cipher_weights(ev, encoder, encryptor, features, weights, num_weights, scale, gal_keys,
-                                  relin_keys, degree, poly=poly)                                            # :282
+                                  relin_keys, degree, poly=poly, level=level)                               # :282
     labels = labels.copy()
     ev.mod_switch_to_inplace(labels, pred.parms_id())                                                      # :286
     pred_labels = ev.sub(pred, labels)                                                                     # :288
@@ -1066,15 +1081,15 @@ def update_weights(ev: Evaluator, encoder: CKKSEncoder, encryptor, features: Seq
 def update_weights_refreshed(ev: Evaluator, encoder: CKKSEncoder, encryptor, decryptor, features: Sequence[Ciphertext],
                              features_T: Sequence[Ciphertext], labels: Ciphertext, weights: Ciphertext,
                              learning_rate: float, gal_keys: KSwitchKeys, relin_keys: KSwitchKeys, scale: float,
-                             degree: int = 3) -> Ciphertext:
+                             degree: int = 3, poly: str = "horner") -> Ciphertext:
     """A training step that ends: w - (learning_rate / num_obs) * gradient, at the first level.  A COMPLETION of the
     reference, not a mirror of it: update_weights above stops where SEAL stops (:336), because the gradient arrives with
     one prime left.  The holder of the secret key -- the reference's train_cipher has a Decryptor for exactly this
     (:348-385) -- refreshes the gradient (Decryptor.refresh: decrypt, exact lift, encrypt; no decode / encode), after which
-    the reference's own lines go through, plus the rescale they omit."""
+    the reference's own lines go through, plus the rescale they omit.  poly: as lr_gradient."""
     num_obs = len(features)
     gradient, _ = lr_gradient(ev, encoder, encryptor, features, features_T, labels, weights, gal_keys, relin_keys,
-                              scale, degree)                                                                # :275-323
+                              scale, degree, poly)                                                          # :275-323
     gradient = decryptor.refresh(gradient, encryptor)                  # first level, scale 2^40: room for the product
     n_pt = encoder.encode(float(learning_rate) / num_obs, scale)                                           # :330-331
     ev.mod_switch_to_inplace(n_pt, gradient.parms_id())                                                    # :333
@@ -1090,12 +1105,131 @@ def update_weights_refreshed(ev: Evaluator, encoder: CKKSEncoder, encryptor, dec
 
 def train_cipher(ev: Evaluator, encoder: CKKSEncoder, encryptor, decryptor, features: Sequence[Ciphertext],
                  features_T: Sequence[Ciphertext], labels: Ciphertext, weights: Ciphertext, learning_rate: float,
-                 iters: int, gal_keys: KSwitchKeys, relin_keys: KSwitchKeys, scale: float, degree: int = 3) -> Ciphertext:
+                 iters: int, gal_keys: KSwitchKeys, relin_keys: KSwitchKeys, scale: float, degree: int = 3,
+                 poly: str = "horner") -> Ciphertext:
     """The loop of train_cipher, /root/reference/logistic_regression_ckks.cpp:356-382, over update_weights_refreshed.
     The reference refreshes by decrypt / decode ... encrypt of a last-level plaintext (:362-381) and so could not start
     a second iteration; here every step already returns first-level weights."""
     new_weights = weights                                                                                  # :354
     for _ in range(int(iters)):                                                                            # :356
         new_weights = update_weights_refreshed(ev, encoder, encryptor, decryptor, features, features_T, labels,
-                                               new_weights, learning_rate, gal_keys, relin_keys, scale, degree)  # :359
+                                               new_weights, learning_rate, gal_keys, relin_keys, scale, degree, poly)  # :359
+    return new_weights
+
+
+# ---- training with evaluation keys only: the bootstrap in place of the Decryptor ----------------------------------------------
+def lr_step_levels(degree: int, poly: str = "horner") -> int:
+    """Levels one whole training step spends, from the level the weights start at to the updated weights: the dot product,
+    the row mask, the sigmoid (`degree` levels for "horner", ceil(log2(degree + 1)) for "ps"), the gradient's dot product, the
+    weight mask, and the product with learning_rate / num_obs with its rescale.  lr_gradient spends all but the last.  That
+    last product needs two primes (its scale is the square of the ciphertext's until the rescale: the reference's throws at
+    :336 because its gradient arrives with one), so a step that ends at level 1 starts at level 1 + lr_step_levels(...)."""
+    if poly not in ("horner", "ps"):
+        raise ValueError("poly must be 'horner' or 'ps'")
+    if int(degree) != degree or degree < 1:
+        raise ValueError("degree must be a positive integer")
+    sigmoid = int(degree) if poly == "horner" else int(degree).bit_length()   # ceil(log2(degree + 1))
+    return 1 + 1 + sigmoid + 1 + 1 + 1
+
+
+def lr_bootstrap_galois_steps(plan, num_obs: int, num_weights: int) -> List[int]:
+    """The rotation steps of ONE KeyGenerator.galois_keys(steps, conjugate=True) call for train_cipher_bootstrapped:
+    plan.galois_steps() (SubSum -- the update's tiling takes the same steps --, both packed transforms) and the steps of the
+    two dot products: 1 for the window sums, -num_weights and -num_obs for their zero-filled copies (helper.h:455)."""
+    return sorted(set(plan.galois_steps()) | {1, -int(num_weights), -int(num_obs)})
+
+
+def _check_bootstrapped_step(ev: Evaluator, plan, num_weights: int, scale: float, degree: int, poly: str) -> int:
+    """the refusals of update_weights_bootstrapped that need no ciphertext; returns the level s a step starts at"""
+    s = 1 + lr_step_levels(degree, poly)
+    if plan.sparse_slots is None:
+        raise ValueError("bootstrapped training needs a sparse plan (bootstrap.plan(..., slots=ns))")
+    if plan.N != ev.ctx.N or list(plan.primes) != list(ev.ctx.primes):
+        raise ValueError("bootstrap: the plan was made for another ring or chain")
+    if plan.sparse_slots < num_weights:
+        raise ValueError("the plan's %d slots do not hold %d weights" % (plan.sparse_slots, num_weights))
+    if plan.result_level < s:
+        raise ValueError("the bootstrap returns at level %d and a step needs %d: the chain is too short"
+                         % (plan.result_level, s))
+    if not ev._close(float(scale), plan.scale):
+        raise ValueError("scale mismatch: the plan was made for another scale")
+    return s
+
+
+def update_weights_bootstrapped(ev: Evaluator, encoder: CKKSEncoder, encryptor, features: Sequence[Ciphertext],
+                                features_T: Sequence[Ciphertext], labels: Ciphertext, weights: Ciphertext,
+                                learning_rate: float, gal_keys: KSwitchKeys, relin_keys: KSwitchKeys, scale: float, plan,
+                                degree: int = 3, poly: str = "ps", encoded=None) -> Ciphertext:
+    """A training step that ends WITHOUT the secret key: w - (learning_rate / num_obs) * gradient, refreshed by one
+    algorithms.bootstrap of the weights where update_weights_refreshed asks the Decryptor twice.  Every operand is at level
+    s = 1 + lr_step_levels(degree, poly) and so is the result.
+
+    plan: a sparse bootstrap.plan(N, chain, scale, slots=ns, max_value=...) with ns >= num_weights, plan.result_level >= s and
+    max_value at least the largest |weight| the training reaches; encoded: plan.encode(encoder) (made here when None; a loop
+    passes it).  gal_keys: galois_keys(lr_bootstrap_galois_steps(plan, num_obs, num_weights), conjugate=True); the secret key
+    behind them is the sparse one bootstrap() needs.  ValueError before anything is submitted when the plan is dense, holds
+    fewer slots than weights, returns below s or was made for another scale or chain, or when an operand is not at level s.
+
+    THE INVARIANT: `weights` is ns-periodic -- its ns values tiled over the N / 2 slots (encode np.tile(w, N / 2 / ns)) --
+    and so is the result.  The feature rows stay zero-padded, so the dot product's products vanish outside the first block
+    and the tiling changes no value the step reads.  The gradient lives in the first block alone; subsum of a message
+    confined to one block IS its tiling (log2(N / 2 ns) key switches at one prime), after which the reference's sub and negate
+    (:341-342) keep the period and bootstrap() finds the subring it expects.  poly: "ps" by default -- Horner_cipher
+    hard-codes the scale 2^40 (:195), at which no bootstrap chain of this engine keeps its precision."""
+    num_obs, num_weights = len(features), len(features_T)
+    s = _check_bootstrapped_step(ev, plan, num_weights, scale, degree, poly)
+    _check_step_level("update_weights_bootstrapped", ev, s, list(features) + list(features_T) + [labels, weights])
+    if not ev._close(weights.scale, plan.scale):
+        raise ValueError("scale mismatch: the weights are not at the plan's scale")
+    if encoded is None:
+        encoded = plan.encode(encoder)
+    gradient, _ = lr_gradient(ev, encoder, encryptor, features, features_T, labels, weights, gal_keys, relin_keys,
+                              scale, degree, poly, level=s)            # :275-323, at level 2: room for the product
+    new_weights = _update_and_tile(ev, encoder, gradient, weights, float(learning_rate) / num_obs, scale,
+                                   plan.sparse_slots, gal_keys)
+    fresh = bootstrap(ev, new_weights, plan, gal_keys, relin_keys, encoded)
+    return ev.mod_switch_to_inplace(fresh, s)
+
+
+def _update_and_tile(ev: Evaluator, encoder: CKKSEncoder, gradient: Ciphertext, weights: Ciphertext, rate: float,
+                     scale: float, ns: int, gal_keys: KSwitchKeys) -> Ciphertext:
+    """weights - rate * gradient at the last prime, ns-periodic: the gradient (level 2, first block only) times the encoded
+    rate, rescaled, tiled by subsum; the weights (ns-periodic, any level) mod-switched down; the reference's sub and negate"""
+    gradient = gradient.copy()
+    n_pt = encoder.encode(rate, scale)                                                                     # :330-331
+    ev.mod_switch_to_inplace(n_pt, gradient.parms_id())                                                    # :333
+    ev.multiply_plain_inplace(gradient, n_pt)                                                              # :336
+    ev.rescale_to_next_inplace(gradient)                               # (omitted by the reference)
+    gradient.scale = 2.0 ** int(np.log2(gradient.scale))               # its own idiom, :323
+    delta = subsum(ev, gradient, ns, gal_keys)                         # first block -> every block
+    weights = weights.copy()
+    ev.mod_switch_to_inplace(weights, delta.parms_id())
+    new_weights = ev.sub(delta, weights)                                                                   # :341
+    ev.negate_inplace(new_weights)                                                                         # :342
+    return new_weights
+
+
+def train_cipher_bootstrapped(ev: Evaluator, encoder: CKKSEncoder, encryptor, features: Sequence[Ciphertext],
+                              features_T: Sequence[Ciphertext], labels: Ciphertext, weights: Ciphertext,
+                              learning_rate: float, iters: int, gal_keys: KSwitchKeys, relin_keys: KSwitchKeys,
+                              scale: float, plan, degree: int = 3, poly: str = "ps", encoded=None) -> Ciphertext:
+    """train_cipher with evaluation keys only: `iters` times update_weights_bootstrapped, one bootstrap per iteration.
+    Features, transposed features, labels and the initial weights (tiled: see update_weights_bootstrapped) may sit at any
+    level from s = 1 + lr_step_levels(degree, poly) up and are mod-switched to s ONCE, here; the plan's plaintexts are
+    encoded once.  The result is at level s, ns-periodic."""
+    s = _check_bootstrapped_step(ev, plan, len(features_T), scale, degree, poly)
+    operands = list(features) + list(features_T) + [labels, weights]
+    if any(c.parms_id() < s for c in operands):
+        raise ValueError("train_cipher_bootstrapped: features, labels and weights must be at level %d or above" % s)
+    if not ev._close(weights.scale, plan.scale):
+        raise ValueError("scale mismatch: the weights are not at the plan's scale")
+    if encoded is None:
+        encoded = plan.encode(encoder)
+    features, features_T, labels, new_weights = ([ev.mod_switch_to_inplace(c.copy(), s) for c in features],
+                                                 [ev.mod_switch_to_inplace(c.copy(), s) for c in features_T],
+                                                 ev.mod_switch_to_inplace(labels.copy(), s),
+                                                 ev.mod_switch_to_inplace(weights.copy(), s))
+    for _ in range(int(iters)):
+        new_weights = update_weights_bootstrapped(ev, encoder, encryptor, features, features_T, labels, new_weights,
+                                                  learning_rate, gal_keys, relin_keys, scale, plan, degree, poly, encoded)
     return new_weights
