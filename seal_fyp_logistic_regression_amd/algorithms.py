@@ -772,7 +772,8 @@ def eval_mod(ev: Evaluator, cts: Sequence[Ciphertext], plan, relin_keys: KSwitch
     return ys
 
 
-def bootstrap(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitchKeys, relin_keys: KSwitchKeys, encoded=None) -> Ciphertext:
+def bootstrap(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitchKeys, relin_keys: KSwitchKeys, encoded=None,
+              encaps=None) -> Ciphertext:
     """CKKS bootstrapping with evaluation keys only: a size-2 ciphertext at the last prime q_0 and scale plan.scale comes back
     at level plan.result_level encrypting the same message (to the precision of bootstrap.plan), at plan.scale as a computed
     value.  Evaluator.mod_raise to the top (the plaintext becomes m + q_0 I), coeffs_to_slots with scale / (q_0 K') folded
@@ -780,7 +781,11 @@ def bootstrap(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitchKeys, relin_
     plan: bootstrap.plan(...) for this context's chain; gal_keys: galois_keys(plan.galois_steps(), conjugate=True); the
     secret key must be sparse enough for plan.K (KeyGenerator(hamming_weight=...)); encoded: plan.encode(encoder).
     A sparse plan (bootstrap.plan(..., slots=ns): the message is ns values tiled over the slots) goes mod_raise, subsum,
-    coeffs_to_slots_packed, eval_mod on the ONE ciphertext, slots_to_coeffs_packed; the result is ns-periodic again."""
+    coeffs_to_slots_packed, eval_mod on the ONE ciphertext, slots_to_coeffs_packed; the result is ns-periodic again.
+    encaps: KeyGenerator.encapsulation_keys(...) -- sparse-secret encapsulation: the main secret may then be DENSE.  The
+    ciphertext is switched to the keys' sparse secret at the last prime (Evaluator.switch_key with encaps.low), raised under
+    it and switched back at the top (Evaluator.raise_switch); plan.K is then a matter of the weight of THAT secret, and every
+    step after the raise, like the rest of the program, runs under the main one.  None: the path above, bit for bit."""
     if ct.size() != 2 or ct.parms_id() != 1:
         raise ValueError("bootstrap: needs a size-2 ciphertext at the last prime")
     if plan.N != ev.ctx.N or list(plan.primes) != list(ev.ctx.primes):
@@ -789,7 +794,10 @@ def bootstrap(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitchKeys, relin_
         raise ValueError("scale mismatch")
     if encoded is None:
         encoded = plan.encode(CKKSEncoder(ev.ctx, device_encode=False))
-    raised = ev.mod_raise(ct, plan.top_level)
+    if encaps is not None:
+        raised = ev.raise_switch(ev.switch_key(ct, encaps.low), encaps, plan.top_level)
+    else:
+        raised = ev.mod_raise(ct, plan.top_level)
     if plan.sparse_slots is not None:
         x = coeffs_to_slots_packed(ev, subsum(ev, raised, plan.sparse_slots, gal_keys), plan.c2s, gal_keys, encoded[0])
         (y,) = eval_mod(ev, [x], plan, relin_keys)
@@ -1159,7 +1167,7 @@ def _check_bootstrapped_step(ev: Evaluator, plan, num_weights: int, scale: float
 def update_weights_bootstrapped(ev: Evaluator, encoder: CKKSEncoder, encryptor, features: Sequence[Ciphertext],
                                 features_T: Sequence[Ciphertext], labels: Ciphertext, weights: Ciphertext,
                                 learning_rate: float, gal_keys: KSwitchKeys, relin_keys: KSwitchKeys, scale: float, plan,
-                                degree: int = 3, poly: str = "ps", encoded=None) -> Ciphertext:
+                                degree: int = 3, poly: str = "ps", encoded=None, encaps=None) -> Ciphertext:
     """A training step that ends WITHOUT the secret key: w - (learning_rate / num_obs) * gradient, refreshed by one
     algorithms.bootstrap of the weights where update_weights_refreshed asks the Decryptor twice.  Every operand is at level
     s = 1 + lr_step_levels(degree, poly) and so is the result.
@@ -1175,7 +1183,8 @@ def update_weights_bootstrapped(ev: Evaluator, encoder: CKKSEncoder, encryptor, 
     and the tiling changes no value the step reads.  The gradient lives in the first block alone; subsum of a message
     confined to one block IS its tiling (log2(N / 2 ns) key switches at one prime), after which the reference's sub and negate
     (:341-342) keep the period and bootstrap() finds the subring it expects.  poly: "ps" by default -- Horner_cipher
-    hard-codes the scale 2^40 (:195), at which no bootstrap chain of this engine keeps its precision."""
+    hard-codes the scale 2^40 (:195), at which no bootstrap chain of this engine keeps its precision.
+    encaps: passed to bootstrap() -- with KeyGenerator.encapsulation_keys the secret behind every key may be dense."""
     num_obs, num_weights = len(features), len(features_T)
     s = _check_bootstrapped_step(ev, plan, num_weights, scale, degree, poly)
     _check_step_level("update_weights_bootstrapped", ev, s, list(features) + list(features_T) + [labels, weights])
@@ -1187,7 +1196,7 @@ def update_weights_bootstrapped(ev: Evaluator, encoder: CKKSEncoder, encryptor, 
                               scale, degree, poly, level=s)            # :275-323, at level 2: room for the product
     new_weights = _update_and_tile(ev, encoder, gradient, weights, float(learning_rate) / num_obs, scale,
                                    plan.sparse_slots, gal_keys)
-    fresh = bootstrap(ev, new_weights, plan, gal_keys, relin_keys, encoded)
+    fresh = bootstrap(ev, new_weights, plan, gal_keys, relin_keys, encoded, encaps)
     return ev.mod_switch_to_inplace(fresh, s)
 
 
@@ -1212,11 +1221,11 @@ def _update_and_tile(ev: Evaluator, encoder: CKKSEncoder, gradient: Ciphertext, 
 def train_cipher_bootstrapped(ev: Evaluator, encoder: CKKSEncoder, encryptor, features: Sequence[Ciphertext],
                               features_T: Sequence[Ciphertext], labels: Ciphertext, weights: Ciphertext,
                               learning_rate: float, iters: int, gal_keys: KSwitchKeys, relin_keys: KSwitchKeys,
-                              scale: float, plan, degree: int = 3, poly: str = "ps", encoded=None) -> Ciphertext:
+                              scale: float, plan, degree: int = 3, poly: str = "ps", encoded=None, encaps=None) -> Ciphertext:
     """train_cipher with evaluation keys only: `iters` times update_weights_bootstrapped, one bootstrap per iteration.
     Features, transposed features, labels and the initial weights (tiled: see update_weights_bootstrapped) may sit at any
     level from s = 1 + lr_step_levels(degree, poly) up and are mod-switched to s ONCE, here; the plan's plaintexts are
-    encoded once.  The result is at level s, ns-periodic."""
+    encoded once.  The result is at level s, ns-periodic.  encaps: passed to every step's bootstrap()."""
     s = _check_bootstrapped_step(ev, plan, len(features_T), scale, degree, poly)
     operands = list(features) + list(features_T) + [labels, weights]
     if any(c.parms_id() < s for c in operands):
@@ -1231,5 +1240,5 @@ def train_cipher_bootstrapped(ev: Evaluator, encoder: CKKSEncoder, encryptor, fe
                                                  ev.mod_switch_to_inplace(weights.copy(), s))
     for _ in range(int(iters)):
         new_weights = update_weights_bootstrapped(ev, encoder, encryptor, features, features_T, labels, new_weights,
-                                                  learning_rate, gal_keys, relin_keys, scale, plan, degree, poly, encoded)
+                                                  learning_rate, gal_keys, relin_keys, scale, plan, degree, poly, encoded, encaps)
     return new_weights

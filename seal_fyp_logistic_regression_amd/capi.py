@@ -214,6 +214,15 @@ PRODUCT_COMBINE_MAX_ITEMS = 64     # HEFX_PRODUCT_COMBINE_MAX_ITEMS
 PRODUCT_COMBINE_MAX_WORDS = 10240  # one descriptor-ring slot
 
 
+# include/hefx_encaps.h: sparse-secret encapsulation (the plain key switch, the collapsed key, mod-raise + switch in one call)
+_ENCAPS_SIGS = {
+    "hefx_switch_key": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "hefx_collapse_key": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "hefx_raise_switch": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+}
+ENCAPS_SYMBOLS = sorted(_ENCAPS_SIGS)
+
+
 def product_combine_words(L: int, n: int, P: int, m: int) -> int:
     """words of hefx_product_combine's table with a constant: strides, weights and the constant per row, n pointer records"""
     return 2 * P + m + L * (P + m + 1) + n * (2 * P + m + 1)
@@ -234,7 +243,8 @@ def lib():
         raise HefxError(f"{path} is missing: build the HIP extension first (__graft_entry__.build())")
     L = C.CDLL(path, mode=C.RTLD_GLOBAL)
     for name, (res, args) in (list(_SIGS.items()) + list(_REFRESH_SIGS.items()) + list(_BFV_SIGS.items())
-                              + list(_POLY_SIGS.items()) + list(_DFT_SIGS.items()) + list(_BOOTSTRAP_SIGS.items())):
+                              + list(_POLY_SIGS.items()) + list(_DFT_SIGS.items()) + list(_BOOTSTRAP_SIGS.items())
+                              + list(_ENCAPS_SIGS.items())):
         f = getattr(L, name)
         f.restype = res
         f.argtypes = args

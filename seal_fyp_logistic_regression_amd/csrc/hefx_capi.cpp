@@ -8,6 +8,7 @@
 #include "../../include/hefx_poly.h"
 #include "../../include/hefx_dft.h"
 #include "../../include/hefx_bootstrap.h"
+#include "../../include/hefx_encaps.h"
 
 #include <chrono>
 #include <cmath>
@@ -3385,6 +3386,82 @@ extern "C" int hefx_refresh_batch(hefx_context *c, int L_in, int size, int L_out
             return HEFX_OK;
         },
         cap);
+}
+
+// ---------------------------------------------------------------------------------------------
+// sparse-secret encapsulation (include/hefx_encaps.h, hefx_encaps.hip)
+// ---------------------------------------------------------------------------------------------
+// the bytes of a switching key [k-1][2][k][N] that level L reads: its first L digits
+static size_t key_bytes(const hefx_context *c, int L) { return (size_t)L * 2 * c->k * c->n * sizeof(u64); }
+
+// The key switch without an automorphism is the rotation path with the identity Galois element: its gather is the
+// identity, out-of-place it stages nothing, and the exact in-place form is served from the path's own scratch copy.  The
+// batch check of ks_run covers the ciphertexts; the key is checked here.
+extern "C" int hefx_switch_key(hefx_context *c, int L, const uint64_t *ct_in, const uint64_t *key, uint64_t *ct_out, void *stream)
+{
+    CTXCHK(c);
+    if (int rc = check_ks_level(c, L)) return rc;
+    if (!ct_in || !key || !ct_out) return fail(HEFX_ERR_INVALID, "bad switch_key arguments: null pointer");
+    if (int rc = check_ranges("switch_key", 1, &ct_out, 2 * (size_t)L * c->n * sizeof(u64), {{&key, 1, key_bytes(c, L)}}, {"d_key"}))
+        return rc;
+    const uint32_t elt = 1;
+    return ks_run(c, L, {.n = 1, .ct_in = &ct_in, .elts = &elt, .keys = &key, .ct_out = &ct_out}, stream);
+}
+
+extern "C" int hefx_collapse_key(hefx_context *c, int L, const uint64_t *key, uint64_t *out, void *stream)
+{
+    CTXCHK(c);
+    if (int rc = check_ks_level(c, L)) return rc;
+    if (!key || !out) return fail(HEFX_ERR_INVALID, "bad collapse_key arguments: null pointer");
+    if (int rc = check_ranges("collapse_key", 1, &out, 2 * (size_t)(L + 1) * c->n * sizeof(u64), {{&key, 1, key_bytes(c, L)}}, {"d_key"}))
+        return rc;
+    HIPCHK(launch_collapse_key(c->T, L, (const u64 *)key, (u64 *)out, (hipStream_t)stream));
+    return HEFX_OK;
+}
+
+// a transform of hefx_raise_switch's scratch rows: in place below N = 32768 (raw == done), through the out-of-place split
+// launcher there (raw -> done)
+static hipError_t rs_transform(const hefx_context *c, bool inverse, const u64 *raw, u64 *done, int npoly, int nrows, int mod_first,
+                               hipStream_t s)
+{
+    if (c->logn == 15) return launch_ntt_split15(c->T, inverse, raw, done, npoly, nrows, mod_first, s);
+    return launch_ntt(c->T, inverse, done, npoly, nrows, mod_first, s);
+}
+
+extern "C" int hefx_raise_switch(hefx_context *c, int L, const uint64_t *ct_in, const uint64_t *ckey, uint64_t *ct_out, void *stream)
+{
+    CTXCHK(c);
+    if (int rc = check_ks_level(c, L)) return rc;
+    if (L < 2) return fail(HEFX_ERR_INVALID, "raise_switch: the target level must be at least 2");
+    if (!ct_in || !ckey || !ct_out) return fail(HEFX_ERR_INVALID, "bad raise_switch arguments: null pointer");
+    const size_t N = c->n, row = N * sizeof(u64);
+    if (int rc = check_ranges("raise_switch", 1, &ct_out, 2 * row * L, {{&ct_in, 1, 2 * row}, {&ckey, 1, 2 * row * (L + 1)}},
+                              {"d_ct_in", "d_ckey"}))
+        return rc;
+    // scratch, in rows of N words: coef [2] | xb [2 (L-1)] | xp [1] | accp [2] | tt [2 L]  = 4 L + 3 rows, every one of them
+    // transformed exactly once; at N = 32768 a second set behind it, which the element-wise passes write and the
+    // out-of-place transforms read (the first inverse transform reads the caller's input: no copy there)
+    const bool split = c->logn == 15;
+    const size_t set = (size_t)(4 * L + 3) * N;
+    if (int rc = ensure_scratch(c, set * (split ? 2 : 1))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    u64 *coef = c->scratch, *xb = coef + 2 * N, *xp = xb + 2 * (size_t)(L - 1) * N, *accp = xp + N, *tt = accp + 2 * N;
+    const size_t raw = split ? set : 0;  // where a pass writes what the next transform reads
+    if (split) {
+        HIPCHK(launch_ntt_split15(c->T, true, (const u64 *)ct_in, coef, 2, 1, 0, s));
+    } else {
+        HIPCHK(hipMemcpyAsync(coef, ct_in, 2 * row, hipMemcpyDeviceToDevice, s));
+        HIPCHK(launch_ntt(c->T, true, coef, 2, 1, 0, s));
+    }
+    HIPCHK(launch_rs_expand(c->T, L, coef, xb + raw, xp + raw, s));
+    HIPCHK(rs_transform(c, false, xb + raw, xb, 2, L - 1, 1, s));
+    HIPCHK(rs_transform(c, false, xp + raw, xp, 1, 1, c->k - 1, s));
+    HIPCHK(launch_rs_product_p(c->T, L, xp, (const u64 *)ckey, accp + raw, s));
+    HIPCHK(rs_transform(c, true, accp + raw, accp, 2, 1, c->k - 1, s));
+    HIPCHK(launch_rs_spread(c->T, L, accp, tt + raw, s));
+    HIPCHK(rs_transform(c, false, tt + raw, tt, 2, L, 0, s));
+    HIPCHK(launch_rs_finish(c->T, L, (const u64 *)ct_in, xb, (const u64 *)ckey, tt, (u64 *)ct_out, s));
+    return HEFX_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -271,6 +271,15 @@ hipError_t launch_plain_combine(const DevTables &T, int L, int m, int G, int gt,
 // device table laid out there (product_combine_table_words words)
 size_t product_combine_table_words(int L, int n, int P, int m, bool has_const);
 hipError_t launch_product_combine(const DevTables &T, int L, int n, int P, int m, const u64 *d_tab, bool has_const, hipStream_t s);
+// sparse-secret encapsulation (hefx_encaps.hip, include/hefx_encaps.h): the collapsed key [2][L+1][N] of key [k-1][2][k][N],
+// and the element-wise passes of hefx_raise_switch between its transforms -- coef [2][N] -> xb [2][L-1][N], xp [N];
+// xp, ckey -> accp [2][N]; u [2][N] -> tt [2][L][N]; in [2][1][N], xb, ckey, tt -> out [2][L][N]
+hipError_t launch_collapse_key(const DevTables &T, int L, const u64 *key, u64 *out, hipStream_t s);
+hipError_t launch_rs_expand(const DevTables &T, int L, const u64 *coef, u64 *xb, u64 *xp, hipStream_t s);
+hipError_t launch_rs_product_p(const DevTables &T, int L, const u64 *xp, const u64 *ckey, u64 *accp, hipStream_t s);
+hipError_t launch_rs_spread(const DevTables &T, int L, const u64 *u, u64 *tt, hipStream_t s);
+hipError_t launch_rs_finish(const DevTables &T, int L, const u64 *in, const u64 *xb, const u64 *ckey, const u64 *tt, u64 *out,
+                            hipStream_t s);
 hipError_t warm_kernels(hipStream_t s);
 hipError_t warm_keyswitch(hipStream_t s);
 hipError_t warm_encode(hipStream_t s);

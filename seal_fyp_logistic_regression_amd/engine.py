@@ -625,6 +625,27 @@ class Engine:
             int(first_stream_id), capi.ptr_array([o.ptr for o in outs]), stream))
         return outs
 
+    # ---- sparse-secret encapsulation (include/hefx_encaps.h)
+    def switch_key(self, L, ct, key, out=None, stream=None):
+        """(c0 + ks0(c1), ks1(c1)): the key switch without an automorphism (hefx_switch_key); out may be ct itself"""
+        out = out if out is not None else DeviceArray(self, (2, L, self.N))
+        capi.check(capi.lib().hefx_switch_key(self._h, L, ct.ptr, key.ptr, out.ptr, stream))
+        return out
+
+    def collapse_key(self, L, key, out=None, stream=None):
+        """the row-wise sum of the first L digits of key [k-1][2][k][N] over the rows 0 .. L-1 and k-1: [2][L+1][N]
+        (hefx_collapse_key)"""
+        out = out if out is not None else DeviceArray(self, (2, L + 1, self.N))
+        capi.check(capi.lib().hefx_collapse_key(self._h, L, key.ptr, out.ptr, stream))
+        return out
+
+    def raise_switch(self, L_out, ct, ckey, out=None, stream=None):
+        """ct [2][1][N] at q_0 -> [2][L_out][N]: the centred lift of both polynomials and the key switch of the lifted c1
+        with the collapsed key ckey = collapse_key(L_out, key), in 4 L_out + 3 row transforms (hefx_raise_switch)"""
+        out = out if out is not None else DeviceArray(self, (2, L_out, self.N))
+        capi.check(capi.lib().hefx_raise_switch(self._h, L_out, ct.ptr, ckey.ptr, out.ptr, stream))
+        return out
+
     # ---- scalar combinations of ciphertexts (include/hefx_poly.h)
     def scalar_combine(self, L, size, ins, in_rows, weights, consts=None, outs=None, stream=None):
         """outs[g] = sum_k weights[g][k] * ins[k] + consts[g] over the first L rows of every input, one pass over the inputs

@@ -299,6 +299,17 @@ class GpuBackend:
     def mod_raise(self, L_in, L_out, x, count=1):
         return self.engine.mod_raise(L_in, L_out, x, count)
 
+    def switch_key(self, L, ct, key):
+        return self.engine.switch_key(L, ct, key)
+
+    def collapse_key(self, L, key):
+        return self.engine.collapse_key(L, key)
+
+    def raise_switch(self, L_out, ct, ckey):
+        """mod-raise from one prime and the collapsed key switch in one engine call (hefx_raise_switch); the oracle-backed
+        twin of the tests has no such method and Evaluator.raise_switch states the same words through its apply_galois"""
+        return self.engine.raise_switch(L_out, ct, ckey)
+
     def refresh(self, L_in, size, L_out, ct, sk, pk, key32, stream_id):
         """decrypt -> exact lift -> encrypt in one engine call (hefx_refresh); the oracle-backed twin of the tests has no
         such method and Decryptor.refresh composes the same words from its decrypt, transforms and encrypt"""
@@ -494,6 +505,31 @@ class KSwitchKeys:
 GaloisKeys = KSwitchKeys
 RelinKeys = KSwitchKeys
 
+
+class EncapsKeys:
+    """The two switching keys of sparse-secret encapsulation (KeyGenerator.encapsulation_keys): `low` takes a ciphertext at
+    the last prime from the main secret s to the auxiliary sparse secret s' (zero outside digit 0, rows {0, k-1}: it lives
+    at modulus q_0 P), `high` takes one at any level from s' back to s.  s' itself is not kept.  The collapsed form of
+    `high` that Evaluator.raise_switch reads is cached here per level."""
+
+    def __init__(self, low, high, hamming_weight: int):
+        self.low, self.high, self.hamming_weight = low, high, int(hamming_weight)
+        self._collapsed: Dict[int, object] = {}
+
+
+def collapse_key_host(key: np.ndarray, primes: Sequence[int], L: int) -> np.ndarray:
+    """The collapsed key of level L on the host: key [k-1][2][k][N] -> [2][k][N], row m the sum of the first L digits' rows m
+    mod q_m (hefx_collapse_key keeps the rows 0 .. L-1 and k-1 of it).  Exact in uint64: canonical words of primes below
+    2^61, reduced after every addition."""
+    k = len(primes)
+    key = np.asarray(key, dtype=np.uint64).reshape(k - 1, 2, k, -1)
+    q = np.asarray([int(p) for p in primes], dtype=np.uint64)[None, :, None]
+    out = key[0].copy()
+    for j in range(1, L):
+        out += key[j]
+        out -= np.where(out >= q, q, np.uint64(0))
+    return out
+
 CT_SIZE_MAX = 16  # HEFX_CT_SIZE_MAX (hefx.h): the most polynomials a ciphertext may have in this engine
 
 
@@ -581,12 +617,14 @@ class KeyGenerator:
     def secret_key(self) -> SecretKey:
         return self._sk
 
-    def _encrypt_zero(self, npoly: int, rows: int, sid: int):
+    def _encrypt_zero(self, npoly: int, rows: int, sid: int, sk: Optional[SecretKey] = None, key32: Optional[bytes] = None):
         """npoly fresh symmetric encryptions of zero over the first `rows` primes: returns host (c0, c1);
-        a uniform from sampler stream 2*sid, e noise from 2*sid+1 (what hefx_keygen_kswitch draws)"""
-        be, sk = self.ctx.backend, self._sk
-        a = be.sample("uniform", self._key32, 2 * sid, npoly, rows)
-        e = be.sample("noise", self._key32, 2 * sid + 1, npoly, rows)
+        a uniform from sampler stream 2*sid, e noise from 2*sid+1 (what hefx_keygen_kswitch draws).  sk, key32: another
+        secret and sampler key than the generator's own (encapsulation_keys)"""
+        be, sk = self.ctx.backend, sk if sk is not None else self._sk
+        key32 = key32 if key32 is not None else self._key32
+        a = be.sample("uniform", key32, 2 * sid, npoly, rows)
+        e = be.sample("noise", key32, 2 * sid + 1, npoly, rows)
         be.ntt_forward(e, npoly, rows, 0)
         sk_rows = be.from_host(sk.host[:rows])
         as_ = be.multiply_plain(rows, npoly, a, sk_rows)
@@ -601,21 +639,26 @@ class KeyGenerator:
             self._pk = np.stack([c0[0], c1[0]])  # [2][k][N]
         return self._pk
 
-    def _kswitch_key(self, new_sk_host, new_sk_dev=None):
+    def _kswitch_key(self, new_sk_host, new_sk_dev=None, sk: Optional[SecretKey] = None, key32: Optional[bytes] = None,
+                     sid: Optional[int] = None):
         """key-switching key for new_sk under sk.  On the HIP engine: one call (hefx_keygen_kswitch -- sampling, NTT and
         assembly on the device); otherwise the same arithmetic composed from backend ops (the oracle twin in tests:
-        same sampler streams, same bits)."""
+        same sampler streams, same bits).  sk, key32, sid (all three: encapsulation_keys): a key under another secret, from a
+        sampler key and stream id of its own -- the generator's stream counter stays where it is."""
         ctx, be = self.ctx, self.ctx.backend
         k, N, q = ctx.k, ctx.N, ctx.primes
-        sid = self._next_stream()
+        if sid is None:
+            sid = self._next_stream()
+        sk = sk if sk is not None else self._sk
+        key32 = key32 if key32 is not None else self._key32
         native = getattr(be, "keygen_kswitch", None)
         if native is not None:
             if new_sk_dev is None:
                 new_sk_dev = be.from_host(new_sk_host)
-            return native(self._sk.data, new_sk_dev, self._key32, sid)
+            return native(sk.data, new_sk_dev, key32, sid)
         if new_sk_host is None:
             new_sk_host = be.to_host(new_sk_dev).reshape(k, N)
-        c0, c1 = self._encrypt_zero(k - 1, k, sid)
+        c0, c1 = self._encrypt_zero(k - 1, k, sid, sk, key32)
         P = q[k - 1]
         # c0[i][row i] += (P mod q_i) * new_sk[row i]
         factor = np.empty((k, N), dtype=np.uint64)
@@ -641,6 +684,31 @@ class KeyGenerator:
             power = be.multiply_plain(self.ctx.k, 1, power, sk.data)
             rk.keys[p - 2] = self._kswitch_key(None, power)
         return rk
+
+    def encapsulation_keys(self, hamming_weight: int = 32, seed: Optional[int] = None) -> EncapsKeys:
+        """The keys of sparse-secret encapsulation (Bossuat, Troncoso-Pastoriza, Hubaux, ACNS 2022) for bootstrapping under
+        THIS generator's secret s, which may be dense: an auxiliary secret s' of exactly hamming_weight entries of +-1
+        (sparse_ternary_secret) is drawn from a sampler key of its own -- seed=None: from the OS; an integer: tests only --
+        and two switching keys are made, both from that sampler key (streams 1 and 2; the generator's other keys keep their
+        stream ids).  low: s -> s' (hefx_keygen_kswitch(sk = s', new_sk = s)), of which a key switch at the last prime reads
+        digit 0, rows {0, k-1} only; every other word is zeroed before the key leaves the generator, so nothing under s' at
+        the full modulus is published.  high: s' -> s, under the main secret.  s' is not kept on the result."""
+        ctx, be = self.ctx, self.ctx.backend
+        k, N = ctx.k, ctx.N
+        if k < 2:
+            raise ValueError("encapsulation_keys: key switching needs a special prime")
+        key32 = _key32(seed)
+        coef = sparse_ternary_secret(key32, N, hamming_weight)
+        h = be.from_host(np.stack([(coef % int(q)).astype(np.uint64) for q in ctx.primes[:k]])[None])
+        be.ntt_forward(h, 1, k, 0)
+        aux = SecretKey(np.array(be.to_host(h), dtype=np.uint64).reshape(k, N), h)
+        low = np.array(be.to_host(self._kswitch_key(self._sk.host, self._sk.data, sk=aux, key32=key32, sid=1)),
+                       dtype=np.uint64).reshape(k - 1, 2, k, N)
+        keep = low[0][:, [0, k - 1]].copy()
+        low[:] = 0
+        low[0][:, [0, k - 1]] = keep
+        high = self._kswitch_key(aux.host, aux.data, key32=key32, sid=2)
+        return EncapsKeys(be.from_host(low), high, hamming_weight)
 
     def default_galois_elts(self) -> List[int]:
         N = self.ctx.N
@@ -1293,6 +1361,64 @@ class Evaluator:
             new = np.asarray(be.to_host(be.ntt_forward(be.from_host(new), 2, L_out - L_in, L_in))).reshape(2, L_out - L_in, N)
             data = be.from_host(np.concatenate([old, new], axis=1))
         return Ciphertext()._set(data, 2, L_out, ct.scale)
+
+    def switch_key(self, ct: Ciphertext, key) -> Ciphertext:
+        """(c0 + ks0(c1), ks1(c1)) with a switching key [k-1][2][k][N] from the secret ct is under to another one: the key
+        switch of a rotation without its automorphism.  Size 2, any level.  hefx_switch_key where the backend has it, else
+        its apply_galois with the Galois element 1 -- the same words."""
+        if ct.size() != 2:
+            raise ValueError("encrypted size must be 2")
+        L = ct.parms_id()
+        native = getattr(self.be, "switch_key", None)
+        data = native(L, ct.data, key) if native is not None else self.be.apply_galois(L, ct.data, 1, key)
+        return Ciphertext()._set(data, 2, L, ct.scale)
+
+    def raise_switch(self, ct: Ciphertext, keys: "EncapsKeys", parms_id: Optional[int] = None) -> Ciphertext:
+        """Mod-raise under the sparse secret and switch back to the main one, as one step: ct, a size-2 ciphertext at the last
+        prime q_0 under the auxiliary secret of `keys` (switch_key(., keys.low)), comes back at level parms_id (default: the
+        first level) under the main secret, decrypting to m + q_0 I with the I of the SPARSE secret.  x, the centred lift of
+        c1, has |x| < q_0 / 2 -- one digit -- so the switch is moddown(x * Kc) with the collapsed key Kc = sum of the
+        digits of keys.high: 4 L + 3 row transforms where mod_raise + switch_key take about L^2 + 5 L.  The scale is
+        unchanged.  Any N the engine serves, 32768 included.
+
+        hefx_raise_switch where the backend has it (the collapsed key is cached on `keys` per level).  Otherwise the
+        REFERENCE: the backend's ordinary apply_galois(L, ., 1, .) on a synthetic two-digit operand -- x = c1 - q_0 neg,
+        neg the 0/1 polynomial of the coefficients above q_0 // 2, as target rows (c1's row, NTT_q1(neg), zeros) against
+        the key (Kc, (-q_0 mod q_m) Kc, zeros) -- so that every modulus sees x Kc: the same words by exact modular
+        arithmetic, with the lift of c0 (lift_coefficients) as the c0 the key switch adds to."""
+        if ct.size() != 2:
+            raise ValueError("encrypted size must be 2")
+        if ct.parms_id() != 1:
+            raise ValueError("raise_switch: needs a ciphertext at the last prime")
+        L = int(parms_id) if parms_id is not None else self.ctx.first_parms_id()
+        if L < 2 or L > self.ctx.first_parms_id():
+            raise ValueError("raise_switch: the target level must lie between 2 and the first level")
+        be, N, k, q = self.be, self.ctx.N, self.ctx.k, [int(p) for p in self.ctx.primes]
+        native, collapse = getattr(be, "raise_switch", None), getattr(be, "collapse_key", None)
+        if native is not None and collapse is not None:
+            ckey = keys._collapsed.get(L)
+            if ckey is None:
+                ckey = keys._collapsed[L] = collapse(L, keys.high)
+            return Ciphertext()._set(native(L, ct.data, ckey), 2, L, ct.scale)
+        return Ciphertext()._set(self._raise_switch_composed(ct, keys, L), 2, L, ct.scale)
+
+    def _raise_switch_composed(self, ct: Ciphertext, keys: "EncapsKeys", L: int):
+        """raise_switch's words from the backend's ordinary key switch (the reference form its docstring states)"""
+        be, N, k, q = self.be, self.ctx.N, self.ctx.k, [int(p) for p in self.ctx.primes]
+        old = np.array(be.to_host(ct.data), dtype=np.uint64).reshape(2, 1, N)
+        coef = np.asarray(be.to_host(be.ntt_inverse(be.from_host(old), 2, 1, 0))).reshape(2, N)
+        target = np.zeros((2, L, N), dtype=np.uint64)
+        target[:, 0] = old[:, 0]
+        lifted = be.ntt_forward(be.from_host(lift_coefficients(coef[0][None], q, 1, L)), 1, L - 1, 1)
+        target[0, 1:] = np.asarray(be.to_host(lifted)).reshape(L - 1, N)
+        neg = (coef[1] > np.uint64(q[0] // 2)).astype(np.uint64)
+        target[1, 1] = np.asarray(be.to_host(be.ntt_forward(be.from_host(neg[None, None]), 1, 1, 1))).reshape(N)
+        kc = collapse_key_host(be.to_host(keys.high), q, L)
+        synth = np.zeros((k - 1, 2, k, N), dtype=np.uint64)
+        synth[0] = kc
+        for m in range(k):
+            synth[1][:, m] = (kc[:, m].astype(object) * ((-q[0]) % q[m]) % q[m]).astype(np.uint64)
+        return be.apply_galois(L, be.from_host(target), 1, be.from_host(synth))
 
     def plain_combine(self, cts: Sequence[Ciphertext], pts_matrix: Sequence[Sequence[Optional[Plaintext]]]) -> List[Ciphertext]:
         """G plaintext combinations of the same ciphertexts: out[g] = sum_k pts_matrix[g][k] (.) cts[k] over the entries that
