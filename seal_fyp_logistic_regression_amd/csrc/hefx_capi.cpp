@@ -329,6 +329,23 @@ static int ensure_scratch(hefx_context *c, size_t words)
     return grow_retiring(c, &c->scratch, &c->scratch_words, words, (size_t)8 << 20, "scratch");
 }
 
+// The transform of every entry, at every ring size.  Below N = 32768 it is in place on dst (src != dst: after one copy
+// src -> dst); at N = 32768 a row does not fit one workgroup's LDS and the split kernels go src -> dst, src != dst.
+// The convention that makes one code path of it: the pass in front of a transform writes its `words` of rows at
+// rows + xf_raw(c, words), the transform goes rows + raw -> rows, and the scratch is reserved as words + raw.  raw is 0
+// below N = 32768: in place there, no copy, nothing reserved behind.
+static size_t xf_raw(const hefx_context *c, size_t words) { return c->logn == 15 ? words : 0; }
+static hipError_t transform(const hefx_context *c, bool inverse, const u64 *src, u64 *dst, int npoly, int nrows, int mod_first,
+                            hipStream_t s)
+{
+    if (c->logn == 15) return src == dst ? hipErrorInvalidValue : launch_ntt_split15(c->T, inverse, src, dst, npoly, nrows, mod_first, s);
+    if (src != dst) {
+        const hipError_t e = hipMemcpyAsync(dst, src, (size_t)c->n * npoly * nrows * sizeof(u64), hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) return e;
+    }
+    return launch_ntt(c->T, inverse, dst, npoly, nrows, mod_first, s);
+}
+
 // One slot of the descriptor ring: h its pinned host mirror, d its device copy -- KS_MAX_CHUNK key-switch descriptors or,
 // through htab() / dtab(), a table of RING_SLOT_PTRS pointers.  ring_take hands out the next slot once its previous user has
 // drained; the caller fills h, copies it to d (or wherever the descriptors live) and launches on `s`; ring_commit then
@@ -881,14 +898,11 @@ static int ntt_common(hefx_context *c, bool inv, uint64_t *d, int npoly, int nro
     CTXCHK(c);
     if (!d || npoly < 1 || nrows < 1 || mod_first < 0 || mod_first + nrows > c->k)
         return fail(HEFX_ERR_INVALID, "bad NTT arguments");
-    if (c->logn == 15) {  // split kernels are out of place: transform into scratch, copy back
-        const size_t words = (size_t)c->n * npoly * nrows;
-        if (int rc = ensure_scratch(c, words)) return rc;
-        HIPCHK(launch_ntt_split15(c->T, inv, (const u64 *)d, c->scratch, npoly, nrows, mod_first, (hipStream_t)stream));
-        HIPCHK(hipMemcpyAsync(d, c->scratch, words * sizeof(u64), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-        return HEFX_OK;
-    }
-    HIPCHK(launch_ntt(c->T, inv, (u64 *)d, npoly, nrows, mod_first, (hipStream_t)stream));
+    const size_t words = (size_t)c->n * npoly * nrows, raw = xf_raw(c, words);
+    if (int rc = ensure_scratch(c, raw)) return rc;
+    u64 *t = raw ? c->scratch : (u64 *)d;  // out of place: into scratch, and back
+    HIPCHK(transform(c, inv, (const u64 *)d, t, npoly, nrows, mod_first, (hipStream_t)stream));
+    if (raw) HIPCHK(hipMemcpyAsync(d, t, words * sizeof(u64), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return HEFX_OK;
 }
 extern "C" int hefx_ntt_forward(hefx_context *c, uint64_t *d, int npoly, int nrows, int mod_first, void *stream)
@@ -2409,15 +2423,11 @@ static int encode_impl(hefx_context *c, int L, const double *h_re, const double 
         return encode_range_fail(bits);
     hipStream_t s = (hipStream_t)stream;
     if (int rc = stage_encode_values(c, h_re, h_im, nv, s)) return rc;
-    if (c->logn == 15) {  // the N = 32768 transform is out of place: coefficients into scratch, NTT into d_out
-        const size_t words = (size_t)count * L * c->n;
-        if (int rc = ensure_scratch(c, words)) return rc;
-        HIPCHK(launch_encode(c->T, c->E, c->d_vals, h_im ? c->d_vals + nv : nullptr, nvalues, count, scale, L, c->scratch, wide, s));
-        HIPCHK(launch_ntt_split15(c->T, false, c->scratch, (u64 *)d_out, count, L, 0, s));
-        return HEFX_OK;
-    }
-    HIPCHK(launch_encode(c->T, c->E, c->d_vals, h_im ? c->d_vals + nv : nullptr, nvalues, count, scale, L, (u64 *)d_out, wide, s));
-    HIPCHK(launch_ntt(c->T, false, (u64 *)d_out, count, L, 0, s));
+    const size_t raw = xf_raw(c, (size_t)count * L * c->n);  // out of place: coefficients into scratch, NTT into d_out
+    if (int rc = ensure_scratch(c, raw)) return rc;
+    u64 *coef = raw ? c->scratch : (u64 *)d_out;
+    HIPCHK(launch_encode(c->T, c->E, c->d_vals, h_im ? c->d_vals + nv : nullptr, nvalues, count, scale, L, coef, wide, s));
+    HIPCHK(transform(c, false, coef, (u64 *)d_out, count, L, 0, s));
     return HEFX_OK;
 }
 
@@ -3015,6 +3025,24 @@ extern "C" int hefx_sample_noise(hefx_context *c, const uint8_t *key32, uint64_t
     return sample_common(c, SAMPLE_NOISE, key32, stream_id, npoly, nrows, mod_first, out, stream);
 }
 
+// The launches of cnt encryptions with stream ids first_id + i on the block blk = u | e0 | e1, [cnt][L][N] each (and, at
+// N = 32768, xf_raw of those words behind it): item i's polynomials come from the sub-streams 4 (first_id + i) + {0: u,
+// 1: e0, 2: e1}, `stride` being the sampler's step from one item's sub-stream to the next's.  d_tab == nullptr: cnt == 1,
+// plain (may be null) -> out; otherwise the device table  cnt plaintext pointers (null allowed) | cnt output pointers.
+static hipError_t encrypt_launches(const hefx_context *c, int L, int cnt, const SampleKey &k, uint64_t first_id, u64 stride, u64 *blk,
+                                   const u64 *pk, const u64 *plain, u64 *out, const u64 *const *d_tab, hipStream_t s)
+{
+    const size_t poly = (size_t)cnt * L * c->n, raw = xf_raw(c, 3 * poly);
+    const uint64_t sid = 4 * first_id;
+    const u64 *e0 = blk + poly;
+    hipError_t e = launch_sample(c->T, SAMPLE_TERNARY, k, c->noise, sid + 0, cnt, L, 0, blk + raw, s, stride);
+    if (e == hipSuccess) e = launch_sample(c->T, SAMPLE_NOISE, k, c->noise, sid + 1, cnt, L, 0, blk + raw + poly, s, stride);
+    if (e == hipSuccess) e = launch_sample(c->T, SAMPLE_NOISE, k, c->noise, sid + 2, cnt, L, 0, blk + raw + 2 * poly, s, stride);
+    if (e == hipSuccess) e = transform(c, false, blk + raw, blk, 3 * cnt, L, 0, s);
+    if (e != hipSuccess) return e;
+    return d_tab ? launch_encrypt_combine_table(c->T, L, cnt, pk, blk, e0, d_tab, s) : launch_encrypt_combine(c->T, L, pk, blk, e0, plain, out, s);
+}
+
 extern "C" int hefx_encrypt(hefx_context *c, int L, const uint64_t *pk, const uint64_t *plain, const uint8_t *key32,
                             uint64_t stream_id, uint64_t *out, void *stream)
 {
@@ -3026,23 +3054,9 @@ extern "C" int hefx_encrypt(hefx_context *c, int L, const uint64_t *pk, const ui
     if (int rc = check_ranges("encrypt", 1, &out, 2 * rowsz * sizeof(u64),
                               {{&pk, 1, 2 * (size_t)c->k * N * sizeof(u64)}, {&plain, 1, rowsz * sizeof(u64)}}, {"d_pk", "d_plain"}))
         return rc;
-    const bool split = c->logn == 15;  // the N = 32768 transform is out of place
-    if (int rc = ensure_scratch(c, (split ? 6 : 3) * rowsz)) return rc;
-    u64 *u = c->scratch, *e = u + rowsz;
-    hipStream_t s = (hipStream_t)stream;
-    const SampleKey k = sample_key(key32);
-    // sub-streams 4*id + {0: u, 1: e0, 2: e1}
-    HIPCHK(launch_sample(c->T, SAMPLE_TERNARY, k, c->noise, 4 * stream_id + 0, 1, L, 0, u, s));
-    HIPCHK(launch_sample(c->T, SAMPLE_NOISE, k, c->noise, 4 * stream_id + 1, 1, L, 0, e, s));
-    HIPCHK(launch_sample(c->T, SAMPLE_NOISE, k, c->noise, 4 * stream_id + 2, 1, L, 0, e + rowsz, s));
-    if (split) {
-        HIPCHK(launch_ntt_split15(c->T, false, u, u + 3 * rowsz, 3, L, 0, s));
-        u += 3 * rowsz;
-        e += 3 * rowsz;
-    } else {
-        HIPCHK(launch_ntt(c->T, false, u, 3, L, 0, s));
-    }
-    HIPCHK(launch_encrypt_combine(c->T, L, (const u64 *)pk, u, e, (const u64 *)plain, (u64 *)out, s));
+    if (int rc = ensure_scratch(c, 3 * rowsz + xf_raw(c, 3 * rowsz))) return rc;
+    HIPCHK(encrypt_launches(c, L, 1, sample_key(key32), stream_id, 0, c->scratch, (const u64 *)pk, (const u64 *)plain, (u64 *)out,
+                            nullptr, (hipStream_t)stream));
     return HEFX_OK;
 }
 
@@ -3088,13 +3102,7 @@ extern "C" int hefx_encrypt_batch(hefx_context *c, int L, int n, const uint64_t 
             }
         },
         [&](const u64 *const *dp, int i0, int cnt) -> int {  // cnt <= cap: one slice, one set of launches
-            u64 *u = c->scratch, *ee = u + (size_t)cnt * rowsz;
-            const uint64_t sid = 4 * (first_stream_id + (uint64_t)i0);
-            HIPCHK(launch_sample(c->T, SAMPLE_TERNARY, k, c->noise, sid + 0, cnt, L, 0, u, s, 4));
-            HIPCHK(launch_sample(c->T, SAMPLE_NOISE, k, c->noise, sid + 1, cnt, L, 0, ee, s, 4));
-            HIPCHK(launch_sample(c->T, SAMPLE_NOISE, k, c->noise, sid + 2, cnt, L, 0, ee + (size_t)cnt * rowsz, s, 4));
-            HIPCHK(launch_ntt(c->T, false, u, 3 * cnt, L, 0, s));
-            HIPCHK(launch_encrypt_combine_table(c->T, L, cnt, (const u64 *)pk, u, ee, dp, s));
+            HIPCHK(encrypt_launches(c, L, cnt, k, first_stream_id + (uint64_t)i0, 4, c->scratch, (const u64 *)pk, nullptr, nullptr, dp, s));
             return HEFX_OK;
         },
         cap);
@@ -3122,23 +3130,18 @@ extern "C" int hefx_keygen_kswitch(hefx_context *c, const uint64_t *sk, const ui
     if (!sk || !new_sk || !key32 || !out) return fail(HEFX_ERR_INVALID, "bad key generation arguments");
     if (stream_id >> 62) return fail(HEFX_ERR_INVALID, "stream id must be below 2^62");
     const size_t N = c->n, words = (size_t)(c->k - 1) * c->k * N;
-    const bool split = c->logn == 15;
     if (int rc = check_ranges("keygen_kswitch", 1, &out, 2 * words * sizeof(u64),
                               {{&sk, 1, (size_t)c->k * N * sizeof(u64)}, {&new_sk, 1, (size_t)c->k * N * sizeof(u64)}}, {"d_sk", "d_new_sk"}))
         return rc;
-    if (int rc = ensure_scratch(c, (split ? 3 : 2) * words)) return rc;
+    const size_t raw = xf_raw(c, words);
+    if (int rc = ensure_scratch(c, 2 * words + raw)) return rc;
     u64 *a = c->scratch, *e = a + words;
     hipStream_t s = (hipStream_t)stream;
     const SampleKey k = sample_key(key32);
     // sub-streams 2*id: uniform a, 2*id+1: noise e
     HIPCHK(launch_sample(c->T, SAMPLE_UNIFORM, k, c->noise, 2 * stream_id, c->k - 1, c->k, 0, a, s));
-    HIPCHK(launch_sample(c->T, SAMPLE_NOISE, k, c->noise, 2 * stream_id + 1, c->k - 1, c->k, 0, e, s));
-    if (split) {
-        HIPCHK(launch_ntt_split15(c->T, false, e, e + words, c->k - 1, c->k, 0, s));
-        e += words;
-    } else {
-        HIPCHK(launch_ntt(c->T, false, e, c->k - 1, c->k, 0, s));
-    }
+    HIPCHK(launch_sample(c->T, SAMPLE_NOISE, k, c->noise, 2 * stream_id + 1, c->k - 1, c->k, 0, e + raw, s));
+    HIPCHK(transform(c, false, e + raw, e, c->k - 1, c->k, 0, s));
     HIPCHK(launch_keygen_combine(c->T, (const u64 *)sk, (const u64 *)new_sk, a, e, (u64 *)out, s));
     return HEFX_OK;
 }
@@ -3200,8 +3203,7 @@ extern "C" int hefx_ckks_decode(hefx_context *c, int L, const uint64_t *d_pt, in
     if (!(scale > 0)) return fail(HEFX_ERR_INVALID, "scale out of bounds");
     if (int rc = ensure_encode_tables(c)) return rc;
     const size_t N = c->n, words = (size_t)count * L * N;
-    const bool split = c->logn == 15;
-    if (int rc = ensure_scratch(c, (split ? 2 : 1) * words)) return rc;
+    if (int rc = ensure_scratch(c, words)) return rc;
     const size_t ndbl = (size_t)count * N * 2;  // p [count][N] | re [count][N/2] | im [count][N/2]
     if (c->vals_cap < ndbl) {
         if (c->d_vals) {
@@ -3215,12 +3217,7 @@ extern "C" int hefx_ckks_decode(hefx_context *c, int L, const uint64_t *d_pt, in
     }
     hipStream_t s = (hipStream_t)stream;
     u64 *coef = c->scratch;
-    if (split) {
-        HIPCHK(launch_ntt_split15(c->T, true, (const u64 *)d_pt, coef, count, L, 0, s));
-    } else {
-        HIPCHK(hipMemcpyAsync(coef, d_pt, words * sizeof(u64), hipMemcpyDeviceToDevice, s));
-        HIPCHK(launch_ntt(c->T, true, coef, count, L, 0, s));
-    }
+    HIPCHK(transform(c, true, (const u64 *)d_pt, coef, count, L, 0, s));
     double *p = c->d_vals, *re = p + (size_t)count * N, *im = re + (size_t)count * (N / 2);
     HIPCHK(launch_decode(c->T, c->E, decode_tables(c, L), L, coef, count, scale, p, re, h_im ? im : nullptr, s));
     HIPCHK(hipMemcpyAsync(h_re, re, sizeof(double) * count * (N / 2), hipMemcpyDeviceToHost, s));
@@ -3257,16 +3254,16 @@ static hipError_t lift_rows(hefx_context *c, int L_in, int L_out, int cnt, u64 *
 {
     const size_t N = c->n;
     const int Ln = L_out - L_in;
-    hipError_t e = launch_ntt(c->T, true, coef, cnt, L_in, 0, s);
+    hipError_t e = transform(c, true, coef, coef, cnt, L_in, 0, s);
     if (e != hipSuccess) return e;
     const LiftTables D = lift_tables(c, L_in, L_out);
     if (cnt == 1) {
         e = launch_lift(c->T, D, c->d_qmod, L_in, L_out, 1, coef, dst, 0, s);
-        if (e == hipSuccess) e = launch_ntt(c->T, false, dst, 1, Ln, L_in, s);
+        if (e == hipSuccess) e = transform(c, false, dst, dst, 1, Ln, L_in, s);
         return e;
     }
     e = launch_lift(c->T, D, c->d_qmod, L_in, L_out, cnt, coef, w, (size_t)Ln * N, s);
-    if (e == hipSuccess) e = launch_ntt(c->T, false, w, cnt, Ln, L_in, s);
+    if (e == hipSuccess) e = transform(c, false, w, w, cnt, Ln, L_in, s);
     if (e == hipSuccess)
         e = hipMemcpy2DAsync(dst, dst_stride * sizeof(u64), w, (size_t)Ln * N * sizeof(u64), (size_t)Ln * N * sizeof(u64),
                              (size_t)cnt, hipMemcpyDeviceToDevice, s);
@@ -3304,27 +3301,19 @@ static int refresh_args(const hefx_context *c, int L_in, int size, int L_out)
 }
 
 // One group of cnt items: decrypt into the plaintext rows p[cnt][L_out][N] (and a copy for the inverse transform), lift,
-// then hefx_encrypt[_batch]'s launches on u[3 cnt][L_out][N].  d_tab == nullptr: cnt == 1, ciphertext ct -> out;
+// then encrypt_launches on u[3 cnt][L_out][N].  d_tab == nullptr: cnt == 1, ciphertext ct -> out;
 // otherwise the device table  cnt plaintext pointers (into p) | cnt output pointers | cnt ciphertext pointers.
 static hipError_t refresh_group(hefx_context *c, int L_in, int size, int L_out, int cnt, const u64 *ct, u64 *out,
                                 const u64 *const *d_tab, const u64 *sk, const u64 *pk, const SampleKey &k, uint64_t first_id,
                                 hipStream_t s)
 {
     const size_t N = c->n, rowsz = (size_t)L_out * N;
-    u64 *u = c->scratch, *ee = u + (size_t)cnt * rowsz, *p = u + 3 * (size_t)cnt * rowsz;
+    u64 *u = c->scratch, *p = u + 3 * (size_t)cnt * rowsz;
     u64 *coef = p + (size_t)cnt * rowsz, *w = coef + (size_t)cnt * L_in * N;
     hipError_t e = launch_decrypt_items(c->T, L_in, size, cnt, ct, d_tab ? d_tab + 2 * cnt : nullptr, sk, p, rowsz,
                                         L_in < L_out ? coef : nullptr, s);
     if (e == hipSuccess && L_in < L_out) e = lift_rows(c, L_in, L_out, cnt, coef, w, p + (size_t)L_in * N, rowsz, s);
-    const uint64_t sid = 4 * first_id;
-    const u64 stride = d_tab ? 4 : 0;
-    if (e == hipSuccess) e = launch_sample(c->T, SAMPLE_TERNARY, k, c->noise, sid + 0, cnt, L_out, 0, u, s, stride);
-    if (e == hipSuccess) e = launch_sample(c->T, SAMPLE_NOISE, k, c->noise, sid + 1, cnt, L_out, 0, ee, s, stride);
-    if (e == hipSuccess) e = launch_sample(c->T, SAMPLE_NOISE, k, c->noise, sid + 2, cnt, L_out, 0, ee + (size_t)cnt * rowsz, s, stride);
-    if (e == hipSuccess) e = launch_ntt(c->T, false, u, 3 * cnt, L_out, 0, s);
-    if (e == hipSuccess)
-        e = d_tab ? launch_encrypt_combine_table(c->T, L_out, cnt, pk, u, ee, d_tab, s)
-                  : launch_encrypt_combine(c->T, L_out, pk, u, ee, p, out, s);
+    if (e == hipSuccess) e = encrypt_launches(c, L_out, cnt, k, first_id, d_tab ? 4 : 0, u, pk, p, out, d_tab, s);
     return e;
 }
 // scratch words of one group: u, e0, e1, the plaintext, its coefficient copy, the lifted rows
@@ -3419,15 +3408,6 @@ extern "C" int hefx_collapse_key(hefx_context *c, int L, const uint64_t *key, ui
     return HEFX_OK;
 }
 
-// a transform of hefx_raise_switch's scratch rows: in place below N = 32768 (raw == done), through the out-of-place split
-// launcher there (raw -> done)
-static hipError_t rs_transform(const hefx_context *c, bool inverse, const u64 *raw, u64 *done, int npoly, int nrows, int mod_first,
-                               hipStream_t s)
-{
-    if (c->logn == 15) return launch_ntt_split15(c->T, inverse, raw, done, npoly, nrows, mod_first, s);
-    return launch_ntt(c->T, inverse, done, npoly, nrows, mod_first, s);
-}
-
 extern "C" int hefx_raise_switch(hefx_context *c, int L, const uint64_t *ct_in, const uint64_t *ckey, uint64_t *ct_out, void *stream)
 {
     CTXCHK(c);
@@ -3439,27 +3419,20 @@ extern "C" int hefx_raise_switch(hefx_context *c, int L, const uint64_t *ct_in, 
                               {"d_ct_in", "d_ckey"}))
         return rc;
     // scratch, in rows of N words: coef [2] | xb [2 (L-1)] | xp [1] | accp [2] | tt [2 L]  = 4 L + 3 rows, every one of them
-    // transformed exactly once; at N = 32768 a second set behind it, which the element-wise passes write and the
-    // out-of-place transforms read (the first inverse transform reads the caller's input: no copy there)
-    const bool split = c->logn == 15;
-    const size_t set = (size_t)(4 * L + 3) * N;
-    if (int rc = ensure_scratch(c, set * (split ? 2 : 1))) return rc;
+    // transformed exactly once; at N = 32768 a second set behind it (raw), which the element-wise passes write and the
+    // transforms read (the first inverse transform reads the caller's input)
+    const size_t set = (size_t)(4 * L + 3) * N, raw = xf_raw(c, set);
+    if (int rc = ensure_scratch(c, set + raw)) return rc;
     hipStream_t s = (hipStream_t)stream;
     u64 *coef = c->scratch, *xb = coef + 2 * N, *xp = xb + 2 * (size_t)(L - 1) * N, *accp = xp + N, *tt = accp + 2 * N;
-    const size_t raw = split ? set : 0;  // where a pass writes what the next transform reads
-    if (split) {
-        HIPCHK(launch_ntt_split15(c->T, true, (const u64 *)ct_in, coef, 2, 1, 0, s));
-    } else {
-        HIPCHK(hipMemcpyAsync(coef, ct_in, 2 * row, hipMemcpyDeviceToDevice, s));
-        HIPCHK(launch_ntt(c->T, true, coef, 2, 1, 0, s));
-    }
+    HIPCHK(transform(c, true, (const u64 *)ct_in, coef, 2, 1, 0, s));
     HIPCHK(launch_rs_expand(c->T, L, coef, xb + raw, xp + raw, s));
-    HIPCHK(rs_transform(c, false, xb + raw, xb, 2, L - 1, 1, s));
-    HIPCHK(rs_transform(c, false, xp + raw, xp, 1, 1, c->k - 1, s));
+    HIPCHK(transform(c, false, xb + raw, xb, 2, L - 1, 1, s));
+    HIPCHK(transform(c, false, xp + raw, xp, 1, 1, c->k - 1, s));
     HIPCHK(launch_rs_product_p(c->T, L, xp, (const u64 *)ckey, accp + raw, s));
-    HIPCHK(rs_transform(c, true, accp + raw, accp, 2, 1, c->k - 1, s));
+    HIPCHK(transform(c, true, accp + raw, accp, 2, 1, c->k - 1, s));
     HIPCHK(launch_rs_spread(c->T, L, accp, tt + raw, s));
-    HIPCHK(rs_transform(c, false, tt + raw, tt, 2, L, 0, s));
+    HIPCHK(transform(c, false, tt + raw, tt, 2, L, 0, s));
     HIPCHK(launch_rs_finish(c->T, L, (const u64 *)ct_in, xb, (const u64 *)ckey, tt, (u64 *)ct_out, s));
     return HEFX_OK;
 }

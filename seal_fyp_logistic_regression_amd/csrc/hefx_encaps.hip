@@ -1,6 +1,6 @@
 // hefx_encaps.hip -- the element-wise kernels of sparse-secret encapsulation (include/hefx_encaps.h): the collapsed key and
-// the four passes between the transforms of hefx_raise_switch.  The transforms themselves are the engine's (launch_ntt,
-// launch_ntt_split15 at N = 32768); the host sequence is hefx_capi.cpp's.
+// the four passes between the transforms of hefx_raise_switch.  The transforms themselves are the engine's, through
+// hefx_capi.cpp's transform() at every ring size; the host sequence is hefx_capi.cpp's.
 //
 // hefx_raise_switch, pass by pass (L = L_out, P = q_(k-1); every arrow that crosses a line is a transform):
 //   in [2][1][N]            --INTT_q0-->   coef [2][N]                        (c0, c1 in coefficient form)

@@ -304,6 +304,49 @@ def test_ckks_encode_batch_equals_contiguous_encode(setname, L, count, nvalues):
         assert (outs[i].download() == want[i]).all(), i
 
 
+def _engine_32768():
+    """N = 32768 over CoeffModulus.Create(32768, [60, 40, 60]): the batch entries take their item-by-item path there"""
+    from seal_fyp_logistic_regression_amd import Engine, seal as S
+    primes = [int(p) for p in S.CoeffModulus.Create(32768, [60, 40, 60])]
+    return Engine(32768, primes), len(primes)
+
+
+def test_encrypt_batch_at_32768_equals_single_encryptions_word_for_word():
+    """hefx_encrypt_batch at N = 32768 (item by item: the transform is out of place there), L = 2, three items of which one
+    encrypts zero, stream ids above 2^33: every output is hefx_encrypt's with the ids s0 + i, word for word.  hefx_encrypt
+    is pinned against the oracle at this size in test_gpu_sampling.py."""
+    e, k = _engine_32768()
+    N, L, n = 32768, 2, 3
+    key32 = bytes((11 * i + 5) & 0xFF for i in range(32))
+    pk = e.sample("uniform", bytes(range(32)), 3, 2, k, 0)
+    big = e.sample("uniform", bytes(range(32)), 4, n, L, 0)
+    plains = [big.view(i * L * N, (L, N)) for i in range(n)]
+    plains[1] = None
+    s0 = 2 ** 33 + 7
+    outs = e.encrypt_batch(L, pk, plains, key32, s0)
+    for i in range(n):
+        assert (outs[i].download() == e.encrypt(L, pk, plains[i], key32, s0 + i).download()).all(), i
+    e.close()
+
+
+@pytest.mark.parametrize("wide", [False, True])
+def test_ckks_encode_batch_at_32768_equals_contiguous_encode(wide):
+    """hefx_ckks_encode_batch / hefx_ckks_encode_wide_batch at N = 32768 (vector by vector), L = 2, three vectors of five
+    values: the words of the contiguous single-call encode of the same vectors, which test_gpu_encode.py and
+    test_gpu_encode_wide.py pin against the exact model."""
+    e, _ = _engine_32768()
+    N, L, count, nvalues = 32768, 2, 3, 5
+    vals = np.random.default_rng(32768 + wide).uniform(-3, 3, (count, nvalues))
+    vals[0, :] = 0.0
+    vals[0, 0] = 1.0
+    one, batch, scale = (e.ckks_encode_wide, e.ckks_encode_wide_batch, 2.0 ** 80) if wide else (e.ckks_encode, e.ckks_encode_batch, 2.0 ** 40)
+    want = one(L, vals, scale).download().reshape(count, L, N)
+    outs = batch(L, vals, scale)
+    for i in range(count):
+        assert (outs[i].download() == want[i]).all(), i
+    e.close()
+
+
 def test_large_chunks_bit_exact_and_device_memory():
     """HEFX_CHUNK above 256 (the descriptor ring's slots hold 512 items since round 4; the size rule itself still stops at
     256): 600 items at N = 8192 as chunks of 512 + 88, a sample of outputs word for word against the oracle; and

@@ -113,6 +113,30 @@ def test_row_transforms_every_degree_both_policies(N):
     e.close()
 
 
+@pytest.mark.parametrize("N", [4096, 32768])
+def test_row_transforms_from_the_second_prime_leave_the_rows_behind_alone(N):
+    """hefx_ntt_forward / hefx_ntt_inverse with npoly = 2, nrows = 2, mod_first = 1 (rows under primes 1, 2 of a chain of
+    three) on the first four rows of a six-row buffer, in place below N = 32768 and through scratch and back there: every
+    row is the oracle's transform under ITS prime, the two rows behind keep their words, the round trip returns the input."""
+    from oracle import oracle as O
+    from seal_fyp_logistic_regression_amd import Engine, seal as S
+    primes = [int(p) for p in S.CoeffModulus.Create(N, [60, 40, 60])]
+    o, e = O.Oracle(N, primes), Engine(N, primes)
+    rng = np.random.default_rng(77 + N)
+    x = np.stack([rng.integers(0, primes[1 + r % 2], N, dtype=np.uint64) for r in range(4)] +
+                 [rng.integers(0, 2 ** 64, N, dtype=np.uint64, endpoint=False) for _ in range(2)])  # [2 x 2 rows | 2 rows behind][N]
+    x[3, :] = primes[2] - 1
+    d = e.to_device(x)
+    e.ntt_forward(d, 2, 2, 1)
+    got = d.download().reshape(6, N)
+    for r in range(4):
+        assert (got[r] == o.ntt_fwd(1 + r % 2, x[r])).all(), r
+    assert (got[4:] == x[4:]).all()
+    e.ntt_inverse(d, 2, 2, 1)
+    assert (d.download().reshape(6, N) == x).all()
+    e.close()
+
+
 def test_cc_matrix_multiplication_n8_config5_dense_bit_exact(rescale_mode):
     """BASELINE config 5 as SURVEY App. B reads it -- "64 x 64" are the U matrices, i.e. n = 8, exactly as config 3's
     "16 x 16" is n = 4 -- in the reference's EXACT composition (matrix_mult_benchmark.cpp:13-71: all 64 diagonals of every
