@@ -14,7 +14,23 @@ import operator
 import numpy as np
 
 from . import poly as _poly
-from .seal import Ciphertext, CKKSEncoder, Evaluator, KSwitchKeys, Plaintext
+from .seal import Ciphertext, CKKSEncoder, Evaluator, HybridKeys, KSwitchKeys, Plaintext
+
+
+def _kswitch_only(fn):
+    """The fused composites -- the linear transforms, the plain_combine / product_combine pipelines, the bootstrap -- run kernels
+    that know the one-special-prime key layout: given seal.HybridKeys they refuse before anything is computed.  (Routing them
+    through hybrid key switching is a change of its own.)"""
+    import functools
+
+    @functools.wraps(fn)
+    def checked(*args, **kwargs):
+        for a in (*args, *kwargs.values()):
+            if isinstance(a, HybridKeys):
+                raise TypeError(f"{fn.__name__} with HybridKeys (alpha = {a.alpha}) is not supported: hybrid key switching serves "
+                                "Evaluator.rotate_vector, apply_galois, complex_conjugate, relinearize and switch_key only")
+        return fn(*args, **kwargs)
+    return checked
 
 
 # ---- plain data prep (L0) -------------------------------------------------------------------
@@ -153,6 +169,7 @@ def _duplicate(ev: Evaluator, ct: Ciphertext, d: int, gal_keys: KSwitchKeys) -> 
     return ev.add(ct, ev.rotate_vector(ct, -d, gal_keys))            # helper.h:244-247
 
 
+@_kswitch_only
 def linear_transform_plain(ev: Evaluator, ct: Ciphertext, U_diagonals: Sequence[Plaintext],
                            gal_keys: KSwitchKeys, hoisted: bool = False) -> Ciphertext:
     """Linear_Transform_Plain, helper.h:237-262 (= linear_transformation2.cpp:149-174).
@@ -230,6 +247,7 @@ def _linear_transform_plain_native(ev: Evaluator, native, ct: Ciphertext, U_diag
     return Ciphertext()._set(data, 2, L, scale)
 
 
+@_kswitch_only
 def linear_transforms_plain_many(ev: Evaluator, cts: Sequence[Ciphertext], diag_sets: Sequence[Sequence[Plaintext]],
                                  gal_keys: KSwitchKeys) -> List[Ciphertext]:
     """[Linear_Transform_Plain(cts[t], diag_sets[t], gal_keys) for t] -- INDEPENDENT transforms of one dimension, e.g.
@@ -285,6 +303,7 @@ def bsgs_diagonals(diagonals: np.ndarray, n1: int = None) -> List[np.ndarray]:
     return out
 
 
+@_kswitch_only
 def linear_transform_plain_bsgs(ev: Evaluator, ct: Ciphertext, shifted_diagonals: Sequence[Plaintext],
                                 gal_keys: KSwitchKeys, n1: int = None, hoisted: bool = True) -> Ciphertext:
     """Linear_Transform_Plain (helper.h:237-262) in baby-step / giant-step form; `shifted_diagonals` are the
@@ -319,6 +338,7 @@ def linear_transform_plain_bsgs(ev: Evaluator, ct: Ciphertext, shifted_diagonals
     return ev.add_many(inner)
 
 
+@_kswitch_only
 def linear_transform_cipher(ev: Evaluator, ct: Ciphertext, U_diagonals: Sequence[Ciphertext],
                             gal_keys: KSwitchKeys) -> Ciphertext:
     """Linear_Transform_Cipher, helper.h:212-234: ct x ct products are NOT relinearized (size-3 sum)."""
@@ -597,6 +617,7 @@ def _sparse_products(ev: Evaluator, ct_new: Ciphertext, terms, gal_keys: KSwitch
     return out
 
 
+@_kswitch_only
 def linear_transform_plain_sparse(ev: Evaluator, ct: Ciphertext, d: int, diagonals: dict,
                                   gal_keys: KSwitchKeys, hoisted: bool = False) -> Ciphertext:
     """Linear_Transform_Plain (helper.h:237-262) of a d x d matrix given by its non-zero diagonals {l: Plaintext}"""
@@ -752,6 +773,7 @@ def _run_plan(ev: Evaluator, cts: List[Ciphertext], coeffs, relin_keys: KSwitchK
 
 
 # ---- EvalMod and bootstrapping (bootstrap.py plans, these run) -----------------------------------------------------------------
+@_kswitch_only
 def eval_mod(ev: Evaluator, cts: Sequence[Ciphertext], plan, relin_keys: KSwitchKeys, lazy: bool = True) -> List[Ciphertext]:
     """EvalMod on n ciphertexts in lockstep (the two outputs of CoeffToSlot): slots u = (I + eps) / K' in [-1, 1] become
     sin(2 pi eps), about 2 pi eps.  The Chebyshev interpolant of cos((2 pi K' u - pi / 2) / 2^r) through
@@ -772,6 +794,7 @@ def eval_mod(ev: Evaluator, cts: Sequence[Ciphertext], plan, relin_keys: KSwitch
     return ys
 
 
+@_kswitch_only
 def bootstrap(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitchKeys, relin_keys: KSwitchKeys, encoded=None,
               encaps=None) -> Ciphertext:
     """CKKS bootstrapping with evaluation keys only: a size-2 ciphertext at the last prime q_0 and scale plan.scale comes back
@@ -861,6 +884,7 @@ def _dft_run(ev: Evaluator, xs: List[Ciphertext], plan, gal_keys: KSwitchKeys, e
     return xs
 
 
+@_kswitch_only
 def coeffs_to_slots(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitchKeys, encoded=None):
     """CoeffToSlot: (ct_a, ct_b) whose slots hold the coefficients of ct's plaintext, ct_a[i] = m_R(i) / scale and
     ct_b[i] = m_(N/2 + R(i)) / scale (R: bit reversal of the N/2 slot indices, dft.bit_reversal), both plan.levels levels
@@ -875,6 +899,7 @@ def coeffs_to_slots(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitchKeys, 
     return tuple(ev.add(x, ev.complex_conjugate(x, gal_keys)) for x in xs)    # 2 Re(.)
 
 
+@_kswitch_only
 def slots_to_coeffs(ev: Evaluator, ct_a: Ciphertext, ct_b: Ciphertext, plan, gal_keys: KSwitchKeys, encoded=None) -> Ciphertext:
     """SlotToCoeff, the inverse map: from ct_a, ct_b with REAL slots x_a, x_b (in the bit-reversed order coeffs_to_slots
     leaves) the ciphertext whose plaintext has the coefficients scale * x_a[R^-1], scale * x_b[R^-1] -- slots
@@ -887,6 +912,7 @@ def slots_to_coeffs(ev: Evaluator, ct_a: Ciphertext, ct_b: Ciphertext, plan, gal
 
 
 # ---- sparse packing: a message of ns <= N/4 slots (dft.plan_packed plans, these run) ----------------------------------------
+@_kswitch_only
 def subsum(ev: Evaluator, ct: Ciphertext, ns: int, gal_keys: KSwitchKeys) -> Ciphertext:
     """SubSum: x <- x + rotate_vector(x, ns 2^i) for i < log2 g, g = N / (2 ns).  The steps generate the Galois group that
     fixes the polynomials in X^g, so a plaintext t becomes g times its coefficients at the multiples of g (the slots: the sum
@@ -918,6 +944,7 @@ def _packed_plan(ev: Evaluator, plan, direction: str, name: str):
         raise ValueError(name + ": the plan is not a packed plan of this direction and ring")
 
 
+@_kswitch_only
 def coeffs_to_slots_packed(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitchKeys, encoded=None) -> Ciphertext:
     """CoeffToSlot of a sparsely packed ciphertext: ct's slots are ns-periodic, z tiled (subsum's result); the ONE result has
     2 ns-periodic real slots [R a | R b] tiled, a and b the halves of the 2 ns coefficients on the stride (times the plan's
@@ -929,6 +956,7 @@ def coeffs_to_slots_packed(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitc
     return ev.add(x, ev.complex_conjugate(x, gal_keys))
 
 
+@_kswitch_only
 def slots_to_coeffs_packed(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitchKeys, encoded=None) -> Ciphertext:
     """SlotToCoeff, the inverse map: from real slots [x_a | x_b] tiled to the ns-periodic slots [z | z] tiled of the plaintext
     with x_a[R^-1], x_b[R^-1] on the stride.  plan: dft.plan_packed(N, ns, levels, dft.S2C, ...)."""

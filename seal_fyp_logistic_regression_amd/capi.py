@@ -222,6 +222,16 @@ _ENCAPS_SIGS = {
 }
 ENCAPS_SYMBOLS = sorted(_ENCAPS_SIGS)
 
+# include/hefx_hybrid.h: hybrid key switching (alpha data primes per digit, alpha special primes)
+_HYBRID_SIGS = {
+    "hefx_hybrid_digits": (_i, [_vp, _i]),
+    "hefx_hybrid_keygen": (_i, [_vp, _i, _vp, _vp, C.c_char_p, _u64, _vp, _vp]),
+    "hefx_hybrid_apply_galois_batch": (_i, [_vp, _i, _i, _i, _pp, C.POINTER(_u32), _pp, _pp, _vp]),
+    "hefx_hybrid_relinearize_batch": (_i, [_vp, _i, _i, _i, _pp, _vp, _pp, _vp]),
+}
+HYBRID_SYMBOLS = sorted(_HYBRID_SIGS)
+HYBRID_ALPHA_MAX = 8  # HEFX_HYBRID_ALPHA_MAX
+
 
 def product_combine_words(L: int, n: int, P: int, m: int) -> int:
     """words of hefx_product_combine's table with a constant: strides, weights and the constant per row, n pointer records"""
@@ -244,7 +254,7 @@ def lib():
     L = C.CDLL(path, mode=C.RTLD_GLOBAL)
     for name, (res, args) in (list(_SIGS.items()) + list(_REFRESH_SIGS.items()) + list(_BFV_SIGS.items())
                               + list(_POLY_SIGS.items()) + list(_DFT_SIGS.items()) + list(_BOOTSTRAP_SIGS.items())
-                              + list(_ENCAPS_SIGS.items())):
+                              + list(_ENCAPS_SIGS.items()) + list(_HYBRID_SIGS.items())):
         f = getattr(L, name)
         f.restype = res
         f.argtypes = args

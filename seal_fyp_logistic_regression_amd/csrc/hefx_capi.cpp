@@ -9,6 +9,7 @@
 #include "../../include/hefx_dft.h"
 #include "../../include/hefx_bootstrap.h"
 #include "../../include/hefx_encaps.h"
+#include "../../include/hefx_hybrid.h"
 
 #include <chrono>
 #include <cmath>
@@ -194,6 +195,12 @@ static inline uint32_t h_bitrev(uint32_t x, int bits)
 // ---------------------------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------------------------
+// hybrid key switching: the constants of one (alpha, L) pair as the kernels' table holds them (HyTab's offsets, tab and items unset)
+struct HybridConsts {
+    std::vector<u64> words;
+    HyTab at{};
+};
+
 struct hefx_context {
     int device = 0;
     uint32_t n = 0;
@@ -282,6 +289,7 @@ struct hefx_context {
     size_t prof_chunks = 0;
     // hefx_ks_stats: key switches submitted / of them exactly hoisted / launch sequences / batched calls (host-side counts)
     uint64_t stat_ks_items = 0, stat_ks_hoisted = 0, stat_ks_chunks = 0, stat_ks_calls = 0;
+    std::map<std::pair<int, int>, HybridConsts> hybrid;  // (alpha, L) -> constants, built on the host at first use (under mu)
 };
 
 // The scratch buffer grows geometrically and WITHOUT waiting for the device: a buffer that became too small is retired, not
@@ -3434,6 +3442,196 @@ extern "C" int hefx_raise_switch(hefx_context *c, int L, const uint64_t *ct_in, 
     HIPCHK(launch_rs_spread(c->T, L, accp, tt + raw, s));
     HIPCHK(transform(c, false, tt + raw, tt, 2, L, 0, s));
     HIPCHK(launch_rs_finish(c->T, L, (const u64 *)ct_in, xb, (const u64 *)ckey, tt, (u64 *)ct_out, s));
+    return HEFX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// hybrid key switching (include/hefx_hybrid.h, hefx_hybrid.hip)
+// ---------------------------------------------------------------------------------------------
+static_assert(HY_ALPHA_MAX == HEFX_HYBRID_ALPHA_MAX, "hefx_internal.h and hefx_hybrid.h disagree");
+static int check_hybrid_alpha(const hefx_context *c, int alpha)
+{
+    if (c->logn < 11) return fail(HEFX_ERR_UNSUPPORTED, "key switching / rescale need poly_degree >= 2048");
+    if (alpha < 1 || alpha >= c->k || alpha > HEFX_HYBRID_ALPHA_MAX)
+        return fail(HEFX_ERR_INVALID, "hybrid key switching: alpha must be in [1, min(k - 1, HEFX_HYBRID_ALPHA_MAX = " +
+                                          std::to_string(HEFX_HYBRID_ALPHA_MAX) + ")]");
+    return HEFX_OK;
+}
+static int hybrid_digits(int alpha, int rows) { return (rows + alpha - 1) / alpha; }
+
+extern "C" int hefx_hybrid_digits(hefx_context *c, int alpha)
+{
+    if (!c) return fail(HEFX_ERR_INVALID, "null context");
+    if (int rc = check_hybrid_alpha(c, alpha)) return rc;
+    return hybrid_digits(alpha, c->k - alpha);
+}
+
+// prod_{i in rows, i != skip} q_i mod q
+static u64 h_prod_mod(const hefx_context *c, int first, int last, int skip, u64 q)
+{
+    u64 r = 1 % q;
+    for (int i = first; i < last; ++i)
+        if (i != skip) r = h_mulmod(r, c->primes[i] % q, q);
+    return r;
+}
+
+// The constants of (alpha, L), host only, once per pair (HyTab's layout).  All of them are products of at most k primes
+// mod a prime: k^2 alpha multiplications at most.
+static const HybridConsts &hybrid_consts(hefx_context *c, int alpha, int L)
+{
+    std::lock_guard<std::mutex> lk(c->mu);
+    auto it = c->hybrid.find({alpha, L});
+    if (it != c->hybrid.end()) return it->second;
+    HybridConsts &H = c->hybrid[{alpha, L}];
+    const int k = c->k, R = L + alpha, s0 = k - alpha;
+    auto row_q = [&](int r) { return c->primes[r < L ? r : s0 + (r - L)]; };
+    HyTab &at = H.at;
+    at.L = L, at.alpha = alpha, at.dn = hybrid_digits(alpha, L), at.relin = 0;
+    uint32_t pos = 0;
+    auto take = [&](size_t words) {
+        const uint32_t o = pos;
+        pos += (uint32_t)words;
+        return o;
+    };
+    at.inv = take(2 * (size_t)L), at.conv = take((size_t)L * R), at.zinv = take(2 * (size_t)alpha), at.halfs = take(alpha);
+    at.phat = take((size_t)alpha * L), at.halfd = take(L), at.pinv = take(2 * (size_t)L), at.items = pos;
+    std::vector<u64> &w = H.words;
+    w.assign(pos, 0);
+    for (int i = 0; i < L; ++i) {
+        const int first = i / alpha * alpha, last = std::min(first + alpha, L);  // G_j(L) of i's digit
+        const u64 qi = c->primes[i], inv = h_invmod(h_prod_mod(c, first, last, i, qi), qi);
+        w[at.inv + 2 * i] = inv, w[at.inv + 2 * i + 1] = h_shoup(inv, qi);
+        for (int r = 0; r < R; ++r)
+            if (r >= L || r < first || r >= last) w[at.conv + (size_t)i * R + r] = h_prod_mod(c, first, last, i, row_q(r));
+    }
+    // floor(P/2) = (P - 1) / 2 (P is odd) mod an odd prime q: (P mod q - 1) 2^-1, with 2^-1 = (q + 1) / 2
+    auto half_p = [&](u64 q) { return h_mulmod((h_prod_mod(c, s0, k, -1, q) + q - 1) % q, (q + 1) / 2, q); };
+    for (int t = 0; t < alpha; ++t) {
+        const u64 qt = c->primes[s0 + t], inv = h_invmod(h_prod_mod(c, s0, k, s0 + t, qt), qt);
+        w[at.zinv + 2 * t] = inv, w[at.zinv + 2 * t + 1] = h_shoup(inv, qt);
+        w[at.halfs + t] = half_p(qt);
+        for (int j = 0; j < L; ++j) w[at.phat + (size_t)t * L + j] = h_prod_mod(c, s0, k, s0 + t, c->primes[j]);
+    }
+    for (int j = 0; j < L; ++j) {
+        const u64 qj = c->primes[j], inv = h_invmod(h_prod_mod(c, s0, k, -1, qj), qj);
+        w[at.halfd + j] = half_p(qj);
+        w[at.pinv + 2 * j] = inv, w[at.pinv + 2 * j + 1] = h_shoup(inv, qj);
+    }
+    return H;
+}
+
+// rows of N words one item takes in the scratch: xn, c0p, xc (3 L) | extd dn L, exts dn alpha | accd 2 L | accs 2 alpha | tt 2 L;
+// the blocks a pass writes for a transform to read (ext, accs, tt) twice at N = 32768 (xf_raw)
+static size_t hybrid_item_rows(const hefx_context *c, int alpha, int L)
+{
+    const size_t dn = (size_t)hybrid_digits(alpha, L), xf = c->logn == 15 ? 2 : 1;
+    return 3 * (size_t)L + xf * dn * (L + alpha) + 2 * (size_t)L + xf * 2 * alpha + xf * 2 * (size_t)L;
+}
+
+// One entry for both forms: relin (ins = [3][L][N], single_key) or Galois items (ins = [2][L][N], elts, keys).
+static int hybrid_run(hefx_context *c, int alpha, int L, int n, bool relin, const uint64_t *const *ins, const uint32_t *elts,
+                      const uint64_t *const *keys, const uint64_t *single_key, uint64_t *const *outs, void *stream)
+{
+    CTXCHK(c);
+    const char *who = relin ? "hybrid_relinearize_batch" : "hybrid_apply_galois_batch";
+    if (int rc = check_hybrid_alpha(c, alpha)) return rc;
+    if (L < 1 || L > c->k - alpha) return fail(HEFX_ERR_INVALID, std::string(who) + ": level L must be in [1, k - alpha]");
+    if (n < 1 || !ins || !outs || (relin ? !single_key : (!elts || !keys))) return fail(HEFX_ERR_INVALID, std::string(who) + ": bad arguments: null pointer or n < 1");
+    for (int i = 0; i < n; ++i) {
+        if (!ins[i] || !outs[i] || (!relin && !keys[i])) return fail(HEFX_ERR_INVALID, std::string(who) + ": null pointer in batch");
+        if (!relin && (!(elts[i] & 1) || elts[i] >= 2 * c->n)) return fail(HEFX_ERR_INVALID, "Galois element must be odd and < 2N");
+    }
+    const size_t N = c->n, poly_b = (size_t)L * N * sizeof(u64);
+    const int dn = hybrid_digits(alpha, L);
+    const size_t key_b = (size_t)dn * 2 * c->k * N * sizeof(u64);  // the digits level L reads
+    if (int rc = check_ranges(who, (size_t)n, outs, 2 * poly_b,
+                              {{ins, (size_t)n, (relin ? 3 : 2) * poly_b, !relin, 1, 0}, {relin ? &single_key : keys, relin ? (size_t)1 : (size_t)n, key_b}},
+                              {relin ? "d_ct3" : "d_ct_in", relin ? "d_key" : "d_keys"}, "two items write overlapping outputs",
+                              "items must be independent: an input or key overlaps an item's output"))
+        return rc;
+    const HybridConsts &K = hybrid_consts(c, alpha, L);
+    const size_t item_rows = hybrid_item_rows(c, alpha, L);
+    size_t chunk = ((size_t)1 << 30) / (item_rows * N * sizeof(u64));
+    chunk = std::max<size_t>(1, std::min<size_t>(chunk, ((size_t)RING_SLOT_PTRS - K.words.size()) / 4));
+    chunk = std::min<size_t>(chunk, KS_MAX_CHUNK);  // (the transforms put chunk * dn <= 1024 * 61 polynomials in grid.y)
+    if (K.words.size() + 4 > (size_t)RING_SLOT_PTRS) return fail(HEFX_ERR_UNSUPPORTED, std::string(who) + ": the constants do not fit a descriptor slot");
+    const int cmax = (int)std::min<size_t>(chunk, (size_t)n);
+    if (int rc = ensure_scratch(c, item_rows * N * (size_t)cmax)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    for (int i0 = 0; i0 < n; i0 += cmax) {
+        const int cnt = std::min(cmax, n - i0);
+        const size_t cn = (size_t)cnt * N, Ls = (size_t)L, A = (size_t)alpha, D = (size_t)dn;
+        // the chunk's blocks, in the order of the passes; `raw`: where the pass writes what the next transform reads
+        u64 *xn = c->scratch, *c0p = xn + Ls * cn, *xc = c0p + Ls * cn, *extd = xc + Ls * cn;
+        const size_t ext_w = D * (Ls + A) * cn, ext_raw = xf_raw(c, ext_w);
+        u64 *exts = extd + D * Ls * cn, *accd = extd + ext_w + ext_raw, *accs = accd + 2 * Ls * cn;
+        const size_t accs_raw = xf_raw(c, 2 * A * cn);
+        u64 *tt = accs + 2 * A * cn + accs_raw;
+        const size_t tt_raw = xf_raw(c, 2 * Ls * cn);
+        auto fill = [&](u64 *h) {
+            std::copy(K.words.begin(), K.words.end(), h);
+            for (int i = 0; i < cnt; ++i) {
+                u64 *item = h + K.at.items + 4 * (size_t)i;
+                item[0] = (u64)(uintptr_t)ins[i0 + i], item[1] = (u64)(uintptr_t)outs[i0 + i];
+                item[2] = (u64)(uintptr_t)(relin ? single_key : keys[i0 + i]), item[3] = relin ? 1 : elts[i0 + i];
+            }
+        };
+        auto run = [&](const u64 *d) -> int {
+            HyTab H = K.at;
+            H.tab = d, H.relin = relin ? 1 : 0;
+            HIPCHK(launch_hy_gather(c->T, H, cnt, xn, c0p, s));
+            HIPCHK(transform(c, true, xn, xc, cnt, L, 0, s));
+            HIPCHK(launch_hy_convert(c->T, H, cnt, xc, extd + ext_raw, exts + ext_raw, s));
+            HIPCHK(transform(c, false, extd + ext_raw, extd, cnt * dn, L, 0, s));
+            HIPCHK(transform(c, false, exts + ext_raw, exts, cnt * dn, alpha, c->k - alpha, s));
+            HIPCHK(launch_hy_mac(c->T, H, cnt, xn, extd, exts, accd, accs + accs_raw, s));
+            HIPCHK(transform(c, true, accs + accs_raw, accs, 2 * cnt, alpha, c->k - alpha, s));
+            HIPCHK(launch_hy_spread(c->T, H, cnt, accs, tt + tt_raw, s));
+            HIPCHK(transform(c, false, tt + tt_raw, tt, 2 * cnt, L, 0, s));
+            HIPCHK(launch_hy_finish(c->T, H, cnt, accd, tt, c0p, s));
+            return HEFX_OK;
+        };
+        if (int rc = slot_call(c, s, K.words.size() + 4 * (size_t)cnt, fill, run)) return rc;
+    }
+    return HEFX_OK;
+}
+
+extern "C" int hefx_hybrid_apply_galois_batch(hefx_context *c, int alpha, int L, int n, const uint64_t *const *ct_in, const uint32_t *elts,
+                                              const uint64_t *const *keys, uint64_t *const *ct_out, void *stream)
+{
+    return hybrid_run(c, alpha, L, n, false, ct_in, elts, keys, nullptr, ct_out, stream);
+}
+
+extern "C" int hefx_hybrid_relinearize_batch(hefx_context *c, int alpha, int L, int n, const uint64_t *const *ct3, const uint64_t *key,
+                                             uint64_t *const *ct2, void *stream)
+{
+    return hybrid_run(c, alpha, L, n, true, ct3, nullptr, nullptr, key, ct2, stream);
+}
+
+extern "C" int hefx_hybrid_keygen(hefx_context *c, int alpha, const uint64_t *sk, const uint64_t *new_sk, const uint8_t *key32,
+                                  uint64_t stream_id, uint64_t *out, void *stream)
+{
+    CTXCHK(c);
+    if (int rc = check_hybrid_alpha(c, alpha)) return rc;
+    if (!sk || !new_sk || !key32 || !out) return fail(HEFX_ERR_INVALID, "bad key generation arguments");
+    if (stream_id >> 62) return fail(HEFX_ERR_INVALID, "stream id must be below 2^62");
+    const int k = c->k, dn = hybrid_digits(alpha, k - alpha);
+    const size_t N = c->n, words = (size_t)dn * k * N;
+    if (int rc = check_ranges("hybrid_keygen", 1, &out, 2 * words * sizeof(u64),
+                              {{&sk, 1, (size_t)k * N * sizeof(u64)}, {&new_sk, 1, (size_t)k * N * sizeof(u64)}}, {"d_sk", "d_new_sk"}))
+        return rc;
+    const size_t raw = xf_raw(c, words);
+    if (int rc = ensure_scratch(c, 2 * words + raw)) return rc;
+    u64 *a = c->scratch, *e = a + words;
+    hipStream_t s = (hipStream_t)stream;
+    const SampleKey key = sample_key(key32);
+    HyPmod F{};
+    for (int m = 0; m < k - alpha; ++m) F.v[m] = h_prod_mod(c, k - alpha, k, -1, c->primes[m]);
+    // sub-streams 2*id: uniform a, 2*id+1: noise e (hefx_keygen_kswitch's, over dn polynomials)
+    HIPCHK(launch_sample(c->T, SAMPLE_UNIFORM, key, c->noise, 2 * stream_id, dn, k, 0, a, s));
+    HIPCHK(launch_sample(c->T, SAMPLE_NOISE, key, c->noise, 2 * stream_id + 1, dn, k, 0, e + raw, s));
+    HIPCHK(transform(c, false, e + raw, e, dn, k, 0, s));
+    HIPCHK(launch_hy_keygen(c->T, F, alpha, dn, (const u64 *)sk, (const u64 *)new_sk, a, e, (u64 *)out, s));
     return HEFX_OK;
 }
 

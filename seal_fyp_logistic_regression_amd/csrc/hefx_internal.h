@@ -280,6 +280,34 @@ hipError_t launch_rs_product_p(const DevTables &T, int L, const u64 *xp, const u
 hipError_t launch_rs_spread(const DevTables &T, int L, const u64 *u, u64 *tt, hipStream_t s);
 hipError_t launch_rs_finish(const DevTables &T, int L, const u64 *in, const u64 *xb, const u64 *ckey, const u64 *tt, u64 *out,
                             hipStream_t s);
+// hybrid key switching (hefx_hybrid.hip, include/hefx_hybrid.h).  One device table per chunk (a descriptor-ring slot): the
+// (alpha, L) constants at the word offsets below, then the chunk's items, four words each: input, output, key, Galois element.
+// Rows r of R = L + alpha: r < L is data prime r, r >= L special prime k - alpha + r - L.
+struct HyTab {
+    const u64 *tab;
+    uint32_t inv;    // [L][2]      {Dhat_i^-1 mod q_i, its Shoup companion}
+    uint32_t conv;   // [L][R]      Dhat_i mod q_m(r) (unused inside the digit of i)
+    uint32_t zinv;   // [alpha][2]  {(P/q_t)^-1 mod q_t, its Shoup companion}
+    uint32_t halfs;  // [alpha]     floor(P/2) mod q_t
+    uint32_t phat;   // [alpha][L]  (P/q_t) mod q_j
+    uint32_t halfd;  // [L]         floor(P/2) mod q_j
+    uint32_t pinv;   // [L][2]      {P^-1 mod q_j, its Shoup companion}
+    uint32_t items;  // [n][4]
+    int L, alpha, dn, relin;  // dn = ceil(L / alpha): the digits level L reads
+};
+struct HyPmod {
+    u64 v[62];  // P mod q_m for the data rows m < k - alpha
+};
+constexpr int HY_ALPHA_MAX = 8;  // == HEFX_HYBRID_ALPHA_MAX (hefx_hybrid.h)
+// the passes of one chunk of n items between its transforms; every buffer is the context's scratch, laid out in hefx_hybrid.hip's head
+hipError_t launch_hy_gather(const DevTables &T, const HyTab &H, int n, u64 *xn, u64 *c0p, hipStream_t s);
+hipError_t launch_hy_convert(const DevTables &T, const HyTab &H, int n, const u64 *xc, u64 *extd, u64 *exts, hipStream_t s);
+hipError_t launch_hy_mac(const DevTables &T, const HyTab &H, int n, const u64 *xn, const u64 *extd, const u64 *exts, u64 *accd, u64 *accs,
+                         hipStream_t s);
+hipError_t launch_hy_spread(const DevTables &T, const HyTab &H, int n, const u64 *u, u64 *tt, hipStream_t s);
+hipError_t launch_hy_finish(const DevTables &T, const HyTab &H, int n, const u64 *accd, const u64 *tt, const u64 *c0p, hipStream_t s);
+hipError_t launch_hy_keygen(const DevTables &T, const HyPmod &F, int alpha, int dn, const u64 *sk, const u64 *new_sk, const u64 *a,
+                            const u64 *e, u64 *out, hipStream_t s);
 hipError_t warm_kernels(hipStream_t s);
 hipError_t warm_keyswitch(hipStream_t s);
 hipError_t warm_encode(hipStream_t s);

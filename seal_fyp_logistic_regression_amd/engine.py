@@ -646,6 +646,41 @@ class Engine:
         capi.check(capi.lib().hefx_raise_switch(self._h, L_out, ct.ptr, ckey.ptr, out.ptr, stream))
         return out
 
+    # ---- hybrid key switching (include/hefx_hybrid.h)
+    def hybrid_digits(self, alpha) -> int:
+        """dnum = ceil((k - alpha) / alpha), the digits of a hybrid key (hefx_hybrid_digits)"""
+        rc = capi.lib().hefx_hybrid_digits(self._h, int(alpha))
+        if rc < 0:
+            capi.check(rc)
+        return int(rc)
+
+    def hybrid_keygen(self, alpha, sk, new_sk, key32: bytes, stream_id: int, out=None, stream=None):
+        """hybrid switching key [dnum][2][k][N] for new_sk under sk, sampled and assembled on the device (hefx_hybrid_keygen)"""
+        if len(key32) != 32:
+            raise ValueError("key32 must be 32 bytes")
+        out = out if out is not None else DeviceArray(self, (self.hybrid_digits(alpha), 2, self.k, self.N))
+        capi.check(capi.lib().hefx_hybrid_keygen(self._h, int(alpha), sk.ptr, new_sk.ptr, key32, stream_id, out.ptr, stream))
+        return out
+
+    def hybrid_apply_galois_batch(self, alpha, L, cts, elts, keys, outs=None, stream=None):
+        """outs[i] = (pi_g(c0) + ks0(pi_g(c1)), ks1(pi_g(c1))) with hybrid keys; outs[i] may be cts[i] itself
+        (hefx_hybrid_apply_galois_batch)"""
+        n = len(cts)
+        outs = outs if outs is not None else self.empty_many(n, (2, L, self.N))
+        capi.check(capi.lib().hefx_hybrid_apply_galois_batch(
+            self._h, int(alpha), L, n, capi.ptr_array([c.ptr for c in cts]), capi.u32_array(elts),
+            capi.ptr_array([k.ptr for k in keys]), capi.ptr_array([o.ptr for o in outs]), stream))
+        return outs
+
+    def hybrid_relinearize_batch(self, alpha, L, ct3s, key, outs=None, stream=None):
+        """outs[i] = (c0 + ks0(c2), c1 + ks1(c2)) with the hybrid key of s^2 (hefx_hybrid_relinearize_batch)"""
+        n = len(ct3s)
+        outs = outs if outs is not None else self.empty_many(n, (2, L, self.N))
+        capi.check(capi.lib().hefx_hybrid_relinearize_batch(
+            self._h, int(alpha), L, n, capi.ptr_array([c.ptr for c in ct3s]), key.ptr,
+            capi.ptr_array([o.ptr for o in outs]), stream))
+        return outs
+
     # ---- scalar combinations of ciphertexts (include/hefx_poly.h)
     def scalar_combine(self, L, size, ins, in_rows, weights, consts=None, outs=None, stream=None):
         """outs[g] = sum_k weights[g][k] * ins[k] + consts[g] over the first L rows of every input, one pass over the inputs

@@ -305,6 +305,15 @@ class GpuBackend:
     def collapse_key(self, L, key):
         return self.engine.collapse_key(L, key)
 
+    def hybrid_keygen(self, alpha, sk, new_sk, key32, stream_id):
+        return self.engine.hybrid_keygen(alpha, sk, new_sk, key32, stream_id)
+
+    def hybrid_apply_galois_batch(self, alpha, L, cts, elts, keys):
+        return self.engine.hybrid_apply_galois_batch(alpha, L, cts, elts, keys)
+
+    def hybrid_relinearize_batch(self, alpha, L, ct3s, key):
+        return self.engine.hybrid_relinearize_batch(alpha, L, ct3s, key)
+
     def raise_switch(self, L_out, ct, ckey):
         """mod-raise from one prime and the collapsed key switch in one engine call (hefx_raise_switch); the oracle-backed
         twin of the tests has no such method and Evaluator.raise_switch states the same words through its apply_galois"""
@@ -505,6 +514,71 @@ class KSwitchKeys:
 GaloisKeys = KSwitchKeys
 RelinKeys = KSwitchKeys
 
+HYBRID_ALPHA_MAX = 8  # HEFX_HYBRID_ALPHA_MAX (hefx_hybrid.h)
+
+
+class HybridKeys(KSwitchKeys):
+    """Keys of hybrid key switching (include/hefx_hybrid.h): alpha data primes per digit and the LAST alpha primes of the chain
+    as special primes; index -> device key [dnum][2][k][N], dnum = ceil((k - alpha) / alpha), under the indices of KSwitchKeys
+    (and under 1, the identity element, for Evaluator.switch_key).  Evaluator.rotate_vector, apply_galois, complex_conjugate,
+    relinearize from size 3 and switch_key read them through hybrid_key(); ciphertexts must sit at a level <= k - alpha.  The
+    fused composites (linear transforms, plain_combine / product_combine pipelines, the bootstrap) read their keys through
+    key() / power_key(), which refuse here: their kernels know the one-special-prime layout only."""
+
+    def __init__(self, alpha: int):
+        super().__init__()
+        self.alpha = int(alpha)
+
+    def hybrid_key(self, index: int):
+        return self.keys[index]
+
+    def _refuse(self):
+        raise TypeError(f"HybridKeys (alpha = {self.alpha}) with a fused composite or a size above 3 is not supported: hybrid key "
+                        "switching serves rotate_vector, apply_galois, complex_conjugate, relinearize from size 3 and switch_key; "
+                        "linear transforms, plain_combine / product_combine pipelines and the bootstrap need KSwitchKeys")
+
+    def key(self, elt: int):
+        self._refuse()
+
+    def power_key(self, key_power: int):
+        self._refuse()
+
+
+def hybrid_switch_host(be, primes: Sequence[int], alpha: int, L: int, x: np.ndarray, key: np.ndarray) -> np.ndarray:
+    """The switch of include/hefx_hybrid.h's statement, steps 1 to 5, in Python integers over the backend's own transforms:
+    x [L][N] NTT form, key [dnum][2][k][N] -> ks [2][L][N].  What Evaluator runs with HybridKeys on a backend without the
+    native entries (the oracle twin of the tests)."""
+    q = [int(p) for p in primes]
+    k, N = len(q), np.asarray(x).shape[-1]
+    D = k - alpha
+    S, rows = list(range(D, k)), list(range(L)) + list(range(D, k))
+    P = 1
+    for t in S:
+        P *= q[t]
+    key = np.asarray(key).reshape(-1, 2, k, N)
+    fwd = lambda m, v: np.asarray(be.to_host(be.ntt_forward(be.from_host((v % q[m]).astype(np.uint64)[None, None]), 1, 1, m))).reshape(-1).astype(object)
+    inv = lambda m, v: np.asarray(be.to_host(be.ntt_inverse(be.from_host(np.asarray(v, dtype=np.uint64)[None, None]), 1, 1, m))).reshape(-1).astype(object)
+    x = np.asarray(x, dtype=np.uint64).reshape(L, N)
+    coef = [inv(i, x[i]) for i in range(L)]
+    acc = {(c, m): np.zeros(N, dtype=object) for c in range(2) for m in rows}
+    for j in range((L + alpha - 1) // alpha):
+        G = list(range(j * alpha, min((j + 1) * alpha, L)))
+        Dj = 1
+        for i in G:
+            Dj *= q[i]
+        y = {i: coef[i] * pow(Dj // q[i], -1, q[i]) % q[i] for i in G}
+        for m in rows:
+            ext = x[m].astype(object) if m in G else fwd(m, sum(y[i] * ((Dj // q[i]) % q[m]) for i in G))
+            for c in range(2):
+                acc[c, m] = (acc[c, m] + ext * key[j, c, m].astype(object)) % q[m]
+    out = np.empty((2, L, N), dtype=np.uint64)
+    for c in range(2):
+        z = {t: (inv(t, acc[c, t].astype(np.uint64)) + (P // 2) % q[t]) % q[t] * pow(P // q[t], -1, q[t]) % q[t] for t in S}
+        for j in range(L):
+            v = sum(z[t] * ((P // q[t]) % q[j]) for t in S) % q[j]
+            out[c, j] = ((acc[c, j] - fwd(j, v - (P // 2) % q[j])) * pow(P, -1, q[j]) % q[j]).astype(np.uint64)
+    return out
+
 
 class EncapsKeys:
     """The two switching keys of sparse-secret encapsulation (KeyGenerator.encapsulation_keys): `low` takes a ciphertext at
@@ -684,6 +758,73 @@ class KeyGenerator:
             power = be.multiply_plain(self.ctx.k, 1, power, sk.data)
             rk.keys[p - 2] = self._kswitch_key(None, power)
         return rk
+
+    def _hybrid_key(self, alpha: int, new_sk_host, new_sk_dev=None):
+        """hybrid switching key [dnum][2][k][N] for new_sk under the generator's secret: hefx_hybrid_keygen on the HIP engine,
+        otherwise the same words composed from backend operations as _kswitch_key does (a dnum-polynomial draw from the
+        sub-streams 2 sid, 2 sid + 1; F_j = P mod q_m on the data rows of digit j)"""
+        ctx, be = self.ctx, self.ctx.backend
+        k, N, q = ctx.k, ctx.N, [int(p) for p in ctx.primes]
+        sid = self._next_stream()
+        native = getattr(be, "hybrid_keygen", None)
+        if native is not None:
+            return native(alpha, self._sk.data, new_sk_dev if new_sk_dev is not None else be.from_host(new_sk_host), self._key32, sid)
+        if new_sk_host is None:
+            new_sk_host = be.to_host(new_sk_dev).reshape(k, N)
+        D = k - alpha
+        dnum = (D + alpha - 1) // alpha
+        c0, c1 = self._encrypt_zero(dnum, k, sid)
+        P = 1
+        for t in range(D, k):
+            P *= q[t]
+        factor = np.empty((k, N), dtype=np.uint64)
+        for m in range(k):
+            factor[m, :] = P % q[m]
+        t = be.to_host(be.multiply_plain(k, 1, be.from_host(np.asarray(new_sk_host)[None]), be.from_host(factor)))[0]
+        for j in range(dnum):
+            for m in range(j * alpha, min((j + 1) * alpha, D)):
+                s = c0[j, m] + t[m]
+                c0[j, m] = np.where(s >= q[m], s - q[m], s)
+        return be.from_host(np.stack([c0, c1], axis=1))
+
+    def _check_alpha(self, alpha: int) -> int:
+        alpha = int(alpha)
+        if alpha < 1 or alpha >= self.ctx.k or alpha > HYBRID_ALPHA_MAX:
+            raise ValueError(f"hybrid keys: alpha must lie in 1 .. min(k - 1, {HYBRID_ALPHA_MAX}), k = {self.ctx.k}")
+        return alpha
+
+    def hybrid_relin_keys(self, alpha: int) -> "HybridKeys":
+        """the hybrid relinearisation key of s^2 (index 0): the last alpha primes of the chain are special primes"""
+        alpha = self._check_alpha(alpha)
+        be, sk = self.ctx.backend, self._sk
+        rk = HybridKeys(alpha)
+        rk.keys[0] = self._hybrid_key(alpha, None, be.multiply_plain(self.ctx.k, 1, be.from_host(sk.host[None]), sk.data))
+        return rk
+
+    def hybrid_galois_keys(self, alpha: int, steps: Optional[Sequence[int]] = None, conjugate: bool = False) -> "HybridKeys":
+        """galois_keys(steps, conjugate) as hybrid keys: the same elements in the same order, one sampler stream each"""
+        from . import galois_tables
+        alpha = self._check_alpha(alpha)
+        N = self.ctx.N
+        elts = self.default_galois_elts() if steps is None else [galois_elt_from_step(s, N) for s in steps]
+        if conjugate and 2 * N - 1 not in elts:
+            elts = elts + [2 * N - 1]
+        gk = HybridKeys(alpha)
+        permute = getattr(self.ctx.backend, "galois_permute", None)
+        for g in elts:
+            if permute is not None:
+                gk.keys[g] = self._hybrid_key(alpha, None, permute(g, self._sk.data, self.ctx.k))
+            else:
+                gk.keys[g] = self._hybrid_key(alpha, self._sk.host[:, galois_tables.gather_table(N, g)])
+        return gk
+
+    def hybrid_switching_key(self, alpha: int, from_secret: "SecretKey") -> "HybridKeys":
+        """the hybrid key that takes a ciphertext under from_secret to this generator's secret, under the identity element 1
+        (Evaluator.switch_key)"""
+        alpha = self._check_alpha(alpha)
+        sw = HybridKeys(alpha)
+        sw.keys[1] = self._hybrid_key(alpha, from_secret.host, from_secret.data)
+        return sw
 
     def encapsulation_keys(self, hamming_weight: int = 32, seed: Optional[int] = None) -> EncapsKeys:
         """The keys of sparse-secret encapsulation (Bossuat, Troncoso-Pastoriza, Hubaux, ACNS 2022) for bootstrapping under
@@ -1154,6 +1295,10 @@ class Evaluator:
         f = getattr(self.be, "relinearize_batch", None)
         if not cts:
             return cts
+        if isinstance(relin_keys, HybridKeys):
+            for c in cts:
+                self.relinearize_inplace(c, relin_keys)
+            return cts
         if f is None or not self._uniform(cts) or cts[0].size() != 3:
             for c in cts:
                 self.relinearize_inplace(c, relin_keys)
@@ -1362,6 +1507,55 @@ class Evaluator:
             data = be.from_host(np.concatenate([old, new], axis=1))
         return Ciphertext()._set(data, 2, L_out, ct.scale)
 
+    # ---- hybrid key switching (include/hefx_hybrid.h)
+    def _hybrid_level(self, ct: Ciphertext, keys: "HybridKeys") -> int:
+        L, top = ct.parms_id(), self.ctx.k - keys.alpha
+        if L > top:
+            raise ValueError(f"hybrid key switching with alpha = {keys.alpha} needs a ciphertext at a level <= k - alpha = {top}: "
+                             f"this one is at level {L} (the last alpha primes of the chain are special primes)")
+        return L
+
+    def _hybrid_galois(self, L: int, data, elt: int, keys: "HybridKeys"):
+        """(pi_g(c0) + ks0(pi_g(c1)), ks1(pi_g(c1))): hefx_hybrid_apply_galois_batch, or the statement in Python integers"""
+        key = keys.hybrid_key(elt)
+        native = getattr(self.be, "hybrid_apply_galois_batch", None)
+        if native is not None:
+            return native(keys.alpha, L, [data], [elt], [key])[0]
+        from . import galois_tables
+        be, N, q = self.be, self.ctx.N, self.ctx.primes
+        ct = np.asarray(be.to_host(data), dtype=np.uint64).reshape(2, L, N)[:, :, galois_tables.gather_table(N, elt)]
+        ks = hybrid_switch_host(be, q, keys.alpha, L, ct[1], be.to_host(key))
+        for j in range(L):
+            ks[0, j] = ((ks[0, j].astype(object) + ct[0, j].astype(object)) % int(q[j])).astype(np.uint64)
+        return be.from_host(ks)
+
+    def _hybrid_relinearize(self, L: int, data, keys: "HybridKeys"):
+        """(c0 + ks0(c2), c1 + ks1(c2)): hefx_hybrid_relinearize_batch, or the statement in Python integers"""
+        native = getattr(self.be, "hybrid_relinearize_batch", None)
+        if native is not None:
+            return native(keys.alpha, L, [data], keys.hybrid_key(0))[0]
+        be, N, q = self.be, self.ctx.N, self.ctx.primes
+        ct = np.asarray(be.to_host(data), dtype=np.uint64).reshape(3, L, N)
+        ks = hybrid_switch_host(be, q, keys.alpha, L, ct[2], be.to_host(keys.hybrid_key(0)))
+        for c in range(2):
+            for j in range(L):
+                ks[c, j] = ((ks[c, j].astype(object) + ct[c, j].astype(object)) % int(q[j])).astype(np.uint64)
+        return be.from_host(ks)
+
+    def apply_galois(self, a: Ciphertext, galois_elt: int, galois_keys: KSwitchKeys, destination=None):
+        """Evaluator::apply_galois: the automorphism X -> X^galois_elt and the key switch back, with the key of that element"""
+        if a.size() != 2:
+            raise ValueError("encrypted size must be 2")
+        if not galois_keys.has_key(galois_elt):
+            raise ValueError("Galois key not present")
+        L = a.parms_id()
+        if isinstance(galois_keys, HybridKeys):
+            data = self._hybrid_galois(self._hybrid_level(a, galois_keys), a.data, galois_elt, galois_keys)
+        else:
+            data = self.be.apply_galois(L, a.data, galois_elt, galois_keys.key(galois_elt))
+        out = destination if destination is not None else Ciphertext()
+        return out._set(data, 2, L, a.scale)
+
     def switch_key(self, ct: Ciphertext, key) -> Ciphertext:
         """(c0 + ks0(c1), ks1(c1)) with a switching key [k-1][2][k][N] from the secret ct is under to another one: the key
         switch of a rotation without its automorphism.  Size 2, any level.  hefx_switch_key where the backend has it, else
@@ -1369,6 +1563,10 @@ class Evaluator:
         if ct.size() != 2:
             raise ValueError("encrypted size must be 2")
         L = ct.parms_id()
+        if isinstance(key, HybridKeys):  # the hybrid key under the identity element (KeyGenerator.hybrid_switching_key)
+            if not key.has_key(1):
+                raise ValueError("switch_key: the HybridKeys hold no key under the identity element 1")
+            return Ciphertext()._set(self._hybrid_galois(self._hybrid_level(ct, key), ct.data, 1, key), 2, L, ct.scale)
         native = getattr(self.be, "switch_key", None)
         data = native(L, ct.data, key) if native is not None else self.be.apply_galois(L, ct.data, 1, key)
         return Ciphertext()._set(data, 2, L, ct.scale)
@@ -1526,7 +1724,11 @@ class Evaluator:
         if a.size() == 3:
             if not relin_keys.has_key(0):
                 raise ValueError("not enough relinearization keys")
+            if isinstance(relin_keys, HybridKeys):
+                return a._set(self._hybrid_relinearize(self._hybrid_level(a, relin_keys), a.data, relin_keys), 2, a.parms_id(), a.scale)
             return a._set(self.be.relinearize(a.parms_id(), a.data, relin_keys.key(0)), 2, a.parms_id(), a.scale)
+        if isinstance(relin_keys, HybridKeys):
+            relin_keys._refuse()
         # any larger size: SEAL's relinearize_internal -- from the top, polynomial t with the key of s^t into (c0, c1)
         general = getattr(self.be, "relinearize_sizes", None)
         if general is None or a.size() < 2:
@@ -1585,8 +1787,11 @@ class Evaluator:
         if a.size() != 2:
             raise ValueError("encrypted size must be 2")
         data, L = a.data, a.parms_id()
+        hybrid = isinstance(galois_keys, HybridKeys)
+        if hybrid:
+            self._hybrid_level(a, galois_keys)
         for elt in self.rotation_plan(steps, galois_keys):
-            data = self.be.apply_galois(L, data, elt, galois_keys.key(elt))
+            data = self._hybrid_galois(L, data, elt, galois_keys) if hybrid else self.be.apply_galois(L, data, elt, galois_keys.key(elt))
         out = destination if destination is not None else Ciphertext()
         return out._set(data, 2, L, a.scale)
 
@@ -1600,7 +1805,10 @@ class Evaluator:
         elt = 2 * self.ctx.N - 1
         if not galois_keys.has_key(elt):
             raise ValueError("Galois key not present")
-        data = self.be.apply_galois(a.parms_id(), a.data, elt, galois_keys.key(elt))
+        if isinstance(galois_keys, HybridKeys):
+            data = self._hybrid_galois(self._hybrid_level(a, galois_keys), a.data, elt, galois_keys)
+        else:
+            data = self.be.apply_galois(a.parms_id(), a.data, elt, galois_keys.key(elt))
         out = destination if destination is not None else Ciphertext()
         return out._set(data, 2, a.parms_id(), a.scale)
 
