@@ -13,6 +13,21 @@ THE SETS.  N = 2048, the smallest ring with key switching.  A set is a SHAPE wit
             above60  one data prime just above 2^60, the others below 2^55, 60-bit specials
 and one set at N = 32768, "big": k = 4, alpha = 2, L = 2 (p50_60).  The primes come from tests/policy_sets.py's helpers.
 
+THE SETS AT THE SHAPES THE KERNELS ARE BUILT FOR (WIDE_SHAPES; every one keeps 4 B < Q_L at every level):
+    N = 2048, mixes p50_60, above60, d40_s60
+            k12a5  alpha = 5: L = 7 (digits 5 + 2), 5 (one full digit), 3 (one digit of fewer rows than alpha)
+            k14a6  alpha = 6: L = 8 (6 + 2)         k16a7  alpha = 7: L = 9 (7 + 2)
+            k18a8  alpha = 8, HEFX_HYBRID_ALPHA_MAX: L = 10 (8 + 2), 8 (exactly one full digit)
+            k14a2  alpha = 2: L = 11, six digits, the last of one prime
+            k10a1  alpha = 1: L = 9, 4, nine digits (the scheme of hefx.h again)
+    N = 2048, mix top61: the k largest primes below 2^61 (the context's limit is q >> 61 == 0), the first alpha of them special
+            k24a4  L = 20, 18, 17: five digits, the last one full, of two primes, of one prime
+            k62a1  L = 61: the longest chain the ABI takes, the 61 products the MAC's "below 2^128" counts.  ONE case (operand
+                   max, key max, element 3); in LONG_SET_NAMES, not in SET_NAMES: its key is 118 MiB on the host
+    the rings between, p50_60: n4096, n8192, n16384, each k = 7, alpha = 2, L = 5, 2
+    N = 32768, p50_60: big7, k = 7, alpha = 2, L = 5, 4
+The key kind "max" (every word q_m - 1) with the operand "max" puts every product of the MAC at its largest.
+
 THE NOISE BOUND.  dec(out) - pi_g(dec(in)), centred mod Q_L, has infinity norm at most
     B = ceil(L/alpha) * alpha * N * 19 * Dmax / P + alpha * (1 + N),          Dmax = the largest D_j(L).
 First term: the switch adds sum_j ext_j e_j / P to the decryption, ext_j the integer the uncorrected base conversion stands for,
@@ -29,6 +44,13 @@ SHAPES = {"k7a2": (7, 2, (5, 4, 3, 1)), "k8a3": (8, 3, (5, 2)), "k7a4": (7, 4, (
 MIXES = ("p50_60", "d40_s60", "d60_s40", "above60")
 ELTS = lambda N_: (1, 3, 2 * N_ - 1)
 SEED = 5
+# name -> (N, k, alpha, levels, mixes); a name that starts with "k" is a shape and takes "-mix", the others are whole set names
+N2048_MIXES = ("p50_60", "above60", "d40_s60")
+WIDE_SHAPES = {"k12a5": (N, 12, 5, (7, 5, 3), N2048_MIXES), "k14a6": (N, 14, 6, (8,), N2048_MIXES), "k16a7": (N, 16, 7, (9,), N2048_MIXES),
+               "k18a8": (N, 18, 8, (10, 8), N2048_MIXES), "k14a2": (N, 14, 2, (11,), N2048_MIXES), "k10a1": (N, 10, 1, (9, 4), N2048_MIXES),
+               "k24a4": (N, 24, 4, (20, 18, 17), ("top61",)), "k62a1": (N, 62, 1, (61,), ("top61",)),
+               "n4096": (4096, 7, 2, (5, 2), ("p50_60",)), "n8192": (8192, 7, 2, (5, 2), ("p50_60",)),
+               "n16384": (16384, 7, 2, (5, 2), ("p50_60",)), "big7": (32768, 7, 2, (5, 4), ("p50_60",))}
 
 
 class HSet:
@@ -57,6 +79,9 @@ def mix_primes(mix, N_, k, alpha):
         return PS.primes_below(1 << 60, N_, D) + PS.primes_below(1 << 40, N_, alpha)
     if mix == "above60":
         return PS.primes_above(1 << 60, N_, 1) + PS.primes_below(1 << 55, N_, D - 1) + PS.primes_below(1 << 60, N_, alpha)
+    if mix == "top61":
+        top = PS.primes_below(1 << 61, N_, k)
+        return top[alpha:] + top[:alpha]
     raise ValueError(mix)
 
 
@@ -69,11 +94,24 @@ def sets():
             for mix in MIXES:
                 _SETS[f"{shape}-{mix}"] = HSet(f"{shape}-{mix}", N, k, alpha, levels, mix_primes(mix, N, k, alpha))
         _SETS["big"] = HSet("big", 32768, 4, 2, (2,), mix_primes("p50_60", 32768, 4, 2))
+        for shape, (N_, k, alpha, levels, mixes) in WIDE_SHAPES.items():
+            for mix in mixes:
+                name = wide_name(shape, mix)
+                _SETS[name] = HSet(name, N_, k, alpha, levels, mix_primes(mix, N_, k, alpha))
     return _SETS
 
 
-SET_NAMES = sorted(f"{s}-{m}" for s in SHAPES for m in MIXES) + ["big"]
-SMALL_SET_NAMES = [n for n in SET_NAMES if n != "big"]
+def wide_name(shape, mix):
+    return f"{shape}-{mix}" if shape.startswith("k") else shape
+
+
+LONG_SET_NAMES = ["k62a1-top61"]
+_WIDE_N = {wide_name(s, m): v[0] for s, v in WIDE_SHAPES.items() for m in v[4]}
+WIDE_SET_NAMES = [n for n in _WIDE_N if n not in LONG_SET_NAMES]
+SET_NAMES = sorted(f"{s}-{m}" for s in SHAPES for m in MIXES) + ["big"] + WIDE_SET_NAMES
+SMALL_SET_NAMES = [n for n in SET_NAMES if n != "big" and _WIDE_N.get(n, N) == N]   # the sets at N = 2048
+ALPHA_ONE_SET_NAMES = [f"k4a1-{m}" for m in MIXES] + [f"k10a1-{m}" for m in N2048_MIXES]
+ALPHA_ONE_IDS = list(MIXES) + [f"k10a1-{m}" for m in N2048_MIXES]   # the k4a1 cases keep the ids they had: the mix alone
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -135,6 +173,22 @@ def random_key(s, seed):
     for m, q in enumerate(s.primes):
         key[:, :, m] = rng.integers(0, q, (s.dnum, 2, s.N), dtype=np.uint64)
     return key
+
+
+def max_key(s):
+    """[dnum][2][k][N], every word q_m - 1: with the operand "max" every product of the MAC is the largest there is"""
+    row = np.asarray([q - 1 for q in s.primes], dtype=np.uint64)
+    return np.ascontiguousarray(np.broadcast_to(row[None, None, :, None], (s.dnum, 2, s.k, s.N)))
+
+
+KEYS = ("uniform", "max")
+
+
+def case_key(s, kind):
+    """the key of a word case: the set's random key, or the max key"""
+    if kind not in KEYS:
+        raise ValueError(kind)
+    return random_key(s, SEED) if kind == "uniform" else max_key(s)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -214,18 +268,27 @@ def relinearize_model(be, primes, alpha, L, ct3, key):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # the word cases: per set and level three Galois items (an operand kind and an element each) and one relinearisation, on
-# one random key per set; every model result is computed once per process and shared
+# one random key per set; the wide sets add, at their top level, a Galois item and a relinearisation with the max operand on the
+# max key; every model result is computed once per process and shared
 # ---------------------------------------------------------------------------------------------------------------------
 def word_cases(s):
-    """[(L, form, operand kind, elt)]"""
+    """[(L, form, operand kind, elt, key kind)]"""
     e1, e3, econj = ELTS(s.N)
-    out = []
+    out, top = [], max(s.levels)
     for L in s.levels:
-        out += [(L, "galois", "uniform", e3), (L, "galois", "max", econj), (L, "galois", "zeros", e1), (L, "relin", "uniform", 0)]
-        if L == max(s.levels):
-            out += [(L, "relin", "zeros", 0), (L, "galois", "uniform", econj)]
+        if s.name in WIDE_SET_NAMES and s.N != N:   # n4096 .. n16384, big7: the model costs up to 0.7 s a call there
+            out += [(L, "galois", "uniform", e3, "uniform"), (L, "galois", "max", econj, "uniform"), (L, "relin", "uniform", 0, "uniform")]
+            continue
+        out += [(L, "galois", "uniform", e3, "uniform"), (L, "galois", "max", econj, "uniform"), (L, "galois", "zeros", e1, "uniform"),
+                (L, "relin", "uniform", 0, "uniform")]
+        if L == top:
+            out += [(L, "relin", "zeros", 0, "uniform"), (L, "galois", "uniform", econj, "uniform")]
+    if s.name in WIDE_SET_NAMES:
+        out += [(top, "galois", "max", e3, "max"), (top, "relin", "max", 0, "max")]
     if s.name == "big":
-        out = [(2, "galois", "uniform", e3), (2, "relin", "uniform", 0)]
+        out = [(2, "galois", "uniform", e3, "uniform"), (2, "relin", "uniform", 0, "uniform")]
+    if s.name in LONG_SET_NAMES:
+        out = [(top, "galois", "max", e3, "max")]
     return out
 
 
@@ -233,16 +296,16 @@ _MODEL = {}
 
 
 def case_input(s, case):
-    L, form, kind, elt = case
+    L, form, kind, elt, _ = case
     return operand(s, kind, L, 2 if form == "galois" else 3, seed=SEED + 10 * L + elt % 7)
 
 
 def case_model(s, case):
-    """the statement's words of a word case on the set's random key, from the oracle twin's transforms"""
+    """the statement's words of a word case on the case's key, from the oracle twin's transforms"""
     key_ = (s.name, case)
     if key_ not in _MODEL:
-        L, form, kind, elt = case
-        ct, key = case_input(s, case), random_key(s, SEED)
+        L, form, kind, elt, key_kind = case
+        ct, key = case_input(s, case), case_key(s, key_kind)
         if form == "galois":
             _MODEL[key_] = apply_galois_model(twin(s), s.primes, s.alpha, L, ct, elt, key)
         else:
@@ -288,6 +351,66 @@ def noise_bound(s, L):
     dn = (L + s.alpha - 1) // s.alpha
     B = -(-(dn * s.alpha * s.N * 19 * Dmax) // P) + s.alpha * (1 + s.N)
     return B, int(np.prod(q[:L], dtype=object))
+
+
+def switch_noise(s, L, form, elt, ct, out, sk):
+    """max |dec(out) - pi_g(dec(ct))| centred mod Q_L in exact integers (form "relin": dec(out) - dec(ct), ct of size 3), and Q_L;
+    sk [k][N] the secret's NTT rows, the transforms are the oracle twin's"""
+    q = s.primes
+    want = decrypt_rows(ct, sk, q)
+    if form == "galois":
+        want = [gather(s.N, elt, r) for r in want]
+    got = decrypt_rows(out, sk, q)
+    diff, Q = centred_integers(twin(s), [(g - w) % int(q[j]) for j, (g, w) in enumerate(zip(got, want))], q)
+    return int(np.abs(diff).max()), Q
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the launch rules of the engine, restated (the idiom of tests/policy_sets.py): the GPU tests assert through them that a batch
+# runs the split and the chunking it is there for, so that retuning a rule fails a test where it would silently end the coverage
+# ---------------------------------------------------------------------------------------------------------------------
+KS_MAX_CHUNK = 1024                    # hefx_internal.h  constexpr int KS_MAX_CHUNK
+RING_SLOT_PTRS = 80 * KS_MAX_CHUNK // 8  # hefx_capi.cpp  RING_SLOT_PTRS = sizeof(KsItem) * KS_MAX_CHUNK / sizeof(void *), KsItem of 80 bytes
+
+
+def split_of(N_, groups, targets):
+    """how many ways a lane-loop pass splits its `targets` rows when the batch gives it `groups` row groups (hefx_hybrid.hip,
+    hy_split): 256 records of two words per workgroup, doubled while below 1024 workgroups, at most 4, at most targets / 2"""
+    wgs = (N_ // 2 + 255) // 256 * groups
+    split = 1
+    while split < 4 and wgs * split < 1024 and 2 * split <= targets:
+        split *= 2
+    return split
+
+
+def convert_split(N_, alpha, L, n):
+    """launch_hy_convert: hy_split(T, dn * n, L + alpha)"""
+    return split_of(N_, (L + alpha - 1) // alpha * n, L + alpha)
+
+
+def spread_split(N_, L, n):
+    """launch_hy_spread: hy_split(T, 2 * n, L)"""
+    return split_of(N_, 2 * n, L)
+
+
+def item_rows(N_, alpha, L):
+    """rows of N words one item takes in the scratch (hefx_capi.cpp, hybrid_item_rows): xn, c0p, xc | ext | accd | accs | tt, the
+    blocks a transform reads (ext, accs, tt) twice at N = 32768"""
+    dn, xf = (L + alpha - 1) // alpha, 2 if N_ == 32768 else 1
+    return 3 * L + xf * dn * (L + alpha) + 2 * L + xf * 2 * alpha + xf * 2 * L
+
+
+def table_words(alpha, L):
+    """words of the (alpha, L) constants (hefx_capi.cpp, hybrid_consts: the `take` lines)"""
+    return 2 * L + L * (L + alpha) + 2 * alpha + alpha + alpha * L + L + 2 * L
+
+
+def chunk_of(N_, alpha, L):
+    """items per chunk (hefx_capi.cpp, hybrid_run, the three `chunk` lines): scratch below 1 GiB, the table and four words an item
+    within a descriptor slot, at most KS_MAX_CHUNK"""
+    chunk = (1 << 30) // (item_rows(N_, alpha, L) * N_ * 8)
+    chunk = max(1, min(chunk, (RING_SLOT_PTRS - table_words(alpha, L)) // 4))
+    return min(chunk, KS_MAX_CHUNK)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -74,17 +74,19 @@ def test_at_alpha_one_the_key_is_the_key_of_the_existing_generator(mix):
     assert np.array_equal(np.asarray(old.relin_keys().key(0)).reshape(-1), np.asarray(new.hybrid_relin_keys(1).hybrid_key(0)).reshape(-1))
 
 
-@pytest.mark.parametrize("mix", HC.MIXES)
-def test_at_alpha_one_the_model_is_the_oracles_key_switch(mix):
-    """word for word: apply_galois (the element 1 is switch_key) and relinearize of the oracle, every word case of the set"""
-    s = HC.sets()[f"k4a1-{mix}"]
-    be, key = HC.twin(s), HC.random_key(s, HC.SEED)
-    assert key.shape == (s.k - 1, 2, s.k, s.N)
+@pytest.mark.parametrize("name", HC.ALPHA_ONE_SET_NAMES, ids=HC.ALPHA_ONE_IDS)
+def test_at_alpha_one_the_model_is_the_oracles_key_switch(name):
+    """word for word: apply_galois (the element 1 is switch_key) and relinearize of the oracle, every word case of the set -- at
+    k10a1 with nine digits (L = 9) and on the max key too"""
+    s = HC.sets()[name]
+    be = HC.twin(s)
+    assert s.alpha == 1 and (name.startswith("k4a1") or max(s.levels) == 9)
     for case in HC.word_cases(s):
-        L, form, kind, elt = case
-        ct = HC.case_input(s, case)
+        L, form, kind, elt, key_kind = case
+        ct, key = HC.case_input(s, case), HC.case_key(s, key_kind)
+        assert key.shape == (s.k - 1, 2, s.k, s.N)
         want = be.apply_galois(L, ct.copy(), elt, key) if form == "galois" else be.relinearize(L, ct.copy(), key)
-        assert np.array_equal(HC.case_model(s, case), np.asarray(want).reshape(2, L, s.N)), (mix, case)
+        assert np.array_equal(HC.case_model(s, case), np.asarray(want).reshape(2, L, s.N)), (name, case)
 
 
 def noise_cases():
@@ -99,7 +101,7 @@ def noise_cases():
                 out.append((name, L))
             else:
                 assert "s40" in name, (name, L)   # every set with 60-bit special primes qualifies at every level
-    return out
+    return out + [("n16384", 5), ("big7", 5)]             # the model at the large rings: one level each (the keys cost seconds there)
 
 
 @pytest.mark.parametrize("name,L", noise_cases())
@@ -115,16 +117,33 @@ def test_the_model_keeps_the_noise_bound_under_real_keys(name, L):
         ct = HC.operand(s, kind, L, 2 if form == "galois" else 3, seed=41 + L)
         if form == "galois":
             out = HC.apply_galois_model(be, q, s.alpha, L, ct, elt, host(e, e["gk"].hybrid_key(elt)))
-            want = [HC.gather(N, elt, r) for r in HC.decrypt_rows(ct, sk, q)]
         else:
             out = HC.relinearize_model(be, q, s.alpha, L, ct, host(e, e["rk"].hybrid_key(0)))
-            want = HC.decrypt_rows(ct, sk, q)
-        got = HC.decrypt_rows(out, sk, q)
-        diff, Q_ = HC.centred_integers(be, [(g - w) % int(q[j]) for j, (g, w) in enumerate(zip(got, want))], q)
+        noise, Q_ = HC.switch_noise(s, L, form, elt, ct, out, sk)
         assert Q_ == Q
-        worst = max(worst, int(np.abs(diff).max()))
+        worst = max(worst, noise)
     print(f"[hybrid cpu] {name} L = {L}: noise {worst} (bound {B}, Q_L / 4 = 2^{(Q // 4).bit_length() - 1})")
     assert worst <= B
+
+
+def test_the_restated_launch_rules_at_hand_computed_points():
+    """HC.split_of, item_rows and chunk_of (hy_split, hybrid_item_rows, hybrid_run's chunk lines) at points worked out by hand:
+    N = 2048 has 4 workgroups a row group (1024 records / 256), N = 32768 has 64"""
+    # a chunk: N = 2048, alpha = 2, L = 1: 3 + 1 * 3 + 2 + 4 + 2 = 14 rows, 2^30 / (14 * 2048 * 8) = 4681, the slot (10240 - 16) / 4 = 2556,
+    # the cap 1024
+    assert HC.item_rows(2048, 2, 1) == 14 and HC.table_words(2, 1) == 16 and HC.chunk_of(2048, 2, 1) == 1024
+    # N = 32768, k = 7, alpha = 2, L = 5, dn = 3: 15 + 2 * 3 * 7 + 10 + 2 * 4 + 2 * 10 = 95 rows of 256 KiB: 2^30 / 24903680 = 43.1
+    assert HC.item_rows(32768, 2, 5) == 95 and HC.chunk_of(32768, 2, 5) == 43
+    assert HC.item_rows(16384, 2, 5) == 15 + 21 + 10 + 4 + 10              # every block once below N = 32768
+    assert HC.table_words(1, 61) == 4151 and HC.RING_SLOT_PTRS == 10240     # the largest table the ABI allows fits a slot
+    # the splits of the batch sweep, k7a2 at L = 5: convert has dn n = 3 n groups and 7 targets, spread 2 n groups and 5 targets
+    for n, convert, spread in ((1, 4, 4), (43, 2, 4), (64, 2, 2), (86, 1, 2), (128, 1, 1)):
+        assert (HC.convert_split(2048, 2, 5, n), HC.spread_split(2048, 5, n)) == (convert, spread), n
+    assert HC.split_of(2048, 85 * 3, 7) == 2 and HC.split_of(2048, 86 * 3, 7) == 1     # 1020 < 1024 <= 1032 workgroups
+    assert HC.split_of(2048, 127 * 2, 5) == 2 and HC.split_of(2048, 128 * 2, 5) == 1   # 1016 < 1024 <= 1024
+    assert HC.split_of(2048, 1, 1) == 1 and HC.split_of(2048, 1, 2) == 2 and HC.split_of(2048, 1, 3) == 2   # at most targets / 2
+    assert HC.split_of(32768, 1, 7) == 4 and HC.split_of(32768, 8, 7) == 2 and HC.split_of(32768, 16, 7) == 1   # 64, 512, 1024
+    assert HC.convert_split(2048, 5, 7, 128) == 1 and HC.spread_split(2048, 7, 128) == 1    # k12a5 at L = 7, dn = 2
 
 
 @pytest.mark.parametrize("name", ["k7a2-p50_60", "k8a3-d40_s60"])
