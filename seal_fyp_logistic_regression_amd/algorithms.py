@@ -19,8 +19,8 @@ from .seal import Ciphertext, CKKSEncoder, Evaluator, HybridKeys, KSwitchKeys, P
 
 def _kswitch_only(fn):
     """The fused composites -- the linear transforms, the plain_combine / product_combine pipelines, the bootstrap -- run kernels
-    that know the one-special-prime key layout: given seal.HybridKeys they refuse before anything is computed.  (Routing them
-    through hybrid key switching is a change of its own.)"""
+    that know the one-special-prime key layout: given seal.HybridKeys they refuse before anything is computed.  (The DFT has
+    forms of its own on hybrid keys: coeffs_to_slots_hybrid, slots_to_coeffs_hybrid and their _packed_hybrid forms, below.)"""
     import functools
 
     @functools.wraps(fn)
@@ -963,6 +963,87 @@ def slots_to_coeffs_packed(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitc
     from . import dft
     _packed_plan(ev, plan, dft.S2C, "slots_to_coeffs_packed")
     return _dft_run(ev, [ct], plan, gal_keys, encoded)[0]
+
+
+# ---- the homomorphic DFT on hybrid keys: one decomposition per input, one mod-down per inner sum ----------------------------
+def _dft_stage_hybrid(ev: Evaluator, xs: Sequence[Ciphertext], stage, table, gal_keys: HybridKeys) -> List[Ciphertext]:
+    """_dft_stage on seal.HybridKeys: the baby rotations and ALL inner sums are ONE Evaluator.plain_combine_hoisted (the baby
+    step 0 is its identity term), the giant rotations one hybrid_apply_galois_batch (a step of zero is a copy), then the sums
+    and one batched rescale.  table[matrix][giant][baby]: plan.encode(..., extended=True)[stage], key-level plaintexts."""
+    from .seal import galois_elt_from_step
+    if len(xs) != stage.inputs or any(x.size() != 2 for x in xs) or len({x.parms_id() for x in xs}) != 1:
+        raise ValueError("dft stage: needs %d size-2 ciphertexts of one level" % stage.inputs)
+    nb, ng = len(stage.babies), len(stage.giants)
+    rows = []
+    for c in range(stage.outputs):
+        for gi in range(ng):
+            row = [None] * (len(xs) * nb)
+            feeds = {"split": [(0, c)], "lockstep": [(c, 0)], "merge": [(0, 0), (1, 1)], "single": [(0, 0)]}[stage.mode]
+            for src, mat in feeds:
+                row[src * nb:(src + 1) * nb] = table[mat][gi]
+            rows.append(row)
+    inner = ev.plain_combine_hoisted(xs, list(stage.babies), rows, gal_keys)
+    steps = list(stage.giants) * stage.outputs
+    jobs = [i for i, s in enumerate(steps) if s]
+    elts = [galois_elt_from_step(steps[i], ev.ctx.N) for i in jobs]
+    if any(not gal_keys.has_key(e) for e in elts):
+        raise ValueError("Galois key not present")
+    moved = [c.copy() for c in inner]
+    if jobs:
+        L = inner[0].parms_id()
+        native = getattr(ev.be, "hybrid_apply_galois_batch", None)
+        if native is not None:
+            datas = native(gal_keys.alpha, L, [inner[i].data for i in jobs], elts, [gal_keys.hybrid_key(e) for e in elts])
+        else:
+            datas = [ev.apply_galois(inner[i], e, gal_keys).data for i, e in zip(jobs, elts)]
+        for i, d in zip(jobs, datas):
+            moved[i] = Ciphertext()._set(d, 2, L, inner[i].scale)
+    outs = [moved[c * ng] if ng == 1 else ev.add_many(moved[c * ng:(c + 1) * ng]) for c in range(stage.outputs)]
+    return ev.rescale_to_next_many_inplace(outs)
+
+
+def _dft_run_hybrid(ev: Evaluator, xs: List[Ciphertext], plan, gal_keys: HybridKeys, encoded) -> List[Ciphertext]:
+    if not isinstance(gal_keys, HybridKeys):
+        raise TypeError("the hybrid DFT needs HybridKeys (KeyGenerator.hybrid_galois_keys)")
+    if encoded is None:
+        encoded = plan.encode(CKKSEncoder(ev.ctx, device_encode=False), xs[0].parms_id(), extended=True)
+    for stage, table in zip(plan.stages, encoded):
+        xs = _dft_stage_hybrid(ev, xs, stage, table, gal_keys)
+    return xs
+
+
+def coeffs_to_slots_hybrid(ev: Evaluator, ct: Ciphertext, plan, gal_keys: HybridKeys, encoded=None):
+    """coeffs_to_slots on hybrid keys (include/hefx_hybrid_hoist.h): the same plan, the same values, other words -- every
+    inner sum is rounded once.  ct at a level <= k - alpha; gal_keys: hybrid_galois_keys(alpha, plan.galois_steps(),
+    conjugate=True); encoded: plan.encode(encoder, ct.parms_id(), extended=True)."""
+    from . import dft
+    if plan.direction != dft.C2S or plan.N != ev.ctx.N or plan.slots is not None:
+        raise ValueError("coeffs_to_slots_hybrid: the plan is not a CoeffToSlot plan of this ring")
+    xs = _dft_run_hybrid(ev, [ct], plan, gal_keys, encoded)
+    return tuple(ev.add(x, ev.complex_conjugate(x, gal_keys)) for x in xs)    # 2 Re(.)
+
+
+def slots_to_coeffs_hybrid(ev: Evaluator, ct_a: Ciphertext, ct_b: Ciphertext, plan, gal_keys: HybridKeys, encoded=None) -> Ciphertext:
+    """slots_to_coeffs on hybrid keys; gal_keys: hybrid_galois_keys(alpha, plan.galois_steps())"""
+    from . import dft
+    if plan.direction != dft.S2C or plan.N != ev.ctx.N or plan.slots is not None:
+        raise ValueError("slots_to_coeffs_hybrid: the plan is not a SlotToCoeff plan of this ring")
+    return _dft_run_hybrid(ev, [ct_a, ct_b], plan, gal_keys, encoded)[0]
+
+
+def coeffs_to_slots_packed_hybrid(ev: Evaluator, ct: Ciphertext, plan, gal_keys: HybridKeys, encoded=None) -> Ciphertext:
+    """coeffs_to_slots_packed on hybrid keys: one matrix per stage on one ciphertext, one conjugation"""
+    from . import dft
+    _packed_plan(ev, plan, dft.C2S, "coeffs_to_slots_packed_hybrid")
+    x = _dft_run_hybrid(ev, [ct], plan, gal_keys, encoded)[0]
+    return ev.add(x, ev.complex_conjugate(x, gal_keys))
+
+
+def slots_to_coeffs_packed_hybrid(ev: Evaluator, ct: Ciphertext, plan, gal_keys: HybridKeys, encoded=None) -> Ciphertext:
+    """slots_to_coeffs_packed on hybrid keys"""
+    from . import dft
+    _packed_plan(ev, plan, dft.S2C, "slots_to_coeffs_packed_hybrid")
+    return _dft_run_hybrid(ev, [ct], plan, gal_keys, encoded)[0]
 
 
 def cipher_dot_product_many(ev: Evaluator, As: Sequence[Ciphertext], Bs: Sequence[Ciphertext], size: int,

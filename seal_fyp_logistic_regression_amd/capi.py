@@ -232,6 +232,15 @@ _HYBRID_SIGS = {
 HYBRID_SYMBOLS = sorted(_HYBRID_SIGS)
 HYBRID_ALPHA_MAX = 8  # HEFX_HYBRID_ALPHA_MAX
 
+# include/hefx_hybrid_hoist.h: hoisted hybrid key switching (one decomposition per source, one mod-down per output)
+_HYBRID_HOIST_SIGS = {
+    "hefx_hybrid_rotate_hoisted_batch": (_i, [_vp, _i, _i, _i, _pp, _i, C.POINTER(_u32), _pp, _pp, _vp]),
+    "hefx_hybrid_plain_combine_hoisted": (_i, [_vp, _i, _i, _i, _pp, _i, C.POINTER(_u32), _pp, _i, _pp, _pp, _vp]),
+}
+HYBRID_HOIST_SYMBOLS = sorted(_HYBRID_HOIST_SIGS)
+HYBRID_HOIST_MAX_TERMS = 64  # HEFX_HYBRID_HOIST_MAX_TERMS
+HYBRID_HOIST_MAX_OUT = 64    # HEFX_HYBRID_HOIST_MAX_OUT
+
 
 def product_combine_words(L: int, n: int, P: int, m: int) -> int:
     """words of hefx_product_combine's table with a constant: strides, weights and the constant per row, n pointer records"""
@@ -254,7 +263,7 @@ def lib():
     L = C.CDLL(path, mode=C.RTLD_GLOBAL)
     for name, (res, args) in (list(_SIGS.items()) + list(_REFRESH_SIGS.items()) + list(_BFV_SIGS.items())
                               + list(_POLY_SIGS.items()) + list(_DFT_SIGS.items()) + list(_BOOTSTRAP_SIGS.items())
-                              + list(_ENCAPS_SIGS.items()) + list(_HYBRID_SIGS.items())):
+                              + list(_ENCAPS_SIGS.items()) + list(_HYBRID_SIGS.items()) + list(_HYBRID_HOIST_SIGS.items())):
         f = getattr(L, name)
         f.restype = res
         f.argtypes = args

@@ -10,6 +10,7 @@
 #include "../../include/hefx_bootstrap.h"
 #include "../../include/hefx_encaps.h"
 #include "../../include/hefx_hybrid.h"
+#include "../../include/hefx_hybrid_hoist.h"
 
 #include <chrono>
 #include <cmath>
@@ -3633,6 +3634,107 @@ extern "C" int hefx_hybrid_keygen(hefx_context *c, int alpha, const uint64_t *sk
     HIPCHK(transform(c, false, e + raw, e, dn, k, 0, s));
     HIPCHK(launch_hy_keygen(c->T, F, alpha, dn, (const u64 *)sk, (const u64 *)new_sk, a, e, (u64 *)out, s));
     return HEFX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// hoisted hybrid key switching (include/hefx_hybrid_hoist.h, hefx_hybrid_hoist.hip): one decomposition per source, one
+// mod-down per output.  One table, one launch sequence: no chunking (the header's workspace rule refuses what does not fit).
+// ---------------------------------------------------------------------------------------------
+static int hybrid_hoist_run(hefx_context *c, int alpha, int L, int n, const uint64_t *const *ins, int m, const uint32_t *elts,
+                            const uint64_t *const *keys, int G, const uint64_t *const *pts, uint64_t *const *outs, void *stream,
+                            bool combine)
+{
+    CTXCHK(c);
+    const char *who = combine ? "hybrid_plain_combine_hoisted" : "hybrid_rotate_hoisted_batch";
+    if (int rc = check_hybrid_alpha(c, alpha)) return rc;
+    if (L < 1 || L > c->k - alpha) return fail(HEFX_ERR_INVALID, std::string(who) + ": level L must be in [1, k - alpha]");
+    if (n < 1 || m < 1 || !ins || !elts || !keys || !outs || (combine && !pts))
+        return fail(HEFX_ERR_INVALID, std::string(who) + ": bad arguments: null pointer, n < 1 or m < 1");
+    if ((long)n * m > HEFX_HYBRID_HOIST_MAX_TERMS)
+        return fail(HEFX_ERR_INVALID, std::string(who) + ": more than HEFX_HYBRID_HOIST_MAX_TERMS = " + std::to_string(HEFX_HYBRID_HOIST_MAX_TERMS) + " terms (n * m)");
+    if (combine && (G < 1 || G > HEFX_HYBRID_HOIST_MAX_OUT))
+        return fail(HEFX_ERR_INVALID, std::string(who) + ": G must be in [1, HEFX_HYBRID_HOIST_MAX_OUT = " + std::to_string(HEFX_HYBRID_HOIST_MAX_OUT) + "]");
+    const int T = n * m, O = combine ? G : T;
+    for (int i = 0; i < n; ++i)
+        if (!ins[i]) return fail(HEFX_ERR_INVALID, std::string(who) + ": null pointer in d_ct_in");
+    for (int k = 0; k < m; ++k) {
+        if (!(elts[k] & 1) || elts[k] >= 2 * c->n) return fail(HEFX_ERR_INVALID, "Galois element must be odd and < 2N");
+        if (!keys[k] && elts[k] != 1) return fail(HEFX_ERR_INVALID, std::string(who) + ": a NULL key denotes the identity term: its element must be 1");
+    }
+    for (int o = 0; o < O; ++o) {
+        if (!outs[o]) return fail(HEFX_ERR_INVALID, std::string(who) + ": null pointer in d_ct_out");
+        bool any = !combine;
+        for (int t = 0; combine && t < T && !any; ++t) any = pts[(size_t)o * T + t] != nullptr;
+        if (!any) return fail(HEFX_ERR_INVALID, std::string(who) + ": an output has no term");
+    }
+    const size_t N = c->n, poly_b = (size_t)L * N * sizeof(u64);
+    const int dn = hybrid_digits(alpha, L);
+    const size_t key_b = (size_t)dn * 2 * c->k * N * sizeof(u64);  // the digits level L reads
+    if (int rc = check_ranges(who, (size_t)O, outs, 2 * poly_b,
+                              {{ins, (size_t)n, 2 * poly_b}, {keys, (size_t)m, key_b}, {pts, combine ? (size_t)G * T : 0, (size_t)c->k * N * sizeof(u64)}},
+                              {"d_ct_in", "d_keys", "d_pts"}))
+        return rc;
+    // the workspace of the header, block by block; `raw`: where a pass writes what the next transform reads
+    const size_t Ls = (size_t)L, A = (size_t)alpha, D = (size_t)dn, R = Ls + A;
+    const size_t xc_w = n * Ls * N, ext_w = n * D * R * N, ext_raw = xf_raw(c, ext_w), ad_w = 2 * T * Ls * N, as_w = 2 * T * A * N;
+    const size_t as_raw = combine ? 0 : xf_raw(c, as_w), bd_w = combine ? 2 * G * Ls * N : 0, bs_w = combine ? 2 * G * A * N : 0;
+    const size_t bs_raw = xf_raw(c, bs_w), tt_w = 2 * O * Ls * N, tt_raw = xf_raw(c, tt_w);
+    const size_t total = xc_w + ext_w + ext_raw + ad_w + as_w + as_raw + bd_w + bs_w + bs_raw + tt_w + tt_raw;
+    if (total * sizeof(u64) > ((size_t)1 << 30))
+        return fail(HEFX_ERR_UNSUPPORTED, std::string(who) + ": the workspace of this call passes 1 GiB (include/hefx_hybrid_hoist.h, WORKSPACE): split the call");
+    const HybridConsts &K = hybrid_consts(c, alpha, L);
+    HyhTab X{};
+    uint32_t pos = (uint32_t)K.words.size();
+    auto take = [&](size_t words) {
+        const uint32_t o = pos;
+        pos += (uint32_t)words;
+        return o;
+    };
+    X.pmod = take(Ls), X.srcs = take(n), X.keys = take(m), X.elts = take(m), X.pts = take(combine ? (size_t)G * T : 0), X.outs = take(O);
+    X.n = n, X.m = m, X.G = combine ? G : 0;
+    if (pos > (uint32_t)RING_SLOT_PTRS) return fail(HEFX_ERR_UNSUPPORTED, std::string(who) + ": the call's table does not fit a descriptor slot");
+    if (int rc = ensure_scratch(c, total)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    u64 *xc = c->scratch, *extd = xc + xc_w, *exts = extd + n * D * Ls * N, *Ad = extd + ext_w + ext_raw, *As = Ad + ad_w;
+    u64 *Bd = combine ? As + as_w : Ad, *Bs = combine ? Bd + bd_w : As, *tt = (combine ? Bs + bs_w + bs_raw : As + as_w + as_raw);
+    auto fill = [&](u64 *h) {
+        std::copy(K.words.begin(), K.words.end(), h);
+        for (int j = 0; j < L; ++j) h[X.pmod + j] = h_prod_mod(c, c->k - alpha, c->k, -1, c->primes[j]);
+        for (int i = 0; i < n; ++i) h[X.srcs + i] = (u64)(uintptr_t)ins[i];
+        for (int k = 0; k < m; ++k) h[X.keys + k] = (u64)(uintptr_t)keys[k], h[X.elts + k] = elts[k];
+        for (size_t i = 0; combine && i < (size_t)G * T; ++i) h[X.pts + i] = (u64)(uintptr_t)pts[i];
+        for (int o = 0; o < O; ++o) h[X.outs + o] = (u64)(uintptr_t)outs[o];
+    };
+    auto run = [&](const u64 *d) -> int {
+        HyTab H = K.at;
+        H.tab = d, H.relin = 0;
+        for (int i = 0; i < n; ++i)  // c1 of source i, from the caller's input to the scratch (src != dst at every ring size)
+            HIPCHK(transform(c, true, (const u64 *)ins[i] + Ls * N, xc + (size_t)i * Ls * N, 1, L, 0, s));
+        HIPCHK(launch_hy_convert(c->T, H, n, xc, extd + ext_raw, exts + ext_raw, s));
+        HIPCHK(transform(c, false, extd + ext_raw, extd, n * dn, L, 0, s));
+        HIPCHK(transform(c, false, exts + ext_raw, exts, n * dn, alpha, c->k - alpha, s));
+        HIPCHK(launch_hyh_term(c->T, H, X, extd, exts, Ad, As + as_raw, s));
+        if (combine) HIPCHK(launch_hyh_combine(c->T, H, X, Ad, As, Bd, Bs + bs_raw, s));
+        HIPCHK(transform(c, true, Bs + (combine ? bs_raw : as_raw), Bs, 2 * O, alpha, c->k - alpha, s));
+        HIPCHK(launch_hy_spread(c->T, H, O, Bs, tt + tt_raw, s));
+        HIPCHK(transform(c, false, tt + tt_raw, tt, 2 * O, L, 0, s));
+        HIPCHK(launch_hyh_finish(c->T, H, X, O, Bd, tt, s));
+        return HEFX_OK;
+    };
+    return slot_call(c, s, pos, fill, run);
+}
+
+extern "C" int hefx_hybrid_rotate_hoisted_batch(hefx_context *c, int alpha, int L, int n, const uint64_t *const *ct_in, int m,
+                                                const uint32_t *elts, const uint64_t *const *keys, uint64_t *const *ct_out, void *stream)
+{
+    return hybrid_hoist_run(c, alpha, L, n, ct_in, m, elts, keys, 0, nullptr, ct_out, stream, false);
+}
+
+extern "C" int hefx_hybrid_plain_combine_hoisted(hefx_context *c, int alpha, int L, int n, const uint64_t *const *ct_in, int m,
+                                                 const uint32_t *elts, const uint64_t *const *keys, int G, const uint64_t *const *pts,
+                                                 uint64_t *const *ct_out, void *stream)
+{
+    return hybrid_hoist_run(c, alpha, L, n, ct_in, m, elts, keys, G, pts, ct_out, stream, true);
 }
 
 // ---------------------------------------------------------------------------------------------

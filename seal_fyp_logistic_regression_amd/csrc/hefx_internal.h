@@ -308,6 +308,22 @@ hipError_t launch_hy_spread(const DevTables &T, const HyTab &H, int n, const u64
 hipError_t launch_hy_finish(const DevTables &T, const HyTab &H, int n, const u64 *accd, const u64 *tt, const u64 *c0p, hipStream_t s);
 hipError_t launch_hy_keygen(const DevTables &T, const HyPmod &F, int alpha, int dn, const u64 *sk, const u64 *new_sk, const u64 *a,
                             const u64 *e, u64 *out, hipStream_t s);
+// hoisted hybrid key switching (hefx_hybrid_hoist.hip, include/hefx_hybrid_hoist.h).  The call's device table is HyTab's
+// constants (its `items` block unused) followed by the blocks below, at these word offsets of HyTab::tab.
+struct HyhTab {
+    uint32_t pmod;  // [L]     P mod q_j
+    uint32_t srcs;  // [n]     the source ciphertexts, [2][L][N]
+    uint32_t keys;  // [m]     the keys [dnum][2][k][N], 0: the identity term
+    uint32_t elts;  // [m]     the Galois elements
+    uint32_t pts;   // [G][n m] key-level plaintexts [k][N], 0: a structural zero (the combine entry)
+    uint32_t outs;  // [O]     the outputs, [2][L][N]
+    int n, m, G;
+};
+hipError_t launch_hyh_term(const DevTables &T, const HyTab &H, const HyhTab &X, const u64 *extd, const u64 *exts, u64 *Ad, u64 *As,
+                           hipStream_t s);
+hipError_t launch_hyh_combine(const DevTables &T, const HyTab &H, const HyhTab &X, const u64 *Ad, const u64 *As, u64 *Bd, u64 *Bs,
+                              hipStream_t s);
+hipError_t launch_hyh_finish(const DevTables &T, const HyTab &H, const HyhTab &X, int outs, const u64 *Bd, const u64 *tt, hipStream_t s);
 hipError_t warm_kernels(hipStream_t s);
 hipError_t warm_keyswitch(hipStream_t s);
 hipError_t warm_encode(hipStream_t s);

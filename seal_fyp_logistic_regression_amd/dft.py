@@ -194,9 +194,11 @@ class Plan:
             xs = st.apply(xs)
         return [x + np.conj(x) for x in xs] if self.direction == C2S else list(xs)
 
-    def encode(self, encoder, parms_id: int):
+    def encode(self, encoder, parms_id: int, extended: bool = False):
         """[stage][matrix][giant][baby] -> Plaintext or None: the pre-rotated diagonals, stage i at level parms_id - i and
-        scale float(q) of the prime that level's rescale drops.  The context's chain must be the one the plan was made for."""
+        scale float(q) of the prime that level's rescale drops.  The context's chain must be the one the plan was made for.
+        extended: every diagonal is encoded with all k rows, a KEY-LEVEL plaintext (what Evaluator.plain_combine_hoisted
+        reads: the rows of the stage's level and the special rows); the stage levels are checked as before."""
         primes = encoder.ctx.primes
         out = []
         for i, st in enumerate(self.stages):
@@ -207,7 +209,7 @@ class Plan:
                     for bi, b in enumerate(st.babies)]
             todo = [t for t in todo if t[3] is not None]
             reps = self.n // st.n   # (a packed plan's diagonals have period 2 ns: tiled over the N / 2 slots)
-            pts = encoder.encode_many([t[3] if reps == 1 else np.tile(t[3], reps) for t in todo], st.scale(), L)
+            pts = encoder.encode_many([t[3] if reps == 1 else np.tile(t[3], reps) for t in todo], st.scale(), encoder.ctx.k if extended else L)
             table = [[[None] * len(st.babies) for _ in st.giants] for _ in st.mats]
             for (c, gi, bi, _), p in zip(todo, pts):
                 table[c][gi][bi] = p

@@ -681,6 +681,30 @@ class Engine:
             capi.ptr_array([o.ptr for o in outs]), stream))
         return outs
 
+    # ---- hoisted hybrid key switching (include/hefx_hybrid_hoist.h)
+    def hybrid_rotate_hoisted_batch(self, alpha, L, cts, elts, keys, outs=None, stream=None):
+        """outs[i * m + k] = the hoisted rotation of cts[i] by elts[k] with keys[k] (None with the element 1: the identity term):
+        one digit decomposition per source, NOT the words of hybrid_apply_galois_batch (hefx_hybrid_rotate_hoisted_batch)"""
+        n, m = len(cts), len(elts)
+        outs = outs if outs is not None else self.empty_many(n * m, (2, L, self.N))
+        capi.check(capi.lib().hefx_hybrid_rotate_hoisted_batch(
+            self._h, int(alpha), L, n, capi.ptr_array([c.ptr for c in cts]), m, capi.u32_array(elts),
+            capi.ptr_array([None if k is None else k.ptr for k in keys]), capi.ptr_array([o.ptr for o in outs]), stream))
+        return outs
+
+    def hybrid_plain_combine_hoisted(self, alpha, L, cts, elts, keys, pts, outs=None, stream=None):
+        """outs[o] = MD(sum_t pts[o][t] (.) A_t) over the terms t = i * m + k = (cts[i], elts[k], keys[k]); pts[o][t] a key-level
+        plaintext [k][N] or None (a structural zero): one mod-down per output (hefx_hybrid_plain_combine_hoisted)"""
+        n, m, G = len(cts), len(elts), len(pts)
+        if any(len(r) != n * m for r in pts):
+            raise ValueError("hybrid_plain_combine_hoisted: pts must be [G][n * m]")
+        outs = outs if outs is not None else self.empty_many(G, (2, L, self.N))
+        capi.check(capi.lib().hefx_hybrid_plain_combine_hoisted(
+            self._h, int(alpha), L, n, capi.ptr_array([c.ptr for c in cts]), m, capi.u32_array(elts),
+            capi.ptr_array([None if k is None else k.ptr for k in keys]), G,
+            capi.ptr_array([None if p is None else p.ptr for r in pts for p in r]), capi.ptr_array([o.ptr for o in outs]), stream))
+        return outs
+
     # ---- scalar combinations of ciphertexts (include/hefx_poly.h)
     def scalar_combine(self, L, size, ins, in_rows, weights, consts=None, outs=None, stream=None):
         """outs[g] = sum_k weights[g][k] * ins[k] + consts[g] over the first L rows of every input, one pass over the inputs

@@ -314,6 +314,12 @@ class GpuBackend:
     def hybrid_relinearize_batch(self, alpha, L, ct3s, key):
         return self.engine.hybrid_relinearize_batch(alpha, L, ct3s, key)
 
+    def hybrid_rotate_hoisted_batch(self, alpha, L, cts, elts, keys):
+        return self.engine.hybrid_rotate_hoisted_batch(alpha, L, cts, elts, keys)
+
+    def hybrid_plain_combine_hoisted(self, alpha, L, cts, elts, keys, pts):
+        return self.engine.hybrid_plain_combine_hoisted(alpha, L, cts, elts, keys, pts)
+
     def raise_switch(self, L_out, ct, ckey):
         """mod-raise from one prime and the collapsed key switch in one engine call (hefx_raise_switch); the oracle-backed
         twin of the tests has no such method and Evaluator.raise_switch states the same words through its apply_galois"""
@@ -523,7 +529,8 @@ class HybridKeys(KSwitchKeys):
     (and under 1, the identity element, for Evaluator.switch_key).  Evaluator.rotate_vector, apply_galois, complex_conjugate,
     relinearize from size 3 and switch_key read them through hybrid_key(); ciphertexts must sit at a level <= k - alpha.  The
     fused composites (linear transforms, plain_combine / product_combine pipelines, the bootstrap) read their keys through
-    key() / power_key(), which refuse here: their kernels know the one-special-prime layout only."""
+    key() / power_key(), which refuse here: their kernels know the one-special-prime layout only.  Many rotations of the same
+    ciphertexts and their plaintext-weighted sums: Evaluator.rotate_hoisted / plain_combine_hoisted (include/hefx_hybrid_hoist.h)."""
 
     def __init__(self, alpha: int):
         super().__init__()
@@ -578,6 +585,73 @@ def hybrid_switch_host(be, primes: Sequence[int], alpha: int, L: int, x: np.ndar
             v = sum(z[t] * ((P // q[t]) % q[j]) for t in S) % q[j]
             out[c, j] = ((acc[c, j] - fwd(j, v - (P // 2) % q[j])) * pow(P, -1, q[j]) % q[j]).astype(np.uint64)
     return out
+
+
+def hybrid_hoist_host(be, primes: Sequence[int], alpha: int, L: int, cts, elts, keys, pts=None) -> List[np.ndarray]:
+    """The statement of include/hefx_hybrid_hoist.h in Python integers over the backend's own transforms.  cts: n arrays
+    [2][L][N]; elts, keys: m elements and keys [dnum][2][k][N] (None with the element 1: the identity term).  pts None: the
+    n * m hoisted rotations, out[i * m + k]; else pts[o][i * m + k] = a key-level plaintext [k][N] or None, and the G
+    combined outputs, one mod-down each.  What Evaluator.rotate_hoisted / plain_combine_hoisted run on a backend without
+    the native entries (the oracle twin of the tests)."""
+    from . import galois_tables
+    q = [int(p) for p in primes]
+    k, N = len(q), np.asarray(cts[0]).shape[-1]
+    D = k - alpha
+    S = list(range(D, k))
+    rows = list(range(L)) + S
+    P = 1
+    for t in S:
+        P *= q[t]
+    fwd = lambda m, v: np.asarray(be.to_host(be.ntt_forward(be.from_host((v % q[m]).astype(np.uint64)[None, None]), 1, 1, m))).reshape(-1).astype(object)
+    inv = lambda m, v: np.asarray(be.to_host(be.ntt_inverse(be.from_host(np.asarray(v, dtype=np.uint64)[None, None]), 1, 1, m))).reshape(-1).astype(object)
+    groups = [list(range(j * alpha, min((j + 1) * alpha, L))) for j in range((L + alpha - 1) // alpha)]
+    terms = []                                             # A_t: {(c, m): row}
+    for ct in cts:
+        ct = np.asarray(ct, dtype=np.uint64).reshape(2, L, N)
+        coef = [inv(i, ct[1, i]) for i in range(L)]
+        E = []                                             # the digits of c1, not permuted
+        for G_ in groups:
+            Dj = 1
+            for i in G_:
+                Dj *= q[i]
+            y = {i: coef[i] * pow(Dj // q[i], -1, q[i]) % q[i] for i in G_}
+            E.append({m: ct[1, m].astype(object) if m in G_ else fwd(m, sum(y[i] * ((Dj // q[i]) % q[m]) for i in G_)) for m in rows})
+        for elt, key in zip(elts, keys):
+            A = {}
+            if key is None:
+                if elt != 1:
+                    raise ValueError("hybrid hoisting: a missing key denotes the identity term: its element must be 1")
+                for c in range(2):
+                    for m in rows:
+                        A[c, m] = ct[c, m].astype(object) * (P % q[m]) % q[m] if m < L else np.zeros(N, dtype=object)
+            else:
+                key = np.asarray(key).reshape(-1, 2, k, N)
+                g = galois_tables.gather_table(N, elt)
+                for c in range(2):
+                    for m in rows:
+                        A[c, m] = sum(E[j][m][g] * key[j, c, m].astype(object) for j in range(len(groups))) % q[m]
+                for m in range(L):
+                    A[0, m] = (A[0, m] + (P % q[m]) * ct[0, m][g].astype(object)) % q[m]
+            terms.append(A)
+
+    def mod_down(B):
+        out = np.empty((2, L, N), dtype=np.uint64)
+        for c in range(2):
+            z = {t: (inv(t, B[c, t].astype(np.uint64)) + (P // 2) % q[t]) % q[t] * pow(P // q[t], -1, q[t]) % q[t] for t in S}
+            for j in range(L):
+                v = sum(z[t] * ((P // q[t]) % q[j]) for t in S) % q[j]
+                out[c, j] = ((B[c, j] - fwd(j, v - (P // 2) % q[j])) * pow(P, -1, q[j]) % q[j]).astype(np.uint64)
+        return out
+
+    if pts is None:
+        return [mod_down(A) for A in terms]
+    outs = []
+    for row in pts:
+        if len(row) != len(terms) or all(p is None for p in row):
+            raise ValueError("hybrid hoisting: one plaintext (or None) per term, and a term per output")
+        live = [(np.asarray(p, dtype=np.uint64).reshape(k, N), A) for p, A in zip(row, terms) if p is not None]
+        outs.append(mod_down({(c, m): sum(p[m].astype(object) * A[c, m] for p, A in live) % q[m] for c in range(2) for m in rows}))
+    return outs
 
 
 class EncapsKeys:
@@ -1541,6 +1615,90 @@ class Evaluator:
             for j in range(L):
                 ks[c, j] = ((ks[c, j].astype(object) + ct[c, j].astype(object)) % int(q[j])).astype(np.uint64)
         return be.from_host(ks)
+
+    # ---- hoisted hybrid key switching (include/hefx_hybrid_hoist.h)
+    def _hybrid_hoist_args(self, name: str, cts: Sequence[Ciphertext], steps: Sequence[int], keys: "HybridKeys", identity: bool):
+        """the common checks of the two hoisted methods -> (L, elts, device keys): one level (the rule of _hybrid_level) and
+        size 2; every non-zero step needs its direct key; a step of zero is the identity term (element 1, no key) where
+        `identity` says the entry has one, else it is left out"""
+        if not isinstance(keys, HybridKeys):
+            raise TypeError(f"{name}: needs HybridKeys (KeyGenerator.hybrid_galois_keys)")
+        if not cts or not len(steps):
+            raise ValueError(f"{name}: need at least one ciphertext and one step")
+        L = cts[0].parms_id()
+        for c in cts:
+            if c.parms_id() != L:
+                raise ValueError("encrypted1 and encrypted2 parameter mismatch")
+            if c.size() != 2:
+                raise ValueError("encrypted size must be 2")
+            self._hybrid_level(c, keys)
+        elts, dev = [], []
+        for s in steps:
+            if s == 0 and not identity:
+                continue
+            elt = 1 if s == 0 else galois_elt_from_step(int(s), self.ctx.N)
+            if s != 0 and not keys.has_key(elt):
+                raise ValueError("Galois key not present")
+            elts.append(elt)
+            dev.append(None if s == 0 else keys.hybrid_key(elt))
+        if len(cts) * max(len(elts), 1) > capi.HYBRID_HOIST_MAX_TERMS:
+            raise ValueError(f"{name}: more than {capi.HYBRID_HOIST_MAX_TERMS} terms (ciphertexts times steps)")
+        return L, elts, dev
+
+    def rotate_hoisted(self, cts: Sequence[Ciphertext], steps: Sequence[int], hybrid_keys: "HybridKeys") -> List[List[Ciphertext]]:
+        """out[i][k] = cts[i] rotated by steps[k] with ONE digit decomposition per input (hefx_hybrid_rotate_hoisted_batch, or
+        the statement in Python integers); a step of zero is a copy.  The ciphertexts share a level <= k - alpha; every
+        non-zero step needs its direct key.  NOT the words of rotate_vector with the same keys: the decomposition is
+        permuted, not the operand (include/hefx_hybrid_hoist.h) -- the same plaintext and the same noise bound."""
+        cts, steps = list(cts), [int(s) for s in steps]
+        L, elts, dev = self._hybrid_hoist_args("rotate_hoisted", cts, steps, hybrid_keys, False)
+        datas = []
+        if elts:
+            native = getattr(self.be, "hybrid_rotate_hoisted_batch", None)
+            if native is not None:
+                datas = native(hybrid_keys.alpha, L, [c.data for c in cts], elts, dev)
+            else:
+                be, N = self.be, self.ctx.N
+                host = [np.asarray(be.to_host(c.data), dtype=np.uint64).reshape(2, L, N) for c in cts]
+                datas = [be.from_host(w) for w in hybrid_hoist_host(be, self.ctx.primes, hybrid_keys.alpha, L, host, elts,
+                                                                    [be.to_host(k) for k in dev])]
+        out, m = [], len(elts)
+        for i, c in enumerate(cts):
+            moved = iter(datas[i * m:(i + 1) * m])
+            out.append([c.copy() if s == 0 else Ciphertext()._set(next(moved), 2, L, c.scale) for s in steps])
+        return out
+
+    def plain_combine_hoisted(self, cts: Sequence[Ciphertext], steps: Sequence[int], rows: Sequence[Sequence[Optional[Plaintext]]],
+                              hybrid_keys: "HybridKeys") -> List[Ciphertext]:
+        """Double hoisting on hybrid keys: out[o] = sum over i, k of rows[o][i * len(steps) + k] (.) rotate(cts[i], steps[k]) over
+        the entries that are not None, with ONE digit decomposition per input and ONE mod-down per output
+        (hefx_hybrid_plain_combine_hoisted, or the statement in Python integers).  The plaintexts are KEY-LEVEL plaintexts
+        (encode with parms_id = k) of one scale; a step of zero is the identity term and needs no key.  The checks are those
+        of plain_combine, plus the level rule of hybrid key switching; a missing key is a ValueError.  The scale is the
+        product of the operand scales.  One rounding per output: not the words of rotate_vector + multiply_plain + add_many."""
+        cts, steps, rows = list(cts), [int(s) for s in steps], [list(r) for r in rows]
+        L, elts, dev = self._hybrid_hoist_args("plain_combine_hoisted", cts, steps, hybrid_keys, True)
+        terms = len(cts) * len(steps)
+        if not rows or any(len(r) != terms for r in rows):
+            raise ValueError("plain_combine_hoisted: need one plaintext (or None) per output, ciphertext and step")
+        if len(rows) > capi.HYBRID_HOIST_MAX_OUT:
+            raise ValueError(f"plain_combine_hoisted: more than {capi.HYBRID_HOIST_MAX_OUT} outputs")
+        ct_scale = cts[0].scale
+        if any(not self._close(ct_scale, c.scale) for c in cts):
+            raise ValueError("scale mismatch")
+        if any(all(p is None for p in r) for r in rows):
+            raise ValueError("plain_combine_hoisted: an output has no term")
+        scale = self._plain_product_scale(L, ct_scale, [p for r in rows for p in r if p is not None], self.ctx.k)
+        native = getattr(self.be, "hybrid_plain_combine_hoisted", None)
+        if native is not None:
+            datas = native(hybrid_keys.alpha, L, [c.data for c in cts], elts, dev, [[None if p is None else p.data for p in r] for r in rows])
+        else:
+            be, N = self.be, self.ctx.N
+            host = [np.asarray(be.to_host(c.data), dtype=np.uint64).reshape(2, L, N) for c in cts]
+            datas = [be.from_host(w) for w in hybrid_hoist_host(
+                be, self.ctx.primes, hybrid_keys.alpha, L, host, elts, [None if k is None else be.to_host(k) for k in dev],
+                [[None if p is None else be.to_host(p.data) for p in r] for r in rows])]
+        return [Ciphertext()._set(d, 2, L, scale) for d in datas]
 
     def apply_galois(self, a: Ciphertext, galois_elt: int, galois_keys: KSwitchKeys, destination=None):
         """Evaluator::apply_galois: the automorphism X -> X^galois_elt and the key switch back, with the key of that element"""
