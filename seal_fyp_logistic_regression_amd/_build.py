@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libhefx.so")
 SOURCES = ["hefx_keyswitch.hip", "hefx_kernels.hip", "hefx_encode.hip", "hefx_sample.hip", "hefx_bfv.hip", "hefx_poly.hip", "hefx_dft.hip", "hefx_bootstrap.hip", "hefx_encaps.hip", "hefx_hybrid.hip", "hefx_hybrid_hoist.hip", "hefx_capi.cpp"]  # slowest first
-HEADERS = ["hefx_internal.h", "hefx_modarith.cuh", "hefx_ntt.cuh", "hefx_ntt8.cuh", "hefx_mac.cuh", "hefx_ranges.h", "hefx_lt_plan.h", "hefx_poly_plan.h", "hefx_crt.cuh",
+HEADERS = ["hefx_internal.h", "hefx_modarith.cuh", "hefx_ntt.cuh", "hefx_ntt8.cuh", "hefx_mac.cuh", "hefx_ranges.h", "hefx_lt_plan.h", "hefx_poly_plan.h", "hefx_crt.cuh", "hefx_hybrid.cuh",
            "../../include/hefx.h", "../../include/hefx_refresh.h", "../../include/hefx_bfv.h", "../../include/hefx_poly.h", "../../include/hefx_dft.h", "../../include/hefx_bootstrap.h", "../../include/hefx_encaps.h", "../../include/hefx_hybrid.h", "../../include/hefx_hybrid_hoist.h"]
 DEPS = SOURCES + HEADERS  # a change in any of them rebuilds the library (a header: every object; a source: its object)
 # The arithmetic probe (tests/test_gpu_arith_primitives.py): ONE device primitive per thread on the caller's operands.  A test

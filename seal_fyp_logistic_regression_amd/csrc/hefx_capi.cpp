@@ -1290,9 +1290,11 @@ extern "C" int hefx_multiply_sum(hefx_context *c, int L, int n, int group, const
 // ---------------------------------------------------------------------------------------------
 // Galois tables: out[i] = in[ bitrev(((elt*(2*bitrev(i)+1)) mod 2N - 1)/2) ]
 // ---------------------------------------------------------------------------------------------
+static int check_galois_elt(const hefx_context *c, uint32_t elt) { return (elt & 1) && elt < 2 * c->n ? HEFX_OK : fail(HEFX_ERR_INVALID, "Galois element must be odd and < 2N"); }
+
 static int get_perm(hefx_context *c, uint32_t elt, const uint32_t **out)
 {
-    if (!(elt & 1) || elt >= 2 * c->n) return fail(HEFX_ERR_INVALID, "Galois element must be odd and < 2N");
+    if (int rc = check_galois_elt(c, elt)) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     auto it = c->perm.find(elt);
     if (it != c->perm.end()) {
@@ -3450,20 +3452,24 @@ extern "C" int hefx_raise_switch(hefx_context *c, int L, const uint64_t *ct_in, 
 // hybrid key switching (include/hefx_hybrid.h, hefx_hybrid.hip)
 // ---------------------------------------------------------------------------------------------
 static_assert(HY_ALPHA_MAX == HEFX_HYBRID_ALPHA_MAX, "hefx_internal.h and hefx_hybrid.h disagree");
-static int check_hybrid_alpha(const hefx_context *c, int alpha)
+// what every hybrid entry asks of alpha and -- the switching entries, which pass their name -- of the level L
+static int check_hybrid(const hefx_context *c, int alpha, const char *who = nullptr, int L = 0)
 {
     if (c->logn < 11) return fail(HEFX_ERR_UNSUPPORTED, "key switching / rescale need poly_degree >= 2048");
     if (alpha < 1 || alpha >= c->k || alpha > HEFX_HYBRID_ALPHA_MAX)
         return fail(HEFX_ERR_INVALID, "hybrid key switching: alpha must be in [1, min(k - 1, HEFX_HYBRID_ALPHA_MAX = " +
                                           std::to_string(HEFX_HYBRID_ALPHA_MAX) + ")]");
+    if (who && (L < 1 || L > c->k - alpha)) return fail(HEFX_ERR_INVALID, std::string(who) + ": level L must be in [1, k - alpha]");
     return HEFX_OK;
 }
 static int hybrid_digits(int alpha, int rows) { return (rows + alpha - 1) / alpha; }
+// the bytes of a key that level L reads: its first ceil(L / alpha) digits of [dnum][2][k][N]
+static size_t hybrid_key_bytes(const hefx_context *c, int alpha, int L) { return (size_t)hybrid_digits(alpha, L) * 2 * c->k * c->n * sizeof(u64); }
 
 extern "C" int hefx_hybrid_digits(hefx_context *c, int alpha)
 {
     if (!c) return fail(HEFX_ERR_INVALID, "null context");
-    if (int rc = check_hybrid_alpha(c, alpha)) return rc;
+    if (int rc = check_hybrid(c, alpha)) return rc;
     return hybrid_digits(alpha, c->k - alpha);
 }
 
@@ -3475,6 +3481,8 @@ static u64 h_prod_mod(const hefx_context *c, int first, int last, int skip, u64 
         if (i != skip) r = h_mulmod(r, c->primes[i] % q, q);
     return r;
 }
+// P mod q_m, P the product of the alpha special primes: the key's factor (HyPmod) and the hoisted term's (HyhTab::pmod)
+static u64 hybrid_p_mod(const hefx_context *c, int alpha, int m) { return h_prod_mod(c, c->k - alpha, c->k, -1, c->primes[m]); }
 
 // The constants of (alpha, L), host only, once per pair (HyTab's layout).  All of them are products of at most k primes
 // mod a prime: k^2 alpha multiplications at most.
@@ -3514,20 +3522,29 @@ static const HybridConsts &hybrid_consts(hefx_context *c, int alpha, int L)
         for (int j = 0; j < L; ++j) w[at.phat + (size_t)t * L + j] = h_prod_mod(c, s0, k, s0 + t, c->primes[j]);
     }
     for (int j = 0; j < L; ++j) {
-        const u64 qj = c->primes[j], inv = h_invmod(h_prod_mod(c, s0, k, -1, qj), qj);
+        const u64 qj = c->primes[j], inv = h_invmod(hybrid_p_mod(c, alpha, j), qj);
         w[at.halfd + j] = half_p(qj);
         w[at.pinv + 2 * j] = inv, w[at.pinv + 2 * j + 1] = h_shoup(inv, qj);
     }
     return H;
 }
 
-// rows of N words one item takes in the scratch: xn, c0p, xc (3 L) | extd dn L, exts dn alpha | accd 2 L | accs 2 alpha | tt 2 L;
-// the blocks a pass writes for a transform to read (ext, accs, tt) twice at N = 32768 (xf_raw)
-static size_t hybrid_item_rows(const hefx_context *c, int alpha, int L)
-{
-    const size_t dn = (size_t)hybrid_digits(alpha, L), xf = c->logn == 15 ? 2 : 1;
-    return 3 * (size_t)L + xf * dn * (L + alpha) + 2 * (size_t)L + xf * 2 * alpha + xf * 2 * (size_t)L;
-}
+// The scratch of one run, described once: its blocks in the order of the passes, each taken from a running total (`words`).
+// A block that a pass writes for a transform to read (xf) is written at src and transformed src -> dst; the words behind dst
+// that src needs at N = 32768 (xf_raw) are reserved with it.  Every other block is read and written where it lies: src == dst.
+struct HyBlock {
+    size_t dst, src;
+};
+struct HybridCarve {
+    const hefx_context *c;
+    size_t words = 0;
+    HyBlock take(size_t w, bool xf = false)
+    {
+        const size_t at = words, raw = xf ? xf_raw(c, w) : 0;
+        words += w + raw;
+        return {at, at + raw};
+    }
+};
 
 // One entry for both forms: relin (ins = [3][L][N], single_key) or Galois items (ins = [2][L][N], elts, keys).
 static int hybrid_run(hefx_context *c, int alpha, int L, int n, bool relin, const uint64_t *const *ins, const uint32_t *elts,
@@ -3535,40 +3552,36 @@ static int hybrid_run(hefx_context *c, int alpha, int L, int n, bool relin, cons
 {
     CTXCHK(c);
     const char *who = relin ? "hybrid_relinearize_batch" : "hybrid_apply_galois_batch";
-    if (int rc = check_hybrid_alpha(c, alpha)) return rc;
-    if (L < 1 || L > c->k - alpha) return fail(HEFX_ERR_INVALID, std::string(who) + ": level L must be in [1, k - alpha]");
+    if (int rc = check_hybrid(c, alpha, who, L)) return rc;
     if (n < 1 || !ins || !outs || (relin ? !single_key : (!elts || !keys))) return fail(HEFX_ERR_INVALID, std::string(who) + ": bad arguments: null pointer or n < 1");
     for (int i = 0; i < n; ++i) {
         if (!ins[i] || !outs[i] || (!relin && !keys[i])) return fail(HEFX_ERR_INVALID, std::string(who) + ": null pointer in batch");
-        if (!relin && (!(elts[i] & 1) || elts[i] >= 2 * c->n)) return fail(HEFX_ERR_INVALID, "Galois element must be odd and < 2N");
+        if (int rc = relin ? HEFX_OK : check_galois_elt(c, elts[i])) return rc;
     }
     const size_t N = c->n, poly_b = (size_t)L * N * sizeof(u64);
     const int dn = hybrid_digits(alpha, L);
-    const size_t key_b = (size_t)dn * 2 * c->k * N * sizeof(u64);  // the digits level L reads
     if (int rc = check_ranges(who, (size_t)n, outs, 2 * poly_b,
-                              {{ins, (size_t)n, (relin ? 3 : 2) * poly_b, !relin, 1, 0}, {relin ? &single_key : keys, relin ? (size_t)1 : (size_t)n, key_b}},
+                              {{ins, (size_t)n, (relin ? 3 : 2) * poly_b, !relin, 1, 0}, {relin ? &single_key : keys, relin ? (size_t)1 : (size_t)n, hybrid_key_bytes(c, alpha, L)}},
                               {relin ? "d_ct3" : "d_ct_in", relin ? "d_key" : "d_keys"}, "two items write overlapping outputs",
                               "items must be independent: an input or key overlaps an item's output"))
         return rc;
     const HybridConsts &K = hybrid_consts(c, alpha, L);
-    const size_t item_rows = hybrid_item_rows(c, alpha, L);
-    size_t chunk = ((size_t)1 << 30) / (item_rows * N * sizeof(u64));
+    // The blocks of ONE item.  Every block is [items][...]: a chunk of cnt items has each block at cnt times its offset here
+    // (at() below) and takes cnt times these words.  exts [..][dn][alpha][N] lies `exts` words into ext, behind extd [..][dn][L][N].
+    const size_t Ls = (size_t)L, A = (size_t)alpha, D = (size_t)dn, exts = D * Ls * N;
+    HybridCarve w{c};
+    const HyBlock xn = w.take(Ls * N), c0p = w.take(Ls * N), xc = w.take(Ls * N), ext = w.take(D * (Ls + A) * N, true),
+                  accd = w.take(2 * Ls * N), accs = w.take(2 * A * N, true), tt = w.take(2 * Ls * N, true);
+    size_t chunk = ((size_t)1 << 30) / (w.words * sizeof(u64));
     chunk = std::max<size_t>(1, std::min<size_t>(chunk, ((size_t)RING_SLOT_PTRS - K.words.size()) / 4));
     chunk = std::min<size_t>(chunk, KS_MAX_CHUNK);  // (the transforms put chunk * dn <= 1024 * 61 polynomials in grid.y)
     if (K.words.size() + 4 > (size_t)RING_SLOT_PTRS) return fail(HEFX_ERR_UNSUPPORTED, std::string(who) + ": the constants do not fit a descriptor slot");
     const int cmax = (int)std::min<size_t>(chunk, (size_t)n);
-    if (int rc = ensure_scratch(c, item_rows * N * (size_t)cmax)) return rc;
+    if (int rc = ensure_scratch(c, w.words * (size_t)cmax)) return rc;
     hipStream_t s = (hipStream_t)stream;
     for (int i0 = 0; i0 < n; i0 += cmax) {
         const int cnt = std::min(cmax, n - i0);
-        const size_t cn = (size_t)cnt * N, Ls = (size_t)L, A = (size_t)alpha, D = (size_t)dn;
-        // the chunk's blocks, in the order of the passes; `raw`: where the pass writes what the next transform reads
-        u64 *xn = c->scratch, *c0p = xn + Ls * cn, *xc = c0p + Ls * cn, *extd = xc + Ls * cn;
-        const size_t ext_w = D * (Ls + A) * cn, ext_raw = xf_raw(c, ext_w);
-        u64 *exts = extd + D * Ls * cn, *accd = extd + ext_w + ext_raw, *accs = accd + 2 * Ls * cn;
-        const size_t accs_raw = xf_raw(c, 2 * A * cn);
-        u64 *tt = accs + 2 * A * cn + accs_raw;
-        const size_t tt_raw = xf_raw(c, 2 * Ls * cn);
+        auto at = [&](size_t item_offset) { return c->scratch + item_offset * (size_t)cnt; };
         auto fill = [&](u64 *h) {
             std::copy(K.words.begin(), K.words.end(), h);
             for (int i = 0; i < cnt; ++i) {
@@ -3580,16 +3593,16 @@ static int hybrid_run(hefx_context *c, int alpha, int L, int n, bool relin, cons
         auto run = [&](const u64 *d) -> int {
             HyTab H = K.at;
             H.tab = d, H.relin = relin ? 1 : 0;
-            HIPCHK(launch_hy_gather(c->T, H, cnt, xn, c0p, s));
-            HIPCHK(transform(c, true, xn, xc, cnt, L, 0, s));
-            HIPCHK(launch_hy_convert(c->T, H, cnt, xc, extd + ext_raw, exts + ext_raw, s));
-            HIPCHK(transform(c, false, extd + ext_raw, extd, cnt * dn, L, 0, s));
-            HIPCHK(transform(c, false, exts + ext_raw, exts, cnt * dn, alpha, c->k - alpha, s));
-            HIPCHK(launch_hy_mac(c->T, H, cnt, xn, extd, exts, accd, accs + accs_raw, s));
-            HIPCHK(transform(c, true, accs + accs_raw, accs, 2 * cnt, alpha, c->k - alpha, s));
-            HIPCHK(launch_hy_spread(c->T, H, cnt, accs, tt + tt_raw, s));
-            HIPCHK(transform(c, false, tt + tt_raw, tt, 2 * cnt, L, 0, s));
-            HIPCHK(launch_hy_finish(c->T, H, cnt, accd, tt, c0p, s));
+            HIPCHK(launch_hy_gather(c->T, H, cnt, at(xn.dst), at(c0p.dst), s));
+            HIPCHK(transform(c, true, at(xn.dst), at(xc.dst), cnt, L, 0, s));
+            HIPCHK(launch_hy_convert(c->T, H, cnt, at(xc.dst), at(ext.src), at(ext.src + exts), s));
+            HIPCHK(transform(c, false, at(ext.src), at(ext.dst), cnt * dn, L, 0, s));
+            HIPCHK(transform(c, false, at(ext.src + exts), at(ext.dst + exts), cnt * dn, alpha, c->k - alpha, s));
+            HIPCHK(launch_hy_mac(c->T, H, cnt, at(xn.dst), at(ext.dst), at(ext.dst + exts), at(accd.dst), at(accs.src), s));
+            HIPCHK(transform(c, true, at(accs.src), at(accs.dst), 2 * cnt, alpha, c->k - alpha, s));
+            HIPCHK(launch_hy_spread(c->T, H, cnt, at(accs.dst), at(tt.src), s));
+            HIPCHK(transform(c, false, at(tt.src), at(tt.dst), 2 * cnt, L, 0, s));
+            HIPCHK(launch_hy_finish(c->T, H, cnt, at(accd.dst), at(tt.dst), at(c0p.dst), s));
             return HEFX_OK;
         };
         if (int rc = slot_call(c, s, K.words.size() + 4 * (size_t)cnt, fill, run)) return rc;
@@ -3613,7 +3626,7 @@ extern "C" int hefx_hybrid_keygen(hefx_context *c, int alpha, const uint64_t *sk
                                   uint64_t stream_id, uint64_t *out, void *stream)
 {
     CTXCHK(c);
-    if (int rc = check_hybrid_alpha(c, alpha)) return rc;
+    if (int rc = check_hybrid(c, alpha)) return rc;
     if (!sk || !new_sk || !key32 || !out) return fail(HEFX_ERR_INVALID, "bad key generation arguments");
     if (stream_id >> 62) return fail(HEFX_ERR_INVALID, "stream id must be below 2^62");
     const int k = c->k, dn = hybrid_digits(alpha, k - alpha);
@@ -3627,7 +3640,7 @@ extern "C" int hefx_hybrid_keygen(hefx_context *c, int alpha, const uint64_t *sk
     hipStream_t s = (hipStream_t)stream;
     const SampleKey key = sample_key(key32);
     HyPmod F{};
-    for (int m = 0; m < k - alpha; ++m) F.v[m] = h_prod_mod(c, k - alpha, k, -1, c->primes[m]);
+    for (int m = 0; m < k - alpha; ++m) F.v[m] = hybrid_p_mod(c, alpha, m);
     // sub-streams 2*id: uniform a, 2*id+1: noise e (hefx_keygen_kswitch's, over dn polynomials)
     HIPCHK(launch_sample(c->T, SAMPLE_UNIFORM, key, c->noise, 2 * stream_id, dn, k, 0, a, s));
     HIPCHK(launch_sample(c->T, SAMPLE_NOISE, key, c->noise, 2 * stream_id + 1, dn, k, 0, e + raw, s));
@@ -3646,8 +3659,7 @@ static int hybrid_hoist_run(hefx_context *c, int alpha, int L, int n, const uint
 {
     CTXCHK(c);
     const char *who = combine ? "hybrid_plain_combine_hoisted" : "hybrid_rotate_hoisted_batch";
-    if (int rc = check_hybrid_alpha(c, alpha)) return rc;
-    if (L < 1 || L > c->k - alpha) return fail(HEFX_ERR_INVALID, std::string(who) + ": level L must be in [1, k - alpha]");
+    if (int rc = check_hybrid(c, alpha, who, L)) return rc;
     if (n < 1 || m < 1 || !ins || !elts || !keys || !outs || (combine && !pts))
         return fail(HEFX_ERR_INVALID, std::string(who) + ": bad arguments: null pointer, n < 1 or m < 1");
     if ((long)n * m > HEFX_HYBRID_HOIST_MAX_TERMS)
@@ -3658,7 +3670,7 @@ static int hybrid_hoist_run(hefx_context *c, int alpha, int L, int n, const uint
     for (int i = 0; i < n; ++i)
         if (!ins[i]) return fail(HEFX_ERR_INVALID, std::string(who) + ": null pointer in d_ct_in");
     for (int k = 0; k < m; ++k) {
-        if (!(elts[k] & 1) || elts[k] >= 2 * c->n) return fail(HEFX_ERR_INVALID, "Galois element must be odd and < 2N");
+        if (int rc = check_galois_elt(c, elts[k])) return rc;
         if (!keys[k] && elts[k] != 1) return fail(HEFX_ERR_INVALID, std::string(who) + ": a NULL key denotes the identity term: its element must be 1");
     }
     for (int o = 0; o < O; ++o) {
@@ -3669,37 +3681,31 @@ static int hybrid_hoist_run(hefx_context *c, int alpha, int L, int n, const uint
     }
     const size_t N = c->n, poly_b = (size_t)L * N * sizeof(u64);
     const int dn = hybrid_digits(alpha, L);
-    const size_t key_b = (size_t)dn * 2 * c->k * N * sizeof(u64);  // the digits level L reads
     if (int rc = check_ranges(who, (size_t)O, outs, 2 * poly_b,
-                              {{ins, (size_t)n, 2 * poly_b}, {keys, (size_t)m, key_b}, {pts, combine ? (size_t)G * T : 0, (size_t)c->k * N * sizeof(u64)}},
+                              {{ins, (size_t)n, 2 * poly_b}, {keys, (size_t)m, hybrid_key_bytes(c, alpha, L)}, {pts, combine ? (size_t)G * T : 0, (size_t)c->k * N * sizeof(u64)}},
                               {"d_ct_in", "d_keys", "d_pts"}))
         return rc;
-    // the workspace of the header, block by block; `raw`: where a pass writes what the next transform reads
-    const size_t Ls = (size_t)L, A = (size_t)alpha, D = (size_t)dn, R = Ls + A;
-    const size_t xc_w = n * Ls * N, ext_w = n * D * R * N, ext_raw = xf_raw(c, ext_w), ad_w = 2 * T * Ls * N, as_w = 2 * T * A * N;
-    const size_t as_raw = combine ? 0 : xf_raw(c, as_w), bd_w = combine ? 2 * G * Ls * N : 0, bs_w = combine ? 2 * G * A * N : 0;
-    const size_t bs_raw = xf_raw(c, bs_w), tt_w = 2 * O * Ls * N, tt_raw = xf_raw(c, tt_w);
-    const size_t total = xc_w + ext_w + ext_raw + ad_w + as_w + as_raw + bd_w + bs_w + bs_raw + tt_w + tt_raw;
-    if (total * sizeof(u64) > ((size_t)1 << 30))
+    // the workspace of the header, block by block; exts [n][dn][alpha][N] lies `exts` words into ext, behind extd [n][dn][L][N].
+    // The rotate entry transforms the terms' special rows themselves (B = A); the combine entry reads them as hyh_term wrote them.
+    const size_t Ls = (size_t)L, A = (size_t)alpha, D = (size_t)dn, exts = n * D * Ls * N;
+    HybridCarve w{c};
+    const HyBlock xc = w.take(n * Ls * N), ext = w.take(n * D * (Ls + A) * N, true), Ad = w.take(2 * T * Ls * N), As = w.take(2 * T * A * N, !combine),
+                  Bd = combine ? w.take(2 * G * Ls * N) : Ad, Bs = combine ? w.take(2 * G * A * N, true) : As, tt = w.take(2 * O * Ls * N, true);
+    if (w.words * sizeof(u64) > ((size_t)1 << 30))
         return fail(HEFX_ERR_UNSUPPORTED, std::string(who) + ": the workspace of this call passes 1 GiB (include/hefx_hybrid_hoist.h, WORKSPACE): split the call");
     const HybridConsts &K = hybrid_consts(c, alpha, L);
     HyhTab X{};
-    uint32_t pos = (uint32_t)K.words.size();
-    auto take = [&](size_t words) {
-        const uint32_t o = pos;
-        pos += (uint32_t)words;
-        return o;
-    };
-    X.pmod = take(Ls), X.srcs = take(n), X.keys = take(m), X.elts = take(m), X.pts = take(combine ? (size_t)G * T : 0), X.outs = take(O);
+    X.pmod = (uint32_t)K.words.size(), X.srcs = X.pmod + L, X.keys = X.srcs + n, X.elts = X.keys + m, X.pts = X.elts + m;
+    X.outs = X.pts + (combine ? G * T : 0);
+    const uint32_t pos = X.outs + O;  // the words of the call's table
     X.n = n, X.m = m, X.G = combine ? G : 0;
     if (pos > (uint32_t)RING_SLOT_PTRS) return fail(HEFX_ERR_UNSUPPORTED, std::string(who) + ": the call's table does not fit a descriptor slot");
-    if (int rc = ensure_scratch(c, total)) return rc;
+    if (int rc = ensure_scratch(c, w.words)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    u64 *xc = c->scratch, *extd = xc + xc_w, *exts = extd + n * D * Ls * N, *Ad = extd + ext_w + ext_raw, *As = Ad + ad_w;
-    u64 *Bd = combine ? As + as_w : Ad, *Bs = combine ? Bd + bd_w : As, *tt = (combine ? Bs + bs_w + bs_raw : As + as_w + as_raw);
+    u64 *S = c->scratch;
     auto fill = [&](u64 *h) {
         std::copy(K.words.begin(), K.words.end(), h);
-        for (int j = 0; j < L; ++j) h[X.pmod + j] = h_prod_mod(c, c->k - alpha, c->k, -1, c->primes[j]);
+        for (int j = 0; j < L; ++j) h[X.pmod + j] = hybrid_p_mod(c, alpha, j);
         for (int i = 0; i < n; ++i) h[X.srcs + i] = (u64)(uintptr_t)ins[i];
         for (int k = 0; k < m; ++k) h[X.keys + k] = (u64)(uintptr_t)keys[k], h[X.elts + k] = elts[k];
         for (size_t i = 0; combine && i < (size_t)G * T; ++i) h[X.pts + i] = (u64)(uintptr_t)pts[i];
@@ -3709,16 +3715,16 @@ static int hybrid_hoist_run(hefx_context *c, int alpha, int L, int n, const uint
         HyTab H = K.at;
         H.tab = d, H.relin = 0;
         for (int i = 0; i < n; ++i)  // c1 of source i, from the caller's input to the scratch (src != dst at every ring size)
-            HIPCHK(transform(c, true, (const u64 *)ins[i] + Ls * N, xc + (size_t)i * Ls * N, 1, L, 0, s));
-        HIPCHK(launch_hy_convert(c->T, H, n, xc, extd + ext_raw, exts + ext_raw, s));
-        HIPCHK(transform(c, false, extd + ext_raw, extd, n * dn, L, 0, s));
-        HIPCHK(transform(c, false, exts + ext_raw, exts, n * dn, alpha, c->k - alpha, s));
-        HIPCHK(launch_hyh_term(c->T, H, X, extd, exts, Ad, As + as_raw, s));
-        if (combine) HIPCHK(launch_hyh_combine(c->T, H, X, Ad, As, Bd, Bs + bs_raw, s));
-        HIPCHK(transform(c, true, Bs + (combine ? bs_raw : as_raw), Bs, 2 * O, alpha, c->k - alpha, s));
-        HIPCHK(launch_hy_spread(c->T, H, O, Bs, tt + tt_raw, s));
-        HIPCHK(transform(c, false, tt + tt_raw, tt, 2 * O, L, 0, s));
-        HIPCHK(launch_hyh_finish(c->T, H, X, O, Bd, tt, s));
+            HIPCHK(transform(c, true, (const u64 *)ins[i] + Ls * N, S + xc.dst + (size_t)i * Ls * N, 1, L, 0, s));
+        HIPCHK(launch_hy_convert(c->T, H, n, S + xc.dst, S + ext.src, S + ext.src + exts, s));
+        HIPCHK(transform(c, false, S + ext.src, S + ext.dst, n * dn, L, 0, s));
+        HIPCHK(transform(c, false, S + ext.src + exts, S + ext.dst + exts, n * dn, alpha, c->k - alpha, s));
+        HIPCHK(launch_hyh_term(c->T, H, X, S + ext.dst, S + ext.dst + exts, S + Ad.dst, S + As.src, s));
+        if (combine) HIPCHK(launch_hyh_combine(c->T, H, X, S + Ad.dst, S + As.dst, S + Bd.dst, S + Bs.src, s));
+        HIPCHK(transform(c, true, S + Bs.src, S + Bs.dst, 2 * O, alpha, c->k - alpha, s));
+        HIPCHK(launch_hy_spread(c->T, H, O, S + Bs.dst, S + tt.src, s));
+        HIPCHK(transform(c, false, S + tt.src, S + tt.dst, 2 * O, L, 0, s));
+        HIPCHK(launch_hyh_finish(c->T, H, X, O, S + Bd.dst, S + tt.dst, s));
         return HEFX_OK;
     };
     return slot_call(c, s, pos, fill, run);

@@ -1,9 +1,9 @@
 // hefx_hybrid.hip -- the element-wise kernels of hybrid key switching (include/hefx_hybrid.h): alpha data primes per RNS
 // digit, alpha special primes.  The transforms are the engine's, through hefx_capi.cpp's transform() at every ring size; the
-// host sequence and the (alpha, L) constants are hefx_capi.cpp's (hybrid_run, hybrid_consts).
+// host sequence and the (alpha, L) constants are hefx_capi.cpp's (hybrid_run, hybrid_consts).  The rows, the shape of a
+// launch, the arithmetic ranges and the pieces shared with the hoisted form are hefx_hybrid.cuh's.
 //
-// One chunk of c items, pass by pass (R = L + alpha rows: r < L is data prime r, r >= L is special prime k - alpha + r - L;
-// dn = ceil(L / alpha) digits; every arrow that crosses a line is a transform):
+// One chunk of c items, pass by pass (every arrow that crosses a line is a transform):
 //   hy_gather     items -> xn [c][L][N], c0p [c][L][N]     x = pi_g(c1) (or c2 of a relinearisation) and pi_g(c0), NTT form
 //                          --INTT-->  xc [c][L][N]
 //   hy_convert    xc -> extd [c][dn][L][N], exts [c][dn][alpha][N]   fast base conversion of digit j to every row outside it
@@ -17,25 +17,16 @@
 // (d_ct_out[i] == d_ct_in[i]) needs no special case.  The own rows of a digit in extd (m in G_j) are never written and
 // never read: the MAC takes them from xn.
 //
-// SHAPE.  256 lanes per workgroup, one 16-byte record (two adjacent coefficients) per lane.  hy_gather, hy_mac and
-// hy_finish write one row per workgroup row: blockIdx.y = the RNS row, so its modulus is uniform per workgroup.  hy_convert
-// and hy_spread are the two passes with FEWER source rows than target rows (alpha sources -> up to L + alpha - 1 targets):
-// there the LANE loops over the targets.  Write traffic dominates both -- one record written per target either way -- and
-// with the targets in the grid every one of them would read the alpha source rows and redo the alpha products y_i (z_t)
-// again: alpha (L + alpha) reads and products where alpha suffice.  The loop index is uniform, so the constants of the
-// target are scalar loads all the same.  Small batches split the target range over blockIdx.y (at most 4 ways) so that
-// one item still fills the chip; every split part redoes the alpha source products, which is why it stays at 4.
-//
-// ARITHMETIC.  Every word read is canonical (the transforms' outputs, the caller's operands by the ABI) and every word
-// written is canonical.  Lazy values inside a lane: shoup_lazy's [0, 2q), folded by csub at its line; and the 128-bit sums
-// of products of canonical words below 2^61, each product below 2^122 -- at most HEFX_HYBRID_ALPHA_MAX = 8 of them in a
-// conversion (below 2^125) and at most 61 of them in the MAC (k <= 62: below 2^128) -- folded ONCE per word by
-// barrett128, which takes any 128-bit value (hefx_modarith.cuh).  These passes do integer work mod every prime.
-#include "hefx_internal.h"
+// SHAPE of the lane-loop passes.  hy_gather, hy_mac and hy_finish write one row per workgroup row.  hy_convert and hy_spread
+// are the two passes with FEWER source rows than target rows (alpha sources -> up to L + alpha - 1 targets): there the LANE
+// loops over the targets.  Write traffic dominates both -- one record written per target either way -- and with the targets
+// in the grid every one of them would read the alpha source rows and redo the alpha products y_i (z_t) again:
+// alpha (L + alpha) reads and products where alpha suffice.  The loop index is uniform, so the constants of the target are
+// scalar loads all the same.  Small batches split the target range over blockIdx.y (at most 4 ways) so that one item still
+// fills the chip; every split part redoes the alpha source products, which is why it stays at 4.
+#include "hefx_hybrid.cuh"
 
 namespace hefx {
-
-__device__ __forceinline__ int hy_row_mod(const HyTab &H, int k, int r) { return r < H.L ? r : k - H.alpha + (r - H.L); }
 
 // blockIdx.y = row m, blockIdx.z = item * np + p (np = 1: a relinearisation, x = polynomial 2 as it is; np = 2: a Galois
 // item, p == 0 -> x = pi_g(c1), p == 1 -> pi_g(c0)).  out[i] = in[galois_index(i)]; the records 2w, 2w+1 come from ONE
@@ -94,7 +85,7 @@ __global__ __launch_bounds__(256) void hy_convert_kernel(DevTables T, HyTab H, i
         for (int i = 0; i < A; ++i) {
             if (i < cnt) {
                 const u64 f = H.tab[H.conv + (size_t)(first + i) * R + r];  // Dhat_i mod q_m, canonical
-                mac128(xl, xh, y[i].x, f);  // each product < 2^122; A <= 8 of them: < 2^125
+                mac128(xl, xh, y[i].x, f);  // at most HY_ALPHA_MAX products: hefx_hybrid.cuh, ARITHMETIC
                 mac128(yl, yh, y[i].y, f);
             }
         }
@@ -109,36 +100,16 @@ __global__ __launch_bounds__(256) void hy_convert_kernel(DevTables T, HyTab H, i
 __global__ __launch_bounds__(256) void hy_mac_kernel(DevTables T, HyTab H, const u64 *__restrict__ xn, const u64 *__restrict__ extd,
                                                      const u64 *__restrict__ exts, u64 *__restrict__ accd, u64 *__restrict__ accs)
 {
-    const int logn = T.logn, L = H.L, A = H.alpha, k = T.k;
+    const int logn = T.logn, L = H.L;
     const size_t w = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (w >= ((size_t)1 << (logn - 1))) return;
     const int r = (int)blockIdx.y, it = (int)blockIdx.z;
-    const int m = hy_row_mod(H, k, r);
+    const int m = hy_row_mod(H, T.k, r);
     const ModConst mc = T.mods[m];
     const u64 *key = (const u64 *)H.tab[H.items + 4 * (size_t)it + 2] + ((size_t)m << logn) + 2 * w;
-    const size_t poly = (size_t)k << logn, digit = 2 * poly;  // words of one key polynomial / one key digit
-    const int own = r < L ? r / A : -1;
-    u64 a0xl = 0, a0xh = 0, a0yl = 0, a0yh = 0, a1xl = 0, a1xh = 0, a1yl = 0, a1yh = 0;
-    for (int j = 0; j < H.dn; ++j) {
-        const u64 *xs = j == own ? xn + ((size_t)(it * L + r) << logn)
-                        : r < L  ? extd + ((size_t)((it * H.dn + j) * L + r) << logn)
-                                 : exts + ((size_t)((it * H.dn + j) * A + (r - L)) << logn);
-        const ulonglong2 x = gld16(xs + 2 * w);
-        const ulonglong2 k0 = gld16(key + (size_t)j * digit), k1 = gld16(key + (size_t)j * digit + poly);
-        mac128(a0xl, a0xh, x.x, k0.x);  // canonical x canonical < 2^122; dn <= 61 of them: < 2^128
-        mac128(a0yl, a0yh, x.y, k0.y);
-        mac128(a1xl, a1xh, x.x, k1.x);
-        mac128(a1yl, a1yh, x.y, k1.y);
-    }
-    const ulonglong2 r0 = make_ulonglong2(barrett128(a0xl, a0xh, mc), barrett128(a0yl, a0yh, mc));  // one fold per word
-    const ulonglong2 r1 = make_ulonglong2(barrett128(a1xl, a1xh, mc), barrett128(a1yl, a1yh, mc));
-    if (r < L) {
-        gst16(accd + ((size_t)((it * 2 + 0) * L + r) << logn) + 2 * w, r0);
-        gst16(accd + ((size_t)((it * 2 + 1) * L + r) << logn) + 2 * w, r1);
-    } else {
-        gst16(accs + ((size_t)((it * 2 + 0) * A + (r - L)) << logn) + 2 * w, r0);
-        gst16(accs + ((size_t)((it * 2 + 1) * A + (r - L)) << logn) + 2 * w, r1);
-    }
+    HyAcc acc;
+    hy_digits_mac(acc, T, H, r, it, xn + ((size_t)(it * L + r) << logn), extd, exts, key, 2 * w, false);
+    hy_pair_store(T, H, accd, accs, it, r, w, acc.fold(0, mc), acc.fold(1, mc));
 }
 
 // u [c][2][A][N] = INTT of the special rows of acc, canonical.  blockIdx.z = item * 2 + polynomial, blockIdx.y = the split
@@ -167,7 +138,7 @@ __global__ __launch_bounds__(256) void hy_spread_kernel(DevTables T, HyTab H, in
 #pragma unroll
         for (int t = 0; t < A; ++t) {
             const u64 f = H.tab[H.phat + (size_t)t * L + j];  // (P/q_t) mod q_j, canonical
-            mac128(xl, xh, zt[t].x, f);                       // each product < 2^122; A <= 8 of them: < 2^125
+            mac128(xl, xh, zt[t].x, f);                       // at most HY_ALPHA_MAX products: hefx_hybrid.cuh, ARITHMETIC
             mac128(yl, yh, zt[t].y, f);
         }
         const u64 half = H.tab[H.halfd + j];
@@ -186,13 +157,8 @@ __global__ __launch_bounds__(256) void hy_finish_kernel(DevTables T, HyTab H, co
     if (w >= ((size_t)1 << (logn - 1))) return;
     const int j = (int)blockIdx.y, it = (int)blockIdx.z >> 1, c = (int)blockIdx.z & 1;
     const ModConst mc = T.mods[j];
-    const u64 pinv = H.tab[H.pinv + 2 * j], pinvs = H.tab[H.pinv + 2 * j + 1];  // {P^-1 mod q_j, its Shoup companion}
     const u64 *item = H.tab + H.items + 4 * (size_t)it;
-    const size_t at = ((size_t)((it * 2 + c) * L + j) << logn) + 2 * w;
-    const ulonglong2 a = gld16(accd + at), t = gld16(tt + at);
-    ulonglong2 v;
-    v.x = csub(shoup_lazy(submod(a.x, t.x, mc.q), pinv, pinvs, mc.nq), mc.q);  // canonical - canonical -> canonical; shoup_lazy: [0, 2q) -> [0, q)
-    v.y = csub(shoup_lazy(submod(a.y, t.y, mc.q), pinv, pinvs, mc.nq), mc.q);
+    ulonglong2 v = hy_mod_down(T, H, j, (int)blockIdx.z, w, accd, tt);
     if (H.relin || c == 0) {  // uniform
         const u64 *add = H.relin ? (const u64 *)item[0] + ((size_t)(c * L + j) << logn) : c0p + ((size_t)(it * L + j) << logn);
         const ulonglong2 l = gld16(add + 2 * w);
@@ -226,12 +192,6 @@ __global__ __launch_bounds__(256) void hy_keygen_kernel(DevTables T, HyPmod F, i
     }
     gst16(out + ((size_t)(j * 2 + 0) * k << logn) + row, c0);
     gst16(out + ((size_t)(j * 2 + 1) * k << logn) + row, av);
-}
-
-static dim3 hy_grid(const DevTables &T, int rows, int z)
-{
-    const size_t row_pairs = (size_t)1 << (T.logn - 1);
-    return dim3((unsigned)((row_pairs + 255) / 256), (unsigned)rows, (unsigned)z);
 }
 
 // how many ways a lane-loop pass splits its target range: enough workgroups for the chip (about four per CU of 256), at most 4

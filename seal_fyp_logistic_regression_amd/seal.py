@@ -551,39 +551,72 @@ class HybridKeys(KSwitchKeys):
         self._refuse()
 
 
-def hybrid_switch_host(be, primes: Sequence[int], alpha: int, L: int, x: np.ndarray, key: np.ndarray) -> np.ndarray:
-    """The switch of include/hefx_hybrid.h's statement, steps 1 to 5, in Python integers over the backend's own transforms:
-    x [L][N] NTT form, key [dnum][2][k][N] -> ks [2][L][N].  What Evaluator runs with HybridKeys on a backend without the
-    native entries (the oracle twin of the tests)."""
+def _hybrid_basis(primes: Sequence[int], alpha: int, L: int):
+    """(q, S, rows, P) of include/hefx_hybrid.h: the chain, its special rows, the rows of a level-L switch, the special modulus"""
     q = [int(p) for p in primes]
-    k, N = len(q), np.asarray(x).shape[-1]
-    D = k - alpha
-    S, rows = list(range(D, k)), list(range(L)) + list(range(D, k))
+    S = list(range(len(q) - alpha, len(q)))
     P = 1
     for t in S:
         P *= q[t]
-    key = np.asarray(key).reshape(-1, 2, k, N)
-    fwd = lambda m, v: np.asarray(be.to_host(be.ntt_forward(be.from_host((v % q[m]).astype(np.uint64)[None, None]), 1, 1, m))).reshape(-1).astype(object)
-    inv = lambda m, v: np.asarray(be.to_host(be.ntt_inverse(be.from_host(np.asarray(v, dtype=np.uint64)[None, None]), 1, 1, m))).reshape(-1).astype(object)
-    x = np.asarray(x, dtype=np.uint64).reshape(L, N)
-    coef = [inv(i, x[i]) for i in range(L)]
-    acc = {(c, m): np.zeros(N, dtype=object) for c in range(2) for m in rows}
+    return q, S, list(range(L)) + S, P
+
+
+def _row_ntt(be, q, m: int, v) -> np.ndarray:
+    """one row of integers, reduced mod q[m], through the backend's forward transform -> Python integers"""
+    return np.asarray(be.to_host(be.ntt_forward(be.from_host((v % q[m]).astype(np.uint64)[None, None]), 1, 1, m))).reshape(-1).astype(object)
+
+
+def _row_intt(be, m: int, v) -> np.ndarray:
+    """one canonical row through the backend's inverse transform -> Python integers"""
+    return np.asarray(be.to_host(be.ntt_inverse(be.from_host(np.asarray(v, dtype=np.uint64)[None, None]), 1, 1, m))).reshape(-1).astype(object)
+
+
+def _hybrid_digits_host(be, primes: Sequence[int], alpha: int, L: int, x: np.ndarray) -> List[Dict[int, np.ndarray]]:
+    """Steps 1 to 3 of include/hefx_hybrid.h's statement: x [L][N] NTT form -> E[j][m], digit j extended to every row m of the
+    switch (the digit's own rows are x's own)."""
+    q, _, rows, _ = _hybrid_basis(primes, alpha, L)
+    coef = [_row_intt(be, i, x[i]) for i in range(L)]
+    E = []
     for j in range((L + alpha - 1) // alpha):
         G = list(range(j * alpha, min((j + 1) * alpha, L)))
         Dj = 1
         for i in G:
             Dj *= q[i]
         y = {i: coef[i] * pow(Dj // q[i], -1, q[i]) % q[i] for i in G}
-        for m in rows:
-            ext = x[m].astype(object) if m in G else fwd(m, sum(y[i] * ((Dj // q[i]) % q[m]) for i in G))
-            for c in range(2):
-                acc[c, m] = (acc[c, m] + ext * key[j, c, m].astype(object)) % q[m]
-    out = np.empty((2, L, N), dtype=np.uint64)
+        E.append({m: x[m].astype(object) if m in G else _row_ntt(be, q, m, sum(y[i] * ((Dj // q[i]) % q[m]) for i in G)) for m in rows})
+    return E
+
+
+def _hybrid_mod_down_host(be, primes: Sequence[int], alpha: int, L: int, B) -> np.ndarray:
+    """Step 5: B[c, m] canonical over the rows of the switch -> round(B / P) [2][L][N]"""
+    q, S, _, P = _hybrid_basis(primes, alpha, L)
+    out = np.empty((2, L, len(B[0, 0])), dtype=np.uint64)
     for c in range(2):
-        z = {t: (inv(t, acc[c, t].astype(np.uint64)) + (P // 2) % q[t]) % q[t] * pow(P // q[t], -1, q[t]) % q[t] for t in S}
+        z = {t: (_row_intt(be, t, B[c, t].astype(np.uint64)) + (P // 2) % q[t]) % q[t] * pow(P // q[t], -1, q[t]) % q[t] for t in S}
         for j in range(L):
             v = sum(z[t] * ((P // q[t]) % q[j]) for t in S) % q[j]
-            out[c, j] = ((acc[c, j] - fwd(j, v - (P // 2) % q[j])) * pow(P, -1, q[j]) % q[j]).astype(np.uint64)
+            out[c, j] = ((B[c, j] - _row_ntt(be, q, j, v - (P // 2) % q[j])) * pow(P, -1, q[j]) % q[j]).astype(np.uint64)
+    return out
+
+
+def hybrid_switch_host(be, primes: Sequence[int], alpha: int, L: int, x: np.ndarray, key: np.ndarray) -> np.ndarray:
+    """The switch of include/hefx_hybrid.h's statement, steps 1 to 5, in Python integers over the backend's own transforms:
+    x [L][N] NTT form, key [dnum][2][k][N] -> ks [2][L][N].  What Evaluator runs with HybridKeys on a backend without the
+    native entries (the oracle twin of the tests)."""
+    q, _, rows, _ = _hybrid_basis(primes, alpha, L)
+    N = np.asarray(x).shape[-1]
+    key = np.asarray(key).reshape(-1, 2, len(q), N)
+    E = _hybrid_digits_host(be, primes, alpha, L, np.asarray(x, dtype=np.uint64).reshape(L, N))
+    return _hybrid_mod_down_host(be, primes, alpha, L, {(c, m): sum(E[j][m] * key[j, c, m].astype(object) for j in range(len(E))) % q[m]
+                                                       for c in range(2) for m in rows})
+
+
+def _hybrid_rows_add_host(primes: Sequence[int], ks: np.ndarray, add: np.ndarray) -> np.ndarray:
+    """a copy of ks [2][L][N] with add[c, j] added mod q_j to its first len(add) polynomials, in Python integers"""
+    out = ks.copy()
+    for c in range(len(add)):
+        for j in range(ks.shape[1]):
+            out[c, j] = ((ks[c, j].astype(object) + add[c, j].astype(object)) % int(primes[j])).astype(np.uint64)
     return out
 
 
@@ -594,28 +627,12 @@ def hybrid_hoist_host(be, primes: Sequence[int], alpha: int, L: int, cts, elts, 
     combined outputs, one mod-down each.  What Evaluator.rotate_hoisted / plain_combine_hoisted run on a backend without
     the native entries (the oracle twin of the tests)."""
     from . import galois_tables
-    q = [int(p) for p in primes]
+    q, _, rows, P = _hybrid_basis(primes, alpha, L)
     k, N = len(q), np.asarray(cts[0]).shape[-1]
-    D = k - alpha
-    S = list(range(D, k))
-    rows = list(range(L)) + S
-    P = 1
-    for t in S:
-        P *= q[t]
-    fwd = lambda m, v: np.asarray(be.to_host(be.ntt_forward(be.from_host((v % q[m]).astype(np.uint64)[None, None]), 1, 1, m))).reshape(-1).astype(object)
-    inv = lambda m, v: np.asarray(be.to_host(be.ntt_inverse(be.from_host(np.asarray(v, dtype=np.uint64)[None, None]), 1, 1, m))).reshape(-1).astype(object)
-    groups = [list(range(j * alpha, min((j + 1) * alpha, L))) for j in range((L + alpha - 1) // alpha)]
     terms = []                                             # A_t: {(c, m): row}
     for ct in cts:
         ct = np.asarray(ct, dtype=np.uint64).reshape(2, L, N)
-        coef = [inv(i, ct[1, i]) for i in range(L)]
-        E = []                                             # the digits of c1, not permuted
-        for G_ in groups:
-            Dj = 1
-            for i in G_:
-                Dj *= q[i]
-            y = {i: coef[i] * pow(Dj // q[i], -1, q[i]) % q[i] for i in G_}
-            E.append({m: ct[1, m].astype(object) if m in G_ else fwd(m, sum(y[i] * ((Dj // q[i]) % q[m]) for i in G_)) for m in rows})
+        E = _hybrid_digits_host(be, primes, alpha, L, ct[1])  # the digits of c1, not permuted
         for elt, key in zip(elts, keys):
             A = {}
             if key is None:
@@ -629,28 +646,19 @@ def hybrid_hoist_host(be, primes: Sequence[int], alpha: int, L: int, cts, elts, 
                 g = galois_tables.gather_table(N, elt)
                 for c in range(2):
                     for m in rows:
-                        A[c, m] = sum(E[j][m][g] * key[j, c, m].astype(object) for j in range(len(groups))) % q[m]
+                        A[c, m] = sum(E[j][m][g] * key[j, c, m].astype(object) for j in range(len(E))) % q[m]
                 for m in range(L):
                     A[0, m] = (A[0, m] + (P % q[m]) * ct[0, m][g].astype(object)) % q[m]
             terms.append(A)
-
-    def mod_down(B):
-        out = np.empty((2, L, N), dtype=np.uint64)
-        for c in range(2):
-            z = {t: (inv(t, B[c, t].astype(np.uint64)) + (P // 2) % q[t]) % q[t] * pow(P // q[t], -1, q[t]) % q[t] for t in S}
-            for j in range(L):
-                v = sum(z[t] * ((P // q[t]) % q[j]) for t in S) % q[j]
-                out[c, j] = ((B[c, j] - fwd(j, v - (P // 2) % q[j])) * pow(P, -1, q[j]) % q[j]).astype(np.uint64)
-        return out
-
     if pts is None:
-        return [mod_down(A) for A in terms]
+        return [_hybrid_mod_down_host(be, primes, alpha, L, A) for A in terms]
     outs = []
     for row in pts:
         if len(row) != len(terms) or all(p is None for p in row):
             raise ValueError("hybrid hoisting: one plaintext (or None) per term, and a term per output")
         live = [(np.asarray(p, dtype=np.uint64).reshape(k, N), A) for p, A in zip(row, terms) if p is not None]
-        outs.append(mod_down({(c, m): sum(p[m].astype(object) * A[c, m] for p, A in live) % q[m] for c in range(2) for m in rows}))
+        outs.append(_hybrid_mod_down_host(be, primes, alpha, L, {(c, m): sum(p[m].astype(object) * A[c, m] for p, A in live) % q[m]
+                                                                 for c in range(2) for m in rows}))
     return outs
 
 
@@ -1598,10 +1606,7 @@ class Evaluator:
         from . import galois_tables
         be, N, q = self.be, self.ctx.N, self.ctx.primes
         ct = np.asarray(be.to_host(data), dtype=np.uint64).reshape(2, L, N)[:, :, galois_tables.gather_table(N, elt)]
-        ks = hybrid_switch_host(be, q, keys.alpha, L, ct[1], be.to_host(key))
-        for j in range(L):
-            ks[0, j] = ((ks[0, j].astype(object) + ct[0, j].astype(object)) % int(q[j])).astype(np.uint64)
-        return be.from_host(ks)
+        return be.from_host(_hybrid_rows_add_host(q, hybrid_switch_host(be, q, keys.alpha, L, ct[1], be.to_host(key)), ct[:1]))
 
     def _hybrid_relinearize(self, L: int, data, keys: "HybridKeys"):
         """(c0 + ks0(c2), c1 + ks1(c2)): hefx_hybrid_relinearize_batch, or the statement in Python integers"""
@@ -1610,11 +1615,7 @@ class Evaluator:
             return native(keys.alpha, L, [data], keys.hybrid_key(0))[0]
         be, N, q = self.be, self.ctx.N, self.ctx.primes
         ct = np.asarray(be.to_host(data), dtype=np.uint64).reshape(3, L, N)
-        ks = hybrid_switch_host(be, q, keys.alpha, L, ct[2], be.to_host(keys.hybrid_key(0)))
-        for c in range(2):
-            for j in range(L):
-                ks[c, j] = ((ks[c, j].astype(object) + ct[c, j].astype(object)) % int(q[j])).astype(np.uint64)
-        return be.from_host(ks)
+        return be.from_host(_hybrid_rows_add_host(q, hybrid_switch_host(be, q, keys.alpha, L, ct[2], be.to_host(keys.hybrid_key(0))), ct[:2]))
 
     # ---- hoisted hybrid key switching (include/hefx_hybrid_hoist.h)
     def _hybrid_hoist_args(self, name: str, cts: Sequence[Ciphertext], steps: Sequence[int], keys: "HybridKeys", identity: bool):
