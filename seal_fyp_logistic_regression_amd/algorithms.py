@@ -781,6 +781,11 @@ def eval_mod(ev: Evaluator, cts: Sequence[Ciphertext], plan, relin_keys: KSwitch
     weight 2, constant -1), one relinearisation and one rescale: one level each, where the planner would spend two on a
     degree 2.  The weight is the integer 2 at scale 1, so a double angle takes scale s to s^2 / q; the polynomial's target
     scale (plan.poly_target_scale) is the one from which r of them end at plan.scale.  Scales are tracked, never overwritten."""
+    return _eval_mod(ev, cts, plan, relin_keys, lazy)
+
+
+def _eval_mod(ev: Evaluator, cts: Sequence[Ciphertext], plan, relin_keys, lazy: bool) -> List[Ciphertext]:
+    """eval_mod's body: it reads relin_keys through Evaluator.relinearize_inplace / relinearize_many_inplace alone"""
     cts = list(cts)
     L = cts[0].parms_id()
     if L != plan.evalmod_level:
@@ -966,10 +971,13 @@ def slots_to_coeffs_packed(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitc
 
 
 # ---- the homomorphic DFT on hybrid keys: one decomposition per input, one mod-down per inner sum ----------------------------
-def _dft_stage_hybrid(ev: Evaluator, xs: Sequence[Ciphertext], stage, table, gal_keys: HybridKeys) -> List[Ciphertext]:
+def _dft_stage_hybrid(ev: Evaluator, xs: Sequence[Ciphertext], stage, table, gal_keys: HybridKeys, hoist_giants: bool = False) -> List[Ciphertext]:
     """_dft_stage on seal.HybridKeys: the baby rotations and ALL inner sums are ONE Evaluator.plain_combine_hoisted (the baby
     step 0 is its identity term), the giant rotations one hybrid_apply_galois_batch (a step of zero is a copy), then the sums
-    and one batched rescale.  table[matrix][giant][baby]: plan.encode(..., extended=True)[stage], key-level plaintexts."""
+    and one batched rescale.  table[matrix][giant][baby]: plan.encode(..., extended=True)[stage], key-level plaintexts.
+    hoist_giants=True: the whole stage is ONE Evaluator.bsgs_hoisted (include/hefx_hybrid_bsgs.h) and the batched rescale -- the
+    inner sum (c, gi) gets giant_steps[gi] and dest = c; the inner sums keep the extended basis and every output is rounded
+    once, so these are other words with the same values."""
     from .seal import galois_elt_from_step
     if len(xs) != stage.inputs or any(x.size() != 2 for x in xs) or len({x.parms_id() for x in xs}) != 1:
         raise ValueError("dft stage: needs %d size-2 ciphertexts of one level" % stage.inputs)
@@ -982,6 +990,10 @@ def _dft_stage_hybrid(ev: Evaluator, xs: Sequence[Ciphertext], stage, table, gal
             for src, mat in feeds:
                 row[src * nb:(src + 1) * nb] = table[mat][gi]
             rows.append(row)
+    if hoist_giants:
+        outs = ev.bsgs_hoisted(xs, list(stage.babies), rows, list(stage.giants) * stage.outputs,
+                               [c for c in range(stage.outputs) for _ in range(ng)], gal_keys)
+        return ev.rescale_to_next_many_inplace(outs)
     inner = ev.plain_combine_hoisted(xs, list(stage.babies), rows, gal_keys)
     steps = list(stage.giants) * stage.outputs
     jobs = [i for i, s in enumerate(steps) if s]
@@ -1002,48 +1014,106 @@ def _dft_stage_hybrid(ev: Evaluator, xs: Sequence[Ciphertext], stage, table, gal
     return ev.rescale_to_next_many_inplace(outs)
 
 
-def _dft_run_hybrid(ev: Evaluator, xs: List[Ciphertext], plan, gal_keys: HybridKeys, encoded) -> List[Ciphertext]:
+def _dft_run_hybrid(ev: Evaluator, xs: List[Ciphertext], plan, gal_keys: HybridKeys, encoded, hoist_giants: bool = False) -> List[Ciphertext]:
     if not isinstance(gal_keys, HybridKeys):
         raise TypeError("the hybrid DFT needs HybridKeys (KeyGenerator.hybrid_galois_keys)")
     if encoded is None:
         encoded = plan.encode(CKKSEncoder(ev.ctx, device_encode=False), xs[0].parms_id(), extended=True)
     for stage, table in zip(plan.stages, encoded):
-        xs = _dft_stage_hybrid(ev, xs, stage, table, gal_keys)
+        xs = _dft_stage_hybrid(ev, xs, stage, table, gal_keys, hoist_giants)
     return xs
 
 
-def coeffs_to_slots_hybrid(ev: Evaluator, ct: Ciphertext, plan, gal_keys: HybridKeys, encoded=None):
+def coeffs_to_slots_hybrid(ev: Evaluator, ct: Ciphertext, plan, gal_keys: HybridKeys, encoded=None, hoist_giants: bool = False):
     """coeffs_to_slots on hybrid keys (include/hefx_hybrid_hoist.h): the same plan, the same values, other words -- every
     inner sum is rounded once.  ct at a level <= k - alpha; gal_keys: hybrid_galois_keys(alpha, plan.galois_steps(),
     conjugate=True); encoded: plan.encode(encoder, ct.parms_id(), extended=True)."""
     from . import dft
     if plan.direction != dft.C2S or plan.N != ev.ctx.N or plan.slots is not None:
         raise ValueError("coeffs_to_slots_hybrid: the plan is not a CoeffToSlot plan of this ring")
-    xs = _dft_run_hybrid(ev, [ct], plan, gal_keys, encoded)
+    xs = _dft_run_hybrid(ev, [ct], plan, gal_keys, encoded, hoist_giants)
     return tuple(ev.add(x, ev.complex_conjugate(x, gal_keys)) for x in xs)    # 2 Re(.)
 
 
-def slots_to_coeffs_hybrid(ev: Evaluator, ct_a: Ciphertext, ct_b: Ciphertext, plan, gal_keys: HybridKeys, encoded=None) -> Ciphertext:
+def slots_to_coeffs_hybrid(ev: Evaluator, ct_a: Ciphertext, ct_b: Ciphertext, plan, gal_keys: HybridKeys, encoded=None, hoist_giants: bool = False) -> Ciphertext:
     """slots_to_coeffs on hybrid keys; gal_keys: hybrid_galois_keys(alpha, plan.galois_steps())"""
     from . import dft
     if plan.direction != dft.S2C or plan.N != ev.ctx.N or plan.slots is not None:
         raise ValueError("slots_to_coeffs_hybrid: the plan is not a SlotToCoeff plan of this ring")
-    return _dft_run_hybrid(ev, [ct_a, ct_b], plan, gal_keys, encoded)[0]
+    return _dft_run_hybrid(ev, [ct_a, ct_b], plan, gal_keys, encoded, hoist_giants)[0]
 
 
-def coeffs_to_slots_packed_hybrid(ev: Evaluator, ct: Ciphertext, plan, gal_keys: HybridKeys, encoded=None) -> Ciphertext:
+def coeffs_to_slots_packed_hybrid(ev: Evaluator, ct: Ciphertext, plan, gal_keys: HybridKeys, encoded=None, hoist_giants: bool = False) -> Ciphertext:
     """coeffs_to_slots_packed on hybrid keys: one matrix per stage on one ciphertext, one conjugation"""
     from . import dft
     _packed_plan(ev, plan, dft.C2S, "coeffs_to_slots_packed_hybrid")
-    x = _dft_run_hybrid(ev, [ct], plan, gal_keys, encoded)[0]
+    x = _dft_run_hybrid(ev, [ct], plan, gal_keys, encoded, hoist_giants)[0]
     return ev.add(x, ev.complex_conjugate(x, gal_keys))
 
 
-def slots_to_coeffs_packed_hybrid(ev: Evaluator, ct: Ciphertext, plan, gal_keys: HybridKeys, encoded=None) -> Ciphertext:
+def slots_to_coeffs_packed_hybrid(ev: Evaluator, ct: Ciphertext, plan, gal_keys: HybridKeys, encoded=None, hoist_giants: bool = False) -> Ciphertext:
     """slots_to_coeffs_packed on hybrid keys"""
     from . import dft
     _packed_plan(ev, plan, dft.S2C, "slots_to_coeffs_packed_hybrid")
-    return _dft_run_hybrid(ev, [ct], plan, gal_keys, encoded)[0]
+    return _dft_run_hybrid(ev, [ct], plan, gal_keys, encoded, hoist_giants)[0]
+
+
+# ---- the bootstrap on hybrid keys -------------------------------------------------------------------------------------------
+def subsum_hybrid(ev: Evaluator, ct: Ciphertext, ns: int, gal_keys: HybridKeys) -> Ciphertext:
+    """subsum on hybrid keys: the same steps, x <- x + rotate_vector(x, ns 2^i), each a hybrid key switch and an add"""
+    if not isinstance(gal_keys, HybridKeys):
+        raise TypeError("subsum_hybrid needs HybridKeys (KeyGenerator.hybrid_galois_keys)")
+    N = ev.ctx.N
+    if ct.size() != 2:
+        raise ValueError("encrypted size must be 2")
+    if ns < 2 or ns & (ns - 1) or 4 * ns > N:
+        raise ValueError("subsum: slots must be a power of two in 2 .. N/4")
+    x = ct
+    for i in range((N // (2 * ns)).bit_length() - 1):
+        x = ev.add(x, ev.rotate_vector(x, ns << i, gal_keys))
+    return x
+
+
+def eval_mod_hybrid(ev: Evaluator, cts: Sequence[Ciphertext], plan, relin_keys: HybridKeys, lazy: bool = True) -> List[Ciphertext]:
+    """eval_mod on the hybrid relinearisation key (KeyGenerator.hybrid_relin_keys): the same plan and the same steps; every
+    relinearisation is from size 3, a uniform batch of them ONE hefx_hybrid_relinearize_batch."""
+    if not isinstance(relin_keys, HybridKeys):
+        raise TypeError("eval_mod_hybrid needs HybridKeys (KeyGenerator.hybrid_relin_keys)")
+    return _eval_mod(ev, cts, plan, relin_keys, lazy)
+
+
+BOOTSTRAP_HYBRID_HOIST_GIANTS = False  # the measured default of bootstrap_hybrid (profiles/hybrid_bsgs.json; README, hybrid keys)
+
+
+def bootstrap_hybrid(ev: Evaluator, ct: Ciphertext, plan, gal_keys: HybridKeys, relin_keys: HybridKeys, encoded=None,
+                     hoist_giants: bool = BOOTSTRAP_HYBRID_HOIST_GIANTS) -> Ciphertext:
+    """bootstrap on hybrid evaluation keys only, dense and sparse plans (no sparse-secret encapsulation): Evaluator.mod_raise
+    to plan.top_level = k - alpha, subsum_hybrid (sparse plans), the hybrid CoeffToSlot (packed for sparse plans),
+    eval_mod_hybrid, the hybrid SlotToCoeff.  plan: bootstrap.plan(..., special=alpha) for this context's chain; gal_keys:
+    hybrid_galois_keys(alpha, plan.galois_steps(), conjugate=True); relin_keys: hybrid_relin_keys(alpha); encoded:
+    plan.encode(encoder, extended=True).  hoist_giants: every DFT stage as ONE Evaluator.bsgs_hoisted
+    (include/hefx_hybrid_bsgs.h) -- other words, the same values."""
+    if not isinstance(gal_keys, HybridKeys) or not isinstance(relin_keys, HybridKeys):
+        raise TypeError("bootstrap_hybrid needs HybridKeys (KeyGenerator.hybrid_galois_keys, hybrid_relin_keys)")
+    if ct.size() != 2 or ct.parms_id() != 1:
+        raise ValueError("bootstrap: needs a size-2 ciphertext at the last prime")
+    if plan.N != ev.ctx.N or list(plan.primes) != list(ev.ctx.primes):
+        raise ValueError("bootstrap: the plan was made for another ring or chain")
+    if not (plan.special == gal_keys.alpha == relin_keys.alpha):
+        raise ValueError(f"bootstrap_hybrid: the plan has {plan.special} special primes, the keys alpha = {gal_keys.alpha} and "
+                         f"{relin_keys.alpha}: make the plan with bootstrap.plan(..., special=alpha)")
+    if not ev._close(ct.scale, plan.scale):
+        raise ValueError("scale mismatch")
+    if encoded is None:
+        encoded = plan.encode(CKKSEncoder(ev.ctx, device_encode=False), extended=True)
+    raised = ev.mod_raise(ct, plan.top_level)
+    if plan.sparse_slots is not None:
+        x = coeffs_to_slots_packed_hybrid(ev, subsum_hybrid(ev, raised, plan.sparse_slots, gal_keys), plan.c2s, gal_keys, encoded[0], hoist_giants)
+        (y,) = eval_mod_hybrid(ev, [x], plan, relin_keys)
+        return slots_to_coeffs_packed_hybrid(ev, y, plan.s2c, gal_keys, encoded[1], hoist_giants)
+    ca, cb = coeffs_to_slots_hybrid(ev, raised, plan.c2s, gal_keys, encoded[0], hoist_giants)
+    ya, yb = eval_mod_hybrid(ev, [ca, cb], plan, relin_keys)
+    return slots_to_coeffs_hybrid(ev, ya, yb, plan.s2c, gal_keys, encoded[1], hoist_giants)
 
 
 def cipher_dot_product_many(ev: Evaluator, As: Sequence[Ciphertext], Bs: Sequence[Ciphertext], size: int,

@@ -28,13 +28,14 @@ def chebyshev_interpolant(f, degree: int) -> np.ndarray:
 
 
 class Plan:
-    def __init__(self, N, primes, scale, K, r, degree, c2s, s2c, coeffs, poly_target_scale, max_value, model_error, slots=None):
+    def __init__(self, N, primes, scale, K, r, degree, c2s, s2c, coeffs, poly_target_scale, max_value, model_error, slots=None, special=1):
         self.N, self.primes, self.scale, self.K, self.r, self.degree = N, [int(p) for p in primes], float(scale), K, r, degree
         self.Kp = K + 0.25
         self.sparse_slots = slots   # None: all N / 2 slots; ns: plan(..., slots=ns).  (slots() is the embedding below.)
         self.c2s, self.s2c, self.coeffs = c2s, s2c, coeffs
         self.poly_target_scale, self.max_value, self.model_error = poly_target_scale, max_value, model_error
-        self.top_level = len(self.primes) - 1
+        self.special = int(special)   # the special primes at the end of the chain: 1, or the alpha of hybrid keys
+        self.top_level = len(self.primes) - self.special
         self.depth = int(math.ceil(math.log2(degree + 1)))
         self.evalmod_level = self.top_level - c2s.levels
         self.s2c_level = self.evalmod_level - self.depth - r
@@ -65,9 +66,13 @@ class Plan:
         return (len(self.subsum_steps()) + self.c2s.key_switches() + self.s2c.key_switches()
                 + chains * (p.relinearizations(lazy) + self.r))
 
-    def encode(self, encoder):
-        """(CoeffToSlot's plaintexts at the top level, SlotToCoeff's at plan.s2c_level): the `encoded` of algorithms.bootstrap"""
-        return self.c2s.encode(encoder, self.top_level), self.s2c.encode(encoder, self.s2c_level)
+    def encode(self, encoder, extended: bool = False):
+        """(CoeffToSlot's plaintexts at the top level, SlotToCoeff's at plan.s2c_level): the `encoded` of algorithms.bootstrap.
+        extended=True: key-level diagonals for both transforms (dft.Plan.encode's extended form), the `encoded` of
+        algorithms.bootstrap_hybrid"""
+        if not extended:
+            return self.c2s.encode(encoder, self.top_level), self.s2c.encode(encoder, self.s2c_level)
+        return self.c2s.encode(encoder, self.top_level, extended=True), self.s2c.encode(encoder, self.s2c_level, extended=True)
 
     # ---- the float64 model
     def eval_mod(self, u: np.ndarray) -> np.ndarray:
@@ -131,7 +136,7 @@ def model_error(coeffs: np.ndarray, K: int, r: int, band: float) -> float:
 
 
 def plan(N: int, primes: Sequence[int], scale: float, K: int = 12, r: int = 3, degree: int = 31, c2s_levels: int = 2,
-         s2c_levels: int = 2, max_value: float = 1.0, precision: float = 1e-4, slots: Optional[int] = None) -> Plan:
+         s2c_levels: int = 2, max_value: float = 1.0, precision: float = 1e-4, slots: Optional[int] = None, special: int = 1) -> Plan:
     """The bootstrap of a ciphertext at primes[0] and `scale` on the chain `primes` (the context's coeff_modulus, the special
     prime last).  K: the integer part |I| the secret key allows (12 for Hamming weight 32); r double angles; `degree` of the
     interpolant; levels of the two transforms.  max_value: the largest |coefficient| / scale of a message (1.0 covers slots of
@@ -141,9 +146,16 @@ def plan(N: int, primes: Sequence[int], scale: float, K: int = 12, r: int = 3, d
     slots=ns (a power of two, 2 <= ns <= N/4; ValueError otherwise): the sparse plan of a message of ns slots, whose plaintext
     is a polynomial in X^g, g = N / (2 ns).  SubSum (plan.subsum_steps(): log2 g rotate-and-adds) brings the raised plaintext
     back into that subring, times g; the transforms are dft.plan_packed's, of dimension 2 ns on ONE ciphertext, 1 / g folded
-    into CoeffToSlot's diagonals, their levels clipped to log2(ns); EvalMod runs on one chain.  plan.sparse_slots is ns."""
+    into CoeffToSlot's diagonals, their levels clipped to log2(ns); EvalMod runs on one chain.  plan.sparse_slots is ns.
+    special: the special primes at the end of the chain -- 1, or the alpha of the hybrid keys algorithms.bootstrap_hybrid is
+    given (1 <= special <= HYBRID_ALPHA_MAX, ValueError otherwise); the top level is len(primes) - special and every level
+    below follows from it."""
     primes = [int(p) for p in primes]
-    top = len(primes) - 1
+    from .seal import HYBRID_ALPHA_MAX
+    special = int(special)
+    if not 1 <= special <= HYBRID_ALPHA_MAX:
+        raise ValueError("bootstrap plan: special must be in 1 .. %d" % HYBRID_ALPHA_MAX)
+    top = len(primes) - special
     if top < 1:
         raise ValueError("bootstrap plan: the chain needs data primes and a special prime")
     if K < 1 or r < 0 or degree < 1:
@@ -179,4 +191,4 @@ def plan(N: int, primes: Sequence[int], scale: float, K: int = 12, r: int = 3, d
     c2s = make(N, c2s_levels, dft.C2S, [primes[top - 1 - i] for i in range(c2s_levels)], factor=float(scale) / (q0 * Kp * g))
     s2c = make(N, s2c_levels, dft.S2C, [primes[s2c_level - 1 - i] for i in range(s2c_levels)],
                factor=q0 / (2.0 * np.pi * float(scale)))
-    return Plan(N, primes, scale, K, r, degree, c2s, s2c, coeffs, target, max_value, err, slots)
+    return Plan(N, primes, scale, K, r, degree, c2s, s2c, coeffs, target, max_value, err, slots, special)

@@ -241,6 +241,12 @@ HYBRID_HOIST_SYMBOLS = sorted(_HYBRID_HOIST_SIGS)
 HYBRID_HOIST_MAX_TERMS = 64  # HEFX_HYBRID_HOIST_MAX_TERMS
 HYBRID_HOIST_MAX_OUT = 64    # HEFX_HYBRID_HOIST_MAX_OUT
 
+# include/hefx_hybrid_bsgs.h: a baby-step giant-step stage on hybrid keys, the giant steps hoisted (one mod-down per output)
+_HYBRID_BSGS_SIGS = {
+    "hefx_hybrid_bsgs_hoisted": (_i, [_vp, _i, _i, _i, _pp, _i, C.POINTER(_u32), _pp, _i, _pp, C.POINTER(_u32), _pp, C.POINTER(_u32), _i, _pp, _vp]),
+}
+HYBRID_BSGS_SYMBOLS = sorted(_HYBRID_BSGS_SIGS)
+
 
 def product_combine_words(L: int, n: int, P: int, m: int) -> int:
     """words of hefx_product_combine's table with a constant: strides, weights and the constant per row, n pointer records"""
@@ -263,7 +269,8 @@ def lib():
     L = C.CDLL(path, mode=C.RTLD_GLOBAL)
     for name, (res, args) in (list(_SIGS.items()) + list(_REFRESH_SIGS.items()) + list(_BFV_SIGS.items())
                               + list(_POLY_SIGS.items()) + list(_DFT_SIGS.items()) + list(_BOOTSTRAP_SIGS.items())
-                              + list(_ENCAPS_SIGS.items()) + list(_HYBRID_SIGS.items()) + list(_HYBRID_HOIST_SIGS.items())):
+                              + list(_ENCAPS_SIGS.items()) + list(_HYBRID_SIGS.items()) + list(_HYBRID_HOIST_SIGS.items())
+                              + list(_HYBRID_BSGS_SIGS.items())):
         f = getattr(L, name)
         f.restype = res
         f.argtypes = args

@@ -11,6 +11,7 @@
 #include "../../include/hefx_encaps.h"
 #include "../../include/hefx_hybrid.h"
 #include "../../include/hefx_hybrid_hoist.h"
+#include "../../include/hefx_hybrid_bsgs.h"
 
 #include <chrono>
 #include <cmath>
@@ -3741,6 +3742,150 @@ extern "C" int hefx_hybrid_plain_combine_hoisted(hefx_context *c, int alpha, int
                                                  uint64_t *const *ct_out, void *stream)
 {
     return hybrid_hoist_run(c, alpha, L, n, ct_in, m, elts, keys, G, pts, ct_out, stream, true);
+}
+
+// ---------------------------------------------------------------------------------------------
+// hoisted giant steps (include/hefx_hybrid_bsgs.h, hefx_hybrid_bsgs.hip): the combine's inner sums stay in the extended basis,
+// c1 of every giant-rotated one is brought down and switched there, one mod-down per output.  One table; the giant phase
+// runs in chunks of inner sums (the output accumulators carry), the rest once.
+// ---------------------------------------------------------------------------------------------
+static int hybrid_bsgs_run(hefx_context *c, int alpha, int L, int n, const uint64_t *const *ins, int m, const uint32_t *elts,
+                           const uint64_t *const *keys, int G, const uint64_t *const *pts, const uint32_t *gelts,
+                           const uint64_t *const *gkeys, const uint32_t *dest, int O, uint64_t *const *outs, void *stream)
+{
+    CTXCHK(c);
+    const char *who = "hybrid_bsgs_hoisted";
+    if (int rc = check_hybrid(c, alpha, who, L)) return rc;
+    if (n < 1 || m < 1 || !ins || !elts || !keys || !pts || !gelts || !gkeys || !dest || !outs)
+        return fail(HEFX_ERR_INVALID, std::string(who) + ": bad arguments: null pointer, n < 1 or m < 1");
+    if ((long)n * m > HEFX_HYBRID_HOIST_MAX_TERMS)
+        return fail(HEFX_ERR_INVALID, std::string(who) + ": more than HEFX_HYBRID_HOIST_MAX_TERMS = " + std::to_string(HEFX_HYBRID_HOIST_MAX_TERMS) + " terms (n * m)");
+    if (G < 1 || G > HEFX_HYBRID_HOIST_MAX_OUT || O < 1 || O > G)
+        return fail(HEFX_ERR_INVALID, std::string(who) + ": need 1 <= O <= G <= HEFX_HYBRID_HOIST_MAX_OUT = " + std::to_string(HEFX_HYBRID_HOIST_MAX_OUT));
+    const int T = n * m;
+    for (int i = 0; i < n; ++i)
+        if (!ins[i]) return fail(HEFX_ERR_INVALID, std::string(who) + ": null pointer in d_ct_in");
+    for (int k = 0; k < m; ++k) {
+        if (int rc = check_galois_elt(c, elts[k])) return rc;
+        if (!keys[k] && elts[k] != 1) return fail(HEFX_ERR_INVALID, std::string(who) + ": a NULL key denotes the identity term: its element must be 1");
+    }
+    std::vector<int> rank(G, 0), sel;  // the inner sums with a giant key, in the order of o
+    std::vector<bool> fed(O, false);
+    for (int o = 0; o < G; ++o) {
+        bool any = false;
+        for (int t = 0; t < T && !any; ++t) any = pts[(size_t)o * T + t] != nullptr;
+        if (!any) return fail(HEFX_ERR_INVALID, std::string(who) + ": an inner sum has no term");
+        if (int rc = check_galois_elt(c, gelts[o])) return rc;
+        if (!gkeys[o] != (gelts[o] == 1))
+            return fail(HEFX_ERR_INVALID, std::string(who) + ": a NULL giant key means no giant rotation: it goes with the element 1, and only with it");
+        if (dest[o] >= (uint32_t)O) return fail(HEFX_ERR_INVALID, std::string(who) + ": dest out of range");
+        fed[dest[o]] = true;
+        if (gkeys[o]) rank[o] = (int)sel.size(), sel.push_back(o);
+    }
+    for (int q = 0; q < O; ++q) {
+        if (!outs[q]) return fail(HEFX_ERR_INVALID, std::string(who) + ": null pointer in d_ct_out");
+        if (!fed[q]) return fail(HEFX_ERR_INVALID, std::string(who) + ": an output has no inner sum");
+    }
+    const size_t N = c->n, poly_b = (size_t)L * N * sizeof(u64);
+    const int dn = hybrid_digits(alpha, L), Gr = (int)sel.size();
+    if (int rc = check_ranges(who, (size_t)O, outs, 2 * poly_b,
+                              {{ins, (size_t)n, 2 * poly_b}, {keys, (size_t)m, hybrid_key_bytes(c, alpha, L)}, {pts, (size_t)G * T, (size_t)c->k * N * sizeof(u64)},
+                               {gkeys, (size_t)G, hybrid_key_bytes(c, alpha, L)}},
+                              {"d_ct_in", "d_keys", "d_pts", "d_giant_keys"}))
+        return rc;
+    // the workspace of the header, block by block.  Fixed: the baby phase as hybrid_hoist_run lays it out (B is read in NTT
+    // form here, so Bs is not a transform's block), then the accumulators W and their spread.
+    const size_t Ls = (size_t)L, A = (size_t)alpha, D = (size_t)dn, exts = n * D * Ls * N;
+    HybridCarve w{c};
+    const HyBlock xc = w.take(n * Ls * N), ext = w.take(n * D * (Ls + A) * N, true), Ad = w.take(2 * T * Ls * N), As = w.take(2 * T * A * N),
+                  Bd = w.take(2 * G * Ls * N), Bs = w.take(2 * G * A * N), Wd = w.take(2 * O * Ls * N), Ws = w.take(2 * O * A * N, true),
+                  tt = w.take(2 * O * Ls * N, true);
+    // a chunk of C giant-rotated inner sums, behind the fixed blocks; us and tt1 hold an even count (hy_spread takes pairs)
+    const size_t budget = ((size_t)1 << 30) / sizeof(u64);
+    auto chunk_words = [&](size_t C, HyBlock *b) {
+        HybridCarve v{c};
+        const size_t Ce = C + (C & 1);
+        const HyBlock blocks[5] = {v.take(Ce * A * N), v.take(Ce * Ls * N, true), v.take(C * Ls * N), v.take(C * Ls * N), v.take(C * D * (Ls + A) * N, true)};
+        for (int i = 0; b && i < 5; ++i) b[i] = blocks[i];
+        return v.words;
+    };
+    int C = Gr;
+    while (C > 1 && w.words + chunk_words(C, nullptr) > budget) --C;
+    if (w.words + (Gr ? chunk_words(C, nullptr) : 0) > budget)
+        return fail(HEFX_ERR_UNSUPPORTED, std::string(who) + ": the workspace of this call passes 1 GiB with one inner sum per chunk (include/hefx_hybrid_bsgs.h, WORKSPACE): split the call");
+    HyBlock cb[5] = {};
+    const size_t cwords = Gr ? chunk_words(C, cb) : 0, base = w.words;
+    const HybridConsts &K = hybrid_consts(c, alpha, L);
+    HyhTab X{};
+    X.pmod = (uint32_t)K.words.size(), X.srcs = X.pmod + L, X.keys = X.srcs + n, X.elts = X.keys + m, X.pts = X.elts + m;
+    X.outs = X.pts + G * T;
+    X.n = n, X.m = m, X.G = G;
+    HybTab Y{};
+    Y.gelts = X.outs + O, Y.gkeys = Y.gelts + G, Y.dest = Y.gkeys + G, Y.rank = Y.dest + G, Y.sel = Y.rank + G;
+    Y.G = G, Y.O = O;
+    const uint32_t pos = Y.sel + Gr;  // the words of the call's table
+    if (pos > (uint32_t)RING_SLOT_PTRS) return fail(HEFX_ERR_UNSUPPORTED, std::string(who) + ": the call's table does not fit a descriptor slot");
+    if (int rc = ensure_scratch(c, base + cwords)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    u64 *S = c->scratch;
+    auto fill = [&](u64 *h) {
+        std::copy(K.words.begin(), K.words.end(), h);
+        for (int j = 0; j < L; ++j) h[X.pmod + j] = hybrid_p_mod(c, alpha, j);
+        for (int i = 0; i < n; ++i) h[X.srcs + i] = (u64)(uintptr_t)ins[i];
+        for (int k = 0; k < m; ++k) h[X.keys + k] = (u64)(uintptr_t)keys[k], h[X.elts + k] = elts[k];
+        for (size_t i = 0; i < (size_t)G * T; ++i) h[X.pts + i] = (u64)(uintptr_t)pts[i];
+        for (int q = 0; q < O; ++q) h[X.outs + q] = (u64)(uintptr_t)outs[q];
+        for (int o = 0; o < G; ++o)
+            h[Y.gelts + o] = gelts[o], h[Y.gkeys + o] = (u64)(uintptr_t)gkeys[o], h[Y.dest + o] = dest[o], h[Y.rank + o] = (u64)rank[o];
+        for (int r = 0; r < Gr; ++r) h[Y.sel + r] = (u64)sel[r];
+    };
+    auto run = [&](const u64 *d) -> int {
+        HyTab H = K.at;
+        H.tab = d, H.relin = 0;
+        for (int i = 0; i < n; ++i)  // c1 of source i, from the caller's input to the scratch (src != dst at every ring size)
+            HIPCHK(transform(c, true, (const u64 *)ins[i] + Ls * N, S + xc.dst + (size_t)i * Ls * N, 1, L, 0, s));
+        HIPCHK(launch_hy_convert(c->T, H, n, S + xc.dst, S + ext.src, S + ext.src + exts, s));
+        HIPCHK(transform(c, false, S + ext.src, S + ext.dst, n * dn, L, 0, s));
+        HIPCHK(transform(c, false, S + ext.src + exts, S + ext.dst + exts, n * dn, alpha, c->k - alpha, s));
+        HIPCHK(launch_hyh_term(c->T, H, X, S + ext.dst, S + ext.dst + exts, S + Ad.dst, S + As.dst, s));
+        HIPCHK(launch_hyh_combine(c->T, H, X, S + Ad.dst, S + As.dst, S + Bd.dst, S + Bs.dst, s));
+        // the giant phase: inner sums [o_lo, o_hi) per launch, at most C of them with a giant key (ranks c0 .. c0 + cnt - 1)
+        u64 *Q = S + base;
+        for (int o_lo = 0, c0 = 0; o_lo < G;) {
+            int o_hi = o_lo, cnt = 0;
+            while (o_hi < G && (!gkeys[o_hi] || cnt < C)) cnt += gkeys[o_hi++] != nullptr;
+            if (cnt) {
+                const size_t exts2 = (size_t)cnt * D * Ls * N;
+                for (int r = 0; r < cnt; ++r)  // the special rows of B_o[1], straight from the combine's block
+                    HIPCHK(transform(c, true, S + Bs.dst + (size_t)(2 * sel[c0 + r] + 1) * A * N, Q + cb[0].dst + (size_t)r * A * N, 1, alpha, c->k - alpha, s));
+                if (cnt & 1) HIPCHK(hipMemsetAsync(Q + cb[0].dst + (size_t)cnt * A * N, 0, A * N * sizeof(u64), s));  // the pair's other half
+                HIPCHK(launch_hy_spread(c->T, H, (cnt + 1) / 2, Q + cb[0].dst, Q + cb[1].src, s));
+                HIPCHK(transform(c, false, Q + cb[1].src, Q + cb[1].dst, cnt, L, 0, s));
+                HIPCHK(launch_hyb_down(c->T, H, Y, c0, cnt, S + Bd.dst, Q + cb[1].dst, Q + cb[2].dst, s));
+                HIPCHK(transform(c, true, Q + cb[2].dst, Q + cb[3].dst, cnt, L, 0, s));
+                HIPCHK(launch_hy_convert(c->T, H, cnt, Q + cb[3].dst, Q + cb[4].src, Q + cb[4].src + exts2, s));
+                HIPCHK(transform(c, false, Q + cb[4].src, Q + cb[4].dst, cnt * dn, L, 0, s));
+                HIPCHK(transform(c, false, Q + cb[4].src + exts2, Q + cb[4].dst + exts2, cnt * dn, alpha, c->k - alpha, s));
+            }
+            HIPCHK(launch_hyb_giant(c->T, H, Y, o_lo, o_hi, c0, S + Bd.dst, S + Bs.dst, Q + cb[2].dst, Q + cb[4].dst, Q + cb[4].dst + (size_t)cnt * D * Ls * N,
+                                    S + Wd.dst, S + Ws.src, s));
+            o_lo = o_hi, c0 += cnt;
+        }
+        HIPCHK(transform(c, true, S + Ws.src, S + Ws.dst, 2 * O, alpha, c->k - alpha, s));
+        HIPCHK(launch_hy_spread(c->T, H, O, S + Ws.dst, S + tt.src, s));
+        HIPCHK(transform(c, false, S + tt.src, S + tt.dst, 2 * O, L, 0, s));
+        HIPCHK(launch_hyh_finish(c->T, H, X, O, S + Wd.dst, S + tt.dst, s));
+        return HEFX_OK;
+    };
+    return slot_call(c, s, pos, fill, run);
+}
+
+extern "C" int hefx_hybrid_bsgs_hoisted(hefx_context *c, int alpha, int L, int n, const uint64_t *const *ct_in, int m,
+                                        const uint32_t *elts, const uint64_t *const *keys, int G, const uint64_t *const *pts,
+                                        const uint32_t *giant_elts, const uint64_t *const *giant_keys, const uint32_t *dest, int O,
+                                        uint64_t *const *ct_out, void *stream)
+{
+    return hybrid_bsgs_run(c, alpha, L, n, ct_in, m, elts, keys, G, pts, giant_elts, giant_keys, dest, O, ct_out, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 // hefx_hybrid.cuh -- what the element-wise kernels of hybrid key switching (hefx_hybrid.hip) and of its hoisted form
 // (hefx_hybrid_hoist.hip) have in common: the row rule, the grid, the lazy accumulator of a record, the digit loop against a
-// key, the store into a data / special block pair and the mod-down's record.  Included by those two files only.
+// key, the store into a data / special block pair and the mod-down's record.  Included by those two files and by the hoisted
+// giant steps (hefx_hybrid_bsgs.hip), which states its own accumulator's range.
 //
 // ROWS.  R = L + alpha rows: r < L is data prime r, r >= L is special prime k - alpha + r - L (hy_row_mod).  dn = ceil(L / alpha)
 // digits, digit j owning the data rows j alpha .. min((j + 1) alpha, L) - 1.  A result over all R rows lives in a BLOCK PAIR:

@@ -324,6 +324,20 @@ hipError_t launch_hyh_term(const DevTables &T, const HyTab &H, const HyhTab &X, 
 hipError_t launch_hyh_combine(const DevTables &T, const HyTab &H, const HyhTab &X, const u64 *Ad, const u64 *As, u64 *Bd, u64 *Bs,
                               hipStream_t s);
 hipError_t launch_hyh_finish(const DevTables &T, const HyTab &H, const HyhTab &X, int outs, const u64 *Bd, const u64 *tt, hipStream_t s);
+// hoisted giant steps (hefx_hybrid_bsgs.hip, include/hefx_hybrid_bsgs.h).  The call's device table is HyhTab's (G inner sums,
+// its `outs` the O outputs) followed by the blocks below, at these word offsets of HyTab::tab.
+struct HybTab {
+    uint32_t gelts;  // [G]   the giant element of inner sum o
+    uint32_t gkeys;  // [G]   its giant key [dnum][2][k][N], 0: no giant rotation
+    uint32_t dest;   // [G]   the output it is added into
+    uint32_t rank;   // [G]   its index among the inner sums with a giant key, in the order of o (unused without a key)
+    uint32_t sel;    // [Gr]  the inverse: the inner sum of a rank
+    int G, O;
+};
+hipError_t launch_hyb_down(const DevTables &T, const HyTab &H, const HybTab &Y, int c0, int cnt, const u64 *Bd, const u64 *tt1, u64 *dd,
+                           hipStream_t s);
+hipError_t launch_hyb_giant(const DevTables &T, const HyTab &H, const HybTab &Y, int o_lo, int o_hi, int c0, const u64 *Bd, const u64 *Bs,
+                            const u64 *dd, const u64 *extd, const u64 *exts, u64 *Wd, u64 *Ws, hipStream_t s);
 hipError_t warm_kernels(hipStream_t s);
 hipError_t warm_keyswitch(hipStream_t s);
 hipError_t warm_encode(hipStream_t s);

@@ -705,6 +705,28 @@ class Engine:
             capi.ptr_array([None if p is None else p.ptr for r in pts for p in r]), capi.ptr_array([o.ptr for o in outs]), stream))
         return outs
 
+    # ---- hoisted giant steps on hybrid keys (include/hefx_hybrid_bsgs.h)
+    def hybrid_bsgs_hoisted(self, alpha, L, cts, elts, keys, pts, giant_elts, giant_keys, dest, outs=None, stream=None):
+        """outs[q] = MD(sum over the inner sums o with dest[o] == q of W_o): inner sum o is the combine's B_o over pts[o] (as
+        hybrid_plain_combine_hoisted), rotated in the extended basis by giant_elts[o] with giant_keys[o] (None with the
+        element 1: W_o = B_o).  One mod-down per output (hefx_hybrid_bsgs_hoisted)."""
+        n, m, G = len(cts), len(elts), len(pts)
+        if any(len(r) != n * m for r in pts) or len(giant_elts) != G or len(giant_keys) != G or len(dest) != G:
+            raise ValueError("hybrid_bsgs_hoisted: pts must be [G][n * m]; one giant element, giant key and dest per inner sum")
+        if any(int(d) < 0 for d in dest):
+            raise ValueError("hybrid_bsgs_hoisted: dest out of range")
+        # (a dest past G asks for more outputs than inner sums: the entry refuses O = G + 1 just the same)
+        O = len(outs) if outs is not None else min(max(int(d) for d in dest), G) + 1
+        dest = [min(int(d), 0xFFFFFFFF) for d in dest]
+        outs =outs if outs is not None else self.empty_many(O, (2, L, self.N))
+        capi.check(capi.lib().hefx_hybrid_bsgs_hoisted(
+            self._h, int(alpha), L, n, capi.ptr_array([c.ptr for c in cts]), m, capi.u32_array(elts),
+            capi.ptr_array([None if k is None else k.ptr for k in keys]), G,
+            capi.ptr_array([None if p is None else p.ptr for r in pts for p in r]), capi.u32_array(giant_elts),
+            capi.ptr_array([None if k is None else k.ptr for k in giant_keys]), capi.u32_array(dest), O,
+            capi.ptr_array([o.ptr for o in outs]), stream))
+        return outs
+
     # ---- scalar combinations of ciphertexts (include/hefx_poly.h)
     def scalar_combine(self, L, size, ins, in_rows, weights, consts=None, outs=None, stream=None):
         """outs[g] = sum_k weights[g][k] * ins[k] + consts[g] over the first L rows of every input, one pass over the inputs

@@ -320,6 +320,9 @@ class GpuBackend:
     def hybrid_plain_combine_hoisted(self, alpha, L, cts, elts, keys, pts):
         return self.engine.hybrid_plain_combine_hoisted(alpha, L, cts, elts, keys, pts)
 
+    def hybrid_bsgs_hoisted(self, alpha, L, cts, elts, keys, pts, giant_elts, giant_keys, dest):
+        return self.engine.hybrid_bsgs_hoisted(alpha, L, cts, elts, keys, pts, giant_elts, giant_keys, dest)
+
     def raise_switch(self, L_out, ct, ckey):
         """mod-raise from one prime and the collapsed key switch in one engine call (hefx_raise_switch); the oracle-backed
         twin of the tests has no such method and Evaluator.raise_switch states the same words through its apply_galois"""
@@ -626,6 +629,14 @@ def hybrid_hoist_host(be, primes: Sequence[int], alpha: int, L: int, cts, elts, 
     n * m hoisted rotations, out[i * m + k]; else pts[o][i * m + k] = a key-level plaintext [k][N] or None, and the G
     combined outputs, one mod-down each.  What Evaluator.rotate_hoisted / plain_combine_hoisted run on a backend without
     the native entries (the oracle twin of the tests)."""
+    terms = _hybrid_terms_host(be, primes, alpha, L, cts, elts, keys)
+    if pts is None:
+        return [_hybrid_mod_down_host(be, primes, alpha, L, A) for A in terms]
+    return [_hybrid_mod_down_host(be, primes, alpha, L, B) for B in _hybrid_sums_host(primes, alpha, L, terms, pts)]
+
+
+def _hybrid_terms_host(be, primes: Sequence[int], alpha: int, L: int, cts, elts, keys) -> List[Dict]:
+    """the terms A_t of include/hefx_hybrid_hoist.h, t = i * m + k, each {(c, m): row of Python integers} over the rows of R"""
     from . import galois_tables
     q, _, rows, P = _hybrid_basis(primes, alpha, L)
     k, N = len(q), np.asarray(cts[0]).shape[-1]
@@ -650,16 +661,57 @@ def hybrid_hoist_host(be, primes: Sequence[int], alpha: int, L: int, cts, elts, 
                 for m in range(L):
                     A[0, m] = (A[0, m] + (P % q[m]) * ct[0, m][g].astype(object)) % q[m]
             terms.append(A)
-    if pts is None:
-        return [_hybrid_mod_down_host(be, primes, alpha, L, A) for A in terms]
-    outs = []
+    return terms
+
+
+def _hybrid_sums_host(primes: Sequence[int], alpha: int, L: int, terms, pts) -> List[Dict]:
+    """the combine's sums B_o of include/hefx_hybrid_hoist.h over the rows of R, before their mod-down"""
+    q, _, rows, _ = _hybrid_basis(primes, alpha, L)
+    k, N = len(q), len(terms[0][0, 0])
+    sums = []
     for row in pts:
         if len(row) != len(terms) or all(p is None for p in row):
             raise ValueError("hybrid hoisting: one plaintext (or None) per term, and a term per output")
         live = [(np.asarray(p, dtype=np.uint64).reshape(k, N), A) for p, A in zip(row, terms) if p is not None]
-        outs.append(_hybrid_mod_down_host(be, primes, alpha, L, {(c, m): sum(p[m].astype(object) * A[c, m] for p, A in live) % q[m]
-                                                                 for c in range(2) for m in rows}))
-    return outs
+        sums.append({(c, m): sum(p[m].astype(object) * A[c, m] for p, A in live) % q[m] for c in range(2) for m in rows})
+    return sums
+
+
+def hybrid_bsgs_host(be, primes: Sequence[int], alpha: int, L: int, cts, elts, keys, pts, giant_elts, giant_keys, dest) -> List[np.ndarray]:
+    """The statement of include/hefx_hybrid_bsgs.h in Python integers over the backend's own transforms.  The arguments of
+    hybrid_hoist_host up to pts describe the G inner sums B_o; inner sum o is rotated in the extended basis by giant_elts[o]
+    with giant_keys[o] ([dnum][2][k][N]; None with the element 1: W_o = B_o) and added into output dest[o]; the
+    max(dest) + 1 outputs take one mod-down each.  What Evaluator.bsgs_hoisted runs on a backend without the native entry
+    (the oracle twin of the tests)."""
+    from . import galois_tables
+    q, _, rows, _ = _hybrid_basis(primes, alpha, L)
+    k = len(q)
+    sums = _hybrid_sums_host(primes, alpha, L, _hybrid_terms_host(be, primes, alpha, L, cts, elts, keys), pts)
+    if not (len(giant_elts) == len(giant_keys) == len(dest) == len(sums)):
+        raise ValueError("hybrid bsgs: one giant element, giant key and dest per inner sum")
+    O = max(int(d) for d in dest) + 1
+    if min(int(d) for d in dest) < 0 or set(int(d) for d in dest) != set(range(O)):
+        raise ValueError("hybrid bsgs: dest out of range, or an output has no inner sum")
+    N = len(sums[0][0, 0])
+    W = [{(c, m): np.zeros(N, dtype=object) for c in range(2) for m in rows} for _ in range(O)]
+    for B, elt, key, d in zip(sums, giant_elts, giant_keys, dest):
+        if (key is None) != (elt == 1):
+            raise ValueError("hybrid bsgs: a missing giant key means no giant rotation: it goes with the element 1, and only with it")
+        if key is None:
+            Wo = B
+        else:
+            key = np.asarray(key).reshape(-1, 2, k, N)
+            g = galois_tables.gather_table(N, elt)
+            # MD of the ONE polynomial B_o[1] (the mod-down is per polynomial: B_o[1] stands in for both), then its digits
+            d1 = _hybrid_mod_down_host(be, primes, alpha, L, {(c, m): B[1, m] for c in range(2) for m in rows})[1]
+            F = _hybrid_digits_host(be, primes, alpha, L, d1)
+            Wo = {(c, m): sum(F[j][m][g] * key[j, c, m].astype(object) for j in range(len(F))) % q[m] for c in range(2) for m in rows}
+            for m in rows:
+                Wo[0, m] = (Wo[0, m] + B[0, m][g]) % q[m]
+        for c in range(2):
+            for m in rows:
+                W[int(d)][c, m] = (W[int(d)][c, m] + Wo[c, m]) % q[m]
+    return [_hybrid_mod_down_host(be, primes, alpha, L, Wq) for Wq in W]
 
 
 class EncapsKeys:
@@ -1378,8 +1430,17 @@ class Evaluator:
         if not cts:
             return cts
         if isinstance(relin_keys, HybridKeys):
-            for c in cts:
-                self.relinearize_inplace(c, relin_keys)
+            native = getattr(self.be, "hybrid_relinearize_batch", None)
+            if native is None or len(cts) < 2 or not self._uniform(cts) or cts[0].size() != 3:
+                for c in cts:
+                    self.relinearize_inplace(c, relin_keys)
+                return cts
+            # a uniform batch from size 3: ONE call, whose words are those of the single calls (items are independent)
+            if not relin_keys.has_key(0):
+                raise ValueError("not enough relinearization keys")
+            L = self._hybrid_level(cts[0], relin_keys)
+            for c, o in zip(cts, native(relin_keys.alpha, L, [c.data for c in cts], relin_keys.hybrid_key(0))):
+                c._set(o, 2, L, c.scale)
             return cts
         if f is None or not self._uniform(cts) or cts[0].size() != 3:
             for c in cts:
@@ -1699,6 +1760,58 @@ class Evaluator:
             datas = [be.from_host(w) for w in hybrid_hoist_host(
                 be, self.ctx.primes, hybrid_keys.alpha, L, host, elts, [None if k is None else be.to_host(k) for k in dev],
                 [[None if p is None else be.to_host(p.data) for p in r] for r in rows])]
+        return [Ciphertext()._set(d, 2, L, scale) for d in datas]
+
+    def bsgs_hoisted(self, cts: Sequence[Ciphertext], baby_steps: Sequence[int], rows: Sequence[Sequence[Optional[Plaintext]]],
+                     giant_steps: Sequence[int], dest: Sequence[int], hybrid_keys: "HybridKeys") -> List[Ciphertext]:
+        """A baby-step giant-step stage on hybrid keys in one call, the giant steps hoisted too: inner sum o is
+        plain_combine_hoisted's rows[o] over cts and baby_steps, kept in the extended basis; it is rotated by giant_steps[o]
+        (0: no rotation) and added into output dest[o]; every output takes ONE mod-down (hefx_hybrid_bsgs_hoisted, or the
+        statement in Python integers).  rows: key-level plaintexts of one scale, as in plain_combine_hoisted, whose checks
+        hold here; also a ValueError: a giant step without its key, a dest outside 0 .. max(dest), an output that no inner sum
+        feeds.  Not the words of plain_combine_hoisted + rotate_vector + add_many: those round every inner sum and every
+        giant rotation, this rounds c1 of an inner sum once and every output once."""
+        cts, steps, rows = list(cts), [int(s) for s in baby_steps], [list(r) for r in rows]
+        giant_steps, dest = [int(s) for s in giant_steps], [int(d) for d in dest]
+        L, elts, dev = self._hybrid_hoist_args("bsgs_hoisted", cts, steps, hybrid_keys, True)
+        terms = len(cts) * len(steps)
+        if not rows or any(len(r) != terms for r in rows):
+            raise ValueError("bsgs_hoisted: need one plaintext (or None) per inner sum, ciphertext and step")
+        if len(rows) > capi.HYBRID_HOIST_MAX_OUT:
+            raise ValueError(f"bsgs_hoisted: more than {capi.HYBRID_HOIST_MAX_OUT} inner sums")
+        ct_scale = cts[0].scale
+        if any(not self._close(ct_scale, c.scale) for c in cts):
+            raise ValueError("scale mismatch")
+        if any(all(p is None for p in r) for r in rows):
+            raise ValueError("bsgs_hoisted: an inner sum has no term")
+        if len(giant_steps) != len(rows) or len(dest) != len(rows):
+            raise ValueError("bsgs_hoisted: need one giant step and one dest per inner sum")
+        O = max(dest) + 1
+        if min(dest) < 0 or O > len(rows):
+            raise ValueError("bsgs_hoisted: dest out of range")
+        if set(dest) != set(range(O)):
+            raise ValueError("bsgs_hoisted: an output has no inner sum")
+        gelts = [1 if s == 0 else galois_elt_from_step(s, self.ctx.N) for s in giant_steps]
+        if any(s != 0 and not hybrid_keys.has_key(e) for s, e in zip(giant_steps, gelts)):
+            raise ValueError("Galois key not present")
+        gdev = [None if s == 0 else hybrid_keys.hybrid_key(e) for s, e in zip(giant_steps, gelts)]
+        scale = self._plain_product_scale(L, ct_scale, [p for r in rows for p in r if p is not None], self.ctx.k)
+        native = getattr(self.be, "hybrid_bsgs_hoisted", None)
+        if native is not None:
+            datas = native(hybrid_keys.alpha, L, [c.data for c in cts], elts, dev, [[None if p is None else p.data for p in r] for r in rows],
+                           gelts, gdev, dest)
+        else:
+            be, N = self.be, self.ctx.N
+            host = [np.asarray(be.to_host(c.data), dtype=np.uint64).reshape(2, L, N) for c in cts]
+            cache = {}  # a giant key is read by every output's inner sum of its step: brought to the host once
+
+            def to_host(key):
+                if key is not None and id(key) not in cache:
+                    cache[id(key)] = be.to_host(key)
+                return None if key is None else cache[id(key)]
+            datas = [be.from_host(w) for w in hybrid_bsgs_host(
+                be, self.ctx.primes, hybrid_keys.alpha, L, host, elts, [to_host(k) for k in dev],
+                [[None if p is None else be.to_host(p.data) for p in r] for r in rows], gelts, [to_host(k) for k in gdev], dest)]
         return [Ciphertext()._set(d, 2, L, scale) for d in datas]
 
     def apply_galois(self, a: Ciphertext, galois_elt: int, galois_keys: KSwitchKeys, destination=None):
