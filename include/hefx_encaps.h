@@ -12,6 +12,7 @@
  * key's digits, itself an encryption of P s' with noise sum_j e_j), the switch is moddown(x Kc).
  *
  * poly_degree 2048 .. 32768 -- this extension serves the one ring hefx_mod_raise does not.
+ * The three entries are held to stream order by tests/test_gpu_streams_ext.py.
  */
 #ifndef HEFX_ENCAPS_H
 #define HEFX_ENCAPS_H

@@ -43,6 +43,8 @@
  * context; every call copies them, with its item table, through the context's descriptor ring in front of its launches.  NO
  * entry of this header waits for the device, at first use or later (beyond what hefx.h says of a full descriptor ring and
  * of a scratch buffer that cannot grow): no gather table is built, the kernels compute the automorphism's index.
+ * The entries are held to stream order -- operands that arrive on the caller's stream, a wrap of the descriptor ring, scratch
+ * growth and a chunked call behind a shut stream -- by tests/test_gpu_streams_ext.py.
  *
  * poly_degree 2048 .. 32768.  Batches are cut into chunks whose workspace stays below 1 GiB (one item at least).
  * No security claim: alpha special primes add their bits to QP -- {60, 50 x 13, 60, 60} at N = 32768 is 830 of the 881 bits of

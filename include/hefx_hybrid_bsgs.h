@@ -5,7 +5,8 @@
  * conventions as hefx_hybrid_hoist.h: device pointers, NTT form, canonical words in and out, asynchronous on the caller's
  * stream, scratch is the context's, the constants of (alpha, L) travel through the descriptor ring, and the entry never waits
  * for the device: the kernels compute the automorphism's index.  A header of its own because the test suite enumerates
- * hefx_hybrid_hoist.h.
+ * hefx_hybrid_hoist.h.  The entry is held to stream order, alone and behind other users of the context's scratch, by
+ * tests/test_gpu_streams_ext.py.
  *
  * THE INTEGER STATEMENT.  Notation of hefx_hybrid.h and hefx_hybrid_hoist.h: level L, alpha, R = [0, L) u S, P, MD (step 5),
  * pi_g, the terms t = i m + k and their A_t.

@@ -45,6 +45,8 @@
  * HOST.  As hefx_hybrid.h: the constants of (alpha, L) are made on the host at the first use of the pair and travel with the
  * call's table through the descriptor ring.  NO entry of this header waits for the device, at first use of an element or of
  * a pair or later: the kernels compute the automorphism's index, no gather or flip table is built.
+ * Both entries are held to stream order, operands, plaintexts and keys arriving on the caller's stream behind a shut gate, by
+ * tests/test_gpu_streams_ext.py.
  */
 #ifndef HEFX_HYBRID_HOIST_H
 #define HEFX_HYBRID_HOIST_H

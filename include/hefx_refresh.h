@@ -14,7 +14,8 @@
  * the higher level -- exact integer work (mixed-radix digits, Horner), the first step of every CKKS bootstrapping too.
  *
  * None of the entries waits on the host for anything but a pointer-table ring slot of its own (hefx_refresh_batch);
- * their tables travel in kernel arguments and their scratch is the context's.
+ * their tables travel in kernel arguments and their scratch is the context's.  They are held to stream order, against
+ * references outside the engine, by tests/test_gpu_streams_ext.py.
  * This build serves poly_degree 1024 .. 16384 here (32768: HEFX_ERR_UNSUPPORTED).
  */
 #ifndef HEFX_REFRESH_H
