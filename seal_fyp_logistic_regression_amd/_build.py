@@ -7,9 +7,9 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libhefx.so")
-SOURCES = ["hefx_keyswitch.hip", "hefx_kernels.hip", "hefx_encode.hip", "hefx_sample.hip", "hefx_bfv.hip", "hefx_poly.hip", "hefx_dft.hip", "hefx_bootstrap.hip", "hefx_encaps.hip", "hefx_hybrid.hip", "hefx_hybrid_hoist.hip", "hefx_hybrid_bsgs.hip", "hefx_capi.cpp"]  # slowest first
+SOURCES = ["hefx_keyswitch.hip", "hefx_kernels.hip", "hefx_encode.hip", "hefx_sample.hip", "hefx_bfv.hip", "hefx_poly.hip", "hefx_dft.hip", "hefx_bootstrap.hip", "hefx_encaps.hip", "hefx_hybrid.hip", "hefx_hybrid_hoist.hip", "hefx_hybrid_bsgs.hip", "hefx_hybrid_encaps.hip", "hefx_capi.cpp"]  # slowest first
 HEADERS = ["hefx_internal.h", "hefx_modarith.cuh", "hefx_ntt.cuh", "hefx_ntt8.cuh", "hefx_mac.cuh", "hefx_ranges.h", "hefx_lt_plan.h", "hefx_poly_plan.h", "hefx_crt.cuh", "hefx_hybrid.cuh",
-           "../../include/hefx.h", "../../include/hefx_refresh.h", "../../include/hefx_bfv.h", "../../include/hefx_poly.h", "../../include/hefx_dft.h", "../../include/hefx_bootstrap.h", "../../include/hefx_encaps.h", "../../include/hefx_hybrid.h", "../../include/hefx_hybrid_hoist.h", "../../include/hefx_hybrid_bsgs.h"]
+           "../../include/hefx.h", "../../include/hefx_refresh.h", "../../include/hefx_bfv.h", "../../include/hefx_poly.h", "../../include/hefx_dft.h", "../../include/hefx_bootstrap.h", "../../include/hefx_encaps.h", "../../include/hefx_hybrid.h", "../../include/hefx_hybrid_hoist.h", "../../include/hefx_hybrid_bsgs.h", "../../include/ext/hefx_hybrid_encaps.h"]
 DEPS = SOURCES + HEADERS  # a change in any of them rebuilds the library (a header: every object; a source: its object)
 # The arithmetic probe (tests/test_gpu_arith_primitives.py): ONE device primitive per thread on the caller's operands.  A test
 # library of its own -- not linked into libhefx.so, not in capi.EXPORTED_SYMBOLS, not in source_sha16() -- with its own
@@ -86,7 +86,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         objs.append(obj)
         # the public headers and the host-only range check and planner are only seen by the C-ABI translation unit (a doc edit there
         # must not cost four minutes of kernels)
-        hdrs = [h for h in HEADERS if src == "hefx_capi.cpp" or not h.endswith(("hefx.h", "hefx_refresh.h", "hefx_bfv.h", "hefx_poly.h", "hefx_dft.h", "hefx_bootstrap.h", "hefx_encaps.h", "hefx_hybrid.h", "hefx_hybrid_hoist.h", "hefx_hybrid_bsgs.h", "hefx_ranges.h", "hefx_lt_plan.h", "hefx_poly_plan.h"))]
+        hdrs = [h for h in HEADERS if src == "hefx_capi.cpp" or not h.endswith(("hefx.h", "hefx_refresh.h", "hefx_bfv.h", "hefx_poly.h", "hefx_dft.h", "hefx_bootstrap.h", "hefx_encaps.h", "hefx_hybrid.h", "hefx_hybrid_hoist.h", "hefx_hybrid_bsgs.h", "hefx_hybrid_encaps.h", "hefx_ranges.h", "hefx_lt_plan.h", "hefx_poly_plan.h"))]
         hdr_t = max(os.path.getmtime(os.path.join(CSRC, h)) for h in hdrs)
         if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(hdr_t, os.path.getmtime(os.path.join(CSRC, src))):
             continue  # this object is newer than its source and every header it includes

@@ -14,7 +14,7 @@ import operator
 import numpy as np
 
 from . import poly as _poly
-from .seal import Ciphertext, CKKSEncoder, Evaluator, HybridKeys, KSwitchKeys, Plaintext
+from .seal import Ciphertext, CKKSEncoder, Evaluator, HybridEncapsKeys, HybridKeys, KSwitchKeys, Plaintext
 
 
 def _kswitch_only(fn):
@@ -814,6 +814,9 @@ def bootstrap(ev: Evaluator, ct: Ciphertext, plan, gal_keys: KSwitchKeys, relin_
     ciphertext is switched to the keys' sparse secret at the last prime (Evaluator.switch_key with encaps.low), raised under
     it and switched back at the top (Evaluator.raise_switch); plan.K is then a matter of the weight of THAT secret, and every
     step after the raise, like the rest of the program, runs under the main one.  None: the path above, bit for bit."""
+    if isinstance(encaps, HybridEncapsKeys):
+        raise TypeError("bootstrap needs the EncapsKeys of KeyGenerator.encapsulation_keys: HybridEncapsKeys "
+                        "(KeyGenerator.hybrid_encapsulation_keys) go with bootstrap_hybrid")
     if ct.size() != 2 or ct.parms_id() != 1:
         raise ValueError("bootstrap: needs a size-2 ciphertext at the last prime")
     if plan.N != ev.ctx.N or list(plan.primes) != list(ev.ctx.primes):
@@ -1086,15 +1089,20 @@ BOOTSTRAP_HYBRID_HOIST_GIANTS = False  # the measured default of bootstrap_hybri
 
 
 def bootstrap_hybrid(ev: Evaluator, ct: Ciphertext, plan, gal_keys: HybridKeys, relin_keys: HybridKeys, encoded=None,
-                     hoist_giants: bool = BOOTSTRAP_HYBRID_HOIST_GIANTS) -> Ciphertext:
-    """bootstrap on hybrid evaluation keys only, dense and sparse plans (no sparse-secret encapsulation): Evaluator.mod_raise
-    to plan.top_level = k - alpha, subsum_hybrid (sparse plans), the hybrid CoeffToSlot (packed for sparse plans),
-    eval_mod_hybrid, the hybrid SlotToCoeff.  plan: bootstrap.plan(..., special=alpha) for this context's chain; gal_keys:
-    hybrid_galois_keys(alpha, plan.galois_steps(), conjugate=True); relin_keys: hybrid_relin_keys(alpha); encoded:
-    plan.encode(encoder, extended=True).  hoist_giants: every DFT stage as ONE Evaluator.bsgs_hoisted
-    (include/hefx_hybrid_bsgs.h) -- other words, the same values."""
+                     hoist_giants: bool = BOOTSTRAP_HYBRID_HOIST_GIANTS, encaps=None) -> Ciphertext:
+    """bootstrap on hybrid evaluation keys only, dense and sparse plans: Evaluator.mod_raise to plan.top_level = k - alpha,
+    subsum_hybrid (sparse plans), the hybrid CoeffToSlot (packed for sparse plans), eval_mod_hybrid, the hybrid SlotToCoeff.
+    plan: bootstrap.plan(..., special=alpha) for this context's chain; gal_keys: hybrid_galois_keys(alpha,
+    plan.galois_steps(), conjugate=True); relin_keys: hybrid_relin_keys(alpha); encoded: plan.encode(encoder, extended=True).
+    hoist_giants: every DFT stage as ONE Evaluator.bsgs_hoisted (include/hefx_hybrid_bsgs.h) -- other words, the same values.
+    encaps: KeyGenerator.hybrid_encapsulation_keys(alpha, ...) -- sparse-secret encapsulation, the main secret may then be
+    DENSE: Evaluator.switch_key with encaps.low at the last prime (an ordinary key at q_0 q_(k-1)), then Evaluator.raise_switch
+    to plan.top_level (include/ext/hefx_hybrid_encaps.h) in place of mod_raise; nothing else changes.  None: the words above."""
     if not isinstance(gal_keys, HybridKeys) or not isinstance(relin_keys, HybridKeys):
         raise TypeError("bootstrap_hybrid needs HybridKeys (KeyGenerator.hybrid_galois_keys, hybrid_relin_keys)")
+    if encaps is not None and not isinstance(encaps, HybridEncapsKeys):
+        raise TypeError("bootstrap_hybrid needs the HybridEncapsKeys of KeyGenerator.hybrid_encapsulation_keys: EncapsKeys "
+                        "(KeyGenerator.encapsulation_keys) go with bootstrap")
     if ct.size() != 2 or ct.parms_id() != 1:
         raise ValueError("bootstrap: needs a size-2 ciphertext at the last prime")
     if plan.N != ev.ctx.N or list(plan.primes) != list(ev.ctx.primes):
@@ -1102,11 +1110,17 @@ def bootstrap_hybrid(ev: Evaluator, ct: Ciphertext, plan, gal_keys: HybridKeys, 
     if not (plan.special == gal_keys.alpha == relin_keys.alpha):
         raise ValueError(f"bootstrap_hybrid: the plan has {plan.special} special primes, the keys alpha = {gal_keys.alpha} and "
                          f"{relin_keys.alpha}: make the plan with bootstrap.plan(..., special=alpha)")
+    if encaps is not None and encaps.high.alpha != plan.special:
+        raise ValueError(f"bootstrap_hybrid: the plan has {plan.special} special primes, the encapsulation keys alpha = "
+                         f"{encaps.high.alpha}: make them with hybrid_encapsulation_keys(alpha = {plan.special})")
     if not ev._close(ct.scale, plan.scale):
         raise ValueError("scale mismatch")
     if encoded is None:
         encoded = plan.encode(CKKSEncoder(ev.ctx, device_encode=False), extended=True)
-    raised = ev.mod_raise(ct, plan.top_level)
+    if encaps is not None:
+        raised = ev.raise_switch(ev.switch_key(ct, encaps.low), encaps, plan.top_level)
+    else:
+        raised = ev.mod_raise(ct, plan.top_level)
     if plan.sparse_slots is not None:
         x = coeffs_to_slots_packed_hybrid(ev, subsum_hybrid(ev, raised, plan.sparse_slots, gal_keys), plan.c2s, gal_keys, encoded[0], hoist_giants)
         (y,) = eval_mod_hybrid(ev, [x], plan, relin_keys)

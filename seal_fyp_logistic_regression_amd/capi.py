@@ -247,6 +247,13 @@ _HYBRID_BSGS_SIGS = {
 }
 HYBRID_BSGS_SYMBOLS = sorted(_HYBRID_BSGS_SIGS)
 
+# include/ext/hefx_hybrid_encaps.h: sparse-secret encapsulation on hybrid keys (the collapsed hybrid key, mod-raise + switch)
+_HYBRID_ENCAPS_SIGS = {
+    "hefx_hybrid_collapse_key": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "hefx_hybrid_raise_switch": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+}
+HYBRID_ENCAPS_SYMBOLS = sorted(_HYBRID_ENCAPS_SIGS)
+
 
 def product_combine_words(L: int, n: int, P: int, m: int) -> int:
     """words of hefx_product_combine's table with a constant: strides, weights and the constant per row, n pointer records"""
@@ -270,7 +277,7 @@ def lib():
     for name, (res, args) in (list(_SIGS.items()) + list(_REFRESH_SIGS.items()) + list(_BFV_SIGS.items())
                               + list(_POLY_SIGS.items()) + list(_DFT_SIGS.items()) + list(_BOOTSTRAP_SIGS.items())
                               + list(_ENCAPS_SIGS.items()) + list(_HYBRID_SIGS.items()) + list(_HYBRID_HOIST_SIGS.items())
-                              + list(_HYBRID_BSGS_SIGS.items())):
+                              + list(_HYBRID_BSGS_SIGS.items()) + list(_HYBRID_ENCAPS_SIGS.items())):
         f = getattr(L, name)
         f.restype = res
         f.argtypes = args

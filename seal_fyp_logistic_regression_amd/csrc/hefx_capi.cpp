@@ -12,6 +12,7 @@
 #include "../../include/hefx_hybrid.h"
 #include "../../include/hefx_hybrid_hoist.h"
 #include "../../include/hefx_hybrid_bsgs.h"
+#include "../../include/ext/hefx_hybrid_encaps.h"
 
 #include <chrono>
 #include <cmath>
@@ -3648,6 +3649,60 @@ extern "C" int hefx_hybrid_keygen(hefx_context *c, int alpha, const uint64_t *sk
     HIPCHK(transform(c, false, e + raw, e, dn, k, 0, s));
     HIPCHK(launch_hy_keygen(c->T, F, alpha, dn, (const u64 *)sk, (const u64 *)new_sk, a, e, (u64 *)out, s));
     return HEFX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// sparse-secret encapsulation on hybrid keys (include/ext/hefx_hybrid_encaps.h, hefx_hybrid_encaps.hip)
+// ---------------------------------------------------------------------------------------------
+extern "C" int hefx_hybrid_collapse_key(hefx_context *c, int alpha, int L, const uint64_t *key, uint64_t *out, void *stream)
+{
+    CTXCHK(c);
+    if (int rc = check_hybrid(c, alpha, "hybrid_collapse_key", L)) return rc;
+    if (!key || !out) return fail(HEFX_ERR_INVALID, "bad hybrid_collapse_key arguments: null pointer");
+    if (int rc = check_ranges("hybrid_collapse_key", 1, &out, 2 * (size_t)(L + alpha) * c->n * sizeof(u64),
+                              {{&key, 1, hybrid_key_bytes(c, alpha, L)}}, {"d_key"}))
+        return rc;
+    HIPCHK(launch_hye_collapse(c->T, alpha, L, hybrid_digits(alpha, L), (const u64 *)key, (u64 *)out, (hipStream_t)stream));
+    return HEFX_OK;
+}
+
+extern "C" int hefx_hybrid_raise_switch(hefx_context *c, int alpha, int L, const uint64_t *ct_in, const uint64_t *ckey, uint64_t *ct_out,
+                                        void *stream)
+{
+    CTXCHK(c);
+    if (int rc = check_hybrid(c, alpha, "hybrid_raise_switch", L)) return rc;
+    if (L < 2) return fail(HEFX_ERR_INVALID, "hybrid_raise_switch: the target level must be at least 2");
+    if (!ct_in || !ckey || !ct_out) return fail(HEFX_ERR_INVALID, "bad hybrid_raise_switch arguments: null pointer");
+    const size_t N = c->n, row = N * sizeof(u64), A = (size_t)alpha, Ls = (size_t)L;
+    if (int rc = check_ranges("hybrid_raise_switch", 1, &ct_out, 2 * row * Ls, {{&ct_in, 1, 2 * row}, {&ckey, 1, 2 * row * (Ls + A)}},
+                              {"d_ct_in", "d_ckey"}))
+        return rc;
+    const HybridConsts &K = hybrid_consts(c, alpha, L);
+    if (K.words.size() > (size_t)RING_SLOT_PTRS) return fail(HEFX_ERR_UNSUPPORTED, "hybrid_raise_switch: the constants do not fit a descriptor slot");
+    // scratch, in rows of N words: coef [2] | xb [2 (L-1)] | xs [alpha] | accs [2 alpha] | tt [2 L] = 4 L + 3 alpha rows, every one
+    // of them transformed exactly once (the first inverse transform reads the caller's input); xb and xs lie side by side
+    HybridCarve w{c};
+    const HyBlock coef = w.take(2 * N), xb = w.take((2 * (Ls - 1) + A) * N, true), accs = w.take(2 * A * N, true), tt = w.take(2 * Ls * N, true);
+    const size_t xs = 2 * (Ls - 1) * N;  // words of xb in front of xs
+    if (int rc = ensure_scratch(c, w.words)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    u64 *S = c->scratch;
+    auto fill = [&](u64 *h) { std::copy(K.words.begin(), K.words.end(), h); };
+    auto run = [&](const u64 *d) -> int {
+        HyTab H = K.at;
+        H.tab = d, H.relin = 0;
+        HIPCHK(transform(c, true, (const u64 *)ct_in, S + coef.dst, 2, 1, 0, s));
+        HIPCHK(launch_hye_expand(c->T, alpha, L, S + coef.dst, S + xb.src, S + xb.src + xs, s));
+        HIPCHK(transform(c, false, S + xb.src, S + xb.dst, 2, L - 1, 1, s));
+        HIPCHK(transform(c, false, S + xb.src + xs, S + xb.dst + xs, 1, alpha, c->k - alpha, s));
+        HIPCHK(launch_hye_product(c->T, alpha, L, S + xb.dst + xs, (const u64 *)ckey, S + accs.src, s));
+        HIPCHK(transform(c, true, S + accs.src, S + accs.dst, 2, alpha, c->k - alpha, s));
+        HIPCHK(launch_hy_spread(c->T, H, 1, S + accs.dst, S + tt.src, s));
+        HIPCHK(transform(c, false, S + tt.src, S + tt.dst, 2, L, 0, s));
+        HIPCHK(launch_hye_finish(c->T, H, (const u64 *)ct_in, S + xb.dst, (const u64 *)ckey, S + tt.dst, (u64 *)ct_out, s));
+        return HEFX_OK;
+    };
+    return slot_call(c, s, K.words.size(), fill, run);
 }
 
 // ---------------------------------------------------------------------------------------------

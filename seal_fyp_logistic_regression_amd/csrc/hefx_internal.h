@@ -308,6 +308,15 @@ hipError_t launch_hy_spread(const DevTables &T, const HyTab &H, int n, const u64
 hipError_t launch_hy_finish(const DevTables &T, const HyTab &H, int n, const u64 *accd, const u64 *tt, const u64 *c0p, hipStream_t s);
 hipError_t launch_hy_keygen(const DevTables &T, const HyPmod &F, int alpha, int dn, const u64 *sk, const u64 *new_sk, const u64 *a,
                             const u64 *e, u64 *out, hipStream_t s);
+// sparse-secret encapsulation on hybrid keys (hefx_hybrid_encaps.hip, include/ext/hefx_hybrid_encaps.h): the collapsed key
+// [2][L+alpha][N] of the dn = ceil(L / alpha) read digits of key [dnum][2][k][N], and the element-wise passes of
+// hefx_hybrid_raise_switch between its transforms -- coef [2][N] -> xb [2][L-1][N], xs [alpha][N]; xs, ckey -> accs [2][alpha][N];
+// (launch_hy_spread, n = 1: accs -> tt [2][L][N]); in [2][1][N], xb, ckey, tt -> out [2][L][N].  H: the table of (alpha, L)
+hipError_t launch_hye_collapse(const DevTables &T, int alpha, int L, int dn, const u64 *key, u64 *out, hipStream_t s);
+hipError_t launch_hye_expand(const DevTables &T, int alpha, int L, const u64 *coef, u64 *xb, u64 *xs, hipStream_t s);
+hipError_t launch_hye_product(const DevTables &T, int alpha, int L, const u64 *xs, const u64 *ckey, u64 *accs, hipStream_t s);
+hipError_t launch_hye_finish(const DevTables &T, const HyTab &H, const u64 *in, const u64 *xb, const u64 *ckey, const u64 *tt, u64 *out,
+                             hipStream_t s);
 // hoisted hybrid key switching (hefx_hybrid_hoist.hip, include/hefx_hybrid_hoist.h).  The call's device table is HyTab's
 // constants (its `items` block unused) followed by the blocks below, at these word offsets of HyTab::tab.
 struct HyhTab {

@@ -681,6 +681,22 @@ class Engine:
             capi.ptr_array([o.ptr for o in outs]), stream))
         return outs
 
+    # ---- sparse-secret encapsulation on hybrid keys (include/ext/hefx_hybrid_encaps.h)
+    def hybrid_collapse_key(self, alpha, L, key, out=None, stream=None):
+        """the row-wise sum of the first ceil(L / alpha) digits of the hybrid key [dnum][2][k][N] over the rows 0 .. L-1 and the
+        alpha special rows: [2][L+alpha][N] (hefx_hybrid_collapse_key)"""
+        out = out if out is not None else DeviceArray(self, (2, L + int(alpha), self.N))
+        capi.check(capi.lib().hefx_hybrid_collapse_key(self._h, int(alpha), L, key.ptr, out.ptr, stream))
+        return out
+
+    def hybrid_raise_switch(self, alpha, L_out, ct, ckey, out=None, stream=None):
+        """ct [2][1][N] at q_0 -> [2][L_out][N]: the centred lift of both polynomials and the hybrid key switch of the lifted c1
+        with the collapsed key ckey = hybrid_collapse_key(alpha, L_out, key), in 4 L_out + 3 alpha row transforms
+        (hefx_hybrid_raise_switch)"""
+        out = out if out is not None else DeviceArray(self, (2, L_out, self.N))
+        capi.check(capi.lib().hefx_hybrid_raise_switch(self._h, int(alpha), L_out, ct.ptr, ckey.ptr, out.ptr, stream))
+        return out
+
     # ---- hoisted hybrid key switching (include/hefx_hybrid_hoist.h)
     def hybrid_rotate_hoisted_batch(self, alpha, L, cts, elts, keys, outs=None, stream=None):
         """outs[i * m + k] = the hoisted rotation of cts[i] by elts[k] with keys[k] (None with the element 1: the identity term):

@@ -328,6 +328,13 @@ class GpuBackend:
         twin of the tests has no such method and Evaluator.raise_switch states the same words through its apply_galois"""
         return self.engine.raise_switch(L_out, ct, ckey)
 
+    def hybrid_collapse_key(self, alpha, L, key):
+        return self.engine.hybrid_collapse_key(alpha, L, key)
+
+    def hybrid_raise_switch(self, alpha, L_out, ct, ckey):
+        """the same with a collapsed hybrid key (hefx_hybrid_raise_switch); the twin runs seal.hybrid_raise_switch_host"""
+        return self.engine.hybrid_raise_switch(alpha, L_out, ct, ckey)
+
     def refresh(self, L_in, size, L_out, ct, sk, pk, key32, stream_id):
         """decrypt -> exact lift -> encrypt in one engine call (hefx_refresh); the oracle-backed twin of the tests has no
         such method and Decryptor.refresh composes the same words from its decrypt, transforms and encrypt"""
@@ -738,6 +745,57 @@ def collapse_key_host(key: np.ndarray, primes: Sequence[int], L: int) -> np.ndar
         out -= np.where(out >= q, q, np.uint64(0))
     return out
 
+
+class HybridEncapsKeys:
+    """The two switching keys of sparse-secret encapsulation on hybrid keys (KeyGenerator.hybrid_encapsulation_keys).  `low`
+    is an ORDINARY key [k-1][2][k][N], word for word encapsulation_keys(...).low: it takes a ciphertext at the last prime from
+    the main secret s to the auxiliary sparse secret s' and lives at modulus q_0 q_(k-1) (zero outside digit 0, rows {0, k-1}).
+    `high` is a HybridKeys(alpha) holding, under the element 1, the hybrid key [dnum][2][k][N] of s' -> s: an encryption under
+    the MAIN secret at the full modulus q_0 ... q_(k-1), alpha special primes.  s' itself is not kept.  The collapsed forms of
+    `high` that Evaluator.raise_switch reads (include/ext/hefx_hybrid_encaps.h) are cached here per level."""
+
+    def __init__(self, low, high: "HybridKeys", hamming_weight: int):
+        self.low, self.high, self.hamming_weight = low, high, int(hamming_weight)
+        self._collapsed: Dict[int, object] = {}
+
+
+def hybrid_collapse_key_host(key: np.ndarray, primes: Sequence[int], alpha: int, L: int) -> np.ndarray:
+    """hefx_hybrid_collapse_key on the host: key [dnum][2][k][N] -> [2][L + alpha][N], row r the sum of the first
+    ceil(L / alpha) digits' rows m(r) mod q_m(r) (r < L: data prime r, else special prime k - alpha + r - L).  Exact in
+    uint64: canonical words of primes below 2^61, reduced after every addition."""
+    q, _, rows, _ = _hybrid_basis(primes, alpha, L)
+    key = np.asarray(key, dtype=np.uint64).reshape(-1, 2, len(q), np.asarray(key).shape[-1])
+    qr = np.asarray([q[m] for m in rows], dtype=np.uint64)[None, :, None]
+    out = key[0][:, rows].copy()
+    for j in range(1, (L + alpha - 1) // alpha):
+        out += key[j][:, rows]
+        out -= np.where(out >= qr, qr, np.uint64(0))
+    return out
+
+
+def hybrid_raise_switch_host(be, primes: Sequence[int], alpha: int, L: int, ct: np.ndarray, ckey: np.ndarray) -> np.ndarray:
+    """The statement of include/ext/hefx_hybrid_encaps.h in Python integers over the backend's own transforms: ct [2][1][N] at
+    q_0, ckey [2][L + alpha][N] (hybrid_collapse_key_host) -> [2][L][N].  x, y: the centred lifts of c1, c0 (lift_coefficients);
+    acc[c][r] = NTT(x mod q_m(r)) ckey[c][r] over the L + alpha rows; the hybrid mod-down (_hybrid_mod_down_host); y added to
+    polynomial 0.  What Evaluator.raise_switch runs with HybridEncapsKeys on a backend without the native entry (the oracle
+    twin of the tests)."""
+    q, _, rows, _ = _hybrid_basis(primes, alpha, L)
+    ct = np.asarray(ct, dtype=np.uint64).reshape(2, 1, -1)
+    N = ct.shape[2]
+    ckey = np.asarray(ckey, dtype=np.uint64).reshape(2, L + alpha, N)
+    coef = np.asarray(be.to_host(be.ntt_inverse(be.from_host(ct.copy()), 2, 1, 0))).reshape(2, N)
+    lifted = [lift_coefficients(coef[p][None], [q[0]] + [q[m] for m in rows[1:]], 1, len(rows)) for p in range(2)]  # rows[1:] of y, x
+    x = {0: ct[1, 0].astype(object)}
+    y = np.empty((1, L, N), dtype=np.uint64)
+    y[0, 0] = ct[0, 0]
+    for r, m in enumerate(rows[1:]):
+        x[m] = _row_ntt(be, q, m, lifted[1][r].astype(object))
+        if m < L:
+            y[0, m] = _row_ntt(be, q, m, lifted[0][r].astype(object)).astype(np.uint64)
+    B = {(c, m): x[m] * ckey[c, r].astype(object) % q[m] for c in range(2) for r, m in enumerate(rows)}
+    return _hybrid_rows_add_host(primes, _hybrid_mod_down_host(be, primes, alpha, L, B), y)
+
+
 CT_SIZE_MAX = 16  # HEFX_CT_SIZE_MAX (hefx.h): the most polynomials a ciphertext may have in this engine
 
 
@@ -893,21 +951,26 @@ class KeyGenerator:
             rk.keys[p - 2] = self._kswitch_key(None, power)
         return rk
 
-    def _hybrid_key(self, alpha: int, new_sk_host, new_sk_dev=None):
+    def _hybrid_key(self, alpha: int, new_sk_host, new_sk_dev=None, sk: Optional[SecretKey] = None, key32: Optional[bytes] = None,
+                    sid: Optional[int] = None):
         """hybrid switching key [dnum][2][k][N] for new_sk under the generator's secret: hefx_hybrid_keygen on the HIP engine,
         otherwise the same words composed from backend operations as _kswitch_key does (a dnum-polynomial draw from the
-        sub-streams 2 sid, 2 sid + 1; F_j = P mod q_m on the data rows of digit j)"""
+        sub-streams 2 sid, 2 sid + 1; F_j = P mod q_m on the data rows of digit j).  sk, key32, sid: as in _kswitch_key
+        (hybrid_encapsulation_keys) -- with a sid given the generator's stream counter stays where it is."""
         ctx, be = self.ctx, self.ctx.backend
         k, N, q = ctx.k, ctx.N, [int(p) for p in ctx.primes]
-        sid = self._next_stream()
+        if sid is None:
+            sid = self._next_stream()
+        sk = sk if sk is not None else self._sk
+        key32 = key32 if key32 is not None else self._key32
         native = getattr(be, "hybrid_keygen", None)
         if native is not None:
-            return native(alpha, self._sk.data, new_sk_dev if new_sk_dev is not None else be.from_host(new_sk_host), self._key32, sid)
+            return native(alpha, sk.data, new_sk_dev if new_sk_dev is not None else be.from_host(new_sk_host), key32, sid)
         if new_sk_host is None:
             new_sk_host = be.to_host(new_sk_dev).reshape(k, N)
         D = k - alpha
         dnum = (D + alpha - 1) // alpha
-        c0, c1 = self._encrypt_zero(dnum, k, sid)
+        c0, c1 = self._encrypt_zero(dnum, k, sid, sk, key32)
         P = 1
         for t in range(D, k):
             P *= q[t]
@@ -968,11 +1031,18 @@ class KeyGenerator:
         stream ids).  low: s -> s' (hefx_keygen_kswitch(sk = s', new_sk = s)), of which a key switch at the last prime reads
         digit 0, rows {0, k-1} only; every other word is zeroed before the key leaves the generator, so nothing under s' at
         the full modulus is published.  high: s' -> s, under the main secret.  s' is not kept on the result."""
+        key32 = _key32(seed)
+        aux, low = self._encaps_low(hamming_weight, key32)
+        high = self._kswitch_key(aux.host, aux.data, key32=key32, sid=2)
+        return EncapsKeys(low, high, hamming_weight)
+
+    def _encaps_low(self, hamming_weight: int, key32: bytes):
+        """(s', low) of encapsulation_keys and hybrid_encapsulation_keys: the auxiliary secret of key32 and the ordinary key
+        s -> s' from stream 1 of key32, zeroed outside digit 0, rows {0, k-1}"""
         ctx, be = self.ctx, self.ctx.backend
         k, N = ctx.k, ctx.N
         if k < 2:
             raise ValueError("encapsulation_keys: key switching needs a special prime")
-        key32 = _key32(seed)
         coef = sparse_ternary_secret(key32, N, hamming_weight)
         h = be.from_host(np.stack([(coef % int(q)).astype(np.uint64) for q in ctx.primes[:k]])[None])
         be.ntt_forward(h, 1, k, 0)
@@ -982,8 +1052,27 @@ class KeyGenerator:
         keep = low[0][:, [0, k - 1]].copy()
         low[:] = 0
         low[0][:, [0, k - 1]] = keep
-        high = self._kswitch_key(aux.host, aux.data, key32=key32, sid=2)
-        return EncapsKeys(be.from_host(low), high, hamming_weight)
+        return aux, be.from_host(low)
+
+    def hybrid_encapsulation_keys(self, alpha: int, hamming_weight: int = 32, seed: Optional[int] = None) -> HybridEncapsKeys:
+        """encapsulation_keys for a program on HYBRID keys (algorithms.bootstrap_hybrid(..., encaps=)): the same auxiliary
+        secret s' (sparse_ternary_secret of the sampler key of `seed`, exactly hamming_weight entries of +-1) and the same two
+        sampler streams of that key, 1 and 2; the generator's stream counter does not move and s' is not kept.
+        low: word for word encapsulation_keys(hamming_weight, seed).low -- an ORDINARY key, zero outside digit 0, rows
+        {0, k-1}: it lives at modulus q_0 q_(k-1).  The switch at the last prime is Evaluator.switch_key at L = 1
+        (hefx_switch_key), which needs nothing hybrid, and the sparse secret stays at that small modulus instead of q_0 times
+        alpha special primes.
+        high: HybridKeys(alpha) with the hybrid key of s' -> s under the element 1 (hefx_hybrid_keygen, or the composed form on
+        a backend without it), an encryption under the main secret at the full modulus q_0 ... q_(k-1), the last alpha primes
+        special; at alpha = 1 its words are encapsulation_keys(...).high.
+        The collapsed forms Evaluator.raise_switch reads are cached on the result per level.  No security claim is made for
+        either modulus or for the weight of s'."""
+        alpha = self._check_alpha(alpha)
+        key32 = _key32(seed)
+        aux, low = self._encaps_low(hamming_weight, key32)
+        high = HybridKeys(alpha)
+        high.keys[1] = self._hybrid_key(alpha, aux.host, aux.data, key32=key32, sid=2)
+        return HybridEncapsKeys(low, high, hamming_weight)
 
     def default_galois_elts(self) -> List[int]:
         N = self.ctx.N
@@ -1855,11 +1944,16 @@ class Evaluator:
         REFERENCE: the backend's ordinary apply_galois(L, ., 1, .) on a synthetic two-digit operand -- x = c1 - q_0 neg,
         neg the 0/1 polynomial of the coefficients above q_0 // 2, as target rows (c1's row, NTT_q1(neg), zeros) against
         the key (Kc, (-q_0 mod q_m) Kc, zeros) -- so that every modulus sees x Kc: the same words by exact modular
-        arithmetic, with the lift of c0 (lift_coefficients) as the c0 the key switch adds to."""
+        arithmetic, with the lift of c0 (lift_coefficients) as the c0 the key switch adds to.
+
+        keys may be the HybridEncapsKeys of KeyGenerator.hybrid_encapsulation_keys: the same step on hybrid keys, to a level in
+        2 .. k - alpha (default k - alpha): _hybrid_raise_switch."""
         if ct.size() != 2:
             raise ValueError("encrypted size must be 2")
         if ct.parms_id() != 1:
             raise ValueError("raise_switch: needs a ciphertext at the last prime")
+        if isinstance(keys, HybridEncapsKeys):
+            return self._hybrid_raise_switch(ct, keys, parms_id)
         L = int(parms_id) if parms_id is not None else self.ctx.first_parms_id()
         if L < 2 or L > self.ctx.first_parms_id():
             raise ValueError("raise_switch: the target level must lie between 2 and the first level")
@@ -1871,6 +1965,26 @@ class Evaluator:
                 ckey = keys._collapsed[L] = collapse(L, keys.high)
             return Ciphertext()._set(native(L, ct.data, ckey), 2, L, ct.scale)
         return Ciphertext()._set(self._raise_switch_composed(ct, keys, L), 2, L, ct.scale)
+
+    def _hybrid_raise_switch(self, ct: Ciphertext, keys: "HybridEncapsKeys", parms_id: Optional[int]) -> Ciphertext:
+        """raise_switch with KeyGenerator.hybrid_encapsulation_keys (include/ext/hefx_hybrid_encaps.h): the target level lies in
+        2 .. k - alpha (default k - alpha, the top of a hybrid program); 4 L + 3 alpha row transforms.  hefx_hybrid_raise_switch
+        with the collapsed key cached on `keys` per level where the backend has it, otherwise hybrid_raise_switch_host: the
+        same words."""
+        alpha, top = keys.high.alpha, self.ctx.k - keys.high.alpha
+        L = int(parms_id) if parms_id is not None else top
+        if L < 2 or L > top:
+            raise ValueError(f"raise_switch: with alpha = {alpha} the target level must lie between 2 and k - alpha = {top}")
+        be, q = self.be, self.ctx.primes
+        native, collapse = getattr(be, "hybrid_raise_switch", None), getattr(be, "hybrid_collapse_key", None)
+        ckey = keys._collapsed.get(L)
+        if native is not None and collapse is not None:
+            if ckey is None:
+                ckey = keys._collapsed[L] = collapse(alpha, L, keys.high.hybrid_key(1))
+            return Ciphertext()._set(native(alpha, L, ct.data, ckey), 2, L, ct.scale)
+        if ckey is None:
+            ckey = keys._collapsed[L] = hybrid_collapse_key_host(be.to_host(keys.high.hybrid_key(1)), q, alpha, L)
+        return Ciphertext()._set(be.from_host(hybrid_raise_switch_host(be, q, alpha, L, be.to_host(ct.data), ckey)), 2, L, ct.scale)
 
     def _raise_switch_composed(self, ct: Ciphertext, keys: "EncapsKeys", L: int):
         """raise_switch's words from the backend's ordinary key switch (the reference form its docstring states)"""
